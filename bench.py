@@ -31,10 +31,18 @@ environment): a step is one pass over the 64-camera novel-view ring theta_k = 2 
     what its stream still waited for behind its last conversion), so that a scaling run shows where the time went.
 Total work is fixed as N grows: scaling is "strong"; value = frames all ranks rendered / time.
 
-Timing: W warm-up steps, then regions of EXACTLY K steps, each bracketed by barrier +
-torch.cuda.synchronize() on both sides and reduced with MAX over ranks; regions are repeated until
-0.5 s have been timed (a single 20-frame region is 7 ms: too short to be stable) and the MEDIAN
-region gives ms_per_step and value.
+Timing: W warm-up steps, then untimed K-step regions until `--warmup-seconds` (0.5 s) have passed (a
+region right after a few warm-up frames runs 3-4 % slower than the steady state), then ONE timed region
+of exactly K steps, bracketed by barrier + torch.cuda.synchronize() on both sides and reduced with MAX
+over ranks; it gives ms_per_step and value.  `--min-seconds S` repeats the timed K-step region until
+S seconds have been timed and takes the MEDIAN region instead (a single 20-frame region is 7 ms: short
+enough to be noisy).
+
+`--dump-outputs DIR` (N = 1) writes what the timed path handed its caller in its last timed step:
+DIR/colors.npy [H,W,4] (RGB + expected depth) and DIR/alphas.npy [H,W,1] in float32, DIR/n_isects.npy
+in float64.  Past 64 MB in all, the same fixed, seeded sample of pixels is written for every image,
+with the flat pixel indices in DIR/pixel_index.npy (float64).  The scene (seed 0) and the camera are
+fixed, so two builds given the same arguments can be compared output for output.
 
 Rank 0 prints ONE JSON line.  Beside the contract fields it carries
   roofline      tile-raster forward kernel: algorithmic bytes / HIP-event time vs 8 TB/s (+ roofline_projection, _binning)
@@ -115,6 +123,31 @@ def scaling_prediction(rate_by_payload, W, H, worlds=(2, 4, 8)):
 
 
 PMC_FILE = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+DUMP_MAX_BYTES = 64_000_000             # --dump-outputs: all files together, .npy headers included
+
+
+def dump_outputs(path, arrays, max_bytes=DUMP_MAX_BYTES, seed=0):
+    """--dump-outputs: arrays = {"colors": [H,W,C], "alphas": [H,W,1], "n_isects": [1]} (tensors of one frame) ->
+    path/<name>.npy, images in float32 and counts in float64.  When the images would take more than max_bytes, every
+    image keeps the same fixed, seeded sample of pixels, in increasing order of their flat index, and
+    path/pixel_index.npy holds those indices (float64: exact below 2^53)."""
+    os.makedirs(path, exist_ok=True)
+    out = {k: v.detach().cpu().numpy() for k, v in arrays.items()}
+    images = {k: v for k, v in out.items() if v.ndim == 3}
+    shapes = {v.shape[:2] for v in images.values()}
+    assert len(shapes) == 1, shapes
+    H, W = shapes.pop()
+    bytes_per_px = sum(v.shape[2] * 4 for v in images.values())
+    if H * W * bytes_per_px > max_bytes:
+        k = (max_bytes - 4096) // (bytes_per_px + 8)         # (4 KB for the headers and the small arrays)
+        idx = np.sort(np.random.default_rng(seed).choice(H * W, size=k, replace=False))
+        for name, v in images.items():
+            out[name] = v.reshape(H * W, -1)[idx]
+        out["pixel_index"] = idx.astype(np.float64)
+    for name, v in out.items():
+        v = np.ascontiguousarray(v, dtype=np.float32 if name in images else np.float64)
+        np.save(os.path.join(path, name + ".npy"), v)
+    print(f"bench.py: wrote {', '.join(f'{n}.npy {out[n].shape}' for n in out)} to {path}", file=sys.stderr)
 
 
 def parse():
@@ -132,7 +165,13 @@ def parse():
                     help="N > 1: render float frames and convert them to the dataset payload on the consumer stream between "
                          "fetch and release (the round-3 loop) instead of letting the raster write the payload "
                          "(FrameRenderer(dataset_output=)); world of one: 4,124-4,156 against 4,356-4,380 frames/s")
-    ap.add_argument("--min-seconds", type=float, default=0.5, help="repeat the K-step region until this much is timed")
+    ap.add_argument("--warmup-seconds", type=float, default=0.5,
+                    help="after the W warm-up steps, run untimed K-step regions until this much time has passed")
+    ap.add_argument("--min-seconds", type=float, default=0.0,
+                    help="repeat the K-step region until this much is timed (default 0: one region, exactly K timed steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N = 1: after the timed steps, write what the caller received from the last one (the frame's "
+                         "colors and alphas, float32; the tile-intersection count, float64) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-stress", action="store_true", help="skip the configs[4] leg (5 M Gaussians at 3840x2160)")
     ap.add_argument("--no-gather", action="store_true")
@@ -209,6 +248,8 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    if a.dump_outputs and (a.gpus > 1 or world > 1 or a.force_gather):
+        raise SystemExit("--dump-outputs writes the frame of the one-GPU workload: use it with --gpus 1 and no --force-gather")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: start the N ranks ourselves (one process per GPU, what the driver's
         # `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N` does) and pass
@@ -333,10 +374,11 @@ def main():
     # once, and every gather_batch-th frame one collective ships the whole batch.
     per_rank = {}                                  # HIP-event split of this rank's last timed region, per leg (N > 1)
 
-    def time_frames(g_mode, sh=shard, leg=None):
+    def time_frames(g_mode, sh=shard, leg=None, last=None):
         """Warm-up, then regions of K steps until min_seconds are timed; the gathered payload is the dataset frame
         (RGBA8 plane + ray-distance plane), fp32 RGB + expected depth + alpha, or the 8-bit RGB image; `sh` says which
-        cameras this rank renders (make_shard).  Returns (regions, collectives)."""
+        cameras this rank renders (make_shard).  `last` (a dict): filled with copies of what fetch() returned for the
+        last frame of the last timed step, taken after the timed regions.  Returns (regions, collectives)."""
         nonlocal fr
         fr = fr_by_payload.get(g_mode, fr_plain) if ring else fr
         cam_devs, GB, weights = sh["cam_devs"], sh["GB"], sh["weights"]
@@ -377,6 +419,7 @@ def main():
             """Fetch the oldest frame; with N > 1 stage it for the (asynchronous) RCCL gather."""
             tk = tickets.pop(0)
             f = fr.fetch(tk, check=False)
+            state["last_frame"] = f
             c0 = None
             if do_gather and ev["start"] is not None:
                 c0 = torch.cuda.Event(enable_timing=True)
@@ -492,11 +535,21 @@ def main():
         for _ in range(a.warmup):
             step()
         drain()
+        warm, n_warm = 0.0, 0
+        while warm < a.warmup_seconds and n_warm < 400:    # untimed K-step regions, so that the timed one starts in the
+            warm += region(a.steps)                        # steady state (dt is all-reduced: every rank runs as many)
+            n_warm += 1
         regs = []
         while True:                                        # identical trip count on every rank (dt is all-reduced)
             regs.append(region(a.steps))
             if sum(regs) >= a.min_seconds or len(regs) >= 400:
                 break
+        if last is not None:
+            # drain() retired every frame in submission order and nothing was submitted since: the slot still holds the
+            # last frame, and the current stream (which fetch() made wait for it) copies it out
+            f_ = state["last_frame"]
+            last.update({k: f_[k].clone() for k in ("colors", "alphas")}, n_isects=f_["meta"]["n_isects"].clone())
+            torch.cuda.synchronize()
         if do_gather and rank == 0:
             # the collective really delivered every rank's frame (all cameras see the scene)
             for r_ in range(world):
@@ -523,8 +576,12 @@ def main():
 
     g_mode = a.gather_dtype
     g_u8 = g_mode == "u8"
-    regions, n_collectives = time_frames(g_mode)
+    last_frame = {} if a.dump_outputs else None
+    regions, n_collectives = time_frames(g_mode, last=last_frame)
     elapsed = float(np.median(regions))
+    if last_frame:
+        dump_outputs(a.dump_outputs, last_frame)
+        del last_frame
     # the named alternates, timed the same way in the same run (N > 1 only): smaller payloads, and the weighted shard
     alternates = {}
     for leg_name, leg_mode, leg_shard in legs[1:]:

@@ -62,3 +62,33 @@ def test_scaling_prediction_is_min_of_render_and_root_bounds():
     assert p["fp32"]["by_world_size"]["8"]["limited_by"] == "root" and p["fp32"]["by_world_size"]["8"]["speedup_vs_one_rank_fp32"] < 6
     assert p["dataset16"]["by_world_size"]["8"]["speedup_vs_one_rank_fp32"] > 6 > p["dataset"]["by_world_size"]["8"]["speedup_vs_one_rank_fp32"]
     assert p["u8"]["by_world_size"]["8"]["limited_by"] == "render" and p["u8"]["by_world_size"]["8"]["speedup_vs_one_rank_fp32"] == 8.0
+
+
+def test_dump_outputs_writes_whole_frames_and_a_seeded_pixel_sample_past_the_cap(tmp_path):
+    """bench.py --dump-outputs: float32 images and float64 counts; over the byte cap every image keeps the same fixed
+    sample of pixels (flat indices in pixel_index.npy) and the files stay under the cap."""
+    import numpy as np
+    import torch
+    import bench
+    g = torch.Generator().manual_seed(3)
+    frame = {"colors": torch.rand(40, 30, 4, generator=g), "alphas": torch.rand(40, 30, 1, generator=g),
+             "n_isects": torch.tensor([1234], dtype=torch.int32)}
+    bench.dump_outputs(str(tmp_path / "whole"), frame)
+    got = {k: np.load(tmp_path / "whole" / f"{k}.npy") for k in ("colors", "alphas", "n_isects")}
+    assert not (tmp_path / "whole" / "pixel_index.npy").exists()
+    assert got["colors"].dtype == np.float32 and np.array_equal(got["colors"], frame["colors"].numpy())
+    assert got["alphas"].dtype == np.float32 and np.array_equal(got["alphas"], frame["alphas"].numpy())
+    assert got["n_isects"].dtype == np.float64 and got["n_isects"].tolist() == [1234.0]
+    cap = 4096 + 40 * 30 * 20 // 3                        # a third of the frame's 20 bytes per pixel, and the headers
+    runs = []
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), frame, max_bytes=cap)
+        runs.append({k: np.load(tmp_path / d / f"{k}.npy") for k in ("colors", "alphas", "n_isects", "pixel_index")})
+    a, b = runs
+    assert all(np.array_equal(a[k], b[k]) for k in a)     # the same sample every time
+    idx = a["pixel_index"]
+    assert idx.dtype == np.float64 and np.all(np.diff(idx) > 0) and 0 < len(idx) < 40 * 30
+    flat = idx.astype(np.int64)
+    assert np.array_equal(a["colors"], frame["colors"].numpy().reshape(-1, 4)[flat])
+    assert np.array_equal(a["alphas"], frame["alphas"].numpy().reshape(-1, 1)[flat])
+    assert sum(os.path.getsize(tmp_path / "a" / f"{k}.npy") for k in a) <= cap

@@ -69,3 +69,40 @@ def test_gpus_n_without_enough_devices_fails_with_a_clear_message():
                        capture_output=True, text=True, timeout=600)
     assert r.returncode != 0 and r.stdout.strip() == ""
     assert "needs 8 visible GPUs" in r.stderr
+
+
+@pytest.mark.gpu
+def test_bench_times_exactly_k_steps_and_dumps_the_last_frame_it_rendered(tmp_path):
+    """`bench.py --gpus 1 --steps K --dump-outputs DIR`: one region of exactly K timed steps, and DIR holds the frame the
+    caller of the timed path received -- bit for bit the frame rasterization() gives for the same seeded scene and camera."""
+    import math
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    from robosimgs_amd import camera_ring, synthetic_scene
+    from robosimgs_amd.rendering import rasterization
+    W, H, N = 256, 160, 20_000
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--n", str(N), "--width", str(W), "--height", str(H), "--bwd-steps", "2", "--no-cpu-baseline",
+                        "--no-stress", "--dump-outputs", str(out)],
+                       cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, r.stdout[-2000:]
+    res = json.loads(lines[0])
+    assert res["steps"] == 3 and res["config"]["timing"].startswith("median of 1 regions of 3 steps")
+    colors, alphas, n_isects = (np.load(out / f"{k}.npy") for k in ("colors", "alphas", "n_isects"))
+    assert not (out / "pixel_index.npy").exists()
+    assert colors.dtype == alphas.dtype == np.float32 and n_isects.dtype == np.float64
+    assert colors.shape == (H, W, 4) and alphas.shape == (H, W, 1) and float(alphas.max()) > 0
+    g = synthetic_scene(N, math.log(0.012), 3, seed=0)
+    t = g.to_torch("cuda", 3)
+    cam = camera_ring(1, W, H, thetas=[0.3])[0]
+    vm = torch.from_numpy(cam.viewmat().astype(np.float32)).cuda()[None]
+    K = torch.from_numpy(cam.K.astype(np.float32)).cuda()[None]
+    with torch.no_grad():
+        c, a, meta = rasterization(t["means"], t["quats"], t["scales"], t["opacities"], t["colors"], vm, K, W, H,
+                                   sh_degree=3, render_mode="RGB+ED")
+    assert np.array_equal(colors, c[0].cpu().numpy()) and np.array_equal(alphas, a[0].cpu().numpy())
+    assert n_isects.tolist() == [float(meta["n_isects"][0])]
