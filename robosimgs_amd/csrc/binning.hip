@@ -257,42 +257,31 @@ __global__ __launch_bounds__(kBlock) void emit_kernel(
 // tile_sort.hip then lets every tile pick its entries out of its group's segment.
 // Device-scope atomics were measured for the same job and are no option: ~25 G atomics/s on 8160 hot counters
 // (scripts/ubench/atomic_rate.hip), i.e. 108 us per pass at config 2.
-#ifndef MGS_DIRECT_DEAL
-#define MGS_DIRECT_DEAL 1        // runs of Gaussians dealt round-robin to the histogram / scatter workgroups (DealtIndex)
-#endif
-#ifndef MGS_DIRECT_DEAL_RUN
-#define MGS_DIRECT_DEAL_RUN 256
-#endif
-#ifndef MGS_DIRECT_THREADS
-#define MGS_DIRECT_THREADS 512
-#endif
 // Workgroup of the histogram / scatter kernels and Gaussians per thread.  Alone the stage likes big workgroups
 // (1024 x 4: 110.7 us, 512 x 8: 113.3, 512 x 4: 118.1, 256 x 8: 125.0, 256 x 4: 137.8 -- fewer table rows, fewer
 // copies of the scatter's prologue), but a 16-wave workgroup has to wait for a quarter of a CU to drain while other
 // frames' raster waves hold the slots: with three frames in flight 1024 x 4 renders 3,281 frames/s, 512 x 8 3,669,
 // 256 x 8 3,561 (the radix partition: 3,585).
-constexpr int kDirectThreads = MGS_DIRECT_THREADS;
+constexpr int kDirectThreads = 512;
+// Runs of consecutive Gaussians dealt round-robin to the histogram / scatter workgroups (DealtIndex)
+constexpr int kDealRun = 256;
 // DealtIndex covers the index range without holes, and the PAIRS path's "a wave is 64 consecutive Gaussians", only then:
-static_assert(MGS_DIRECT_DEAL_RUN % 64 == 0 && kDirectThreads % MGS_DIRECT_DEAL_RUN == 0 && kDirectThreads >= MGS_DIRECT_DEAL_RUN,
-              "MGS_DIRECT_THREADS must be a multiple of MGS_DIRECT_DEAL_RUN, and the run a multiple of the wave");
-#ifndef MGS_DIRECT_PER_THREAD
+static_assert(kDealRun % 64 == 0 && kDirectThreads % kDealRun == 0 && kDirectThreads >= kDealRun,
+              "kDirectThreads must be a multiple of kDealRun, and the run a multiple of the wave");
 // Round 4: 4 (was 8).  At 1 M Gaussians 512 x 8 is 245 workgroups -- fewer than CUs, two waves per SIMD -- and on a
 // Morton-ordered scene their shares of the pairs differ by 2.7 x (15 k on average, 40 k at most: near Gaussians are
 // neighbours in memory AND cover many tiles).  490 workgroups, rocprofv3 per kernel in bench.py's run: scatter 30.3 ->
 // 25.7 us, histogram 14.3 -> 11.3, the column scan (twice the rows) 6.9 -> 11.6 (8.8 once it kept its rows in registers);
 // three frames in flight 4,503 -> 4,561 frames/s.  With the scene in random order the shares are even and the extra rows
 // cost the scatter ~4 us (fragmented stores), the same frames/s.
-#define MGS_DIRECT_PER_THREAD 4
-#endif
-constexpr int kDirectPerThread = MGS_DIRECT_PER_THREAD;   // Gaussians per thread of those kernels
+constexpr int kDirectPerThread = 4;            // Gaussians per thread of those kernels
 constexpr int kDirectMaxBlocks = 1024;         // table rows (beyond threads x per-thread x this many Gaussians: longer runs per workgroup)
 constexpr int kDirectMaxTiles = 15000;         // the LDS histogram: 4 bytes per bin in 64 KiB, less the static part
 constexpr int kGroupShift = 2;                 // 2^2 consecutive tiles share a segment (1 / 2 / 4 / 8 / 16 tiles: 124 / 113 / 112 / 124 / 150 us)
 constexpr uint32_t kCoopRect = 24;             // rectangles above this many tiles are walked by the whole wave
 constexpr uint32_t kRunRect = 128;             // ... above this many tiles (4K frames are full of rectangles of 25-100 tiles: one trip either way, and the runs' index arithmetic costs more)
-#ifndef MGS_DIRECT_RUNS
-#define MGS_DIRECT_RUNS 1        // ... run of tiles by run (one LDS atomic per bin a row touches: for_each_tile_run); 0: tile by tile
-#endif
+// Grouped bins (shift > 0) are counted and filled run of tiles by run: one LDS atomic per bin a row touches
+// (for_each_tile_run; profiles/r6/00_experiments.md section 7).
 
 // f(tile, g) for every tile of every lane's rectangle; all 64 lanes must arrive together
 template <class F>
@@ -364,7 +353,7 @@ __device__ __forceinline__ void for_each_tile_run(uint32_t pack, uint32_t cnt, u
 }
 
 // Which Gaussian thread t of workgroup w takes as item i of the pass that starts at `base`.  DEALT (deal_nb = the number
-// of workgroups; the default): runs of MGS_DIRECT_DEAL_RUN consecutive Gaussians go round-robin to the workgroups -- run
+// of workgroups; what the host launches): runs of kDealRun consecutive Gaussians go round-robin to the workgroups -- run
 // ((pass * per-thread + i) * runs-per-pass + t / R) * deal_nb + w -- instead of one run of `chunk` per workgroup.  On a
 // Morton-ordered scene the workgroups' shares of the pairs differed by 2.7 x (near Gaussians are neighbours in memory AND
 // cover many tiles), and a scene whose large rectangles are contiguous in index (appended by a densifier, a background
@@ -377,7 +366,7 @@ struct DealtIndex {
   __device__ __forceinline__ int operator()(int base, int i) const {
     if (deal_nb > 0) {
       const int pass = (base - g0) / (kDirectThreads * kDirectPerThread);
-      constexpr int R = MGS_DIRECT_DEAL_RUN, kSub = kDirectThreads / R;      // runs of R consecutive Gaussians
+      constexpr int R = kDealRun, kSub = kDirectThreads / R;      // runs of R consecutive Gaussians
       const int sub = (int)threadIdx.x / R, within = (int)threadIdx.x % R;
       const long long g = (((long long)(pass * kDirectPerThread + i) * kSub + sub) * deal_nb + blockIdx.x) * R + within;
       return g < n ? (int)g : -1;
@@ -418,7 +407,7 @@ __global__ __launch_bounds__(kDirectThreads) void direct_hist_kernel(
     for (int i = 0; i < kDirectPerThread; ++i) {
       const int g = gi(base, i);
       if (g >= 0 && tiles_per_gauss) tiles_per_gauss[g] = (int32_t)info[i].y;
-      if (shift > 0 && MGS_DIRECT_RUNS)
+      if (shift > 0)
         for_each_tile_run(info[i].x, info[i].y, (uint32_t)g, tile_w, shift, [&](uint32_t tile, uint32_t n_run, uint32_t) { atomicAdd(&hist[tile >> shift], n_run); });
       else
         for_each_tile(info[i].x, info[i].y, (uint32_t)g, tile_w, [&](uint32_t tile, uint32_t) { atomicAdd(&hist[tile >> shift], 1u); });
@@ -429,24 +418,16 @@ __global__ __launch_bounds__(kDirectThreads) void direct_hist_kernel(
   for (int i = threadIdx.x; i < n_tiles; i += kDirectThreads) row[i] = hist[i];
 }
 
-// 256 threads: 16 bins (64 bytes of a row) x 16 row groups; two passes over the group's rows (sum, then rewrite as
-// the exclusive prefix), 16 loads in flight per thread
-#ifndef MGS_COLSCAN_BINS
 // 256 threads: kColBins bins (4 bytes each, consecutive in a table row) x 256 / kColBins row groups.  rocprofv3 per
 // kernel at the 490 table rows of 1 M Gaussians (two trips over the column, round 4): 16 bins x 16 groups 11.6 us,
 // 8 x 32 11.3, 4 x 64 14.2, 32 x 8 16.4; 16 x 32 with 512 threads 2 us faster alone but 4,170 against 4,504 frames/s with
 // three frames in flight (a 512-thread workgroup waits for room between other frames' raster waves).  With the rows kept
 // in registers (one trip, below) 16 x 16 takes 8.8 us.
-#define MGS_COLSCAN_BINS 16
-#endif
-#ifndef MGS_COLSCAN_KEEP
-// Table rows a thread keeps in registers between the sum and the rewrite (one trip over the column instead of two) in a
-// TRAINING step, where the launch has the GPU to itself: 11.6 -> 8.8 us at 32 (92 VGPRs).  Inference frames keep the
+// kColKeepTraining: table rows a thread keeps in registers between the sum and the rewrite (one trip over the column
+// instead of two) in a TRAINING step, where the launch has the GPU to itself: 11.6 -> 8.8 us at 32 (92 VGPRs).  Inference frames keep the
 // two-trip scan (kColKeep 1, ~50 VGPRs): with three frames in flight the one-trip scan renders 4,421 against 4,503
 // frames/s (3,846 against 3,927 in the caller's order) -- its fatter waves wait for room between the raster's.
-#define MGS_COLSCAN_KEEP 32
-#endif
-constexpr int kColThreads = 256, kColBins = MGS_COLSCAN_BINS, kColGroups = kColThreads / kColBins;
+constexpr int kColThreads = 256, kColBins = 16, kColGroups = kColThreads / kColBins, kColKeepTraining = 32;
 template <int kColKeep>
 __global__ __launch_bounds__(kColThreads) void direct_colscan_kernel(
     int nb, int n_tiles, uint32_t* __restrict__ table, uint32_t* __restrict__ tile_count) {
@@ -573,8 +554,8 @@ __global__ __launch_bounds__(kDirectThreads) void direct_scatter_kernel(
     tile_offsets[n_tiles] = (int32_t)(total < capacity ? (uint32_t)total : capacity);
     *n_isect = total > 0xffffffffull ? 0xffffffffu : (uint32_t)total;
     *status = total > capacity ? MGS_STATUS_ISECT_OVERFLOW : 0u;
-    // the header of the per-tile sort's list of long tiles (tile_sort.hip: counts of long lists, giant descriptors, pool
-    // entries), instead of a memset
+    // the header of the per-tile sort's deferred lists (tile_sort.hip kListHeader: eight counters -- descriptors, unit
+    // table entries, collect chunks claimed), instead of a memset
     if (zero_word) reinterpret_cast<uint4*>(zero_word)[0] = reinterpret_cast<uint4*>(zero_word)[1] = make_uint4(0u, 0u, 0u, 0u);
   }
   __syncthreads();
@@ -618,7 +599,7 @@ __global__ __launch_bounds__(kDirectThreads) void direct_scatter_kernel(
 #pragma unroll
     for (int i = 0; i < kDirectPerThread; ++i) {
       const int g = gi(base, i);
-      if (shift > 0 && MGS_DIRECT_RUNS)
+      if (shift > 0)
         for_each_tile_run(info[i].x, info[i].y, (uint32_t)g, tile_w, shift, [&](uint32_t tile, uint32_t n_run, uint32_t gs) {
           const uint32_t p = atomicAdd(&cursor[tile >> shift], n_run);
           // grouped: the entry carries its tile's place in the group above the id (ids < 2^(32 - shift))
@@ -830,11 +811,11 @@ extern "C" int mgs_isect_tiles(int n, const float* means2d, const int32_t* radii
       const int bins = (n_tiles + (1 << gshift) - 1) >> gshift;
       const size_t lds = (size_t)bins * sizeof(uint32_t);
       // runs of Gaussians are dealt round-robin to the workgroups (DealtIndex)
-      const int deal_nb = MGS_DIRECT_DEAL ? (int)nb : 0;
+      const int deal_nb = (int)nb;
       hipLaunchKernelGGL(direct_hist_kernel, dim3(nb + (pair_info ? 1 : 0)), dim3(kDirectThreads), lds, s, n, chunk, ginfo, tile_w,
                          n_tiles, gshift, u32(ws.table), tiles_per_gauss, pair_info ? sums : nullptr, nsum, deal_nb);
       if (pair_info)
-        hipLaunchKernelGGL(direct_colscan_kernel<MGS_COLSCAN_KEEP>, dim3(div_up((unsigned)bins, (unsigned)kColBins)), dim3(kColThreads), 0, s,
+        hipLaunchKernelGGL(direct_colscan_kernel<kColKeepTraining>, dim3(div_up((unsigned)bins, (unsigned)kColBins)), dim3(kColThreads), 0, s,
                            (int)nb, bins, u32(ws.table), u32(ws.tile_count));
       else
         hipLaunchKernelGGL(direct_colscan_kernel<1>, dim3(div_up((unsigned)bins, (unsigned)kColBins)), dim3(kColThreads), 0, s,

@@ -6,7 +6,7 @@
 // six moments of d loss / d sigma about the tile centre and the colour gradients (GaussGrad), and the wave reduces those
 // 6 + channels partial sums.  Two ways out:
 //   * records (mgs_rasterize_bwd_det, the render path's default): the sums go through a wave-private LDS transpose
-//     (eight lanes finish one value each) and are stored as one record of `record_floats` floats per (tile, Gaussian)
+//     (four or eight lanes finish each value) and are stored as one record of `record_floats` floats per (tile, Gaussian)
 //     pair; reduce_records_kernel turns every record into the pair's gradients (the slot tells the tile, hence the
 //     mean's offset from its centre) and sums each Gaussian's contiguous slots.  No atomics, bit-reproducible.
 //   * atomics (mgs_rasterize_bwd, for externally supplied tile lists): plain DPP reduction to
@@ -148,46 +148,18 @@ __device__ __forceinline__ void finish_geo(float ca, float cb, float cc, float& 
 // atomics.  RECORDS == true: it stores them as one record at the pair's slot (pair_info) and
 // sets the slot's flag; reduce_records_kernel then sums each Gaussian's slots -- no atomics,
 // bit-reproducible.
-#ifndef MGS_RASTER_BWD_WG_WAVES
-#define MGS_RASTER_BWD_WG_WAVES 1      // independent tiles (waves) per workgroup; 2 / 4 measured slower (564 / 554 vs 537 us)
-#endif
-#ifndef MGS_RASTER_BWD_MIN_WAVES
 // min waves per SIMD asked of the register allocator for the record kernels of up to 4 channels without absgrad.
 // 5 = at most 96 VGPRs (113 when left free: 4 waves), 28 bytes spilled outside the walk; the kernel's LDS (64-byte queue
 // entries, ten rows of reduction buffer: 6.5 KB per wave) allows 24 waves per CU.  Measured with dynamic-LDS caps:
 // 3 waves per SIMD 544 us, 4 waves 474-484, 5 waves 468-475 (memset + backward + reduce); 6 waves (80 VGPRs) spill: 694.
-// The round-3 first pass tried 96 VGPRs with 9 KB of LDS per wave -- 17 waves per CU at most, so only the spills showed.
-#define MGS_RASTER_BWD_MIN_WAVES 5
-#endif
-// HALF (record path only; measured and NOT the default): a wave owns HALF a tile -- two 8x8 blocks side by
-// side, two pixels per lane -- and the pair's record slot is doubled (slot * 2 + half): twice the waves, each
-// half the serial work, 96 instead of 112 VGPRs, against one more wave reduction and record for the pairs
-// that reach both halves.  618 -> 724 us for the whole backward at config 2: the extra reductions and the
-// doubled slots of the reduce cost more than the finer schedule returns (what paid in the forward, where a
-// block's result needs no cross-lane sum, does not pay here).
-#ifndef MGS_RASTER_BWD_LDS_PAD
-#define MGS_RASTER_BWD_LDS_PAD 0       // bytes of unused dynamic LDS per workgroup: caps the waves per CU (occupancy experiments)
-#endif
-#ifndef MGS_RASTER_BWD_HALF
-#define MGS_RASTER_BWD_HALF 0
-#endif
-// PIPE (record path, 9..16 reduced values): the wave reduction of list entry j is finished while entry j+1 is
-// evaluated -- the partial sums parked in LDS by entry j are read back at the top of the next trip, the ~100
-// vector instructions of that entry's evaluation cover the round trip, and the sums are then finished and
-// stored.  Summation order and records are unchanged.  Measured and NOT the default: 572.4 us with it, 569.3 without --
-// the kernel is not waiting on that round trip.
-#ifndef MGS_RASTER_BWD_PIPE
-#define MGS_RASTER_BWD_PIPE 0
-#endif
-#ifndef MGS_RASTER_BWD_QUAD
-#define MGS_RASTER_BWD_QUAD 1
-#endif
-#ifndef MGS_RASTER_BWD_XCD_RUN
-#define MGS_RASTER_BWD_XCD_RUN 4       // segmented launch: consecutive units per XCD (see raster_bwd_kernel); 1 = plain numbering.  FETCH_SIZE 422 / 387 / 360 / 344 MiB for 1 / 2 / 4 / 8, same time
-#endif
-#ifndef MGS_RASTER_BWD_ORDER
-#define MGS_RASTER_BWD_ORDER 1         // launch the tiles by falling list length (tile_order_kernel): 623 -> 572 us
-#endif
+constexpr int kBwdMinWaves = 5;
+// One tile (wave) per workgroup: 2 / 4 measured slower (564 / 554 vs 537 us).
+constexpr int kBwdWgWaves = 1;
+// Segmented launch: consecutive units per XCD (see raster_bwd_kernel).  FETCH_SIZE 422 / 387 / 360 / 344 MiB for runs
+// of 1 / 2 / 4 / 8, same time.
+constexpr int kBwdXcdRun = 4;
+// (Half a tile per wave and an entry's reduction finished during the next entry: measured, not kept --
+//  profiles/r2/00_experiments.md sections 4 and 4b, profiles/r3/00_experiments.md section 7.)
 #ifdef MGS_RASTER_BWD_TIMING          // measurement build (scripts/dbg/bwd_timeline.py): per tile {start, end} on the 100 MHz clock, entries, pairs
 __device__ unsigned long long g_bwd_times[5 * 65536];   // per unit: enter, walk begins, end, entries, pairs
 #endif
@@ -217,7 +189,7 @@ __device__ __forceinline__ UnitTables unit_tables(const int32_t* base, int n_til
   return u;
 }
 
-template <int CHT, bool ABSGRAD, bool RECORDS, bool HALF = false, bool SPLIT = false>
+template <int CHT, bool ABSGRAD, bool RECORDS, bool SPLIT = false>
 __device__ __forceinline__ void raster_bwd_unit(const int unit,
     const float* __restrict__ means2d, const float* __restrict__ conics,
     const float* __restrict__ feats, const float* __restrict__ opacities,
@@ -235,13 +207,12 @@ __device__ __forceinline__ void raster_bwd_unit(const int unit,
   constexpr bool WIDE = ABSGRAD || !RECORDS;
   constexpr int NVR = 6 + CHT + (ABSGRAD ? 2 : 0);      // values reduced over the wave per list entry
   constexpr int kRedRows = !RECORDS ? 1 : (NVR > 8 && NVR <= 16) ? NVR : 8;
-  __shared__ BwdEntry<CHT, WIDE> queues[MGS_RASTER_BWD_WG_WAVES][kQueue];
-  __shared__ float reds[MGS_RASTER_BWD_WG_WAVES][kRedRows][64];  // wave-private transpose buffer of the record reduction
+  __shared__ BwdEntry<CHT, WIDE> queues[kBwdWgWaves][kQueue];
+  __shared__ float reds[kBwdWgWaves][kRedRows][64];  // wave-private transpose buffer of the record reduction
   BwdEntry<CHT, WIDE>* queue = queues[threadIdx.x >> 6];
   float (*red)[64] = reds[threadIdx.x >> 6];
-  static_assert(!HALF || RECORDS, "half tiles exist on the record path only");
-  static_assert(!SPLIT || (RECORDS && !HALF && CHT <= 4), "segments exist on the record path of up to 4 channels");
-  constexpr int NQ = HALF ? 2 : 4;                 // 8x8 blocks per wave
+  static_assert(!SPLIT || (RECORDS && CHT <= 4), "segments exist on the record path of up to 4 channels");
+  constexpr int NQ = 4;                            // 8x8 blocks per wave
 #ifdef MGS_RASTER_BWD_TIMING
   const unsigned long long t_enter = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -269,9 +240,8 @@ __device__ __forceinline__ void raster_bwd_unit(const int unit,
     seg_start = e.z;
     seg_hi = e.w;
   } else {
-    tile = HALF ? (unit >> 1 < n_tiles ? unit >> 1 : -1) : tile_of_unit(unit, n_tiles, tile_order);
+    tile = tile_of_unit(unit, n_tiles, tile_order);
   }
-  const int half = HALF ? unit & 1 : 0;
   if (tile < 0) return;
   const unsigned lane = threadIdx.x & 63u;
   const int tx = tile % tile_w, ty = tile / tile_w;
@@ -284,12 +254,12 @@ __device__ __forceinline__ void raster_bwd_unit(const int unit,
   // (also consumes `capacity` up here: a scalar load still outstanding at the head of the walk would turn every
   //  LDS wait inside it into a wait for everything -- scalar loads return out of order)
   if (RECORDS && capacity == 0u) return;
-  const int ix = tx * 16 + (int)(lane & 7), iy = ty * 16 + 8 * half + (int)(lane >> 3);
+  const int ix = tx * 16 + (int)(lane & 7), iy = ty * 16 + (int)(lane >> 3);
   // this lane's pixels as offsets from the tile centre, with their products (raster_common.h: PixelPoly)
   PixelPoly pq[NQ];
 #pragma unroll
   for (int k = 0; k < NQ; ++k)
-    pq[k] = pixel_poly((float)(lane & 7) - 7.5f + 8.f * (k & 1), (float)(8 * half + (int)(lane >> 3)) - 7.5f + 8.f * (k >> 1));
+    pq[k] = pixel_poly((float)(lane & 7) - 7.5f + 8.f * (k & 1), (float)(int)(lane >> 3) - 7.5f + 8.f * (k >> 1));
 
   BwdPixel<CHT> st[NQ];
   int hi = -1;
@@ -395,81 +365,36 @@ __device__ __forceinline__ void raster_bwd_unit(const int unit,
   const unsigned long long t_begin = __builtin_amdgcn_s_memrealtime();
   unsigned long long n_walked = 0, n_pairs = 0;
 #endif
-#ifdef MGS_RASTER_BWD_PRIO
-  {   // issue priority by the length of the walk (see raster_fwd.hip)
-    const int avg = tile_offsets[n_tiles] / n_tiles, len = hi - start + 1;
-    if (len > 2 * avg) __builtin_amdgcn_s_setprio(3);
-    else if (2 * len > 3 * avg) __builtin_amdgcn_s_setprio(2);
-    else if (len > avg) __builtin_amdgcn_s_setprio(1);
-  }
-#endif
 
   constexpr int NV = 6 + CHT + (ABSGRAD ? 2 : 0);      // values reduced over the wave per list entry
-  constexpr bool PIPE = RECORDS && MGS_RASTER_BWD_PIPE != 0 && NV > 8 && NV <= 16;
-  // QUAD (9..16 reduced values): FOUR lanes finish a value -- each adds a quarter of the value's row, two DPP steps, and
-  // the NV totals leave in one store instruction; the other form gives eight lanes a value and takes two groups of
-  // eight values side by side (the second group mostly idle at 10 values): 4 + 15 + 2 + 1 instead of 4 + 14 + 6 + 2
-  constexpr bool QUAD = MGS_RASTER_BWD_QUAD != 0 && NV > 8 && NV <= 16;
   constexpr int RSP = record_floats(CHT, ABSGRAD);     // floats per record (stride)
   // record position of value j: the values in the order they are reduced (padding channels hold zeros)
   auto rec_pos = [&](int j) { return j; };
-  // the two halves of the 9..16-value reduction (see below): read back the parked partial sums ...
+  // the 9..16-value reduction (see below): the lane's quarter of its value's row, 16-byte piece ((value & 3) ^ step) at
+  // each step: in every step the 16 lanes the LDS serves together -- four values x four quarters -- read 16 different
+  // columns of the 64 banks (rows are 256 bytes apart: all rows alias, only the column tells lanes apart) ...
   auto red_load = [&](float4& a0, float4& b0, float4& a1, float4& b1) {
-    if constexpr (QUAD) {
-      // the lane's quarter of its value's row, 16-byte piece ((value & 3) ^ step) at each step: in every step the 16
-      // lanes the LDS serves together -- four values x four quarters -- read 16 different columns of the 64 banks
-      // (rows are 256 bytes apart: all rows alias, only the column tells lanes apart)
-      const int qv = (int)(lane >> 2), x = qv & 3;
-      const float* q = &red[qv < NV ? qv : NV - 1][16 * (lane & 3)];
-      a0 = *reinterpret_cast<const float4*>(q + 4 * x);
-      b0 = *reinterpret_cast<const float4*>(q + 4 * (x ^ 1));
-      a1 = *reinterpret_cast<const float4*>(q + 4 * (x ^ 2));
-      b1 = *reinterpret_cast<const float4*>(q + 4 * (x ^ 3));
-      return;
-    }
-    const int v1 = 8 + (int)(lane >> 3);                          // second group's value for this lane
-    const float4* s0 = reinterpret_cast<const float4*>(&red[lane >> 3][(lane & 7) * 8]);
-    const float4* s1 = reinterpret_cast<const float4*>(&red[v1 < NV ? v1 : 8][(lane & 7) * 8]);
-    a0 = s0[0]; b0 = s0[1]; a1 = s1[0]; b1 = s1[1];
+    const int qv = (int)(lane >> 2), x = qv & 3;
+    const float* q = &red[qv < NV ? qv : NV - 1][16 * (lane & 3)];
+    a0 = *reinterpret_cast<const float4*>(q + 4 * x);
+    b0 = *reinterpret_cast<const float4*>(q + 4 * (x ^ 1));
+    a1 = *reinterpret_cast<const float4*>(q + 4 * (x ^ 2));
+    b1 = *reinterpret_cast<const float4*>(q + 4 * (x ^ 3));
   };
-  // ... and finish the sums and store the record
+  // ... then its sum, two DPP steps, and the record's NV words in one store
   auto red_finish = [&](size_t rslot, const float4& a0, const float4& b0, const float4& a1, const float4& b1) {
-    if constexpr (QUAD) {
-      float t = (((a0.x + a0.y) + (a0.z + a0.w)) + ((b0.x + b0.y) + (b0.z + b0.w))) +
-                (((a1.x + a1.y) + (a1.z + a1.w)) + ((b1.x + b1.y) + (b1.z + b1.w)));
-      // (as text, see below: the compiler sinks the last add into the storing lanes' branch and unfolds its DPP move)
-      asm volatile("s_nop 1\n\tv_add_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-                   "s_nop 1\n\tv_add_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf" : "+v"(t));
-      // (as text: the record's address is uniform + the lane's word, and the store takes the uniform part from an SGPR
-      //  pair -- the compiler formed a 64-bit address per lane with a quarter-rate v_mad_i64_i32 per pair)
-      const float* rec = records + rslot * RSP;
-      if ((lane & 3) == 0 && (int)(lane >> 2) < NV)                          // one store: NV consecutive words
-        asm volatile("global_store_dword %0, %1, %2" : : "v"((unsigned)(lane >> 2) * 4u), "v"(t), "s"(rec) : "memory");
-      if (lane == 0) flags[rslot] = 1;
-      return;
-    }
-    const int v1 = 8 + (int)(lane >> 3);
-    float t0 = ((a0.x + a0.y) + (a0.z + a0.w)) + ((b0.x + b0.y) + (b0.z + b0.w));
-    float t1 = ((a1.x + a1.y) + (a1.z + a1.w)) + ((b1.x + b1.y) + (b1.z + b1.w));
-    t0 += dpp_f(t0, kDppXor1);
-    t1 += dpp_f(t1, kDppXor1);
-    t0 += dpp_f(t0, kDppXor2);
-    t1 += dpp_f(t1, kDppXor2);
-    // (as text: the compiler sinks the last add into the storing lanes' branch and then cannot fold the DPP move into
-    //  it -- two v_mov 0, two v_mov_dpp and two adds instead of two v_add_f32_dpp)
-    asm volatile("s_nop 1\n\tv_add_f32_dpp %0, %0, %0 row_half_mirror row_mask:0xf bank_mask:0xf\n\t"
-                 "v_add_f32_dpp %1, %1, %1 row_half_mirror row_mask:0xf bank_mask:0xf" : "+v"(t0), "+v"(t1));
-    // (uniform record base + the lane's 32-bit position: the store takes the base from SGPRs instead of a 64-bit
-    //  address per lane kept across the walk)
-    float* rec = records + rslot * RSP;
-    if ((lane & 7) == 0) {
-      rec[lane >> 3] = t0;
-      if (v1 < NV) rec[(unsigned)v1] = t1;
-    }
+    float t = (((a0.x + a0.y) + (a0.z + a0.w)) + ((b0.x + b0.y) + (b0.z + b0.w))) +
+              (((a1.x + a1.y) + (a1.z + a1.w)) + ((b1.x + b1.y) + (b1.z + b1.w)));
+    // (as text: the compiler sinks the last add into the storing lanes' branch and then cannot fold the DPP move into it)
+    asm volatile("s_nop 1\n\tv_add_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+                 "s_nop 1\n\tv_add_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf" : "+v"(t));
+    // (as text: the record's address is uniform + the lane's word, and the store takes the uniform part from an SGPR
+    //  pair -- the compiler formed a 64-bit address per lane with a quarter-rate v_mad_i64_i32 per pair)
+    const float* rec = records + rslot * RSP;
+    if ((lane & 3) == 0 && (int)(lane >> 2) < NV)                          // one store: NV consecutive words
+      asm volatile("global_store_dword %0, %1, %2" : : "v"((unsigned)(lane >> 2) * 4u), "v"(t), "s"(rec) : "memory");
     if (lane == 0) flags[rslot] = 1;
   };
-  bool pend = false;            // PIPE: an entry's partial sums are parked in `red`, its record not yet stored
-  size_t pend_slot = 0;
 
   for (int q = (hi - start) / kQueue; q >= (lo - start) / kQueue; --q) {
     const int b = start + q * kQueue;
@@ -504,7 +429,6 @@ __device__ __forceinline__ void raster_bwd_unit(const int unit,
         op = opacities[g];
       }
       qmask = quadrant_mask(xy.x, xy.y, ca, cb, cc, op, tile_x, tile_y);
-      if (HALF) qmask = (qmask >> (2 * half)) & 3u;       // this half's two blocks
       qmask &= live;
     }
     const unsigned long long keep = ballot(qmask != 0u);
@@ -561,11 +485,6 @@ __device__ __forceinline__ void raster_bwd_unit(const int unit,
         if (4 * f + 2 < CHT) feat[4 * f + 2] = v.z;
         if (4 * f + 3 < CHT) feat[4 * f + 3] = v.w;
       }
-      float4 pa0, pb0, pa1, pb1;
-      if (PIPE) {     // unconditional (stale words when nothing is pending): a branch here would make the compiler
-        red_load(pa0, pb0, pa1, pb1);         // wait for these loads together with the entry's own at the join
-        asm volatile("" ::: "memory");        // keep the read-back up here, ahead of the evaluation
-      }
       const unsigned m = __builtin_amdgcn_readfirstlane(__float_as_uint(g1.z));
       const int gi = __float_as_int(g1.w);
       const int gid = __builtin_amdgcn_readfirstlane(__float_as_int(g2.x));
@@ -580,16 +499,12 @@ __device__ __forceinline__ void raster_bwd_unit(const int unit,
           grad_pixel<CHT, ABSGRAD, SAFE>(st[k], gg, pq[k], g2.y, g2.z, g3.x, g3.y, g3.z, g0.w, g1.x, g1.y,
                                          g0.x, g0.y, g0.z, feat, gi, any);
       }
-      if (PIPE && pend) {
-        red_finish(pend_slot, pa0, pb0, pa1, pb1);
-        pend = false;
-      }
       if (!any) continue;          // (uniform: no lane of any quadrant took the Gaussian -- nothing to reduce)
       if constexpr (RECORDS) {
         // overflowed tile lists (status word set by the binning): slot bases run up to the true
         // n_isect, the workspace only to the capacity -- nothing is written past it
         if ((uint32_t)gid >= capacity) continue;
-        const size_t rslot = HALF ? 2 * (size_t)gid + half : (size_t)gid;
+        const size_t rslot = (size_t)gid;
         // reduce-scatter butterfly: 8 values at a time, totals land in 8 lanes that store the
         // record slice with one instruction
         float vals[NV];
@@ -601,32 +516,27 @@ __device__ __forceinline__ void raster_bwd_unit(const int unit,
         for (int c = 0; c < CHT; ++c) vals[6 + c] = gg.v_f[c];
         if constexpr (ABSGRAD) { vals[6 + CHT] = gg.a_x; vals[7 + CHT] = gg.a_y; }
         int done = 0;
-        // Through LDS, eight values per group: every lane parks its partial sums lane-linear
-        // (red[i][lane], conflict-free), lane L then reads the eight partials red[L >> 3][8 (L & 7) ..]
-        // with two ds_read_b128, adds them, and three DPP steps finish the sum over the eight lanes
-        // that share a value: 10 VALU per eight values against 26 for the all-DPP butterfly (LDS
-        // instructions of one wave execute in order, so the wave-private buffer needs no barrier
-        // beyond the compiler fences).  Up to 16 values (every case up to 8 channels) go in ONE round
-        // trip: all values are parked at once and each lane finishes two groups side by side -- the
-        // tail values used to take a DPP chain plus two ds_bpermute round trips per list entry.
+        // Through LDS: every lane parks its partial sums lane-linear (red[i][lane], conflict-free), then the lanes that
+        // share a value read its row back and finish the sum with DPP steps (LDS instructions of one wave execute in
+        // order, so the wave-private buffer needs no barrier beyond the compiler fences).
+        // 9..16 values (every case up to 8 channels) in ONE round trip: FOUR lanes finish a value -- each adds a quarter
+        // of the value's row, two DPP steps -- and the NV totals leave in one store instruction (eight lanes per value,
+        // two groups side by side, took 4 + 14 + 6 + 2 instructions against 4 + 15 + 2 + 1).
         if constexpr (NV > 8 && NV <= 16) {
 #pragma unroll
           for (int i = 0; i < NV; ++i) red[i][lane] = vals[i];
           __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
           __builtin_amdgcn_wave_barrier();
           __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-          if constexpr (PIPE) {
-            pend = true;                            // finished during the next entry (or after the walk)
-            pend_slot = rslot;
-            continue;
-          } else {
-            float4 a0, b0, a1, b1;
-            red_load(a0, b0, a1, b1);
-            red_finish(rslot, a0, b0, a1, b1);
-            __builtin_amdgcn_wave_barrier();        // the next entry overwrites red
-            continue;
-          }
+          float4 a0, b0, a1, b1;
+          red_load(a0, b0, a1, b1);
+          red_finish(rslot, a0, b0, a1, b1);
+          __builtin_amdgcn_wave_barrier();        // the next entry overwrites red
+          continue;
         }
+        // Up to 8 values: eight per group, lane L reads the eight partials red[L >> 3][8 (L & 7) ..] with two
+        // ds_read_b128, adds them, and three DPP steps finish the sum over the eight lanes that share a value: 10 VALU
+        // per eight values against 26 for the all-DPP butterfly.
         while (NV - done >= 8) {
 #pragma unroll
           for (int i = 0; i < 8; ++i) red[i][lane] = vals[done + i];
@@ -693,17 +603,8 @@ __device__ __forceinline__ void raster_bwd_unit(const int unit,
       }
     }
     };
-#ifdef MGS_RASTER_BWD_NO_SAFE     // measurement: every batch through the general form
-    walk(std::false_type{});
-#else
     if (all_safe) walk(std::true_type{}); else walk(std::false_type{});
-#endif
     __builtin_amdgcn_wave_barrier();
-  }
-  if (PIPE && pend) {
-    float4 a0, b0, a1, b1;
-    red_load(a0, b0, a1, b1);
-    red_finish(pend_slot, a0, b0, a1, b1);
   }
 #ifdef MGS_RASTER_BWD_TIMING
   if (lane == 0 && unit < 65536) {
@@ -716,8 +617,8 @@ __device__ __forceinline__ void raster_bwd_unit(const int unit,
 #endif
 }
 
-template <int CHT, bool ABSGRAD, bool RECORDS, bool HALF = false, bool SPLIT = false>
-__global__ __launch_bounds__(64 * MGS_RASTER_BWD_WG_WAVES, (CHT <= 4 && RECORDS && !ABSGRAD && !HALF) ? MGS_RASTER_BWD_MIN_WAVES : 1) void raster_bwd_kernel(
+template <int CHT, bool ABSGRAD, bool RECORDS, bool SPLIT = false>
+__global__ __launch_bounds__(64 * kBwdWgWaves, (CHT <= 4 && RECORDS && !ABSGRAD) ? kBwdMinWaves : 1) void raster_bwd_kernel(
     const float* __restrict__ means2d, const float* __restrict__ conics,
     const float* __restrict__ feats, const float* __restrict__ opacities,
     const float4* __restrict__ splats, const float* __restrict__ background, int channels,
@@ -734,16 +635,16 @@ __global__ __launch_bounds__(64 * MGS_RASTER_BWD_WG_WAVES, (CHT <= 4 && RECORDS 
 #define MGS_RB_ARGS means2d, conics, feats, opacities, splats, background, channels, width, height, tile_w, n_tiles, \
     tile_offsets, flatten_ids, alphas, last_ids, v_render, v_alphas, v_means2d, v_means2d_abs, v_conics, v_feats,    \
     v_opacities, pair_info, records, flags, capacity, expected_render, tile_order, ckpt, ckpt_shift, seg_table, render_out, splat_slots
-  int unit = blockIdx.x * MGS_RASTER_BWD_WG_WAVES + (int)(threadIdx.x >> 6);
-  if constexpr (SPLIT && MGS_RASTER_BWD_XCD_RUN > 1 && MGS_RASTER_BWD_WG_WAVES == 1) {
+  int unit = blockIdx.x * kBwdWgWaves + (int)(threadIdx.x >> 6);
+  if constexpr (SPLIT && kBwdXcdRun > 1 && kBwdWgWaves == 1) {
     // a tile's whole segments are neighbours in the unit table and re-read the same 10 KB of frame state; workgroup b
     // runs on XCD b % 8 (observed placement, speed only), so runs of R consecutive units go to one XCD's L2:
     // blocks of 8 R workgroups, unit = block + (b % 8) R + (b / 8) % R -- the launch order is kept to within a block
-    constexpr int R = MGS_RASTER_BWD_XCD_RUN;
+    constexpr int R = kBwdXcdRun;
     const int b = unit, in = b % (8 * R);
     unit = b - in + (in & 7) * R + (in >> 3);
   }
-  raster_bwd_unit<CHT, ABSGRAD, RECORDS, HALF, SPLIT>(unit, MGS_RB_ARGS);
+  raster_bwd_unit<CHT, ABSGRAD, RECORDS, SPLIT>(unit, MGS_RB_ARGS);
 #undef MGS_RB_ARGS
 }
 
@@ -757,13 +658,7 @@ __global__ __launch_bounds__(64 * MGS_RASTER_BWD_WG_WAVES, (CHT <= 4 && RECORDS 
 // waves that take them one at a time -- lanes = rows, the rows then added in row order by NV lanes -- and its other waves
 // skip them.  The order of the additions is the one of the rows kernel (within a row by column, then the rows): the same
 // bits.
-#ifndef MGS_REDUCE_BIG
-#define MGS_REDUCE_BIG 256
-#endif
-#ifndef MGS_REDUCE_BIG_WGS
-#define MGS_REDUCE_BIG_WGS 1024
-#endif
-constexpr int kBigPairs = MGS_REDUCE_BIG, kBigLists = 64, kBigWGs = MGS_REDUCE_BIG_WGS, kDiscoverPerThread = 16;
+constexpr int kBigPairs = 256, kBigLists = 64, kBigWGs = 1024, kDiscoverPerThread = 16;
 __host__ __device__ inline uint32_t big_list_room(uint32_t capacity) { return capacity / (uint32_t)kBigPairs + 1u; }
 __host__ __device__ inline size_t big_lists_bytes(uint32_t capacity) { return (size_t)kBigLists * big_list_room(capacity) * sizeof(uint32_t); }
 
@@ -867,10 +762,7 @@ __global__ __launch_bounds__(256) void big_discover_kernel(int n, const int4* __
 // hence m = mean - tile centre (the very expression the raster kernel queued), moments_to_mean the pair's sums about the
 // mean; those add up over the pairs, then the conic is applied once (finish_geo) and -sum s / opacity is the opacity's
 // gradient.
-#ifndef MGS_REDUCE_EXP
-#define MGS_REDUCE_EXP 0
-#endif
-template <int CHT, bool ABSGRAD, int SLOTS = 1>      // SLOTS: record slots per (tile, Gaussian) pair (2: half tiles)
+template <int CHT, bool ABSGRAD>
 __global__ __launch_bounds__(256) void reduce_records_kernel(
     int n, const int4* __restrict__ pair_info, const float* __restrict__ records,
     const uint8_t* __restrict__ flags, uint32_t capacity, const float* __restrict__ means2d,
@@ -883,8 +775,8 @@ __global__ __launch_bounds__(256) void reduce_records_kernel(
   const int4 info = pair_info[g];
   const int rect_w = info.w & 0xffff;
   const int npair = rect_w * ((unsigned)info.w >> 16);
-  const int cnt = npair * SLOTS;
-  const size_t first = (size_t)info.x * SLOTS;
+  const int cnt = npair;
+  const size_t first = (size_t)info.x;
   constexpr int RSP = record_floats(CHT, ABSGRAD), R4 = RSP / 4;
   const float4* rec4 = reinterpret_cast<const float4*>(records);
   float acc[6], af[CHT], ab[2] = {0.f, 0.f};
@@ -911,30 +803,22 @@ __global__ __launch_bounds__(256) void reduce_records_kernel(
   // the Gaussian's range (a group's slots outside the range are skipped), not four byte loads whose 64 lanes each
   // touch a different place -- the kernel is bound by the number of such scattered loads (round-3 ablation: 34 of its
   // 65 us remained with the record loads removed).
-  int col = 0, row = 0;                // the pair's tile inside the rectangle (slots are row-major, SLOTS per pair)
+  int col = 0, row = 0;                // the pair's tile inside the rectangle (slots are row-major)
   const int lead = (int)(first & 3);   // slots of the first group that belong to the previous Gaussian
   for (int sl = -lead; sl < cnt; sl += 4) {
     bool on[4];
-#if MGS_REDUCE_EXP == 2      // measurement: no flag loads (every slot read)
-    const uint32_t fw = 0x01010101u;
-#else
     // (first + sl) is a multiple of 4; groups past the capacity (overflowed lists) lie outside the workspace
-    const uint32_t fw = first + sl < (size_t)capacity * SLOTS ? *reinterpret_cast<const uint32_t*>(flags + (first + sl)) : 0u;
-#endif
+    const uint32_t fw = first + sl < (size_t)capacity ? *reinterpret_cast<const uint32_t*>(flags + (first + sl)) : 0u;
 #pragma unroll
     for (int i = 0; i < 4; ++i)      // slots at or past the capacity do not exist (overflowed lists)
-      on[i] = sl + i >= 0 && sl + i < cnt && (uint32_t)(info.x + (sl + i) / SLOTS) < capacity && ((fw >> (8 * i)) & 0xffu) != 0;
+      on[i] = sl + i >= 0 && sl + i < cnt && (uint32_t)(info.x + (sl + i)) < capacity && ((fw >> (8 * i)) & 0xffu) != 0;
     float r[4][RSP];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const size_t slot = first + sl + i;
 #pragma unroll
       for (int k = 0; k < R4; ++k) {
-#if MGS_REDUCE_EXP == 1      // measurement: no record loads
-        const float4 v = make_float4(on[i] ? 1.f : 0.f, 0.f, 0.f, 0.f);
-#else
         const float4 v = on[i] ? rec4[slot * R4 + k] : make_float4(0.f, 0.f, 0.f, 0.f);
-#endif
         r[i][4 * k] = v.x; r[i][4 * k + 1] = v.y; r[i][4 * k + 2] = v.z; r[i][4 * k + 3] = v.w;
       }
     }
@@ -948,17 +832,13 @@ __global__ __launch_bounds__(256) void reduce_records_kernel(
 #pragma unroll
       for (int c = 0; c < CHT; ++c) af[c] += r[i][6 + c];
       if constexpr (ABSGRAD) { ab[0] += r[i][6 + CHT]; ab[1] += r[i][7 + CHT]; }
-      if (sl + i >= 0 && (SLOTS == 1 || ((sl + i) % SLOTS) == SLOTS - 1))
-        if (++col == rect_w) { col = 0; ++row; }
+      if (sl + i >= 0 && ++col == rect_w) { col = 0; ++row; }
     }
   }
   if (cnt > 0) {   // apply the Gaussian's conic once, here; opacity * d/d opacity = -sum v_sigma
     finish_geo(ca, cb, cc, acc[0], acc[1], acc[2], acc[4]);
     acc[5] = op > 0.f ? -acc[5] / op : 0.f;     // (an opacity of exactly 0 owns slots under classic tile bounds: s is 0 there, not 0 / 0)
   }
-#if MGS_REDUCE_EXP == 3      // measurement: (nearly) no stores
-  if (acc[0] != 12345.f) return;
-#endif
   reinterpret_cast<float2*>(v_means2d)[g] = make_float2(acc[0], acc[1]);
   v_conics[3 * (size_t)g + 0] = acc[2];
   v_conics[3 * (size_t)g + 1] = acc[3];
@@ -971,16 +851,6 @@ __global__ __launch_bounds__(256) void reduce_records_kernel(
 }
 
 
-#ifndef MGS_REDUCE_TRIP
-#define MGS_REDUCE_TRIP 4       // slots of a row fetched together (reduce_records_rows_kernel)
-#endif
-#ifndef MGS_REDUCE_RUN
-#define MGS_REDUCE_RUN 16       // reduce_records_rows_kernel: consecutive Gaussians per run of a wave (four runs; 0: 64 consecutive)
-#endif
-#ifndef MGS_REDUCE_ROWS
-// 1: reduce_records_rows_kernel (below) for up to 4 channels and one slot per pair; 0: reduce_records_kernel everywhere
-#define MGS_REDUCE_ROWS 1
-#endif
 // The same sums with the ROWS of the tile rectangles as the units of work.  reduce_records_kernel gives every lane one
 // Gaussian and lets it walk all its slots: a wave takes as long as its largest rectangle (25 trips of four slots where
 // the average lane needs 1-2), one dependent round trip after another -- 14 SIMD-cycles per vector instruction, pure
@@ -1011,7 +881,7 @@ __global__ __launch_bounds__(256) void reduce_records_rows_kernel(
     const int ow = oi.w & 0xffff;
     const uint32_t slot0 = (uint32_t)oi.x + (uint32_t)(r * ow);
     const float my = om.y - ((float)((oi.z + r) * 16) + 8.f);     // m exactly as the raster kernel formed it
-    constexpr int TR = MGS_REDUCE_TRIP;
+    constexpr int TR = 4;                             // slots of a row fetched together
     // the flags of a trip out of the two aligned words that hold them (slots at or past the capacity -- overflowed lists --
     // do not exist and lie outside the workspace); fetched one trip AHEAD: a trip is then one round trip (its records)
     // instead of two dependent ones -- a 120-tile row of a screen-filling Gaussian is 30 trips
@@ -1116,22 +986,18 @@ __global__ __launch_bounds__(256) void reduce_records_rows_kernel(
     return;
   }
   const int block = (int)blockIdx.x - kBigWGs, n_blocks = (int)gridDim.x - kBigWGs;
-  // Which 64 Gaussians a wave owns: four RUNS of MGS_REDUCE_RUN consecutive ones, a whole launch of waves apart (run r
+  // Which 64 Gaussians a wave owns: four RUNS of kRun consecutive ones, a whole launch of waves apart (run r
   // of wave W is run r * n_waves + W of the index space) instead of 64 consecutive.  Large rectangles that sit together
   // in the index range -- appended by a densifier, neighbours in a Morton order -- then land in many waves, each with a
   // few, instead of a few waves with 64 each (a wave's time is its row tasks; profiles/r5/00_experiments.md 18, 22).
   // A run still reads whole lines of pair_info and writes whole sectors of the outputs.  Training step, ms (runs of
   // 64 = consecutive / 32 / 16 / 8): configs[2] as given 0.823 / 0.823 / 0.824 / 0.827, in Morton order 0.786 / 0.780 /
   // 0.779 / 0.777; a clustered scene as given 1.526 / 1.460 / 1.397 / 1.376, in Morton order 1.082 / 1.056 / 1.002 / 0.998.
-#if MGS_REDUCE_RUN > 0
-  constexpr int kRun = MGS_REDUCE_RUN, kRunsPerWave = 64 / kRun;
+  constexpr int kRun = 16, kRunsPerWave = 64 / kRun;
   const int wave_global = block * 4 + wv, n_waves = n_blocks * 4;
   const long long g_ll = ((long long)(lane / kRun) * n_waves + wave_global) * kRun + lane % kRun;
   const int g = g_ll < n ? (int)g_ll : n;
   static_assert(64 % kRun == 0 && kRunsPerWave >= 1, "runs of a power of two up to 64");
-#else
-  const int g = block * 256 + (int)threadIdx.x;
-#endif
   int4 info = make_int4(0, 0, 0, 0);
   int h = 0;
   bool is_big = false;
@@ -1246,7 +1112,7 @@ extern "C" int mgs_rasterize_bwd(int n, const float* means2d, const float* conic
   const int n_tiles = tile_w * tile_h;
   hipStream_t s = (hipStream_t)stream;
 #define MGS_RB_LAUNCH(C, A)                                                                    \
-  hipLaunchKernelGGL((raster_bwd_kernel<C, A, false>), dim3(div_up(n_tiles, MGS_RASTER_BWD_WG_WAVES)), dim3(64 * MGS_RASTER_BWD_WG_WAVES), 0, s, means2d,  \
+  hipLaunchKernelGGL((raster_bwd_kernel<C, A, false>), dim3(div_up(n_tiles, kBwdWgWaves)), dim3(64 * kBwdWgWaves), 0, s, means2d,  \
                      conics, feats, opacities, (const float4*)nullptr, background, channels,   \
                      width, height, tile_w,                                                    \
                      n_tiles, tile_offsets, flatten_ids, alphas, last_ids, v_render, v_alphas, \
@@ -1288,13 +1154,11 @@ extern "C" int mgs_rasterize_bwd_det(int n, const float* means2d, const float* c
   MGS_REQUIRE(workspace_bytes, "rasterize_bwd_det: workspace_bytes is null");
   const int rs = record_floats(padded_channels(channels), v_means2d_abs != nullptr);   // floats per record
   const size_t cap = isect_capacity ? isect_capacity : 1;
-  constexpr bool kHalf = MGS_RASTER_BWD_HALF != 0;
-  constexpr size_t kSlots = kHalf ? 2 : 1;
-  const size_t rec_bytes = align_up(cap * kSlots * rs * sizeof(float), 256);
-  const size_t flag_bytes = align_up(cap * kSlots, 256);
+  const size_t rec_bytes = align_up(cap * rs * sizeof(float), 256);
+  const size_t flag_bytes = align_up(cap, 256);
   // segmented walk (checkpoints from mgs_rasterize_fwd): up to 4 channels, whole tiles
   int ckpt_shift = 0;
-  const bool split = checkpoints != nullptr && channels <= 4 && !kHalf;
+  const bool split = checkpoints != nullptr && channels <= 4;
   if (checkpoints) {
     MGS_REQUIRE(checkpoint_interval >= 64 && (checkpoint_interval & (checkpoint_interval - 1)) == 0,
                 "rasterize_bwd_det: checkpoint_interval %d is not a power of two >= 64", checkpoint_interval);
@@ -1311,7 +1175,7 @@ extern "C" int mgs_rasterize_bwd_det(int n, const float* means2d, const float* c
   // them), the items at the end
   constexpr size_t big_hdr = 256;
   static_assert(kBigLists * sizeof(uint32_t) <= big_hdr, "the big lists' counters fit their header");
-  const bool big_path = MGS_REDUCE_ROWS && channels <= 4 && kSlots == 1;
+  const bool big_path = channels <= 4;
   const size_t big_bytes = big_path ? align_up(big_lists_bytes((uint32_t)cap), 256) : 0;
   const size_t need = rec_bytes + flag_bytes + big_hdr + order_bytes + big_bytes;
   if (!workspace) {
@@ -1350,7 +1214,7 @@ extern "C" int mgs_rasterize_bwd_det(int n, const float* means2d, const float* c
     const unsigned n_disc = big_path && !records_only ? div_up(n, 256 * kDiscoverPerThread) : 0;
     hipLaunchKernelGGL(unit_table_kernel, dim3(div_up(n_tiles, 256) + n_disc), dim3(256), 0, s, n_tiles, tile_offsets,
                        reinterpret_cast<const int32_t*>(checkpoints), ckpt_shift, (uint32_t)cap, seg_table, n, info, big_counts, big_items);
-  } else if (!kHalf && MGS_RASTER_BWD_ORDER) {
+  } else {
     order = tile_group_order;
     if (!order) {       // the caller's lists came without one (mgs_isect_tiles writes it): compute it here
       int32_t* mine = reinterpret_cast<int32_t*>(static_cast<uint8_t*>(workspace) + rec_bytes + flag_bytes + big_hdr);
@@ -1362,10 +1226,10 @@ extern "C" int mgs_rasterize_bwd_det(int n, const float* means2d, const float* c
   if (!split && big_path && !records_only)
     hipLaunchKernelGGL(big_discover_kernel, dim3(div_up(n, 256 * kDiscoverPerThread)), dim3(256), 0, s, n, info, (uint32_t)cap, big_counts, big_items);
   // (segmented: whole blocks of the XCD-aware unit numbering; units past the live count leave at once)
-  const int n_units = split ? (int)((n_seg_units + 8 * MGS_RASTER_BWD_XCD_RUN - 1) / (8 * MGS_RASTER_BWD_XCD_RUN)) * 8 * MGS_RASTER_BWD_XCD_RUN
-                            : order ? (n_tiles + 3) / 4 * 4 : n_tiles * (int)kSlots;
+  const int n_units = split ? (int)((n_seg_units + 8 * kBwdXcdRun - 1) / (8 * kBwdXcdRun)) * 8 * kBwdXcdRun
+                            : order ? (n_tiles + 3) / 4 * 4 : n_tiles;
 #define MGS_RD_RASTER(C, A, SP)                                                                 \
-  hipLaunchKernelGGL((raster_bwd_kernel<C, A, true, kHalf, SP>), dim3(div_up(n_units, MGS_RASTER_BWD_WG_WAVES)), dim3(64 * MGS_RASTER_BWD_WG_WAVES), MGS_RASTER_BWD_LDS_PAD, s, means2d,   \
+  hipLaunchKernelGGL((raster_bwd_kernel<C, A, true, SP>), dim3(div_up(n_units, kBwdWgWaves)), dim3(64 * kBwdWgWaves), 0, s, means2d, \
                      conics, feats, opacities, reinterpret_cast<const float4*>(splats),        \
                      background, channels, width, height, tile_w,                              \
                      n_tiles, tile_offsets, flatten_ids, alphas, last_ids, v_render, v_alphas, \
@@ -1373,15 +1237,15 @@ extern "C" int mgs_rasterize_bwd_det(int n, const float* means2d, const float* c
                      (float*)nullptr, info, records, flags, (uint32_t)cap, expected_render,    \
                      (const int32_t*)order, checkpoints, ckpt_shift, (const int32_t*)seg_table, render_out, splat_slots)
 #define MGS_RD_LAUNCH(C, A)                                                                     \
-  if (split) MGS_RD_RASTER(C, A, ((C) <= 4 && !kHalf)); else MGS_RD_RASTER(C, A, false);        \
+  if (split) MGS_RD_RASTER(C, A, ((C) <= 4)); else MGS_RD_RASTER(C, A, false);                  \
   if (!records_only) {                                                                          \
-    if constexpr (MGS_REDUCE_ROWS && (C) <= 4 && kSlots == 1)                                   \
+    if constexpr ((C) <= 4)                                                                     \
       hipLaunchKernelGGL((reduce_records_rows_kernel<((C) <= 4 ? (C) : 4), A>), dim3(kBigWGs + div_up(n, 256)), dim3(256), 0, s, n, \
                          info, records, flags, (uint32_t)cap, means2d, conics, opacities,      \
                          reinterpret_cast<const float4*>(splats),                              \
                          channels, v_means2d, v_means2d_abs, v_conics, v_feats, v_opacities, big_counts, big_items);  \
     else                                                                                        \
-      hipLaunchKernelGGL((reduce_records_kernel<C, A, (int)kSlots>), dim3(div_up(n, 256)), dim3(256), 0, s, n,   \
+      hipLaunchKernelGGL((reduce_records_kernel<C, A>), dim3(div_up(n, 256)), dim3(256), 0, s, n,  \
                          info, records, flags, (uint32_t)cap, means2d, conics, opacities,      \
                          reinterpret_cast<const float4*>(splats),                              \
                          channels, v_means2d, v_means2d_abs, v_conics, v_feats, v_opacities); }

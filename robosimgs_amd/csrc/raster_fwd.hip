@@ -13,35 +13,20 @@
 #include "tile_order.h"
 #include "dataset_pixel.h"
 
-#ifndef MGS_RASTER_WAVES
+namespace mgs {
+namespace {
+
 // min waves per SIMD asked of the register allocator (one-wave-per-tile kernel).  5 = at most 96 VGPRs: with the
 // hand-written blend body the 4-channel kernels sat at 106-107 registers (4 waves) -- at 5 the same box renders
 // 3,818 instead of 3,674 frames/s with three frames in flight (189.5 vs 191.6 us alone); 6 (80 VGPRs) spills: 3,571
-#define MGS_RASTER_WAVES 5
-#endif
-#ifndef MGS_RASTER_PIPE
-// 1: the one-wave-per-tile kernel reads queue entry j + 1 from LDS while it blends entry j (two register sets in turn).
-// PMC has the waves parked on s_waitcnt for 39 % of their cycles, but both forms of the prefetch lose: 249 us (copies
-// between the sets) / 214 us (ping-pong) against 188 us -- 30 more dwords spilled around the cull at the 96-register
-// bound, and the read-ahead does not shorten the entry's own dependency chain.  Off.
-#define MGS_RASTER_PIPE 0
-#endif
-#ifndef MGS_RASTER_NO_PREFETCH
-#define MGS_RASTER_NO_PREFETCH 1     // 1: the one-wave-per-tile kernel fetches a batch when it needs it instead of one batch ahead (ten
-                                     // registers live across the walk less): 188.2 -> 186.2 us alone, 3,819 -> 3,866 frames/s; 0 = prefetch
-#endif
-#ifndef MGS_RASTER_WG_WAVES
+constexpr int kFwdMinWaves = 5;
 // Independent tiles (waves) per workgroup of the INFERENCE variant; no workgroup barrier is ever
 // used.  One-wave workgroups grab every wave slot the moment it frees up and starve the 4-wave
 // workgroups of the other frames' binning kernels, which need four slots on one CU at once; with
 // 4 tiles per workgroup the frames in flight interleave better: 2873 -> 2956 frames/s (8 / 16
 // tiles: 2858 / 2832, load imbalance).  A lone launch is 3 % slower that way (the workgroup lives
 // as long as its heaviest tile), so the training variant, which runs alone, keeps one tile.
-#define MGS_RASTER_WG_WAVES 4
-#endif
-
-namespace mgs {
-namespace {
+constexpr int kFwdWgWaves = 4;
 
 template <int CHT>
 struct QueueEntry {
@@ -120,72 +105,10 @@ __device__ __forceinline__ void blend_pixel(PixelState<CHT>& px, unsigned long l
 #endif
 }
 
-#ifndef MGS_RASTER_CMPX
-#define MGS_RASTER_CMPX 1
-#endif
-#ifndef MGS_RASTER_MASKS
-#define MGS_RASTER_MASKS 1          // 0: the sign of T is the "finished" flag in every kernel (measurement)
-#endif
-#ifndef MGS_RASTER_Q_BREAK
-#define MGS_RASTER_Q_BREAK 0        // one wave per 8x8 block: leave the batch at the entry that closes the block's last pixel
-#endif
-#ifndef MGS_RASTER_CLOSE_BRANCH
-// 1: the lane-mask bookkeeping of a pixel that closes (s_andn2 / s_cselect / s_and) sits behind a scalar branch on "some
-// pixel closed" -- nearly always skipped: 4 instead of 6 scalar instructions per quadrant body
-#define MGS_RASTER_CLOSE_BRANCH 0
-#endif
-#ifndef MGS_RASTER_LIVE_BITS
-#define MGS_RASTER_LIVE_BITS 1      // one wave per tile: a quadrant whose last pixel closes is skipped for the rest of the batch
-#endif
-// Measurement only (MGS_RASTER_MASKS=0, profiles/r3/00_experiments.md): the SAFE body with the sign of T as the
-// "finished" flag -- 16 vector instructions, two of them selects, no scalar bookkeeping.
-template <int CHT, bool TRACK_LAST>
-__device__ __forceinline__ void blend_pixel_safe_asm_sign(PixelState<CHT>& px, const PixelPoly& pp, float q0, float q1,
-                                                     float q2, float A, float B, float C, const float* feat, int idx) {
-  static_assert(CHT == 3 || CHT == 4, "hand-written blend: 3 or 4 channels");
-  float dx, t0, t1;               // dx: the weight w, t0: T (1 - alpha), t1: exponent, then alpha
-  const float amin = kAlphaMin, tstop = kTStop;
-  float c3 = CHT == 4 ? px.C[CHT - 1] : 0.f;
-  const float f3 = CHT == 4 ? feat[CHT - 1] : 0.f;
-  asm volatile(
-      "v_fma_f32 %[t1], %[q1], %[x], %[q0]\n"          // pair_power_poly, same order
-      "v_fmac_f32 %[t1], %[q2], %[y]\n"
-      "v_fmac_f32 %[t1], %[A], %[xx]\n"
-      "v_fmac_f32 %[t1], %[B], %[xy]\n"
-      "v_fmac_f32 %[t1], %[C], %[yy]\n"
-      "v_exp_f32 %[t1], %[t1]\n"
-      "s_nop 0\n"
-      "v_cmpx_le_f32 vcc, %[amin], %[t1]\n"
-      "v_fma_f32 %[t0], -%[t1], %[T], %[T]\n"
-      "v_mul_f32 %[dx], %[t1], %[T]\n"
-      "v_cmp_lt_f32 vcc, %[tstop], %[t0]\n"
-      "s_nop 1\n"
-      "v_cndmask_b32 %[dx], 0, %[dx], vcc\n"
-      "v_cndmask_b32_e64 %[T], -|%[T]|, %[t0], vcc\n"
-      "v_fmac_f32 %[c0], %[dx], %[f0]\n"
-      "v_fmac_f32 %[c1], %[dx], %[f1]\n"
-      "v_fmac_f32 %[c2], %[dx], %[f2]\n"
-      ".if %[four]\n"
-      "v_fmac_f32 %[c3], %[dx], %[f3]\n"
-      ".endif\n"
-      ".if %[track]\n"
-      "v_cndmask_b32 %[last], %[last], %[idx], vcc\n"     // EXEC = valid lanes, VCC = accumulated
-      ".endif\n"
-      "s_mov_b64 exec, -1\n"
-      : [dx] "=&v"(dx), [t0] "=&v"(t0), [t1] "=&v"(t1),
-        [T] "+v"(px.T), [c0] "+v"(px.C[0]), [c1] "+v"(px.C[1]), [c2] "+v"(px.C[2]), [c3] "+v"(c3), [last] "+v"(px.last)
-      : [q0] "v"(q0), [q1] "v"(q1), [q2] "v"(q2), [x] "v"(pp.x), [y] "v"(pp.y), [xx] "v"(pp.xx), [xy] "v"(pp.xy),
-        [yy] "v"(pp.yy), [A] "v"(A), [B] "v"(B), [C] "v"(C),
-        [f0] "v"(feat[0]), [f1] "v"(feat[1]), [f2] "v"(feat[2]), [f3] "v"(f3), [amin] "s"(amin), [tstop] "s"(tstop),
-        [four] "n"(CHT == 4 ? 1 : 0), [track] "n"(TRACK_LAST ? 1 : 0), [idx] "v"(idx)
-      : "vcc");
-  if (CHT == 4) px.C[CHT - 1] = c3;
-}
-
 // Kernels of 3 and 4 channels keep "finished" in lane masks (PixelState above) and run the SAFE blend as the
 // hand-written body below.
 template <int CHT>
-constexpr bool kMasks = MGS_RASTER_MASKS != 0 && MGS_RASTER_CMPX != 0 && (CHT == 3 || CHT == 4);
+constexpr bool kMasks = CHT == 3 || CHT == 4;
 
 // The SAFE blend (3 or 4 channels; inference and, with one more move for last_ids, training) as hand-written gfx950
 // code: the same arithmetic in the same order as blend_pixel<CHT, ., true> -- bit-identical pixels -- under an EXEC that
@@ -233,15 +156,11 @@ __device__ __forceinline__ void blend_pixel_safe_asm(PixelState<CHT>& px, unsign
       "v_mov_b32 %[last], %[idx]\n"
       ".endif\n"
       "s_xor_b64 vcc, vcc, %[acc]\n"                   // counted but not accumulated: the pixels this Gaussian closes
-      ".if %[closebranch]\n"                           // (SCC = some pixel closes: rare -- the bookkeeping sits behind a branch)
-      "s_cbranch_scc0 1f\n"
-      ".endif\n"
       "s_andn2_b64 %[alive], %[alive], vcc\n"          // (SCC = some pixel of the quadrant is still open)
       ".if %[livebit] >= 0\n"
       "s_cselect_b32 vcc_lo, -1, %[clr]\n"
       "s_and_b32 %[live], %[live], vcc_lo\n"
       ".endif\n"
-      "1:\n"
       "s_mov_b64 exec, -1\n"
       : [dx] "=&v"(dx), [t0] "=&v"(t0), [t1] "=&v"(t1), [acc] "=&s"(acc), [alive] "+s"(alive), [live] "+s"(live),
         [T] "+v"(px.T), [c0] "+v"(px.C[0]), [c1] "+v"(px.C[1]), [c2] "+v"(px.C[2]), [c3] "+v"(c3), [last] "+v"(px.last)
@@ -249,7 +168,7 @@ __device__ __forceinline__ void blend_pixel_safe_asm(PixelState<CHT>& px, unsign
         [yy] "v"(pp.yy), [A] "v"(A), [B] "v"(B), [C] "v"(C),
         [f0] "v"(feat[0]), [f1] "v"(feat[1]), [f2] "v"(feat[2]), [f3] "v"(f3), [amin] "s"(amin), [tstop] "s"(tstop),
         [four] "n"(CHT == 4 ? 1 : 0), [track] "n"(TRACK_LAST ? 1 : 0), [idx] "v"(idx), [livebit] "n"(LIVE_BIT),
-        [clr] "n"(LIVE_BIT >= 0 ? ~(1 << LIVE_BIT) : -1), [closebranch] "n"(MGS_RASTER_CLOSE_BRANCH)
+        [clr] "n"(LIVE_BIT >= 0 ? ~(1 << LIVE_BIT) : -1)
       : "vcc", "scc");            // (s_xor / s_andn2 write SCC: the loop counter's compare must not straddle the body)
   if (CHT == 4) px.C[CHT - 1] = c3;
 }
@@ -260,7 +179,7 @@ __device__ __forceinline__ void blend_pixel_safe_asm(PixelState<CHT>& px, unsign
 // code is what it was.
 struct NoDataset {};
 template <int CHT, bool TRACK_LAST, bool DATASET = false>
-__global__ __launch_bounds__(64 * (TRACK_LAST ? 1 : MGS_RASTER_WG_WAVES), (CHT <= 4 ? MGS_RASTER_WAVES : 1)) void raster_fwd_kernel(
+__global__ __launch_bounds__(64 * (TRACK_LAST ? 1 : kFwdWgWaves), (CHT <= 4 ? kFwdMinWaves : 1)) void raster_fwd_kernel(
     const float* __restrict__ means2d, const float* __restrict__ conics,
     const float* __restrict__ feats, const float* __restrict__ opacities,
     const float4* __restrict__ splats, const float* __restrict__ background, int channels,
@@ -269,7 +188,7 @@ __global__ __launch_bounds__(64 * (TRACK_LAST ? 1 : MGS_RASTER_WG_WAVES), (CHT <
     float* __restrict__ alphas, int32_t* __restrict__ last_ids, int cull, int expected_last, int opts,
     const int32_t* __restrict__ group_order, float* __restrict__ ckpt, int ckpt_shift,
     std::conditional_t<DATASET, DatasetOut, NoDataset> ds) {
-  constexpr int kWgWaves = TRACK_LAST ? 1 : MGS_RASTER_WG_WAVES;
+  constexpr int kWgWaves = TRACK_LAST ? 1 : kFwdWgWaves;
   __shared__ QueueEntry<CHT> queues[kWgWaves][kQueue + 1];
   QueueEntry<CHT>* queue = queues[threadIdx.x >> 6];
   const int tile = tile_of_unit(blockIdx.x * kWgWaves + (int)(threadIdx.x >> 6), n_tiles, group_order);   // tile_order.h
@@ -314,7 +233,7 @@ __global__ __launch_bounds__(64 * (TRACK_LAST ? 1 : MGS_RASTER_WG_WAVES), (CHT <
     for (int c = 0; c < CHT; ++c) st[k].C[c] = 0.f;
   }
 
-  // raw batch registers (software prefetch of the next 64 list entries)
+  // the batch registers: the list entries of the batch about to be queued (fetched when the batch starts)
   int r_idx = start + (int)lane;
   bool r_ok = r_idx < end;
   float2 r_xy = make_float2(0.f, 0.f);
@@ -366,9 +285,7 @@ __global__ __launch_bounds__(64 * (TRACK_LAST ? 1 : MGS_RASTER_WG_WAVES), (CHT <
     }
 
     // take the prefetched batch, start the next one
-#if MGS_RASTER_NO_PREFETCH
     if (b != start) { r_idx = b + (int)lane; r_ok = r_idx < end; fetch(r_idx, r_ok); }
-#endif
     const int c_idx = r_idx;
     const bool c_ok = r_ok;
     const float2 c_xy = r_xy;
@@ -376,11 +293,6 @@ __global__ __launch_bounds__(64 * (TRACK_LAST ? 1 : MGS_RASTER_WG_WAVES), (CHT <
     float c_feat[CHT];
 #pragma unroll
     for (int c = 0; c < CHT; ++c) c_feat[c] = r_feat[c];
-#if !MGS_RASTER_NO_PREFETCH
-    r_idx = b + kQueue + (int)lane;
-    r_ok = r_idx < end;
-    fetch(r_idx, r_ok);
-#endif
 
     unsigned qmask = 0;
     if (c_ok) qmask = (cull ? quadrant_mask(c_xy.x, c_xy.y, c_ca, c_cb, c_cc, c_op, tile_x, tile_y) : 0xfu) & live;
@@ -437,10 +349,8 @@ __global__ __launch_bounds__(64 * (TRACK_LAST ? 1 : MGS_RASTER_WG_WAVES), (CHT <
         constexpr int k = decltype(kc)::value;
         if (m & (1u << k)) {
           if constexpr (kMasks<CHT> && SAFE)
-            blend_pixel_safe_asm<CHT, TRACK_LAST, MGS_RASTER_LIVE_BITS ? k : -1>(st[k], alive[k], live, pq[k], g0.x, g0.y, g0.z,
-                                                                                g0.w, g1.x, g1.y, feat, idx);
-          else if constexpr (!MGS_RASTER_MASKS && MGS_RASTER_CMPX && SAFE && (CHT == 3 || CHT == 4))
-            blend_pixel_safe_asm_sign<CHT, TRACK_LAST>(st[k], pq[k], g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, feat, idx);
+            blend_pixel_safe_asm<CHT, TRACK_LAST, k>(st[k], alive[k], live, pq[k], g0.x, g0.y, g0.z, g0.w, g1.x, g1.y,
+                                                     feat, idx);
           else
             blend_pixel<CHT, TRACK_LAST, SAFE, kMasks<CHT>>(st[k], alive[k], pq[k], g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g3.x,
                                                              g3.y, feat, idx);
@@ -453,32 +363,6 @@ __global__ __launch_bounds__(64 * (TRACK_LAST ? 1 : MGS_RASTER_WG_WAVES), (CHT <
     };
     auto walk = [&](auto safe_tag) {
       constexpr bool SAFE = decltype(safe_tag)::value;
-#if MGS_RASTER_PIPE
-      // entry j + 1 is read from LDS while entry j is blended (the queue has one spare slot: the read past the last
-      // entry is harmless): PMC had the waves parked on s_waitcnt for 39 % of their cycles, most of it these reads
-      if constexpr (CHT <= 4) {
-        // two register sets in turn (no copies): while set A is blended set B is on its way, and vice versa
-        float4 a0 = queue[0].geo0, a1 = queue[0].geo1, af = queue[0].feat[0], a3 = make_float4(0.f, 0.f, 0.f, 0.f);
-        float4 b0, b1, bf, b3 = a3;
-        if constexpr (!SAFE) a3 = queue[0].geo3;
-        for (int j = 0; j < count; j += 2) {
-          {
-            const QueueEntry<CHT>& e = queue[j + 1];
-            b0 = e.geo0; b1 = e.geo1; bf = e.feat[0];
-            if constexpr (!SAFE) b3 = e.geo3;
-          }
-          blend_entry(safe_tag, a0, a1, &af, a3);
-          if (j + 1 >= count) break;
-          {
-            const QueueEntry<CHT>& e = queue[min(j + 2, kQueue)];
-            a0 = e.geo0; a1 = e.geo1; af = e.feat[0];
-            if constexpr (!SAFE) a3 = e.geo3;
-          }
-          blend_entry(safe_tag, b0, b1, &bf, b3);
-        }
-        return;
-      }
-#endif
       for (int j = 0; j < count; ++j) {
         const QueueEntry<CHT>& e = queue[j];
         float4 g0, g1, ef[(CHT + 3) / 4];
@@ -570,11 +454,6 @@ __global__ __launch_bounds__(256) void raster_fwd_q_kernel(    // (bounded to 64
     const int32_t* __restrict__ group_order, float* __restrict__ ckpt, int ckpt_shift,
     std::conditional_t<DATASET, DatasetOut, NoDataset> ds) {
   __shared__ QueueEntry<CHT> queues[4][kQueue];
-#ifdef MGS_RASTER_Q_VGPR_CLOBBER
-  // occupancy experiment: naming a high VGPR raises the kernel's register allocation (and lowers its
-  // waves per SIMD) without touching LDS, which the other frames' kernels need
-  asm volatile("" ::: MGS_RASTER_Q_VGPR_CLOBBER);
-#endif
   const int k = (int)(threadIdx.x >> 6);
   QueueEntry<CHT>* queue = queues[k];
   const int tile = tile_of_unit(blockIdx.x, n_tiles, group_order);      // tile_order.h
@@ -660,19 +539,11 @@ __global__ __launch_bounds__(256) void raster_fwd_q_kernel(    // (bounded to 64
         keep_me = false;
         if (c_op >= kAlphaMin) {
           // (single v_log_f32 / v_rcp_f32, as in quadrant_mask: the slack is orders above their error)
-#ifdef MGS_Q_CULL_IEEE      // measurement: the divides and the denormal-safe logf
-          const float thr = __logf(255.0f * c_op);
-#else
           const float thr = 0.6931471805599453f * __builtin_amdgcn_logf(255.0f * c_op);
-#endif
           const float fx = fmaxf(fabsf(tile_x - c_xy.x), fabsf(tile_x + 16.f - c_xy.x));
           const float fy = fmaxf(fabsf(tile_y - c_xy.y), fabsf(tile_y + 16.f - c_xy.y));
           const float slack = 0.05f + 4e-6f * (fabsf(c_ca) + fabsf(c_cc) + 2.f * fabsf(c_cb)) * (fx * fx + fy * fy);
-#ifdef MGS_Q_CULL_IEEE
-          const float smin = rect_min_sigma(c_xy.x, c_xy.y, c_ca, c_cb, c_cc, 1.0f / c_ca, 1.0f / c_cc, rect);
-#else
           const float smin = rect_min_sigma(c_xy.x, c_xy.y, c_ca, c_cb, c_cc, __builtin_amdgcn_rcpf(c_ca), __builtin_amdgcn_rcpf(c_cc), rect);
-#endif
           keep_me = !(smin > thr + slack);
         }
       }
@@ -711,9 +582,6 @@ __global__ __launch_bounds__(256) void raster_fwd_q_kernel(    // (bounded to 64
         if (j0 && (kMasks<CHT> ? alive : ballot(st.T > 0.f)) == 0ull) break;
         const int j1 = min(j0 + kChunk, count);
       for (int j = j0; j < j1; ++j) {
-#if MGS_RASTER_Q_BREAK
-        if (kMasks<CHT> && alive == 0ull) break;     // (a scalar compare: the block's last pixel closed)
-#endif
         const QueueEntry<CHT>& e = queue[j];
         float4 g0, g1, ef0;
         if constexpr (CHT <= 4) lds_read_3f4(&e.geo0, &e.geo1, &e.feat[0], g0, g1, ef0);
@@ -730,8 +598,6 @@ __global__ __launch_bounds__(256) void raster_fwd_q_kernel(    // (bounded to 64
         if constexpr (kMasks<CHT> && SAFE) {
           unsigned unused = 0;
           blend_pixel_safe_asm<CHT, TRACK_LAST>(st, alive, unused, pp, g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, feat, __float_as_int(g1.w));
-        } else if constexpr (!MGS_RASTER_MASKS && MGS_RASTER_CMPX && SAFE && (CHT == 3 || CHT == 4)) {
-          blend_pixel_safe_asm_sign<CHT, TRACK_LAST>(st, pp, g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, feat, __float_as_int(g1.w));
         } else {
           float4 g3 = make_float4(0.f, 0.f, 0.f, 0.f);
           if constexpr (!SAFE) g3 = e.geo3;
@@ -874,8 +740,8 @@ extern "C" int mgs_rasterize_fwd(int n, const float* means2d, const float* conic
   if ((g_raster_opts & 16) && !per_block && !last_ids) tile_group_order = nullptr;
   const int n_units = tile_group_order ? (n_tiles + 3) / 4 * 4 : n_tiles;       // tile slots of the launch
 #define MGS_RF_LAUNCH_T(C, T)                                                                  \
-  hipLaunchKernelGGL((raster_fwd_kernel<C, T>), dim3(div_up(n_units, (T) ? 1 : MGS_RASTER_WG_WAVES)),   \
-                     dim3(64 * ((T) ? 1 : MGS_RASTER_WG_WAVES)), (T) ? 0 : (size_t)(g_raster_opts >> 8) * 1024, s, means2d, conics, \
+  hipLaunchKernelGGL((raster_fwd_kernel<C, T>), dim3(div_up(n_units, (T) ? 1 : kFwdWgWaves)),   \
+                     dim3(64 * ((T) ? 1 : kFwdWgWaves)), (T) ? 0 : (size_t)(g_raster_opts >> 8) * 1024, s, means2d, conics, \
                      feats, opacities, reinterpret_cast<const float4*>(splats), background,     \
                      channels, width, height, tile_w, n_tiles,                                 \
                      tile_offsets, flatten_ids, render, alphas, last_ids, g_raster_cull,            \
@@ -895,8 +761,8 @@ extern "C" int mgs_rasterize_fwd(int n, const float* means2d, const float* conic
                          height, tile_w, n_tiles, tile_offsets, flatten_ids, render, alphas, last_ids, g_raster_cull, 1,
                          tile_group_order, checkpoints, ckpt_shift, ds);
     else
-      hipLaunchKernelGGL((raster_fwd_kernel<4, false, true>), dim3(div_up(n_units, MGS_RASTER_WG_WAVES)),
-                         dim3(64 * MGS_RASTER_WG_WAVES), (size_t)(g_raster_opts >> 8) * 1024, s, means2d, conics, feats, opacities,
+      hipLaunchKernelGGL((raster_fwd_kernel<4, false, true>), dim3(div_up(n_units, kFwdWgWaves)),
+                         dim3(64 * kFwdWgWaves), (size_t)(g_raster_opts >> 8) * 1024, s, means2d, conics, feats, opacities,
                          reinterpret_cast<const float4*>(splats), background, channels, width, height, tile_w, n_tiles,
                          tile_offsets, flatten_ids, render, alphas, last_ids, g_raster_cull, 1, g_raster_opts, tile_group_order,
                          checkpoints, ckpt_shift, ds);

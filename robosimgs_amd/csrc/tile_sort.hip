@@ -49,34 +49,17 @@ constexpr int kTSMain = 256;        // threads per tile
 // of ~kUnit entries (file comment) which a second and a third launch take: the collect kernel and the units' kernel
 // (kTSUnit threads, an LDS list of kFastUnit entries, the same levels).  The launches cost a few microseconds even when
 // no list is long, so they exist only where the capacity says lists are long (tile_depth_sort below).
-#ifndef MGS_TSORT_UNIT
-#define MGS_TSORT_UNIT 2048            // entries per unit aimed at (the units' LDS list holds kFastUnit: room for an uneven split)
-#endif
-#ifndef MGS_TSORT_UNIT_THREADS
-#define MGS_TSORT_UNIT_THREADS 512
-#endif
-#ifndef MGS_TSORT_UNIT_GRID
-#define MGS_TSORT_UNIT_GRID 768
-#endif
-#ifndef MGS_TSORT_COLLECT_GRID
-#define MGS_TSORT_COLLECT_GRID 2048
-#endif
-constexpr int kUnit = MGS_TSORT_UNIT, kTSUnit = MGS_TSORT_UNIT_THREADS, kFastUnit = 4096, kUnitGrid = MGS_TSORT_UNIT_GRID;
+// kUnit: entries per unit aimed at (the units' LDS list holds kFastUnit: room for an uneven split)
+constexpr int kUnit = 2048, kTSUnit = 512, kFastUnit = 4096, kUnitGrid = 768;
 constexpr int kMaxUnits = 256;                        // units per list (a list over kMaxUnits * kUnit entries: larger units)
 constexpr int kUnitSample = 256;                      // sample a unit's own bucket function is taken from (lds_level) ...
-#ifndef MGS_TSORT_ADAPT
-#define MGS_TSORT_ADAPT 48
-#endif
-constexpr int kAdapt = MGS_TSORT_ADAPT;               // ... when the bit field leaves a bucket of more entries than this
-#ifndef MGS_TSORT_SAMPLE_FROM
-#define MGS_TSORT_SAMPLE_FROM 3     // the group filter starts sampling a list once it holds this many quarters of the LDS list
-#endif
-constexpr int kSamplePerUnit = 24;                    // ... of which this many per unit are ranked
+constexpr int kAdapt = 48;                            // ... when the bit field leaves a bucket of more entries than this
 constexpr int kSample = 512;                          // entries the splitters are taken from at most: every 2^k-th of the list
-constexpr int kCollectThreads = 256, kCollectPer = 8, kCollectGrid = MGS_TSORT_COLLECT_GRID;   // unit_collect_kernel
+constexpr int kSamplePerUnit = 24;                    // ... of which this many per unit are ranked
+constexpr int kCollectThreads = 256, kCollectPer = 8, kCollectGrid = 2048;   // unit_collect_kernel
 // header of the deferred lists (two 16-byte stores zero it): [0] descriptors claimed, [1] units claimed from the bottom of the
 // unit tables (lists of kBigList entries and more: their units read the whole list, the units' kernel starts with them),
-// [2] collect chunks claimed, [3] units handed out by the units' kernel beyond its workgroups' first ones, [4] units
+// [2] collect chunks claimed, [3] unused, [4] units
 // claimed from the top of the tables (all other lists)
 constexpr int kListHeader = 8;
 constexpr int kBigList = 6144;
@@ -94,35 +77,18 @@ struct SortAux {
   uint32_t* unit_hist;               // per unit: its entry count (zeroed by the main kernel, counted by the collect kernel)
   unsigned long long* unit_split;    // per unit u of a list (but its last): the splitter between buckets u and u + 1
 };
-#ifndef MGS_TSORT_LONG_BUCKETS
-#define MGS_TSORT_LONG_BUCKETS 512     // buckets per level in the units' kernel (the main kernel: 1024): ~2,000 entries per unit; 1,024 would cost the third workgroup per CU its LDS
-#endif
-// buckets of one MSD level
-constexpr int buckets_for(int fast) { return fast > 2048 ? MGS_TSORT_LONG_BUCKETS : 1024; }   // (256 for the short-list variant: fewer counters to zero / scan, but ~2 entries per
+// buckets of one MSD level: 512 in the units' kernel (~2,000 entries per unit; 1,024 would cost the third workgroup per CU
+// its LDS), 1,024 in the main kernel
+constexpr int buckets_for(int fast) { return fast > 2048 ? 512 : 1024; }   // (256 for the short-list variant: fewer counters to zero / scan, but ~2 entries per
                                                   //  bucket make the wave's rank loop as long as its fullest bucket: 22.6 M VALU against 21.8 M)
 constexpr int log2i(int v) { return v <= 1 ? 0 : 1 + log2i(v >> 1); }
-#ifndef MGS_TSORT_SMALL
 // buckets up to this size are finished by rank counting out of LDS; larger ones are bucketed again, one after the other, through
 // global scratch.  48 until round 5; on a clustered scene most tiles of 1-2 k entries hold a few dozen buckets of 50-150
 // near-identical depths: at 128 the main kernel takes 75 instead of 104 us there (256: 90), on SURVEY 8(d)'s scene 33.0 either way
-#define MGS_TSORT_SMALL 128
-#endif
-constexpr int kSmall = MGS_TSORT_SMALL;
-#ifndef MGS_TSORT_SMALL_LONG
-#define MGS_TSORT_SMALL_LONG 256
-#endif
-constexpr int kSmallLong = MGS_TSORT_SMALL_LONG;   // ... in the units' kernel (sort_one_tile)
+constexpr int kSmall = 128;
+constexpr int kSmallLong = 256;     // ... in the units' kernel (sort_one_tile)
 constexpr int kStack = 96;          // pending heavy buckets; beyond it a bucket is rank-counted whatever its size
-#ifndef MGS_TSORT_STOP
-#define MGS_TSORT_STOP 0      // measurement only: leave the kernel after phase 1..4 (filter / keys / scan / scatter)
-#endif
-#ifndef MGS_TSORT_LDS_LEVELS
-#define MGS_TSORT_LDS_LEVELS 1     // popped heavy buckets that fit the LDS list take a level out of LDS (sort_one_tile)
-#endif
-#ifndef MGS_TSORT_FAST
-#define MGS_TSORT_FAST 2048
-#endif
-constexpr int kFastLong = MGS_TSORT_FAST;   // longest list of the LDS-resident fast path (8 KiB of LDS per 1024) ...
+constexpr int kFastLong = 2048;             // longest list of the LDS-resident fast path (8 KiB of LDS per 1024) ...
 constexpr int kFastShort = 1024;            // ... and where the capacity says lists are short on average: 17 instead of
                                             // 25 KiB of LDS per workgroup = 8 instead of 6 workgroups per CU
 constexpr int kFastMid = 1536;              // ... and in between (up to 1,000 entries per tile on average: configs[4] has 806,
@@ -469,9 +435,6 @@ __device__ __forceinline__ void sort_one_tile(
     }
     return;
   }
-#if MGS_TSORT_STOP == 1
-  return;
-#endif
   if (tile_ids && !UNIT)
     for (int i = s + tid; i < e; i += kTS) tile_ids[i] = (uint32_t)tile;
   if (!UNIT && e - s <= 1) {
@@ -550,9 +513,6 @@ __device__ __forceinline__ void sort_one_tile(
       for (int w = 0; w < kTS / 64; ++w) { ior |= red_or[w]; iand &= red_and[w]; }
       hb = 31 - __clz((int)(ior ^ iand));
     }
-#if MGS_TSORT_STOP == 2
-    if (hb >= 0) { if (tid == 0) ids_final[s] = (uint32_t)hb; return 0u; }
-#endif
     const int shift = hb > kDigitBits - 1 ? hb - (kDigitBits - 1) : 0;
     // shift >= 32 (the depths differ above their lowest kDigitBits - 1 bits: nearly always): the digit is a bit
     // field of the 32-bit key
@@ -658,9 +618,6 @@ __device__ __forceinline__ void sort_one_tile(
     } else {
       htot = hist_and_scan((uint32_t)kSm, true);
     }
-#if MGS_TSORT_STOP == 3
-    if (n > 0) { if (tid == 0) ids_final[s] = cnt[3]; return 0u; }
-#endif
 #pragma unroll
     for (int it = 0; it < kItems; ++it) {
       if (it * kTS >= n) continue;
@@ -673,9 +630,6 @@ __device__ __forceinline__ void sort_one_tile(
       }
     }
     __syncthreads();
-#if MGS_TSORT_STOP == 4
-    if (n > 0) { if (tid == 0) ids_final[s] = (uint32_t)lc[3]; return 0u; }
-#endif
 #pragma unroll
     for (int it = 0; it < kItems; ++it) {
       const int i = it * kTS + tid;
@@ -798,9 +752,10 @@ __device__ __forceinline__ void sort_one_tile(
     uint32_t* di = src ? id0 : id1;
     const int m = hi - lo;
 
-    // (the units' kernel only: a second copy of the level takes the main kernel from 47-53 to 64-86 VGPRs, a
-    //  workgroup per CU less for every scene, and its heavy buckets are few)
-    if constexpr (LONG && MGS_TSORT_LDS_LEVELS != 0) {
+    // popped heavy buckets that fit the LDS list take a level out of LDS -- in the units' kernel only: a second copy of the
+    // level takes the main kernel from 47-53 to 64-86 VGPRs, a workgroup per CU less for every scene, and its heavy buckets
+    // are few (profiles/r5/00_experiments.md section 16)
+    if constexpr (LONG) {
       if (m > kSm && m <= kFast) {              // fits the LDS list: one level out of LDS (heavy sub-buckets to the other buffer)
         (void)lds_level(Mode0{}, lo, m, sk, si, dk, di, (uint8_t)(src ^ 1), sn - 1);
         __syncthreads();
@@ -955,11 +910,10 @@ __device__ __forceinline__ void sort_one_tile(
   }
 }
 
-#ifndef MGS_TSORT_MAIN_SGPRS
-#define MGS_TSORT_MAIN_SGPRS 96
-#endif
+// (96 SGPRs: seven waves per SIMD need <= 96 on gfx950, eight <= 80 -- the SGPR-occupancy micro-benchmark of
+//  profiles/r6/00_experiments.md section 8)
 template <bool GROUPED, int kFast, bool DEFER>
-__global__ __launch_bounds__(kTSMain) __attribute__((amdgpu_num_sgpr(MGS_TSORT_MAIN_SGPRS))) void tile_depth_sort_kernel(
+__global__ __launch_bounds__(kTSMain) __attribute__((amdgpu_num_sgpr(96))) void tile_depth_sort_kernel(
     int n_tiles, const int32_t* __restrict__ offsets, const float* __restrict__ depths,
     uint32_t* ids_final, uint32_t* __restrict__ tile_ids, uint32_t* key0, uint32_t* id0, uint32_t* key1,
     uint32_t* id1, const uint32_t* __restrict__ staging, int shift, int32_t* __restrict__ offsets_out,
@@ -1074,10 +1028,7 @@ __global__ __launch_bounds__(kCollectThreads) void unit_collect_kernel(
 // lists are (ck, ci).
 // (compiled for six waves per SIMD: 71 VGPRs without a spill where the launch bound alone let the compiler take 113 -- three
 //  workgroups per CU, which is what LDS allows, and with units of 2,048 entries the clustered scene's ~750 units are resident at once)
-#ifndef MGS_TSORT_UNIT_WAVES
-#define MGS_TSORT_UNIT_WAVES 6
-#endif
-__global__ __launch_bounds__(kTSUnit) __attribute__((amdgpu_waves_per_eu(MGS_TSORT_UNIT_WAVES, 8))) void tile_sort_units_kernel(
+__global__ __launch_bounds__(kTSUnit) __attribute__((amdgpu_waves_per_eu(6, 8))) void tile_sort_units_kernel(
     int n_tiles, uint32_t* ids_final, const uint32_t* __restrict__ ck, const uint32_t* __restrict__ ci, uint32_t* key0,
     uint32_t* id0, uint32_t* key1, uint32_t* id1, const SortAux aux) {
   // units [0, n_big) of the tables belong to the big lists, the last n_small to the others: item i is unit i, or unit
@@ -1085,13 +1036,9 @@ __global__ __launch_bounds__(kTSUnit) __attribute__((amdgpu_waves_per_eu(MGS_TSO
   const uint32_t n_big = aux.hdr[1] < aux.max_units ? aux.hdr[1] : aux.max_units;
   const uint32_t n_small = aux.hdr[4] < aux.max_units - n_big ? aux.hdr[4] : aux.max_units - n_big;
   const uint32_t n_units = n_big + n_small;
-#ifndef MGS_TSORT_DYNAMIC
-#define MGS_TSORT_DYNAMIC 0        // 1: a workgroup's units beyond its first come off a counter (measured: 47 against 41-42 us)
-#endif
-  __shared__ uint32_t next_f;
+  // (a workgroup's units beyond its first taken off a counter instead: 47 against 41-42 us, profiles/r6/00_experiments.md)
   uint32_t f = blockIdx.x;
   while (f < n_units) {
-    if (MGS_TSORT_DYNAMIC && threadIdx.x == 0) next_f = gridDim.x + atomicAdd(&aux.hdr[3], 1u);     // (in flight while the unit is sorted)
 #ifdef MGS_TSORT_TIMING            // measurement build: per unit {start, end} on the 100 MHz clock (scripts/dbg/long_sort_timeline.py)
     const unsigned long long t_start = wall_clock64();
 #endif
@@ -1111,12 +1058,7 @@ __global__ __launch_bounds__(kTSUnit) __attribute__((amdgpu_waves_per_eu(MGS_TSO
       }
     }
 #endif
-    if (MGS_TSORT_DYNAMIC) {
-      f = next_f;
-      __syncthreads();               // (read before the next round's store)
-    } else {
-      f += gridDim.x;
-    }
+    f += gridDim.x;
   }
 }
 
@@ -1172,7 +1114,8 @@ size_t tile_depth_sort_temp_bytes(uint32_t capacity, int n_tiles) {
 
 // Sorts flatten_ids[offsets[t] .. offsets[t+1]) of every tile by (depth bits, id).  temp:
 // tile_depth_sort_temp_bytes(capacity, n_tiles) bytes.  long_list_zeroed: the caller's earlier kernel has already stored
-// zeros in the four header words of the deferred lists (tile_depth_sort_long_list(temp, capacity)); otherwise a memset does.
+// zeros in the kListHeader words of the deferred lists' header (tile_depth_sort_long_list(temp, capacity)); otherwise a
+// memset does.
 // scratch_k / scratch_i: two more arrays of `capacity` words nobody reads once the lists have been collected (the binning's
 // radix ping-pong buffers; scratch_i may be `staging` itself) -- the units' second scratch pair.
 uint32_t* tile_depth_sort_long_list(void* temp, uint32_t capacity) {
@@ -1203,12 +1146,8 @@ int tile_depth_sort(int n_tiles, const int32_t* tile_offsets, const float* depth
   // where the capacity leaves 640 entries per tile on average a list over 1,024 entries is the rare exception and takes the
   // main kernel's generic path, while launches that find nothing to do would cost every frame a few microseconds
   // (bench.py's headline: 4,313 against 4,345 frames/s for one of them).  Scenes whose capacity says lists are long get all three.
-#ifdef MGS_TSORT_FORCE_LONG     // measurement (scripts/ab_builds.py): the three-launch form whatever the capacity says
-  const bool short_lists = false, mid_lists = false;
-#else
   const bool short_lists = capacity_says_short_lists(capacity, n_tiles) || !scratch_k || !scratch_i;
   const bool mid_lists = !short_lists && (size_t)capacity <= (size_t)n_tiles * 1000;
-#endif
   // (GROUPED launches are padded to whole blocks of 8 groups: the kernel's XCD-aware tile numbering)
   const int per = 8 << group_shift, n_wg = staging ? (n_tiles + per - 1) / per * per : n_tiles;
 #define MGS_TS_LAUNCH(G, F, D, OFFS, STG, SH, OUT)                                                              \

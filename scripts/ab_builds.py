@@ -1,8 +1,9 @@
 """Same-process, interleaved A/B of two BUILDS of libmgs.so (the shipped one against a variant of one source compiled
 with extra flags): kernel-alone times of the forward stages and frames/s with three frames in flight, the two builds
 taking turns so that clock drift hits both alike.
-    python scripts/ab_builds.py raster_fwd.hip "-DMGS_RASTER_CLOSE_BRANCH=1" [tile_sort.hip "-D..."]
-VARIANT_LIB=<path of a libmgs.so built from another tree>: that library is B (nothing is compiled); SCENE=4k | heavy.
+    python scripts/ab_builds.py raster_fwd.hip "-fslp-vectorize" [tile_sort.hip "<flags>"]
+VARIANT_LIB=<path of a libmgs.so built from another tree>: that library is B (nothing is compiled) -- the way to sweep a
+tuning constant: edit it in a copy of the tree, build there, point VARIANT_LIB at its libmgs.so.  SCENE=4k | heavy.
 """
 import math, os, subprocess, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -1,7 +1,7 @@
 """Same-process, interleaved A/B of two BUILDS of libmgs.so for the BACKWARD raster (the shipped one against a variant of
 raster_bwd.hip compiled with extra flags): memset + unit tables + raster backward + reduce between HIP events, the two
 builds taking turns; gradients compared bit for bit.
-    python scripts/ab_builds_bwd.py "-DMGS_RASTER_BWD_IDS_AHEAD=1"
+    python scripts/ab_builds_bwd.py "-fslp-vectorize" [raster_bwd.hip]
 """
 import math, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

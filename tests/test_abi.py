@@ -70,6 +70,21 @@ def test_library_is_gfx950_only_and_links_no_torch():
         assert archs == {"gfx950"}, archs
 
 
+@pytest.mark.parametrize("src,define,symbol", [("raster_fwd.hip", "MGS_RASTER_STATS", "g_raster_stats"),
+                                               ("raster_bwd.hip", "MGS_RASTER_BWD_TIMING", "g_bwd_times"),
+                                               ("tile_sort.hip", "MGS_TSORT_TIMING", "g_tsort_log")])
+def test_observation_builds_compile(src, define, symbol, tmp_path):
+    """The measurement builds the evidence scripts use (scripts/raster_stats.py, scripts/dbg/bwd_timeline.py,
+    scripts/dbg/main_sort_timeline.py) are one -D away from the shipped sources; no other build compiles them.  A
+    device-only compile with build.py's flags must succeed and define the build's counters."""
+    from robosimgs_amd.csrc import build as B
+    out = tmp_path / (src + ".s")
+    r = subprocess.run([B._hipcc(), *B.FLAGS, "-D" + define, "--cuda-device-only", "-S", os.path.join(B.HERE, src),
+                        "-o", str(out)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-4000:]
+    assert re.search(r"^\w*" + symbol + r"\w*:", out.read_text(), flags=re.M), f"{define}: {symbol} not defined"
+
+
 def test_argument_errors_are_reported_without_a_gpu():
     from robosimgs_amd import _lib
     L = _lib.lib()

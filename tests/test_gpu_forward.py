@@ -191,12 +191,14 @@ def test_tile_depth_order_uneven_lists_under_each_capacity_rule(ops, per_list, t
 @pytest.mark.parametrize("n,tw,th,kind,opts", [(30_000, 7, 6, "uniform", 0), (30_000, 7, 6, "clustered", 0), (9_500, 9, 5, "bimodal", 0),
                                                (20_000, 3, 2, "clustered", 4), (20_000, 3, 2, "outliers", 0), (70_000, 2, 1, "equal", 0)])
 def test_giant_lists_are_spread_over_the_chip(ops, n, tw, th, kind, opts):
-    """Lists over 8,192 entries take the cooperative path of csrc/tile_sort.hip (descriptor + pool, collect kernel, units of
-    whole buckets in the long kernel).  Cases: 42 giant tiles of 28 k entries (more than the 32 descriptors and more than
-    the 1 M-entry pool: the rest falls back to the long kernel's generic path), 45 giant tiles of which 32 get a descriptor,
-    two depth clusters far apart (most buckets empty), the radix partition (debug knob 4: ungrouped lists), a
-    sample that misses the outliers (the bucket function clamps) and 70 k identical depths (one bucket holds everything:
-    the unit is the whole list, ordered by index).  Lists bit-identical to the stable sort on (tile, depth bits)."""
+    """Lists longer than the main kernel's LDS list are split into units by sample sort (csrc/tile_sort.hip): the main
+    kernel gives each such list a descriptor and stores splitters taken from a sample of its composites (depth bits << 32
+    | id), unit_collect_kernel gathers the entries and counts them per unit, tile_sort_units_kernel sorts every unit of
+    ~2,048 entries.  Cases: 42 tiles of ~28 k entries (lists of 6,144 entries and more: units that read the whole list),
+    the same with four clusters of near-identical depths, 45 tiles of ~9 k entries with two depth clusters far apart, the
+    radix partition (debug knob 4: ungrouped lists), outliers that the sample misses (a unit is the number of splitters at
+    or below the composite: they fall into the first or last unit) and 70 k identical depths (the ids in the composite
+    split them).  Lists bit-identical to the stable sort on (tile, depth bits)."""
     from robosimgs_amd import _lib
     rng = np.random.default_rng(n + tw + len(kind))
     w, h = 16 * tw, 16 * th
