@@ -41,8 +41,9 @@ extern "C" {
  * 100 round 1; 200 round 2 (seed / splats / tile_group_order arguments); 300 round 3; 400 round 4 (forward
  * checkpoints + segmented backward, batched training entry points, debug hooks out of the production build);
  * 410 round 4 (the radius rule as a policy: radii_y / radius_rule arguments, MGS_BIN_* / MGS_FRAMES_RADIUS_* flags,
- * one more field in the training state; 420: the dataset frame as an output of the raster forward, ds_* arguments). */
-#define MGS_VERSION 430
+ * one more field in the training state; 420: the dataset frame as an output of the raster forward, ds_* arguments;
+ * 440: the camera model as a policy: camera_model arguments, MGS_BIN_CAMERA_* / MGS_FRAMES_CAMERA_* flags). */
+#define MGS_VERSION 440
 
 #define MGS_OK 0
 #define MGS_ERR_INVALID_ARGUMENT (-1)
@@ -64,6 +65,22 @@ extern "C" {
                                        classic lists (a caller that sized its capacity with them) */
 
 #define MGS_FRAMES_RADIUS_OPACITY_AWARE 8 /* project with MGS_RADIUS_OPACITY_AWARE (below) instead of the classic rule */
+#define MGS_FRAMES_CAMERA_ORTHO 16        /* project with MGS_CAMERA_ORTHO (below) instead of the pinhole model */
+#define MGS_FRAMES_CAMERA_FISHEYE 32      /* project with MGS_CAMERA_FISHEYE; at most one MGS_FRAMES_CAMERA_* bit; the
+                                             backward must be given the forward's bit.  Dataset output (ds_rgba /
+                                             ds_distance) is pinhole-only: MGS_ERR_UNSUPPORTED otherwise */
+
+/* The camera model, a compile-time policy of the projection kernels like the radius rule (all three instantiations ship,
+ * the caller picks one per call).  Camera point p = (x, y, z) in OpenCV axes, K = [[fx, 0, cx], [0, fy, cy], [0, 0, 1]]:
+ *   MGS_CAMERA_PINHOLE  (fx x/z + cx, fy y/z + cy); the EWA Jacobian with x/z, y/z clamped to 1.3 x the half field of view.
+ *   MGS_CAMERA_ORTHO    (fx x + cx, fy y + cy); J = [[fx, 0, 0], [0, fy, 0]]; no frustum clamp.
+ *   MGS_CAMERA_FISHEYE  ideal equidistant lens (r = f theta, no distortion coefficients): rho = |(x, y)|,
+ *                       theta = atan2(rho, z), (fx x theta/rho + cx, fy y theta/rho + cy); J the dense Jacobian of that
+ *                       map; no frustum clamp.
+ * Depth is camera z under every model (near / far cull, sort key, "D" / "ED"); the SH view direction is mean - campos. */
+#define MGS_CAMERA_PINHOLE 0
+#define MGS_CAMERA_ORTHO 1
+#define MGS_CAMERA_FISHEYE 2
 
 /* The radius rule ("make the radius rule a compile-time policy so the tighter one can be benchmarked").
  * Inside the library the rule is a template constant of the projection kernels; both instantiations ship and the
@@ -83,6 +100,8 @@ extern "C" {
 /* mgs_project_color_fwd bin_flags */
 #define MGS_BIN_TIGHT 1                 /* tightened tile rectangles in the binning seed (mgs_isect_tiles) */
 #define MGS_BIN_RADIUS_OPACITY_AWARE 2  /* MGS_RADIUS_OPACITY_AWARE instead of MGS_RADIUS_CLASSIC */
+#define MGS_BIN_CAMERA_ORTHO 4          /* MGS_CAMERA_ORTHO instead of MGS_CAMERA_PINHOLE */
+#define MGS_BIN_CAMERA_FISHEYE 8        /* MGS_CAMERA_FISHEYE instead of MGS_CAMERA_PINHOLE (at most one MGS_BIN_CAMERA_* bit) */
 
 /* mgs_rasterize_bwd_det flags */
 #define MGS_RASTER_BWD_SPLAT_SLOTS 2  /* the splat records carry the pairs' record slots (mgs_isect_tiles: splat_slots): pair_info is
@@ -123,26 +142,27 @@ void mgs_debug_set_sort_opts(int opts);
  *   radius_rule: MGS_RADIUS_CLASSIC (opacities / radii_y not read or written, may be NULL) or
  *   MGS_RADIUS_OPACITY_AWARE: opacities[N] nullable (as gsplat >= 1.5's optional argument; multiplied by the compensation
  *   iff compensations is given, gsplat's calc_compensations), radii = extent along x, radii_y[N] = extent along y.
+ *   camera_model: MGS_CAMERA_PINHOLE, MGS_CAMERA_ORTHO or MGS_CAMERA_FISHEYE (anything else: MGS_ERR_INVALID_ARGUMENT).
  * ----------------------------------------------------------------------------------- */
 int mgs_projection_fwd(int n, const float *means, const float *quats, const float *scales,
                        const float *viewmat, const float *K, int width, int height,
                        float eps2d, float near_plane, float far_plane, float radius_clip,
                        int32_t *radii, float *means2d, float *depths, float *conics,
                        float *compensations, const float *opacities, int radius_rule,
-                       int32_t *radii_y, mgs_stream_t stream);
+                       int32_t *radii_y, int camera_model, mgs_stream_t stream);
 
 /* Projection backward (gsplat `fully_fused_projection` backward).
  *   v_means2d[N,2] v_depths[N] v_conics[N,3] v_compensations[N] (nullable) are the
  *   incoming cotangents; v_means[N,3] v_quats[N,4] v_scales[N,3] are ACCUMULATED into
  *   (+=) so several cameras can be summed; pass zeroed buffers for a single camera.
- *   v_viewmat[16] (nullable) is accumulated with atomics. */
+ *   v_viewmat[16] (nullable) is accumulated with atomics.  camera_model: the forward's. */
 int mgs_projection_bwd(int n, const float *means, const float *quats, const float *scales,
                        const float *viewmat, const float *K, int width, int height,
                        float eps2d, const int32_t *radii, const float *conics,
                        const float *compensations, const float *v_means2d,
                        const float *v_depths, const float *v_conics,
                        const float *v_compensations, float *v_means, float *v_quats,
-                       float *v_scales, float *v_viewmat, mgs_stream_t stream);
+                       float *v_scales, float *v_viewmat, int camera_model, mgs_stream_t stream);
 
 /* -------------------------------------------------------------------------------------
  * Spherical harmonics  (gsplat `spherical_harmonics` forward / backward)
@@ -281,7 +301,8 @@ int mgs_render_frames(int n, const float *means, const float *quats, const float
  *   feats[N,channels] | splats[N,12] | tiles_per_gauss[N] i32 | pair_info[N,4] i32 | tile_ids[cap] u32 |
  *   flatten_ids[cap] i32 | tile_offsets[n_tiles+1] i32 | tile_group_order[ceil(n_tiles/4)] i32 | last_ids[H,W] i32 |
  *   checkpoints | {n_isect, status} u32 | radii_y[N] i32 (written under MGS_FRAMES_RADIUS_OPACITY_AWARE only)
- * flags: MGS_RASTER_EXPECTED_LAST, MGS_RASTER_LATENCY, MGS_FRAMES_CLASSIC_BOUNDS, MGS_FRAMES_RADIUS_OPACITY_AWARE.  Workspace (shared by the cameras):
+ * flags: MGS_RASTER_EXPECTED_LAST, MGS_RASTER_LATENCY, MGS_FRAMES_CLASSIC_BOUNDS, MGS_FRAMES_RADIUS_OPACITY_AWARE,
+ * MGS_FRAMES_CAMERA_ORTHO / _FISHEYE (the backward must get the forward's).  Workspace (shared by the cameras):
  * two-phase size query, 256-byte aligned.
  * mgs_render_frames_backward: per camera mgs_rasterize_bwd_det (segmented when checkpoint_interval != 0) ->
  * mgs_project_color_bwd; v_means / v_quats / v_scales / v_sh_coeffs / v_opacities are OVERWRITTEN by the first camera
@@ -414,7 +435,7 @@ int mgs_rasterize_bwd_det(int n, const float *means2d, const float *conics, cons
  *   so the cameras of a batch can be summed without a separate zero-fill pass.
  *   v_viewmat[4,4] (nullable): gradient of the world-to-camera matrix (projection and the SH
  *   view direction, dir = mean + R^T t), ALWAYS accumulated with one float atomic per entry
- *   per wave: zero it first.  Camera-pose optimisation only. */
+ *   per wave: zero it first.  Camera-pose optimisation only.  camera_model: MGS_CAMERA_*, the forward's (its bin_flags). */
 int mgs_project_color_bwd(int n, const float *means, const float *quats, const float *scales,
                           const float *opacities, int sh_degree, int coeff_stride,
                           const float *sh_coeffs, const float *viewmat, const float *K,
@@ -424,7 +445,7 @@ int mgs_project_color_bwd(int n, const float *means, const float *quats, const f
                           const float *v_conics, const float *v_depths,
                           const float *v_opac_out, float *v_means, float *v_quats,
                           float *v_scales, float *v_sh_coeffs, float *v_opacities,
-                          float *v_viewmat, int accumulate, mgs_stream_t stream);
+                          float *v_viewmat, int accumulate, int camera_model, mgs_stream_t stream);
 
 /* -------------------------------------------------------------------------------------
  * Compositing (the step downstream of the render path): depth-tested

@@ -1,4 +1,4 @@
-"""Pinhole cameras in the conventions RoboSimGS uses.
+"""Cameras in the conventions RoboSimGS uses (pinhole, orthographic or ideal equidistant fisheye).
 
 The reference stores cameras as OpenGL camera-to-world matrices (+X right, +Y up, camera
 looks down -Z) plus a 3x3 intrinsic matrix:
@@ -20,11 +20,14 @@ from typing import Dict, List, Sequence
 import numpy as np
 
 _FLIP_YZ = np.diag([1.0, -1.0, -1.0, 1.0])
+CAMERA_MODELS = ("pinhole", "ortho", "fisheye")      # rasterization(camera_model=...); include/mgs.h MGS_CAMERA_*
 
 
 @dataclass
 class Camera:
-    """One pinhole camera.  `c2w` is OpenGL camera-to-world (4x4, float64)."""
+    """One camera.  `c2w` is OpenGL camera-to-world (4x4, float64).  `model`: "pinhole", "ortho" (pixel =
+    (fx x + cx, fy y + cy) in camera space: fx is pixels per world unit) or "fisheye" (ideal equidistant lens,
+    pixel radius = f theta, theta the angle off the optical axis)."""
 
     c2w: np.ndarray
     fx: float
@@ -35,8 +38,11 @@ class Camera:
     height: int
     near: float = 0.01
     far: float = 1e10
+    model: str = "pinhole"
 
     def __post_init__(self):
+        if self.model not in CAMERA_MODELS:
+            raise ValueError(f"camera model {self.model!r} not in {CAMERA_MODELS}")
         self.c2w = np.asarray(self.c2w, dtype=np.float64).reshape(4, 4)
         self.width = int(self.width)
         self.height = int(self.height)
@@ -93,11 +99,21 @@ class Camera:
 
     def project(self, pts: np.ndarray, return_dists: bool = False):
         """Pixel coordinates of world points; same contract as the reference's
-        `project_3d_to_2d(pts, w2c, K, return_dists)` (nerf2physic_utils.py:10-23)."""
+        `project_3d_to_2d(pts, w2c, K, return_dists)` (nerf2physic_utils.py:10-23) for a pinhole camera, and the
+        camera model's map otherwise (the one the renderer projects Gaussian means with)."""
         pts = np.asarray(pts, dtype=np.float64)
         pc = pts @ self.viewmat()[:3, :3].T + self.viewmat()[:3, 3]
-        uvw = pc @ self.K.T
-        uv = uvw[:, :2] / uvw[:, 2:]
+        if self.model == "pinhole":
+            uvw = pc @ self.K.T
+            uv = uvw[:, :2] / uvw[:, 2:]
+        else:
+            xy = pc[:, :2]
+            if self.model == "fisheye":       # r = f theta: scale the camera-plane offset by theta / rho
+                rho = np.linalg.norm(xy, axis=-1)
+                theta = np.arctan2(rho, pc[:, 2])
+                safe = np.where(rho > 0, rho, 1.0)
+                xy = xy * np.where(rho > 0, theta / safe, 0.0)[:, None]
+            uv = xy * np.array([self.fx, self.fy]) + np.array([self.cx, self.cy])
         if return_dists:
             return uv, np.linalg.norm(pc, axis=-1)
         return uv
@@ -107,13 +123,17 @@ class Camera:
         return Camera(self.c2w.copy(), self.fx * factor, self.fy * factor,
                       self.cx * factor, self.cy * factor,
                       int(round(self.width * factor)), int(round(self.height * factor)),
-                      self.near, self.far)
+                      self.near, self.far, self.model)
 
 
 def cameras_from_transforms_json(path: str, width: int | None = None,
                                  height: int | None = None) -> List[Camera]:
     """nerfstudio `transforms.json` -> cameras.  Accepts global or per-frame intrinsics,
-    the two layouts `parse_transforms_json` reads (nerf2physic_utils.py:30-45)."""
+    the two layouts `parse_transforms_json` reads (nerf2physic_utils.py:30-45).
+
+    nerfstudio's `camera_model` key (top level or per frame): "OPENCV_FISHEYE" is read as the ideal equidistant
+    fisheye when its distortion coefficients k1..k4 are absent or zero, and raises ValueError otherwise (lens distortion
+    is not modelled); every other value loads as a pinhole camera, as before."""
     with open(path, "rb") as f:
         t = json.load(f)
     cams = []
@@ -122,8 +142,21 @@ def cameras_from_transforms_json(path: str, width: int | None = None,
         w = int(src.get("w", t.get("w", width or round(2 * src["cx"]))))
         h = int(src.get("h", t.get("h", height or round(2 * src["cy"]))))
         cams.append(Camera(fr["transform_matrix"], src["fl_x"], src["fl_y"], src["cx"],
-                           src["cy"], w, h))
+                           src["cy"], w, h, model=_transforms_camera_model(fr, t)))
     return cams
+
+
+def _transforms_camera_model(frame: Dict, top: Dict) -> str:
+    """The Camera.model of one transforms.json frame (per-frame keys override top-level ones)."""
+    name = frame.get("camera_model", top.get("camera_model", "OPENCV"))
+    if name != "OPENCV_FISHEYE":
+        return "pinhole"
+    ks = {k: float(frame.get(k, top.get(k, 0.0))) for k in ("k1", "k2", "k3", "k4")}
+    nonzero = {k: v for k, v in ks.items() if v != 0.0}
+    if nonzero:
+        raise ValueError(f"OPENCV_FISHEYE with distortion coefficients {nonzero}: fisheye lens distortion (k1..k4) is "
+                         "not supported; only the ideal equidistant fisheye (all k zero) is")
+    return "fisheye"
 
 
 def cameras_from_camera_params_json(path: str) -> Dict[str, Camera]:

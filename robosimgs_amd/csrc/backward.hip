@@ -35,6 +35,7 @@ __device__ __forceinline__ void reduce_viewmat(const ProjectedGrad& g, bool acti
   }
 }
 
+template <int CAM>
 __global__ __launch_bounds__(kBlock) void projection_bwd_kernel(
     int n, const float* __restrict__ means, const float* __restrict__ quats,
     const float* __restrict__ scales, const float* __restrict__ viewmat,
@@ -60,8 +61,8 @@ __global__ __launch_bounds__(kBlock) void projection_bwd_kernel(
     vm2[0] = v2.x; vm2[1] = v2.y;
     float comp = compensations ? compensations[g] : 0.f;
     float vcomp = (compensations && v_compensations) ? v_compensations[g] : 0.f;
-    r = project_gaussian_vjp(m, q, s, cam, W, H, eps2d, con, comp, vm2, v_depths ? v_depths[g] : 0.f,
-                             vcon, vcomp);
+    r = project_gaussian_vjp<CAM>(m, q, s, cam, W, H, eps2d, con, comp, vm2, v_depths ? v_depths[g] : 0.f,
+                                  vcon, vcomp);
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
       v_means[3 * (size_t)g + k] += r.v_mean[k];
@@ -170,7 +171,7 @@ __global__ __launch_bounds__(kBlock) void sh_bwd_kernel(
   }
 }
 
-template <int DEG, bool STAGED, bool ACCUM, bool VIEWGRAD>
+template <int DEG, bool STAGED, bool ACCUM, bool VIEWGRAD, int CAM>
 __global__ __launch_bounds__(kBlock) void project_color_bwd_kernel(
     int n, const float* __restrict__ means, const float* __restrict__ quats,
     const float* __restrict__ scales, const float* __restrict__ opacities, int stride_f,
@@ -227,7 +228,7 @@ __global__ __launch_bounds__(kBlock) void project_color_bwd_kernel(
       v_comp = vo * opacities[g];
       v_opac = vo * comp;
     }
-    r = project_gaussian_vjp(m, q, s, cam, W, H, eps2d, con, comp, vm2, v_depth, vcon, v_comp);
+    r = project_gaussian_vjp<CAM>(m, q, s, cam, W, H, eps2d, con, comp, vm2, v_depth, vcon, v_comp);
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
       om[k] = r.v_mean[k] + v_dir[k];
@@ -287,15 +288,24 @@ extern "C" int mgs_projection_bwd(int n, const float* means, const float* quats,
                                   const float* v_means2d, const float* v_depths,
                                   const float* v_conics, const float* v_compensations,
                                   float* v_means, float* v_quats, float* v_scales,
-                                  float* v_viewmat, mgs_stream_t stream) {
+                                  float* v_viewmat, int camera_model, mgs_stream_t stream) {
   MGS_REQUIRE(n >= 0 && width > 0 && height > 0, "projection_bwd: bad sizes");
+  MGS_REQUIRE(camera_model >= MGS_CAMERA_PINHOLE && camera_model <= MGS_CAMERA_FISHEYE,
+              "projection_bwd: camera_model %d is not MGS_CAMERA_PINHOLE, _ORTHO or _FISHEYE", camera_model);
   if (n == 0) return MGS_OK;
   MGS_REQUIRE(means && quats && scales && viewmat && K && radii && conics && v_means2d &&
                   v_conics && v_means && v_quats && v_scales, "projection_bwd: null pointer");
-  hipLaunchKernelGGL(projection_bwd_kernel, dim3(div_up(n, kBlock)), dim3(kBlock), 0,
-                     (hipStream_t)stream, n, means, quats, scales, viewmat, K, (float)width,
-                     (float)height, eps2d, radii, conics, compensations, v_means2d, v_depths,
-                     v_conics, v_compensations, v_means, v_quats, v_scales, v_viewmat);
+#define MGS_PB_LAUNCH(CAM)                                                                     \
+  hipLaunchKernelGGL(projection_bwd_kernel<CAM>, dim3(div_up(n, kBlock)), dim3(kBlock), 0,        \
+                     (hipStream_t)stream, n, means, quats, scales, viewmat, K, (float)width,      \
+                     (float)height, eps2d, radii, conics, compensations, v_means2d, v_depths,     \
+                     v_conics, v_compensations, v_means, v_quats, v_scales, v_viewmat)
+  switch (camera_model) {
+    case MGS_CAMERA_PINHOLE: MGS_PB_LAUNCH(MGS_CAMERA_PINHOLE); break;
+    case MGS_CAMERA_ORTHO: MGS_PB_LAUNCH(MGS_CAMERA_ORTHO); break;
+    default: MGS_PB_LAUNCH(MGS_CAMERA_FISHEYE); break;
+  }
+#undef MGS_PB_LAUNCH
   return check_launch("projection_bwd");
 }
 
@@ -332,8 +342,10 @@ extern "C" int mgs_project_color_bwd(int n, const float* means, const float* qua
                                      const float* v_conics, const float* v_depths,
                                      const float* v_opac_out, float* v_means, float* v_quats,
                                      float* v_scales, float* v_sh_coeffs, float* v_opacities,
-                                     float* v_viewmat, int accumulate, mgs_stream_t stream) {
+                                     float* v_viewmat, int accumulate, int camera_model, mgs_stream_t stream) {
   MGS_REQUIRE(n >= 0 && width > 0 && height > 0, "project_color_bwd: bad sizes");
+  MGS_REQUIRE(camera_model >= MGS_CAMERA_PINHOLE && camera_model <= MGS_CAMERA_FISHEYE,
+              "project_color_bwd: camera_model %d is not MGS_CAMERA_PINHOLE, _ORTHO or _FISHEYE", camera_model);
   MGS_REQUIRE(sh_degree >= 0 && sh_degree <= 3, "project_color_bwd: sh_degree %d not in 0..3", sh_degree);
   MGS_REQUIRE(coeff_stride >= (sh_degree + 1) * (sh_degree + 1), "project_color_bwd: coeff_stride too small");
   MGS_REQUIRE(feat_stride == 3 || feat_stride == 4, "project_color_bwd: feat_stride must be 3 or 4");
@@ -348,9 +360,13 @@ extern "C" int mgs_project_color_bwd(int n, const float* means, const float* qua
   int sf = coeff_stride * 3;
   bool staged = coeff_stride == 16;
 #define MGS_PCB(D, S, A)                                                                        \
-  if (v_viewmat) MGS_PCB_V(D, S, A, true); else MGS_PCB_V(D, S, A, false)
-#define MGS_PCB_V(D, S, A, V)                                                                   \
-  hipLaunchKernelGGL((project_color_bwd_kernel<D, S, A, V>), grid, block, 0, s, n, means, quats, \
+  if (v_viewmat) MGS_PCB_C(D, S, A, true); else MGS_PCB_C(D, S, A, false)
+#define MGS_PCB_C(D, S, A, V)                                                                   \
+  if (camera_model == MGS_CAMERA_PINHOLE) MGS_PCB_V(D, S, A, V, MGS_CAMERA_PINHOLE);             \
+  else if (camera_model == MGS_CAMERA_ORTHO) MGS_PCB_V(D, S, A, V, MGS_CAMERA_ORTHO);            \
+  else MGS_PCB_V(D, S, A, V, MGS_CAMERA_FISHEYE)
+#define MGS_PCB_V(D, S, A, V, CAM)                                                              \
+  hipLaunchKernelGGL((project_color_bwd_kernel<D, S, A, V, CAM>), grid, block, 0, s, n, means, quats, \
                      scales, opacities, sf, sh_coeffs, viewmat, K, (float)width, (float)height, \
                      eps2d, radii, conics, antialiased, feat_stride, feats, v_feats, v_means2d, \
                      v_conics, v_depths, v_opac_out, v_means, v_quats, v_scales, v_sh_coeffs,   \
@@ -366,6 +382,7 @@ extern "C" int mgs_project_color_bwd(int n, const float* means, const float* qua
   }
 #undef MGS_PCB_D
 #undef MGS_PCB
+#undef MGS_PCB_C
 #undef MGS_PCB_V
   return check_launch("project_color_bwd");
 }

@@ -10,6 +10,18 @@
 #include "mgs_common.h"
 
 namespace {
+// the MGS_FRAMES_CAMERA_* bits of a flags word: at most one, and what they mean to the stage entry points
+bool camera_flags_valid(int flags) {
+  return (flags & (MGS_FRAMES_CAMERA_ORTHO | MGS_FRAMES_CAMERA_FISHEYE)) != (MGS_FRAMES_CAMERA_ORTHO | MGS_FRAMES_CAMERA_FISHEYE);
+}
+int camera_model_of(int flags) {
+  return (flags & MGS_FRAMES_CAMERA_ORTHO) ? MGS_CAMERA_ORTHO
+         : (flags & MGS_FRAMES_CAMERA_FISHEYE) ? MGS_CAMERA_FISHEYE : MGS_CAMERA_PINHOLE;
+}
+int camera_bin_flags(int flags) {
+  return ((flags & MGS_FRAMES_CAMERA_ORTHO) ? MGS_BIN_CAMERA_ORTHO : 0) | ((flags & MGS_FRAMES_CAMERA_FISHEYE) ? MGS_BIN_CAMERA_FISHEYE : 0);
+}
+
 struct FrameWs {
   size_t total, depths, opac, splats, bin_info, bin_sums, flatten, offsets, order, isect;
   size_t isect_bytes;
@@ -44,6 +56,11 @@ extern "C" int mgs_render_frames(int n, const float* means, const float* quats, 
   MGS_REQUIRE(channels == 3 || channels == 4, "render_frames: channels must be 3 (RGB) or 4 (RGB + depth), got %d", channels);
   MGS_REQUIRE(workspace_bytes, "render_frames: workspace_bytes is null");
   MGS_REQUIRE(isect_capacity > 0, "render_frames: zero capacity");
+  MGS_REQUIRE(camera_flags_valid(flags), "render_frames: flags set both MGS_FRAMES_CAMERA_ORTHO and MGS_FRAMES_CAMERA_FISHEYE");
+  if ((ds_rgba || ds_distance) && camera_model_of(flags) != MGS_CAMERA_PINHOLE)
+    return mgs::set_error(MGS_ERR_UNSUPPORTED, "render_frames: dataset output (ds_rgba / ds_distance) converts depth to ray "
+                                               "distance through a pinhole K^-1; it is not available for an orthographic "
+                                               "or fisheye camera");
   const int tile_w = (width + MGS_TILE_SIZE - 1) / MGS_TILE_SIZE, tile_h = (height + MGS_TILE_SIZE - 1) / MGS_TILE_SIZE;
   const int n_tiles = tile_w * tile_h;
   size_t isect_ws = 0;
@@ -79,7 +96,8 @@ extern "C" int mgs_render_frames(int n, const float* means, const float* quats, 
                                viewmats + 16 * (size_t)c, Ks + 9 * (size_t)c, width, height, eps2d, near_plane, far_plane,
                                radius_clip, nullptr, nullptr, depths, nullptr, opac_aa, channels, nullptr, splats,
                                ((flags & MGS_FRAMES_CLASSIC_BOUNDS) ? 0 : MGS_BIN_TIGHT /* same pixels, shorter lists */) |
-                                   ((flags & MGS_FRAMES_RADIUS_OPACITY_AWARE) ? MGS_BIN_RADIUS_OPACITY_AWARE : 0),
+                                   ((flags & MGS_FRAMES_RADIUS_OPACITY_AWARE) ? MGS_BIN_RADIUS_OPACITY_AWARE : 0) |
+                                   camera_bin_flags(flags),
                                bin_info, bin_sums, nullptr, stream);
     if (rc) return rc;
     size_t iw = ws.isect_bytes;
@@ -194,6 +212,8 @@ extern "C" int mgs_render_frames_train(int n, const float* means, const float* q
   MGS_REQUIRE(channels == 3 || channels == 4, "render_frames_train: channels must be 3 (RGB) or 4 (RGB + depth), got %d", channels);
   MGS_REQUIRE(workspace_bytes, "render_frames_train: workspace_bytes is null");
   MGS_REQUIRE(isect_capacity > 0, "render_frames_train: zero capacity");
+  MGS_REQUIRE(camera_flags_valid(flags),
+              "render_frames_train: flags set both MGS_FRAMES_CAMERA_ORTHO and MGS_FRAMES_CAMERA_FISHEYE");
   const int tile_w = (width + MGS_TILE_SIZE - 1) / MGS_TILE_SIZE, tile_h = (height + MGS_TILE_SIZE - 1) / MGS_TILE_SIZE;
   size_t isect_ws = 0;
   int rc = mgs_isect_tiles(n, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, MGS_TILE_SIZE, tile_w, tile_h, 0, 1,
@@ -218,7 +238,7 @@ extern "C" int mgs_render_frames_train(int n, const float* means, const float* q
   uint32_t* bin_sums = reinterpret_cast<uint32_t*>(w + ws.bin_sums);
   const size_t n_px = (size_t)width * height;
   const int tight = ((flags & MGS_FRAMES_CLASSIC_BOUNDS) ? 0 : MGS_BIN_TIGHT) |
-                    ((flags & MGS_FRAMES_RADIUS_OPACITY_AWARE) ? MGS_BIN_RADIUS_OPACITY_AWARE : 0);
+                    ((flags & MGS_FRAMES_RADIUS_OPACITY_AWARE) ? MGS_BIN_RADIUS_OPACITY_AWARE : 0) | camera_bin_flags(flags);
   for (int c = 0; c < n_cams; ++c) {
     char* s = static_cast<char*>(state) + st.total * (size_t)c;
     auto F = [&](int f) { return reinterpret_cast<float*>(s + st.at[f]); };
@@ -260,6 +280,8 @@ extern "C" int mgs_render_frames_backward(int n, const float* means, const float
   MGS_REQUIRE(channels == 3 || channels == 4, "render_frames_backward: channels must be 3 or 4, got %d", channels);
   MGS_REQUIRE(workspace_bytes, "render_frames_backward: workspace_bytes is null");
   MGS_REQUIRE(isect_capacity > 0, "render_frames_backward: zero capacity");
+  MGS_REQUIRE(camera_flags_valid(flags),
+              "render_frames_backward: flags set both MGS_FRAMES_CAMERA_ORTHO and MGS_FRAMES_CAMERA_FISHEYE");
   const int tile_w = (width + MGS_TILE_SIZE - 1) / MGS_TILE_SIZE, tile_h = (height + MGS_TILE_SIZE - 1) / MGS_TILE_SIZE;
   float* const dummy = reinterpret_cast<float*>(16);      // (size query: the absgrad record layout follows this pointer)
   size_t raster_ws = 0;
@@ -319,7 +341,7 @@ extern "C" int mgs_render_frames_backward(int n, const float* means, const float
                                antialiased, channels, F(TF_FEATS), g_feat, g_m2d, g_con, nullptr,
                                antialiased ? g_opac : nullptr, v_means, v_quats, v_scales, v_sh_coeffs,
                                antialiased ? v_opacities : nullptr, v_viewmats ? v_viewmats + 16 * (size_t)c : nullptr,
-                               c > 0 ? 1 : 0, stream);
+                               c > 0 ? 1 : 0, camera_model_of(flags), stream);
     if (rc) return rc;
     if (!antialiased && n > 0 && c > 0)     // later cameras add theirs
       hipLaunchKernelGGL(add_rows_kernel, dim3(mgs::div_up((unsigned)n, 256u)), dim3(256), 0, hs, (size_t)n, g_opac, v_opacities, 0);

@@ -106,7 +106,52 @@ struct Projected {
 #define MGS_RADIUS_CLASSIC 0
 #define MGS_RADIUS_OPACITY_AWARE 1
 
+// The camera model is a compile-time policy like the radius rule (include/mgs.h MGS_CAMERA_*).  It changes the projected
+// mean, the 2 x 3 Jacobian J of cov2d = J Sigma_c J^T and the frustum clamp (camera point p = (x, y, z), OpenCV axes):
+//   MGS_CAMERA_PINHOLE  mean (fx x/z + cx, fy y/z + cy); J of that map with x/z, y/z clamped to 1.3 x the half field of view
+//   MGS_CAMERA_ORTHO    mean (fx x + cx, fy y + cy); J = [[fx, 0, 0], [0, fy, 0]]; no clamp
+//   MGS_CAMERA_FISHEYE  ideal equidistant lens, r = f theta: rho = |(x, y)|, theta = atan2(rho, z), s = theta / rho,
+//                       mean (fx s x + cx, fy s y + cy); J is the (dense) Jacobian of that map; no clamp
+// Depth is camera z and near / far cull on it under every model.
+#ifndef MGS_CAMERA_PINHOLE
+#define MGS_CAMERA_PINHOLE 0
+#define MGS_CAMERA_ORTHO 1
+#define MGS_CAMERA_FISHEYE 2
+#endif
+
+// Below t = rho^2 / z^2 = 0.1 the fisheye terms come from their series in t (nine terms: truncation < 1e-8 relative):
+// the closed forms are 0/0 on the optical axis and lose digits to cancellation near it.
+#define MGS_FISHEYE_SERIES_T 0.1f
+
+// Equidistant fisheye at camera point (x, y, z), with q = rho^2 and r2 = q + z^2:
+//   s = theta / rho                     -> 1/z on the axis
+//   a = (z / r2 - s) / q = ds/dq / ...  -> -2 / (3 z^3)   (ds/dx = a x, ds/dy = a y, ds/dz = -1 / r2)
+//   b = da/dq = (-z / r2^2 - 3a/2) / q  -> 4 / (5 z^5)    (da/dx = 2 x b, da/dy = 2 y b, da/dz = 2 / r2^2; backward only)
+//   ir2 = 1 / r2
+// Series with t = q / z^2:  s z = sum (-t)^n / (2n+1);  a z^3 = sum (-1)^(n+1) 2(n+1)/(2n+3) t^n;  b z^5 = d(a z^3)/dt.
+template <bool WITH_B>
+MGS_HD void fisheye_terms(float x, float y, float z, float& s, float& a, float& b, float& ir2) {
+  const float q = x * x + y * y;
+  ir2 = 1.0f / (q + z * z);
+  if (z > 0.f && q < MGS_FISHEYE_SERIES_T * (z * z)) {
+    const float rz = 1.0f / z, rz2 = rz * rz, t = q * rz2;
+    s = rz * (1.f + t * (-1.f / 3.f + t * (1.f / 5.f + t * (-1.f / 7.f + t * (1.f / 9.f + t * (-1.f / 11.f +
+        t * (1.f / 13.f + t * (-1.f / 15.f + t * (1.f / 17.f)))))))));
+    a = rz * rz2 * (-2.f / 3.f + t * (4.f / 5.f + t * (-6.f / 7.f + t * (8.f / 9.f + t * (-10.f / 11.f +
+        t * (12.f / 13.f + t * (-14.f / 15.f + t * (16.f / 17.f + t * (-18.f / 19.f)))))))));
+    if (WITH_B)
+      b = rz2 * rz2 * rz * (4.f / 5.f + t * (-12.f / 7.f + t * (24.f / 9.f + t * (-40.f / 11.f + t * (60.f / 13.f +
+          t * (-84.f / 15.f + t * (112.f / 17.f + t * (-144.f / 19.f + t * (180.f / 21.f)))))))));
+  } else {
+    const float rho = sqrtf(q);
+    s = atan2f(rho, z) / rho;
+    a = (z * ir2 - s) / q;
+    if (WITH_B) b = (-z * ir2 * ir2 - 1.5f * a) / q;
+  }
+}
+
 // A.2 steps 1-5.  Returns radius == 0 for culled Gaussians (all other fields zeroed).
+template <int CAM = MGS_CAMERA_PINHOLE>
 MGS_HD Projected project_gaussian(const float mean[3], const float quat[4],
                                   const float scale[3], const CameraParams& cam, float W,
                                   float H, float eps2d, float near_plane, float far_plane,
@@ -125,14 +170,31 @@ MGS_HD Projected project_gaussian(const float mean[3], const float quat[4],
   float z = R[6] * mean[0] + R[7] * mean[1] + R[8] * mean[2] + cam.t[2];
   if (!(z >= near_plane) || !(z <= far_plane)) return out;
 
-  float rz = 1.0f / z, rz2 = rz * rz;
-  float tanx = 0.5f * W / cam.fx, tany = 0.5f * H / cam.fy;
-  float lim_xp = (W - cam.cx) / cam.fx + 0.3f * tanx, lim_xn = cam.cx / cam.fx + 0.3f * tanx;
-  float lim_yp = (H - cam.cy) / cam.fy + 0.3f * tany, lim_yn = cam.cy / cam.fy + 0.3f * tany;
-  float tx = z * fminf(lim_xp, fmaxf(-lim_xn, x * rz));
-  float ty = z * fminf(lim_yp, fmaxf(-lim_yn, y * rz));
-  float j00 = cam.fx * rz, j02 = -cam.fx * tx * rz2;
-  float j11 = cam.fy * rz, j12 = -cam.fy * ty * rz2;
+  // J = [[j00, j01, j02], [j10, j11, j12]]; j01 = j10 = 0 except under the fisheye model
+  float j00, j01 = 0.f, j02, j10 = 0.f, j11, j12, rz, fs = 0.f;
+  if constexpr (CAM == MGS_CAMERA_PINHOLE) {
+    rz = 1.0f / z;
+    float rz2 = rz * rz;
+    float tanx = 0.5f * W / cam.fx, tany = 0.5f * H / cam.fy;
+    float lim_xp = (W - cam.cx) / cam.fx + 0.3f * tanx, lim_xn = cam.cx / cam.fx + 0.3f * tanx;
+    float lim_yp = (H - cam.cy) / cam.fy + 0.3f * tany, lim_yn = cam.cy / cam.fy + 0.3f * tany;
+    float tx = z * fminf(lim_xp, fmaxf(-lim_xn, x * rz));
+    float ty = z * fminf(lim_yp, fmaxf(-lim_yn, y * rz));
+    j00 = cam.fx * rz; j02 = -cam.fx * tx * rz2;
+    j11 = cam.fy * rz; j12 = -cam.fy * ty * rz2;
+  } else if constexpr (CAM == MGS_CAMERA_ORTHO) {
+    rz = 1.f;
+    j00 = cam.fx; j02 = 0.f;
+    j11 = cam.fy; j12 = 0.f;
+  } else {
+    static_assert(CAM == MGS_CAMERA_FISHEYE, "camera model");
+    float fa, fb, ir2;
+    fisheye_terms<false>(x, y, z, fs, fa, fb, ir2);
+    rz = 1.f;
+    const float xya = x * y * fa;
+    j00 = cam.fx * (fs + x * x * fa); j01 = cam.fx * xya; j02 = -cam.fx * x * ir2;
+    j10 = cam.fy * xya; j11 = cam.fy * (fs + y * y * fa); j12 = -cam.fy * y * ir2;
+  }
   float Rq[9];
   quat_to_rotmat(quat, Rq);
 #if MGS_PROJ_FACTORED
@@ -146,8 +208,13 @@ MGS_HD Projected project_gaussian(const float mean[3], const float quat[4],
   mat3_mul(R, Rq, RR);
   float m0[3], m1[3];
   for (int k = 0; k < 3; ++k) {
-    m0[k] = (j00 * RR[k] + j02 * RR[6 + k]) * scale[k];
-    m1[k] = (j11 * RR[3 + k] + j12 * RR[6 + k]) * scale[k];
+    if constexpr (CAM == MGS_CAMERA_FISHEYE) {
+      m0[k] = (j00 * RR[k] + j01 * RR[3 + k] + j02 * RR[6 + k]) * scale[k];
+      m1[k] = (j10 * RR[k] + j11 * RR[3 + k] + j12 * RR[6 + k]) * scale[k];
+    } else {
+      m0[k] = (j00 * RR[k] + j02 * RR[6 + k]) * scale[k];
+      m1[k] = (j11 * RR[3 + k] + j12 * RR[6 + k]) * scale[k];
+    }
   }
   float a = m0[0] * m0[0] + m0[1] * m0[1] + m0[2] * m0[2];
   float b = m0[0] * m1[0] + m0[1] * m1[1] + m0[2] * m1[2];
@@ -166,16 +233,36 @@ MGS_HD Projected project_gaussian(const float mean[3], const float quat[4],
   mat3_mul_bt(M, M, cov);       // Sigma = M M^T
   mat3_mul(R, cov, tmp);        // R Sigma
   mat3_mul_bt(tmp, R, covc);    // R Sigma R^T
-  // cov2d = J covc J^T with J = [[j00,0,j02],[0,j11,j12]]
-  float a = j00 * (j00 * covc[0] + j02 * covc[6]) + j02 * (j00 * covc[2] + j02 * covc[8]);
-  float b = j00 * (j11 * covc[1] + j12 * covc[2]) + j02 * (j11 * covc[7] + j12 * covc[8]);
-  float c = j11 * (j11 * covc[4] + j12 * covc[7]) + j12 * (j11 * covc[5] + j12 * covc[8]);
+  float a, b, c;
+  if constexpr (CAM == MGS_CAMERA_FISHEYE) {
+    // cov2d = J covc J^T with a dense J: T = J covc (2 x 3), then T J^T
+    float t0[3], t1[3];
+    for (int k = 0; k < 3; ++k) {
+      t0[k] = j00 * covc[k] + j01 * covc[3 + k] + j02 * covc[6 + k];
+      t1[k] = j10 * covc[k] + j11 * covc[3 + k] + j12 * covc[6 + k];
+    }
+    a = t0[0] * j00 + t0[1] * j01 + t0[2] * j02;
+    b = t0[0] * j10 + t0[1] * j11 + t0[2] * j12;
+    c = t1[0] * j10 + t1[1] * j11 + t1[2] * j12;
+  } else {
+    // cov2d = J covc J^T with J = [[j00,0,j02],[0,j11,j12]]
+    a = j00 * (j00 * covc[0] + j02 * covc[6]) + j02 * (j00 * covc[2] + j02 * covc[8]);
+    b = j00 * (j11 * covc[1] + j12 * covc[2]) + j02 * (j11 * covc[7] + j12 * covc[8]);
+    c = j11 * (j11 * covc[4] + j12 * covc[7]) + j12 * (j11 * covc[5] + j12 * covc[8]);
+  }
   float det0 = a * c - b * b;
   a += eps2d;
   c += eps2d;
   float det = a * c - b * b;
 #endif
-  float mx = cam.fx * x * rz + cam.cx, my = cam.fy * y * rz + cam.cy;
+  float mx, my;
+  if constexpr (CAM == MGS_CAMERA_PINHOLE) {
+    mx = cam.fx * x * rz + cam.cx; my = cam.fy * y * rz + cam.cy;
+  } else if constexpr (CAM == MGS_CAMERA_ORTHO) {
+    mx = cam.fx * x + cam.cx; my = cam.fy * y + cam.cy;
+  } else {
+    mx = cam.fx * (fs * x) + cam.cx; my = cam.fy * (fs * y) + cam.cy;
+  }
 
   if (!(det > 0.f)) return out;
   float inv_det = 1.0f / det;
@@ -313,6 +400,7 @@ struct ProjectedGrad {
 
 // VJP of project_gaussian for a VISIBLE Gaussian (radius > 0).  `conic` is the forward
 // output; v_comp is the cotangent of the compensation factor (0 unless antialiased).
+template <int CAM = MGS_CAMERA_PINHOLE>
 MGS_HD ProjectedGrad project_gaussian_vjp(const float mean[3], const float quat[4],
                                           const float scale[3], const CameraParams& cam, float W,
                                           float H, float eps2d, const float conic[3],
@@ -332,6 +420,7 @@ MGS_HD ProjectedGrad project_gaussian_vjp(const float mean[3], const float quat[
   mat3_mul_bt(M, M, cov);
   mat3_mul(R, cov, tmp);
   mat3_mul_bt(tmp, R, covc);
+  // (the pinhole model's J and clamp state; the other models' code after it leaves the pinhole build unchanged)
   float tanx = 0.5f * W / cam.fx, tany = 0.5f * H / cam.fy;
   float lim_xp = (W - cam.cx) / cam.fx + 0.3f * tanx, lim_xn = cam.cx / cam.fx + 0.3f * tanx;
   float lim_yp = (H - cam.cy) / cam.fy + 0.3f * tany, lim_yn = cam.cy / cam.fy + 0.3f * tany;
@@ -341,6 +430,16 @@ MGS_HD ProjectedGrad project_gaussian_vjp(const float mean[3], const float quat[
   float tx = z * fminf(lim_xp, fmaxf(-lim_xn, xr));
   float ty = z * fminf(lim_yp, fmaxf(-lim_yn, yr));
   float j00 = cam.fx * rz, j02 = -cam.fx * tx * rz2, j11 = cam.fy * rz, j12 = -cam.fy * ty * rz2;
+  float j01 = 0.f, j10 = 0.f, fs = 0.f, fa = 0.f, fb = 0.f, ir2 = 0.f;   // fisheye: s, a, b, 1 / r2 (fisheye_terms)
+  if constexpr (CAM == MGS_CAMERA_ORTHO) {
+    j00 = cam.fx; j02 = 0.f; j11 = cam.fy; j12 = 0.f;
+  } else if constexpr (CAM == MGS_CAMERA_FISHEYE) {
+    fisheye_terms<true>(x, y, z, fs, fa, fb, ir2);
+    const float xya = x * y * fa;
+    j00 = cam.fx * (fs + x * x * fa); j01 = cam.fx * xya; j02 = -cam.fx * x * ir2;
+    j10 = cam.fy * xya; j11 = cam.fy * (fs + y * y * fa); j12 = -cam.fy * y * ir2;
+  }
+  static_assert(CAM == MGS_CAMERA_PINHOLE || CAM == MGS_CAMERA_ORTHO || CAM == MGS_CAMERA_FISHEYE, "camera model");
 
   // conic = inv(cov2d + eps I):  G2 = -conic * Vc * conic, Vc = [[va, vb/2],[vb/2, vc]]
   float ca = conic[0], cb = conic[1], cc = conic[2];
@@ -360,7 +459,7 @@ MGS_HD ProjectedGrad project_gaussian_vjp(const float mean[3], const float quat[
     g11 += v_sqr * (om * cc - eps2d * det_conic);
   }
   // cov2d = J covc J^T ;  v_covc = J^T G2 J ;  v_J = (G2 + G2^T) J covc
-  float J[6] = {j00, 0.f, j02, 0.f, j11, j12};
+  float J[6] = {j00, j01, j02, j10, j11, j12};
   float G2[4] = {g00, g01, g10, g11};
   float GJ[6];    // G2 * J (2x3)
   for (int c = 0; c < 3; ++c) {
@@ -376,7 +475,7 @@ MGS_HD ProjectedGrad project_gaussian_vjp(const float mean[3], const float quat[
     GsJ[c] = Gs[0] * J[c] + Gs[1] * J[3 + c];
     GsJ[3 + c] = Gs[2] * J[c] + Gs[3] * J[3 + c];
   }
-  float vJ00 = 0.f, vJ02 = 0.f, vJ11 = 0.f, vJ12 = 0.f;   // only the non-constant entries of J
+  float vJ00 = 0.f, vJ02 = 0.f, vJ11 = 0.f, vJ12 = 0.f;   // only the non-constant entries of a pinhole J
   for (int k = 0; k < 3; ++k) {
     vJ00 += GsJ[k] * covc[k * 3 + 0];
     vJ02 += GsJ[k] * covc[k * 3 + 2];
@@ -387,10 +486,43 @@ MGS_HD ProjectedGrad project_gaussian_vjp(const float mean[3], const float quat[
   float vx = cam.fx * rz * v_mean2d[0];
   float vy = cam.fy * rz * v_mean2d[1];
   float vz = -(cam.fx * x * v_mean2d[0] + cam.fy * y * v_mean2d[1]) * rz2 + v_depth;
-  if (x_in) vx += -cam.fx * rz2 * vJ02; else vz += -cam.fx * rz3 * vJ02 * tx;
-  if (y_in) vy += -cam.fy * rz2 * vJ12; else vz += -cam.fy * rz3 * vJ12 * ty;
-  vz += -cam.fx * rz2 * vJ00 - cam.fy * rz2 * vJ11 + 2.f * cam.fx * tx * rz3 * vJ02 +
-        2.f * cam.fy * ty * rz3 * vJ12;
+  if constexpr (CAM == MGS_CAMERA_PINHOLE) {
+    if (x_in) vx += -cam.fx * rz2 * vJ02; else vz += -cam.fx * rz3 * vJ02 * tx;
+    if (y_in) vy += -cam.fy * rz2 * vJ12; else vz += -cam.fy * rz3 * vJ12 * ty;
+    vz += -cam.fx * rz2 * vJ00 - cam.fy * rz2 * vJ11 + 2.f * cam.fx * tx * rz3 * vJ02 +
+          2.f * cam.fy * ty * rz3 * vJ12;
+  } else if constexpr (CAM == MGS_CAMERA_ORTHO) {
+    // J is constant: the mean alone depends on the camera point
+    vx = cam.fx * v_mean2d[0];
+    vy = cam.fy * v_mean2d[1];
+    vz = v_depth;
+  } else {
+    // J is the Jacobian of the mean map: the mean's share is J^T v_mean2d
+    vx = j00 * v_mean2d[0] + j10 * v_mean2d[1];
+    vy = j01 * v_mean2d[0] + j11 * v_mean2d[1];
+    vz = j02 * v_mean2d[0] + j12 * v_mean2d[1] + v_depth;
+    float vJ[6];          // all six entries of J depend on the camera point
+    for (int r = 0; r < 2; ++r)
+      for (int c = 0; c < 3; ++c)
+        vJ[r * 3 + c] = GsJ[r * 3] * covc[c] + GsJ[r * 3 + 1] * covc[3 + c] + GsJ[r * 3 + 2] * covc[6 + c];
+    // closed-form dJ/d(x, y, z) from ds = (a x, a y, -1/r2), da = (2 x b, 2 y b, 2/r2^2), d(1/r2) = -2 (x, y, z)/r2^2
+    const float ir4 = ir2 * ir2, xx = x * x, yy = y * y, xy = x * y;
+    const float wx = cam.fx * vJ[0], w01 = cam.fx * vJ[1], w02 = cam.fx * vJ[2];
+    const float w10 = cam.fy * vJ[3], wy = cam.fy * vJ[4], w12 = cam.fy * vJ[5];
+    const float wxy = w01 + w10;      // J01 and J10 share x y a
+    // J00 = fx (s + x^2 a),  J11 = fy (s + y^2 a)
+    vx += wx * x * (3.f * fa + 2.f * xx * fb) + wy * x * (fa + 2.f * yy * fb);
+    vy += wx * y * (fa + 2.f * xx * fb) + wy * y * (3.f * fa + 2.f * yy * fb);
+    vz += wx * (2.f * xx * ir4 - ir2) + wy * (2.f * yy * ir4 - ir2);
+    // J01 = fx x y a,  J10 = fy x y a
+    vx += wxy * y * (fa + 2.f * xx * fb);
+    vy += wxy * x * (fa + 2.f * yy * fb);
+    vz += wxy * 2.f * xy * ir4;
+    // J02 = -fx x / r2,  J12 = -fy y / r2
+    vx += w02 * (2.f * xx * ir4 - ir2) + w12 * 2.f * xy * ir4;
+    vy += w02 * 2.f * xy * ir4 + w12 * (2.f * yy * ir4 - ir2);
+    vz += (w02 * x + w12 * y) * 2.f * z * ir4;
+  }
   // world mean, view matrix
   g.v_mean[0] = R[0] * vx + R[3] * vy + R[6] * vz;
   g.v_mean[1] = R[1] * vx + R[4] * vy + R[7] * vz;

@@ -27,6 +27,7 @@ __device__ __forceinline__ void load3(const float* p, float v[3]) {
   v[0] = p[0]; v[1] = p[1]; v[2] = p[2];
 }
 
+template <int CAM>
 __global__ __launch_bounds__(kBlock) void projection_fwd_kernel(
     int n, const float* __restrict__ means, const float* __restrict__ quats,
     const float* __restrict__ scales, const float* __restrict__ viewmat,
@@ -43,8 +44,8 @@ __global__ __launch_bounds__(kBlock) void projection_fwd_kernel(
   load3(scales + 3 * (size_t)g, s);
   float4 qq = reinterpret_cast<const float4*>(quats)[g];
   q[0] = qq.x; q[1] = qq.y; q[2] = qq.z; q[3] = qq.w;
-  Projected p = project_gaussian(m, q, s, cam, W, H, eps2d, near_plane, far_plane, radius_clip, radius_rule,
-                                 opacities != nullptr, opacities ? opacities[g] : 1.f, compensations != nullptr);
+  Projected p = project_gaussian<CAM>(m, q, s, cam, W, H, eps2d, near_plane, far_plane, radius_clip, radius_rule,
+                                      opacities != nullptr, opacities ? opacities[g] : 1.f, compensations != nullptr);
   radii[g] = p.radius;
   if (radii_y) radii_y[g] = p.radius_y;
   reinterpret_cast<float2*>(means2d)[g] = make_float2(p.mean2d[0], p.mean2d[1]);
@@ -135,7 +136,7 @@ __global__ __launch_bounds__(kBlock) void sh_fwd_kernel(
   colors[3 * (size_t)g + 2] = rgb[2];
 }
 
-template <int DEG, bool STAGED, int RULE>
+template <int DEG, bool STAGED, int RULE, int CAM>
 __global__ __launch_bounds__(kBlock) void project_color_fwd_kernel(
     int n, const float* __restrict__ means, const float* __restrict__ quats,
     const float* __restrict__ scales, const float* __restrict__ opacities, int stride_f,
@@ -159,10 +160,10 @@ __global__ __launch_bounds__(kBlock) void project_color_fwd_kernel(
     float4 qq = reinterpret_cast<const float4*>(quats)[g];
     q[0] = qq.x; q[1] = qq.y; q[2] = qq.z; q[3] = qq.w;
     if (RULE == MGS_RADIUS_CLASSIC)
-      p = project_gaussian(m, q, s, cam, W, H, eps2d, near_plane, far_plane, radius_clip);
+      p = project_gaussian<CAM>(m, q, s, cam, W, H, eps2d, near_plane, far_plane, radius_clip);
     else
-      p = project_gaussian(m, q, s, cam, W, H, eps2d, near_plane, far_plane, radius_clip, RULE, opacities != nullptr,
-                           opacities ? opacities[g] : 1.f, opac_out != nullptr);
+      p = project_gaussian<CAM>(m, q, s, cam, W, H, eps2d, near_plane, far_plane, radius_clip, RULE, opacities != nullptr,
+                                opacities ? opacities[g] : 1.f, opac_out != nullptr);
     // radii / means2d / conics (and feats below) are null in an inference frame: the raster reads the packed
     // records, the seeded binning reads bin_info + depths -- 36 MB of stores per 1 M Gaussians nobody would read
     if (radii) radii[g] = p.radius;
@@ -242,18 +243,27 @@ extern "C" int mgs_projection_fwd(int n, const float* means, const float* quats,
                                   float far_plane, float radius_clip, int32_t* radii,
                                   float* means2d, float* depths, float* conics,
                                   float* compensations, const float* opacities, int radius_rule,
-                                  int32_t* radii_y, mgs_stream_t stream) {
+                                  int32_t* radii_y, int camera_model, mgs_stream_t stream) {
   MGS_REQUIRE(n >= 0 && width > 0 && height > 0, "projection_fwd: bad sizes n=%d %dx%d", n, width, height);
+  MGS_REQUIRE(camera_model >= MGS_CAMERA_PINHOLE && camera_model <= MGS_CAMERA_FISHEYE,
+              "projection_fwd: camera_model %d is not MGS_CAMERA_PINHOLE, _ORTHO or _FISHEYE", camera_model);
   if (n == 0) return MGS_OK;
   MGS_REQUIRE(means && quats && scales && viewmat && K && radii && means2d && depths && conics,
               "projection_fwd: null pointer");
   MGS_REQUIRE(radius_rule == MGS_RADIUS_CLASSIC || radius_rule == MGS_RADIUS_OPACITY_AWARE,
               "projection_fwd: radius_rule %d is neither MGS_RADIUS_CLASSIC nor MGS_RADIUS_OPACITY_AWARE", radius_rule);
   MGS_REQUIRE(radius_rule == MGS_RADIUS_CLASSIC || radii_y, "projection_fwd: the per-axis radius rule needs radii_y");
-  hipLaunchKernelGGL(projection_fwd_kernel, dim3(div_up(n, kBlock)), dim3(kBlock), 0,
-                     (hipStream_t)stream, n, means, quats, scales, viewmat, K, (float)width,
-                     (float)height, eps2d, near_plane, far_plane, radius_clip, radii, means2d,
-                     depths, conics, compensations, opacities, radius_rule, radii_y);
+#define MGS_PF_LAUNCH(CAM)                                                                      \
+  hipLaunchKernelGGL(projection_fwd_kernel<CAM>, dim3(div_up(n, kBlock)), dim3(kBlock), 0,         \
+                     (hipStream_t)stream, n, means, quats, scales, viewmat, K, (float)width,       \
+                     (float)height, eps2d, near_plane, far_plane, radius_clip, radii, means2d,     \
+                     depths, conics, compensations, opacities, radius_rule, radii_y)
+  switch (camera_model) {
+    case MGS_CAMERA_PINHOLE: MGS_PF_LAUNCH(MGS_CAMERA_PINHOLE); break;
+    case MGS_CAMERA_ORTHO: MGS_PF_LAUNCH(MGS_CAMERA_ORTHO); break;
+    default: MGS_PF_LAUNCH(MGS_CAMERA_FISHEYE); break;
+  }
+#undef MGS_PF_LAUNCH
   return check_launch("projection_fwd");
 }
 
@@ -292,6 +302,10 @@ extern "C" int mgs_project_color_fwd(int n, const float* means, const float* qua
                                      uint32_t* bin_sums, int32_t* radii_y, mgs_stream_t stream) {
   const int bin_tight = bin_flags & MGS_BIN_TIGHT;
   const bool per_axis = (bin_flags & MGS_BIN_RADIUS_OPACITY_AWARE) != 0;
+  MGS_REQUIRE((bin_flags & (MGS_BIN_CAMERA_ORTHO | MGS_BIN_CAMERA_FISHEYE)) != (MGS_BIN_CAMERA_ORTHO | MGS_BIN_CAMERA_FISHEYE),
+              "project_color_fwd: bin_flags sets both MGS_BIN_CAMERA_ORTHO and MGS_BIN_CAMERA_FISHEYE");
+  const int cam_model = (bin_flags & MGS_BIN_CAMERA_ORTHO) ? MGS_CAMERA_ORTHO
+                        : (bin_flags & MGS_BIN_CAMERA_FISHEYE) ? MGS_CAMERA_FISHEYE : MGS_CAMERA_PINHOLE;
   MGS_REQUIRE(n >= 0 && width > 0 && height > 0, "project_color_fwd: bad sizes");
   MGS_REQUIRE(sh_degree >= 0 && sh_degree <= 3, "project_color_fwd: sh_degree %d not in 0..3", sh_degree);
   MGS_REQUIRE(coeff_stride >= (sh_degree + 1) * (sh_degree + 1), "project_color_fwd: coeff_stride too small");
@@ -314,9 +328,13 @@ extern "C" int mgs_project_color_fwd(int n, const float* means, const float* qua
   int sf = coeff_stride * 3;
   bool staged = coeff_stride == 16 && sh_degree >= 2;
 #define MGS_PC_LAUNCH(D, S)                                                                   \
-  if (per_axis) MGS_PC_LAUNCH_R(D, S, MGS_RADIUS_OPACITY_AWARE); else MGS_PC_LAUNCH_R(D, S, MGS_RADIUS_CLASSIC)
-#define MGS_PC_LAUNCH_R(D, S, R)                                                              \
-  hipLaunchKernelGGL((project_color_fwd_kernel<D, S, R>), grid, block, 0, s, n, means, quats, \
+  if (per_axis) MGS_PC_LAUNCH_C(D, S, MGS_RADIUS_OPACITY_AWARE); else MGS_PC_LAUNCH_C(D, S, MGS_RADIUS_CLASSIC)
+#define MGS_PC_LAUNCH_C(D, S, R)                                                              \
+  if (cam_model == MGS_CAMERA_PINHOLE) MGS_PC_LAUNCH_R(D, S, R, MGS_CAMERA_PINHOLE);         \
+  else if (cam_model == MGS_CAMERA_ORTHO) MGS_PC_LAUNCH_R(D, S, R, MGS_CAMERA_ORTHO);        \
+  else MGS_PC_LAUNCH_R(D, S, R, MGS_CAMERA_FISHEYE)
+#define MGS_PC_LAUNCH_R(D, S, R, CAM)                                                         \
+  hipLaunchKernelGGL((project_color_fwd_kernel<D, S, R, CAM>), grid, block, 0, s, n, means, quats, \
                      scales, opacities, sf, sh_coeffs, viewmat, K, (float)width,              \
                      (float)height, eps2d, near_plane, far_plane, radius_clip, radii,         \
                      means2d, depths, conics, opac_out, feat_stride, feats,                    \
@@ -329,6 +347,7 @@ extern "C" int mgs_project_color_fwd(int n, const float* means, const float* qua
     default: if (staged) { MGS_PC_LAUNCH(3, true); } else { MGS_PC_LAUNCH(3, false); } break;
   }
 #undef MGS_PC_LAUNCH
+#undef MGS_PC_LAUNCH_C
 #undef MGS_PC_LAUNCH_R
   return check_launch("project_color_fwd");
 }

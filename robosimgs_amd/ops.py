@@ -44,6 +44,17 @@ def radius_rule_id(radius_rule) -> int:
     return RADIUS_RULES[radius_rule]
 
 
+CAMERA_MODELS = {"pinhole": 0, "ortho": 1, "fisheye": 2}    # include/mgs.h MGS_CAMERA_PINHOLE / _ORTHO / _FISHEYE
+CAMERA_BIN_FLAGS = {0: 0, 1: 4, 2: 8}                      # MGS_BIN_CAMERA_ORTHO / _FISHEYE (mgs_project_color_fwd bin_flags)
+CAMERA_FRAME_FLAGS = {0: 0, 1: 16, 2: 32}                  # MGS_FRAMES_CAMERA_ORTHO / _FISHEYE (mgs_render_frames* flags)
+
+
+def camera_model_id(camera_model) -> int:
+    if camera_model not in CAMERA_MODELS:
+        raise ValueError(f"camera_model {camera_model!r} not in {tuple(CAMERA_MODELS)}")
+    return CAMERA_MODELS[camera_model]
+
+
 def radii_x(radii):
     """The per-Gaussian visibility / x-extent array of either radii layout: [N] (classic rule) or the planar [2,N]
     pair of per-axis extents the raw calls keep under the opacity-aware rule."""
@@ -56,8 +67,9 @@ def radii_meta(radii):
 
 
 def projection_fwd_raw(means, quats, scales, viewmat, K, width, height, eps2d, near_plane,
-                       far_plane, radius_clip, calc_compensations, opacities=None, radius_rule=0):
-    """radius_rule 1 (MGS_RADIUS_OPACITY_AWARE): radii comes back planar [2,N] (x extents, y extents)."""
+                       far_plane, radius_clip, calc_compensations, opacities=None, radius_rule=0, camera=0):
+    """radius_rule 1 (MGS_RADIUS_OPACITY_AWARE): radii comes back planar [2,N] (x extents, y extents).
+    camera: MGS_CAMERA_* (camera_model_id)."""
     n = means.shape[0]
     dev = means.device
     radii = torch.empty((2, n) if radius_rule else (n,), dtype=torch.int32, device=dev)
@@ -69,20 +81,22 @@ def projection_fwd_raw(means, quats, scales, viewmat, K, width, height, eps2d, n
                                         ptr(K), width, height, eps2d, near_plane, far_plane,
                                         radius_clip, ptr(radii_x(radii)), ptr(means2d), ptr(depths),
                                         ptr(conics), ptr(comp), ptr(opacities) if radius_rule else None,
-                                        int(radius_rule), ptr(radii[1]) if radius_rule else None, stream_handle()),
+                                        int(radius_rule), ptr(radii[1]) if radius_rule else None, int(camera),
+                                        stream_handle()),
           "mgs_projection_fwd")
     return radii, means2d, depths, conics, comp
 
 
 def project_color_fwd_raw(means, quats, scales, opacities, sh_degree, sh_coeffs, viewmat, K,
                           width, height, eps2d, near_plane, far_plane, radius_clip,
-                          antialiased, with_depth, want_splats=False, bin_seed=None, lean=False, per_axis=False):
+                          antialiased, with_depth, want_splats=False, bin_seed=None, lean=False, per_axis=False, camera=0):
     """Returns (radii, means2d, depths, conics, opac_aa|None, feats) and, with want_splats, a 7th
     item: the packed [N,12] records the raster kernels gather from.  bin_seed = "tight" | "classic":
     an 8th item (seed_info [N,2] i32, seed_sums [ceil(N/64)] i32) for isect_tiles_raw(seed=...).
     lean (needs want_splats and bin_seed): radii / means2d / conics / feats are not written and come back
     as None -- an inference frame, whose raster reads the records and whose binning reads the seed.
-    per_axis: project with MGS_RADIUS_OPACITY_AWARE; radii is then planar [2,N] (radii_x / radii_meta)."""
+    per_axis: project with MGS_RADIUS_OPACITY_AWARE; radii is then planar [2,N] (radii_x / radii_meta).
+    camera: the camera model, MGS_CAMERA_* (camera_model_id)."""
     n = means.shape[0]
     dev = means.device
     if lean and not (want_splats and bin_seed is not None):
@@ -107,7 +121,8 @@ def project_color_fwd_raw(means, quats, scales, opacities, sh_degree, sh_coeffs,
         n, ptr(means), ptr(quats), ptr(scales), ptr(opacities), sh_degree, sh_coeffs.shape[1],
         ptr(sh_coeffs), ptr(viewmat), ptr(K), width, height, eps2d, near_plane, far_plane,
         radius_clip, ptr(radii_x(radii)), ptr(means2d), ptr(depths), ptr(conics), ptr(opac), stride,
-        ptr(feats), ptr(splats), int(bin_seed == "tight") | (2 if per_axis else 0), ptr(seed[0]) if seed else None,
+        ptr(feats), ptr(splats), int(bin_seed == "tight") | (2 if per_axis else 0) | CAMERA_BIN_FLAGS[int(camera)],
+        ptr(seed[0]) if seed else None,
         ptr(seed[1]) if seed else None, ptr(radii[1]) if (per_axis and radii is not None) else None, stream_handle()),
         "mgs_project_color_fwd")
     out = (radii, means2d, depths, conics, opac, feats)
@@ -200,7 +215,7 @@ def isect_tiles_raw(means2d, radii, depths, tile_w, tile_h, capacity: int, cam_i
 def render_frames_raw(means, quats, scales, opacities, sh_degree, sh_coeffs, viewmats, Ks, width, height,
                       eps2d, near_plane, far_plane, radius_clip, antialiased, with_depth, capacity,
                       backgrounds=None, expected_last=False, latency=False, out=None, tight=True, per_axis=False,
-                      dataset=None, float_frame=True):
+                      dataset=None, float_frame=True, camera=0):
     """mgs_render_frames: C inference frames in one C call (no per-Gaussian outputs, scratch reused from camera to
     camera).  viewmats [C,4,4], Ks [C,3,3], backgrounds [C,ch] or None.  Returns (render [C,H,W,ch], alphas [C,H,W],
     n_isects [C] i32, isect_status [C] i32); out = (render, alphas) to write into existing buffers.
@@ -222,7 +237,8 @@ def render_frames_raw(means, quats, scales, opacities, sh_degree, sh_coeffs, vie
     args = [n, ptr(means), ptr(quats), ptr(scales), ptr(opacities), int(sh_degree), sh_coeffs.shape[1], ptr(sh_coeffs),
             C, ptr(viewmats), ptr(Ks), int(width), int(height), eps2d, near_plane, far_plane, radius_clip,
             int(bool(antialiased)), ch,
-            int(bool(expected_last)) | (2 if latency else 0) | (0 if tight else 4) | (8 if per_axis else 0),
+            int(bool(expected_last)) | (2 if latency else 0) | (0 if tight else 4) | (8 if per_axis else 0)
+            | CAMERA_FRAME_FLAGS[int(camera)],
             ptr(backgrounds),
             int(capacity), ptr(render) if (float_frame or dataset is None) else None,
             ptr(alphas) if (float_frame or dataset is None) else None, ptr(n_isect), ptr(status)]
@@ -311,7 +327,8 @@ def _aligned_ws(nbytes, dev):
 
 def render_frames_train_raw(means, quats, scales, opacities, sh_degree, sh_coeffs, viewmats, Ks, width, height, eps2d,
                             near_plane, far_plane, radius_clip, antialiased, with_depth, capacity, interval,
-                            backgrounds=None, expected_last=False, latency=True, tight=True, out=None, per_axis=False):
+                            backgrounds=None, expected_last=False, latency=True, tight=True, out=None, per_axis=False,
+                            camera=0):
     """mgs_render_frames_train: C training frames in one C call.  Returns (render [C,H,W,ch], alphas [C,H,W], TrainState)."""
     dev = means.device
     C, n = viewmats.shape[0], means.shape[0]
@@ -322,7 +339,8 @@ def render_frames_train_raw(means, quats, scales, opacities, sh_degree, sh_coeff
     else:
         render, alphas = out
     st = TrainState(n, C, width, height, ch, capacity, antialiased, interval, dev)
-    flags = int(bool(expected_last)) | (2 if latency else 0) | (0 if tight else 4) | (8 if per_axis else 0)
+    flags = int(bool(expected_last)) | (2 if latency else 0) | (0 if tight else 4) | (8 if per_axis else 0) \
+        | CAMERA_FRAME_FLAGS[int(camera)]
     L = _lib.lib()
     nbytes = ctypes.c_size_t(0)
     args = [n, ptr(means), ptr(quats), ptr(scales), ptr(opacities), int(sh_degree), sh_coeffs.shape[1], ptr(sh_coeffs), C,
@@ -512,11 +530,11 @@ def rasterize_bwd_det_raw(means2d, conics, feats, opacities, background, width, 
 class _Projection(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means, quats, scales, viewmats, Ks, width, height, eps2d, near_plane,
-                far_plane, radius_clip, calc_compensations, opacities=None, radius_rule=0):
+                far_plane, radius_clip, calc_compensations, opacities=None, radius_rule=0, camera=0):
         C = viewmats.shape[0]
         outs = [projection_fwd_raw(means, quats, scales, viewmats[c], Ks[c], width, height,
                                    eps2d, near_plane, far_plane, radius_clip,
-                                   calc_compensations, opacities, radius_rule) for c in range(C)]
+                                   calc_compensations, opacities, radius_rule, camera) for c in range(C)]
         radii_out = torch.stack([radii_meta(o[0]) for o in outs])      # [C,N], or [C,N,2] under the per-axis rule
         radii = torch.stack([radii_x(o[0]) for o in outs])             # [C,N]: > 0 = visible (what the backward reads)
         means2d = torch.stack([o[1] for o in outs])
@@ -524,14 +542,14 @@ class _Projection(torch.autograd.Function):
         conics = torch.stack([o[3] for o in outs])
         comps = torch.stack([o[4] for o in outs]) if calc_compensations else None
         ctx.save_for_backward(means, quats, scales, viewmats, Ks, radii, conics, comps)
-        ctx.dims = (width, height, eps2d)
+        ctx.dims = (width, height, eps2d, camera)
         ctx.mark_non_differentiable(radii_out)
         return radii_out, means2d, depths, conics, comps
 
     @staticmethod
     def backward(ctx, _v_radii, v_means2d, v_depths, v_conics, v_comps):
         means, quats, scales, viewmats, Ks, radii, conics, comps = ctx.saved_tensors
-        width, height, eps2d = ctx.dims
+        width, height, eps2d, camera = ctx.dims
         n, C = means.shape[0], viewmats.shape[0]
         v_means = torch.zeros_like(means)
         v_quats = torch.zeros_like(quats)
@@ -547,10 +565,10 @@ class _Projection(torch.autograd.Function):
                 ptr(comps[c]) if comps is not None else None,
                 ptr(v_means2d[c]), ptr(v_depths[c]), ptr(v_conics[c]),
                 ptr(v_comps[c]) if v_comps is not None else None, ptr(v_means), ptr(v_quats),
-                ptr(v_scales), ptr(v_viewmats[c]) if want_view else None, stream_handle()),
+                ptr(v_scales), ptr(v_viewmats[c]) if want_view else None, int(camera), stream_handle()),
                 "mgs_projection_bwd")
         return (v_means, v_quats, v_scales, v_viewmats, None, None, None, None, None, None,
-                None, None, None, None)
+                None, None, None, None, None)
 
 
 def fully_fused_projection(means: Tensor, covars: Optional[Tensor], quats: Tensor,
@@ -559,14 +577,16 @@ def fully_fused_projection(means: Tensor, covars: Optional[Tensor], quats: Tenso
                            far_plane: float = 1e10, radius_clip: float = 0.0,
                            packed: bool = False, sparse_grad: bool = False,
                            calc_compensations: bool = False, opacities: Optional[Tensor] = None,
-                           radius_rule: str = "classic"
+                           radius_rule: str = "classic", camera_model: str = "pinhole"
                            ) -> Tuple[Tensor, Tensor, Tensor, Tensor, Optional[Tensor]]:
     """World -> screen EWA projection of N Gaussians for C cameras.
     Returns radii [C,N] i32, means2d [C,N,2], depths [C,N], conics [C,N,3],
     compensations [C,N] | None.
     radius_rule: "classic" (gsplat 1.4, SURVEY.md A.2 step 5: one radius ceil(3 sqrt(lambda_1))) or "opacity_aware"
     (gsplat >= 1.5, SURVEY.md A.4: per-axis extents min(3.33, sqrt(2 ln(255 opacity))) sqrt(Sigma_ii), radii [C,N,2];
-    `opacities` [N] optional as in that operator, no gradient flows to it -- the extent is not differentiable)."""
+    `opacities` [N] optional as in that operator, no gradient flows to it -- the extent is not differentiable).
+    camera_model: "pinhole", "ortho" or "fisheye" (ideal equidistant, r = f theta), as gsplat's operator; include/mgs.h
+    MGS_CAMERA_* gives the maps.  Depths are camera z under every model."""
     if covars is not None:
         raise NotImplementedError("precomputed covariances are not supported; pass quats+scales")
     if packed:
@@ -580,6 +600,7 @@ def fully_fused_projection(means: Tensor, covars: Optional[Tensor], quats: Tenso
     if viewmats.dim() != 3 or viewmats.shape[1:] != (4, 4) or Ks.shape != (viewmats.shape[0], 3, 3):
         raise ValueError("expected viewmats [C,4,4], Ks [C,3,3]")
     rule = radius_rule_id(radius_rule)
+    camera = camera_model_id(camera_model)
     if opacities is not None:
         require_device(opacities)
         opacities = _f32c(opacities.detach())
@@ -587,7 +608,7 @@ def fully_fused_projection(means: Tensor, covars: Optional[Tensor], quats: Tenso
             raise ValueError("expected opacities [N]")
     return _Projection.apply(means, quats, scales, viewmats, Ks, int(width), int(height),
                              float(eps2d), float(near_plane), float(far_plane),
-                             float(radius_clip), bool(calc_compensations), opacities if rule else None, rule)
+                             float(radius_clip), bool(calc_compensations), opacities if rule else None, rule, camera)
 
 
 class _SphericalHarmonics(torch.autograd.Function):

@@ -152,6 +152,9 @@ class FrameRenderer:
         self.kw = dict(raster_kw)
         self.dataset_dtype, self.dataset_K, self.dataset_keep_float = dataset_output, None, bool(dataset_keep_float)
         if dataset_output is not None:
+            if self.kw.get("camera_model", "pinhole") != "pinhole":
+                raise ValueError(f"dataset_output converts depth to ray distance through a pinhole K^-1: camera_model "
+                                 f"{self.kw['camera_model']!r} has no dataset output")
             if dataset_K is None or render_mode != "RGB+ED":
                 raise ValueError("dataset_output needs dataset_K (the shared 3x3 intrinsics) and render_mode='RGB+ED'")
             if dataset_output not in (torch.float16, torch.float32, torch.float64):

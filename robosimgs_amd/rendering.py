@@ -60,8 +60,9 @@ class _RenderSH(torch.autograd.Function):
                 latency, lean, segment, dataset=None):
         C = viewmats.shape[0]
         dev = means.device
-        # `tight` carries the binning policy: bit 0 tightened tile rectangles, bit 1 the per-axis (gsplat >= 1.5) radius rule
-        per_axis, tight = bool(int(tight) & 2), bool(int(tight) & 1)
+        # `tight` carries the binning policy: bit 0 tightened tile rectangles, bit 1 the per-axis (gsplat >= 1.5) radius rule,
+        # bits 2-3 the camera model (MGS_CAMERA_*)
+        per_axis, camera, tight = bool(int(tight) & 2), (int(tight) >> 2) & 3, bool(int(tight) & 1)
         tile_w, tile_h = -(-width // TILE_SIZE), -(-height // TILE_SIZE)
         ch = 4 if with_depth else 3
         render = torch.empty(C, height, width, ch, dtype=torch.float32, device=dev)
@@ -84,7 +85,7 @@ class _RenderSH(torch.autograd.Function):
                 means, quats, scales, opacities, sh_degree, sh_coeffs, viewmats, Ks, width, height, eps2d,
                 near_plane, far_plane, radius_clip, antialiased, with_depth, isect_capacity, backgrounds=backgrounds,
                 expected_last=expected_depth, latency=latency, out=(render, alphas), tight=tight, per_axis=per_axis,
-                dataset=dataset[:3] if dataset is not None else None,
+                camera=camera, dataset=dataset[:3] if dataset is not None else None,
                 float_frame=dataset is None or bool(dataset[3]))
             meta_out["lean"] = dict(n_isects=n_isects, isect_status=status)
             ctx.set_materialize_grads(False)
@@ -95,7 +96,8 @@ class _RenderSH(torch.autograd.Function):
             _, _, st = ops.render_frames_train_raw(
                 means, quats, scales, opacities, sh_degree, sh_coeffs, viewmats, Ks, width, height, eps2d, near_plane,
                 far_plane, radius_clip, antialiased, with_depth, isect_capacity, segment, backgrounds=backgrounds,
-                expected_last=expected_depth, latency=latency, tight=tight, out=(render, alphas), per_axis=per_axis)
+                expected_last=expected_depth, latency=latency, tight=tight, out=(render, alphas), per_axis=per_axis,
+                camera=camera)
             per_cam = []
             for c in range(C):
                 v = st.views(c)
@@ -117,7 +119,7 @@ class _RenderSH(torch.autograd.Function):
             radii, means2d, depths, conics, opac_aa, feats, splats, seed = ops.project_color_fwd_raw(
                 means, quats, scales, opacities, sh_degree, sh_coeffs, viewmats[c], Ks[c], width,
                 height, eps2d, near_plane, far_plane, radius_clip, antialiased, with_depth,
-                want_splats=True, bin_seed="tight" if tight else "classic", lean=lean, per_axis=per_axis)
+                want_splats=True, bin_seed="tight" if tight else "classic", lean=lean, per_axis=per_axis, camera=camera)
             opac = opac_aa if antialiased else opacities
             cap = isect_capacity
             if cap is None:
@@ -154,6 +156,7 @@ class _RenderSH(torch.autograd.Function):
                               render if ((expected_depth or segment) and training) else None)
         ctx.cfg = (width, height, tile_w, tile_h, sh_degree, eps2d, antialiased, with_depth,
                    absgrad)
+        ctx.camera = camera
         meta_out["per_cam"] = per_cam
         ctx.meta_out = meta_out
         return render, alphas.unsqueeze(-1)
@@ -225,7 +228,7 @@ class _RenderSH(torch.autograd.Function):
                 ptr(v_feats), ptr(v_means2d), ptr(v_conics), None,
                 ptr(v_opac) if antialiased else None, ptr(v_means), ptr(v_quats), ptr(v_scales),
                 ptr(v_sh), ptr(v_opacities),
-                ptr(v_viewmats[c]) if v_viewmats is not None else None, int(c > 0),
+                ptr(v_viewmats[c]) if v_viewmats is not None else None, int(c > 0), int(ctx.camera),
                 stream_handle()),
                 "mgs_project_color_bwd")
             if not antialiased:
@@ -261,7 +264,8 @@ def rasterization(means: Tensor, quats: Tensor, scales: Tensor, opacities: Tenso
                   lean_meta: bool = False,
                   backward_segment: int = 256,
                   radius_rule: str = "classic",
-                  dataset_out=None) -> Tuple[Tensor, Tensor, Dict]:
+                  dataset_out=None,
+                  camera_model: str = "pinhole") -> Tuple[Tensor, Tensor, Dict]:
     """Render N Gaussians from C cameras.
 
     dataset_out = (rgba uint8 [C,H,W,4], distance [C,H,W,1] float16 / 32 / 64 or None, K [3,3], keep_float_frame):
@@ -274,6 +278,11 @@ def rasterization(means: Tensor, quats: Tensor, scales: Tensor, opacities: Tenso
     min(3.33, sqrt(2 ln(255 opacity))) sqrt(Sigma_ii): meta["radii"] is then [C,N,2], Gaussians of
     opacity < 1/255 are culled, n_isect shrinks and pixels change in the corners of the classic square and beyond
     3 sigma of opaque Gaussians.  A compile-time policy of the projection kernels (both instantiations ship).
+
+    camera_model: "pinhole", "ortho" (fx x + cx, fy y + cy) or "fisheye" (ideal equidistant lens, r = f theta, no
+    distortion coefficients), gsplat's names; include/mgs.h MGS_CAMERA_* gives the maps.  Every path honours it (a
+    compile-time policy of the projection kernels, like the radius rule).  Depths stay camera z and the SH view
+    direction mean - campos under every model.  dataset_out is pinhole-only (its ray distance is pinhole's).
 
     backward_segment (SH path, when gradients are wanted): list entries per unit of work of the backward raster
     (a power of two >= 64; 0 = one unit per tile, the whole-list walk).  The training forward stores per-pixel
@@ -312,6 +321,10 @@ def rasterization(means: Tensor, quats: Tensor, scales: Tensor, opacities: Tenso
     if tile_bounds not in ("tight", "classic"):
         raise ValueError(f"tile_bounds {tile_bounds!r} not in ('tight', 'classic')")
     rule = ops.radius_rule_id(radius_rule)
+    camera = ops.camera_model_id(camera_model)
+    if dataset_out is not None and camera != 0:
+        raise ValueError(f"dataset_out converts depth to ray distance through a pinhole K^-1: camera_model "
+                         f"{camera_model!r} has no dataset output")
     if backward_segment and (backward_segment < 64 or backward_segment & (backward_segment - 1)):
         raise ValueError(f"backward_segment {backward_segment} is not 0 or a power of two >= 64")
     if raster_schedule not in ("latency", "throughput"):
@@ -355,7 +368,8 @@ def rasterization(means: Tensor, quats: Tensor, scales: Tensor, opacities: Tenso
             means, quats, scales, opacities, colors, viewmats, Ks, backgrounds, width, height,
             int(sh_degree), float(eps2d), float(near_plane), float(far_plane),
             float(radius_clip), antialiased, want_depth, isect_capacity, bool(absgrad), store,
-            int(tile_bounds == "tight") | (2 if rule else 0), render_mode in ("RGB+ED", "ED"), raster_schedule == "latency",
+            int(tile_bounds == "tight") | (2 if rule else 0) | (camera << 2), render_mode in ("RGB+ED", "ED"),
+            raster_schedule == "latency",
             bool(lean_meta), int(backward_segment), dataset_out)
         if depth_only_via_sh:
             render = render[..., 3:4]
@@ -396,7 +410,7 @@ def rasterization(means: Tensor, quats: Tensor, scales: Tensor, opacities: Tenso
         radii, means2d, depths, conics, comps = ops.fully_fused_projection(
             means, None, quats, scales, viewmats, Ks, width, height, eps2d, near_plane, far_plane,
             radius_clip, calc_compensations=antialiased, opacities=opacities if rule else None,
-            radius_rule=radius_rule)
+            radius_rule=radius_rule, camera_model=camera_model)
         opac = opacities.unsqueeze(0).expand(C, N)
         if antialiased:
             opac = opac * comps
@@ -442,6 +456,9 @@ def render(gaussians, cameras: Sequence, sh_degree: Optional[int] = None,
     w, h = cams[0].width, cams[0].height
     if any(c.width != w or c.height != h for c in cams):
         raise ValueError("all cameras of one call must share a resolution")
+    if any(c.model != cams[0].model for c in cams):
+        raise ValueError("all cameras of one call must share a camera model")
+    kw.setdefault("camera_model", cams[0].model)
     t = tensors if tensors is not None else gaussians.to_torch(device, sh_degree)
     viewmats = torch.from_numpy(np.stack([c.viewmat() for c in cams]).astype(np.float32)).to(device)
     Ks = torch.from_numpy(np.stack([c.K for c in cams]).astype(np.float32)).to(device)

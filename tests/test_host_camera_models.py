@@ -1,0 +1,262 @@
+"""CPU test of the orthographic and fisheye camera models in the per-Gaussian DEVICE math (robosimgs_amd/csrc/mgs_math.h,
+project_gaussian<CAM> / project_gaussian_vjp<CAM>, compiled with g++) against the fp64 restatement of
+tests/camera_models_ref.py: forward values, backward against autograd, the fisheye's optical axis and wide angles, the
+pinhole default call, and the -DMGS_PROJ_FACTORED=1 build."""
+import ctypes
+import math
+import os
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+import camera_models_ref as CM
+from robosimgs_amd import camera_ring, synthetic_scene
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+MODEL_ID = {"default": -1, "pinhole": 0, "ortho": 1, "fisheye": 2}
+RULE_ID = {"classic": 0, "opacity_aware": 1}
+
+
+def _build(tmp_path_factory, name, *flags):
+    so = tmp_path_factory.mktemp("hh_cam") / f"lib{name}.so"
+    subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", *flags,
+                    os.path.join(HERE, "host_harness", "camera_models.cpp"), "-o", str(so)], check=True)
+    return ctypes.CDLL(str(so))
+
+
+@pytest.fixture(scope="module")
+def hh(tmp_path_factory):
+    return _build(tmp_path_factory, "cam")
+
+
+@pytest.fixture(scope="module")
+def hh_factored(tmp_path_factory):
+    return _build(tmp_path_factory, "cam_factored", "-DMGS_PROJ_FACTORED=1")
+
+
+def _p(a):
+    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _f(a):
+    return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def _K(model, w, h):
+    """Intrinsics that put most of the test scene on screen: pinhole 60 degrees, ortho w/5 pixels per unit (the scene
+    spans about 4 units), fisheye 180 degrees across the width (r = f theta)."""
+    f = {"pinhole": (w / 2) / math.tan(math.radians(30)), "ortho": w / 5.0, "fisheye": w / math.pi}[model]
+    return np.array([[f, 0, w / 2 + 0.3], [0, f * 1.05, h / 2 - 0.2], [0, 0, 1]])
+
+
+def _scene(n=2000, mu=0.1, w=160, h=120, theta=0.7, seed=11):
+    g = synthetic_scene(n, math.log(mu), 3, seed)
+    cam = camera_ring(1, w, h, thetas=[theta], radius=5.0)[0]
+    return g, cam.viewmat(), w, h
+
+
+def project(L, model, means, quats, scales, vm, K, w, h, rule="classic", opacities=None, aa=False, near=0.01):
+    n = len(means)
+    out = (np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros((n, 2), np.float32), np.zeros(n, np.float32),
+           np.zeros((n, 3), np.float32), np.zeros(n, np.float32))
+    rc = L.hh_project_model(MODEL_ID[model], n, _p(_f(means)), _p(_f(quats)), _p(_f(scales)), _p(_f(vm)), _p(_f(K)),
+                            w, h, ctypes.c_float(0.3), ctypes.c_float(near), ctypes.c_float(1e10), ctypes.c_float(0.0),
+                            RULE_ID[rule], _p(_f(opacities)) if opacities is not None else None, int(aa),
+                            *[_p(a) for a in out])
+    assert rc == 0
+    return dict(zip(("radii", "radii_y", "means2d", "depths", "conics", "compensations"), out))
+
+
+def vjp(L, model, means, quats, scales, vm, K, w, h, fw, cot):
+    n = len(means)
+    out = (np.zeros((n, 3), np.float32), np.zeros((n, 4), np.float32), np.zeros((n, 3), np.float32),
+           np.zeros((n, 9), np.float32), np.zeros((n, 3), np.float32))
+    rc = L.hh_project_vjp_model(MODEL_ID[model], n, _p(_f(means)), _p(_f(quats)), _p(_f(scales)), _p(_f(vm)),
+                                _p(_f(K)), w, h, ctypes.c_float(0.3), _p(fw["radii"]), _p(fw["conics"]),
+                                _p(fw["compensations"]), *[_p(_f(c)) for c in cot], *[_p(a) for a in out])
+    assert rc == 0
+    return dict(zip(("v_means", "v_quats", "v_scales", "v_R", "v_t"), out))
+
+
+def _check_forward(got, ref, rule, min_vis=300):
+    """test_host_math.py's pinhole tolerances."""
+    rr = ref["radii"] if rule == "classic" else ref["radii"][:, 0]
+    gv, rv = got["radii"] > 0, rr > 0
+    assert rv.sum() >= min_vis, rv.sum()
+    assert (gv != rv).sum() <= 1
+    both = gv & rv
+    assert (got["radii"][both] != rr[both]).sum() <= 2
+    if rule != "classic":
+        assert (got["radii_y"][both] != ref["radii"][both, 1]).sum() <= 2
+    np.testing.assert_allclose(got["means2d"][both], ref["means2d"][both], rtol=2e-5, atol=2e-3)
+    np.testing.assert_allclose(got["depths"][both], ref["depths"][both], rtol=1e-6, atol=1e-6)
+    np.testing.assert_allclose(got["conics"][both], ref["conics"][both], rtol=3e-4, atol=1e-6)
+    np.testing.assert_allclose(got["compensations"][both], ref["compensations"][both], rtol=3e-4, atol=1e-6)
+    return both
+
+
+@pytest.mark.parametrize("model", ["ortho", "fisheye"])
+@pytest.mark.parametrize("rule", ["classic", "opacity_aware"])
+@pytest.mark.parametrize("aa", [False, True])
+def test_forward_matches_fp64_reference(hh, model, rule, aa):
+    g, vm, w, h = _scene(n=3000)
+    K = _K(model, w, h)
+    op = _f(g.opacities) if rule == "opacity_aware" else None
+    got = project(hh, model, g.means, g.quats, g.scales, vm, K, w, h, rule, op, aa)
+    f64 = lambda a: _f(a).astype(np.float64)          # what the device is given
+    ref = CM.project(f64(g.means), f64(g.quats), f64(g.scales), f64(vm), f64(K), w, h, radius_rule=rule,
+                     opacities=None if op is None else op.astype(np.float64), antialiased=aa, camera_model=model)
+    _check_forward(got, ref, rule, min_vis=1000)
+
+
+def _autograd(model, means, quats, scales, vm, K, w, h, vis, cot):
+    t = lambda a: torch.tensor(_f(a).astype(np.float64), requires_grad=True)
+    tm, tq, ts, tv = t(means), t(quats), t(scales), t(vm)
+    p = CM.project_torch(tm, tq, ts, tv, torch.tensor(_f(K).astype(np.float64)), w, h, camera_model=model)
+    mask = torch.tensor(vis.astype(np.float64))
+    v_m2d, v_dep, v_con, v_comp = (torch.tensor(c.astype(np.float64)) for c in cot)
+    loss = (((p["means2d"] * v_m2d).sum(-1) + p["depths"] * v_dep + (p["conics"] * v_con).sum(-1)
+             + p["compensations"] * v_comp) * mask).sum()
+    loss.backward()
+    return tm.grad.numpy(), tq.grad.numpy(), ts.grad.numpy(), tv.grad.numpy()
+
+
+def _close(a, b, name, tol=2e-3):
+    """test_host_math.py's gate: max error scaled by the row's magnitude (plus 1e-3 of the largest row)."""
+    scale = np.abs(b).max(axis=-1, keepdims=True) + 1e-3 * np.abs(b).max() + 1e-12
+    err = (np.abs(a - b) / scale).max()
+    assert err < tol, f"{name}: max scaled error {err:.3e}"
+
+
+@pytest.mark.parametrize("model", ["ortho", "fisheye"])
+@pytest.mark.parametrize("aa", [False, True])
+def test_backward_matches_fp64_autograd(hh, model, aa):
+    g, vm, w, h = _scene(1500)
+    n = len(g)
+    K = _K(model, w, h)
+    fw = project(hh, model, g.means, g.quats, g.scales, vm, K, w, h)
+    rng = np.random.default_rng(1)
+    cot = [rng.normal(size=(n, 2)), rng.normal(size=n), rng.normal(size=(n, 3)),
+           rng.normal(size=n) if aa else np.zeros(n)]
+    ref_vis = CM.project(_f(g.means).astype(np.float64), _f(g.quats).astype(np.float64), _f(g.scales).astype(np.float64),
+                         _f(vm).astype(np.float64), _f(K).astype(np.float64), w, h, camera_model=model)["radii"] > 0
+    vis = ref_vis & (fw["radii"] > 0)
+    assert vis.sum() > 500
+    fw["radii"] = np.where(vis, fw["radii"], 0).astype(np.int32)
+    got = vjp(hh, model, g.means, g.quats, g.scales, vm, K, w, h, fw, cot)
+    gm, gq, gs, gv = _autograd(model, g.means, g.quats, g.scales, vm, K, w, h, vis, cot)
+    _close(got["v_means"][vis], gm[vis], "v_means")
+    _close(got["v_quats"][vis], gq[vis], "v_quats")
+    _close(got["v_scales"][vis], gs[vis], "v_scales")
+    _close(got["v_R"].sum(0).reshape(1, 9), gv[:3, :3].reshape(1, 9), "v_viewmat R")
+    _close(got["v_t"].sum(0).reshape(1, 3), gv[:3, 3].reshape(1, 3), "v_viewmat t")
+
+
+def _axis_scene():
+    """Gaussians at chosen camera-space points of an identity camera (camera at the origin looking down +z): exactly on
+    the optical axis, rho/z = 1e-6 and 1e-3, and directions from 5 to 85 degrees off axis in several azimuths."""
+    rng = np.random.default_rng(5)
+    pts = []
+    for z in (0.5, 2.0, 7.0):
+        pts.append((0.0, 0.0, z))                                    # rho = 0 exactly
+        for r in (1e-6, 1e-3):
+            for phi in (0.3, 2.0, 4.4):
+                pts.append((r * z * math.cos(phi), r * z * math.sin(phi), z))
+    for deg in (5, 20, 45, 60, 75, 80, 85):
+        for phi in np.linspace(0, 2 * math.pi, 7, endpoint=False):
+            th = math.radians(deg)
+            d = 3.0
+            pts.append((d * math.sin(th) * math.cos(phi), d * math.sin(th) * math.sin(phi), d * math.cos(th)))
+    means = np.array(pts)
+    n = len(means)
+    quats = rng.normal(size=(n, 4))
+    scales = np.exp(rng.uniform(math.log(0.02), math.log(0.1), size=(n, 3)))
+    return means, quats, scales, np.eye(4), n
+
+
+def test_fisheye_from_the_axis_to_85_degrees(hh):
+    means, quats, scales, vm, n = _axis_scene()
+    w = h = 512
+    K = np.array([[w / math.pi, 0, w / 2], [0, w / math.pi, h / 2], [0, 0, 1]])     # 180 degrees across
+    fw = project(hh, "fisheye", means, quats, scales, vm, K, w, h)
+    assert (fw["radii"] > 0).all(), "every test point is in front of the lens and on the image"
+    for k, v in fw.items():
+        assert np.isfinite(v).all(), k
+    ref = CM.project(_f(means).astype(np.float64), _f(quats).astype(np.float64), _f(scales).astype(np.float64), vm,
+                     _f(K).astype(np.float64), w, h, camera_model="fisheye")
+    _check_forward(fw, ref, "classic", min_vis=n)
+    rng = np.random.default_rng(2)
+    cot = [rng.normal(size=(n, 2)), rng.normal(size=n), rng.normal(size=(n, 3)), rng.normal(size=n)]
+    got = vjp(hh, "fisheye", means, quats, scales, vm, K, w, h, fw, cot)
+    for k, v in got.items():
+        assert np.isfinite(v).all(), k
+    gm, gq, gs, gv = _autograd("fisheye", means, quats, scales, vm, K, w, h, np.ones(n, bool), cot)
+    _close(got["v_means"], gm, "v_means")
+    _close(got["v_quats"], gq, "v_quats")
+    _close(got["v_scales"], gs, "v_scales")
+    _close(got["v_R"].sum(0).reshape(1, 9), gv[:3, :3].reshape(1, 9), "v_viewmat R")
+
+    # on the optical axis the fisheye map is the pinhole map to first order: same outputs and gradients to fp32 rounding
+    on = np.arange(0, 3 * 7, 7)                                      # the rho = 0 points
+    pin = project(hh, "pinhole", means, quats, scales, vm, K, w, h)
+    for k in ("radii", "means2d", "depths", "conics", "compensations"):
+        np.testing.assert_allclose(fw[k][on], pin[k][on], rtol=2e-6, atol=1e-7, err_msg=k)
+    gp = vjp(hh, "pinhole", means, quats, scales, vm, K, w, h, pin, cot)
+    for k in got:
+        scale = np.abs(gp[k][on]).max(axis=-1, keepdims=True) + 1e-12
+        assert (np.abs(got[k][on] - gp[k][on]) / scale).max() < 1e-5, k
+
+
+def test_pinhole_instantiation_is_the_default_call(hh, tmp_path):
+    """project_gaussian<MGS_CAMERA_PINHOLE> is what the default call compiles to -- and what the untouched pinhole
+    harness (tests/host_harness/harness.cpp) computes, bit for bit, forward and backward."""
+    g, vm, w, h = _scene(3000)
+    K = _K("pinhole", w, h)
+    for rule, aa in (("classic", False), ("opacity_aware", True)):
+        op = _f(g.opacities) if rule == "opacity_aware" else None
+        a = project(hh, "default", g.means, g.quats, g.scales, vm, K, w, h, rule, op, aa)
+        b = project(hh, "pinhole", g.means, g.quats, g.scales, vm, K, w, h, rule, op, aa)
+        for k in a:
+            assert np.array_equal(a[k], b[k]), (rule, k)
+    so = tmp_path / "libhh.so"
+    subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", os.path.join(HERE, "host_harness", "harness.cpp"),
+                    "-o", str(so)], check=True)
+    old = ctypes.CDLL(str(so))
+    n = len(g)
+    radii, m2d, dep, con, comp = (np.zeros(n, np.int32), np.zeros((n, 2), np.float32), np.zeros(n, np.float32),
+                                  np.zeros((n, 3), np.float32), np.zeros(n, np.float32))
+    old.hh_project(n, _p(_f(g.means)), _p(_f(g.quats)), _p(_f(g.scales)), _p(_f(vm)), _p(_f(K)), w, h,
+                   ctypes.c_float(0.3), ctypes.c_float(0.01), ctypes.c_float(1e10), ctypes.c_float(0.0), _p(radii),
+                   _p(m2d), _p(dep), _p(con), _p(comp))
+    b = project(hh, "pinhole", g.means, g.quats, g.scales, vm, K, w, h)
+    for k, v in (("radii", radii), ("means2d", m2d), ("depths", dep), ("conics", con), ("compensations", comp)):
+        assert np.array_equal(b[k], v), k
+    rng = np.random.default_rng(3)
+    cot = [rng.normal(size=(n, 2)), rng.normal(size=n), rng.normal(size=(n, 3)), rng.normal(size=n)]
+    ga = vjp(hh, "default", g.means, g.quats, g.scales, vm, K, w, h, b, cot)
+    gb = vjp(hh, "pinhole", g.means, g.quats, g.scales, vm, K, w, h, b, cot)
+    vo = [np.zeros((n, 3), np.float32), np.zeros((n, 4), np.float32), np.zeros((n, 3), np.float32),
+          np.zeros(9, np.float32), np.zeros(3, np.float32)]
+    old.hh_project_vjp(n, _p(_f(g.means)), _p(_f(g.quats)), _p(_f(g.scales)), _p(_f(vm)), _p(_f(K)), w, h,
+                       ctypes.c_float(0.3), _p(b["radii"]), _p(b["conics"]), _p(b["compensations"]),
+                       *[_p(_f(c)) for c in cot], *[_p(a) for a in vo])
+    for k in ga:
+        assert np.array_equal(ga[k], gb[k]), k
+    for k, v in zip(("v_means", "v_quats", "v_scales"), vo[:3]):
+        assert np.array_equal(gb[k], v), k
+
+
+@pytest.mark.parametrize("model", ["pinhole", "ortho", "fisheye"])
+def test_factored_build_matches_reference(hh_factored, model):
+    """-DMGS_PROJ_FACTORED=1 (cov2d from the 2 x 3 factor J R Rq S, a build knob) with a dense fisheye J."""
+    g, vm, w, h = _scene(3000)
+    K = _K(model, w, h)
+    f64 = lambda a: _f(a).astype(np.float64)
+    for rule in ("classic", "opacity_aware"):
+        op = _f(g.opacities) if rule == "opacity_aware" else None
+        got = project(hh_factored, model, g.means, g.quats, g.scales, vm, K, w, h, rule, op, True)
+        ref = CM.project(f64(g.means), f64(g.quats), f64(g.scales), f64(vm), f64(K), w, h, radius_rule=rule,
+                         opacities=None if op is None else op.astype(np.float64), antialiased=True, camera_model=model)
+        _check_forward(got, ref, rule, min_vis=1000)
