@@ -295,17 +295,12 @@ extern "C" int mgs_projection_bwd(int n, const float* means, const float* quats,
   if (n == 0) return MGS_OK;
   MGS_REQUIRE(means && quats && scales && viewmat && K && radii && conics && v_means2d &&
                   v_conics && v_means && v_quats && v_scales, "projection_bwd: null pointer");
-#define MGS_PB_LAUNCH(CAM)                                                                     \
-  hipLaunchKernelGGL(projection_bwd_kernel<CAM>, dim3(div_up(n, kBlock)), dim3(kBlock), 0,        \
-                     (hipStream_t)stream, n, means, quats, scales, viewmat, K, (float)width,      \
-                     (float)height, eps2d, radii, conics, compensations, v_means2d, v_depths,     \
-                     v_conics, v_compensations, v_means, v_quats, v_scales, v_viewmat)
-  switch (camera_model) {
-    case MGS_CAMERA_PINHOLE: MGS_PB_LAUNCH(MGS_CAMERA_PINHOLE); break;
-    case MGS_CAMERA_ORTHO: MGS_PB_LAUNCH(MGS_CAMERA_ORTHO); break;
-    default: MGS_PB_LAUNCH(MGS_CAMERA_FISHEYE); break;
-  }
-#undef MGS_PB_LAUNCH
+  with_camera(camera_model, [&](auto cam) {
+    hipLaunchKernelGGL(projection_bwd_kernel<decltype(cam)::value>, dim3(div_up(n, kBlock)), dim3(kBlock), 0,
+                       (hipStream_t)stream, n, means, quats, scales, viewmat, K, (float)width, (float)height, eps2d,
+                       radii, conics, compensations, v_means2d, v_depths, v_conics, v_compensations, v_means, v_quats,
+                       v_scales, v_viewmat);
+  });
   return check_launch("projection_bwd");
 }
 
@@ -320,15 +315,12 @@ extern "C" int mgs_sh_bwd(int n, int degree, int coeff_stride, const float* dirs
   hipStream_t s = (hipStream_t)stream;
   int sf = coeff_stride * 3;
   bool staged = coeff_stride == 16;
-#define MGS_SHB(D, S) \
-  hipLaunchKernelGGL((sh_bwd_kernel<D, S>), grid, block, 0, s, n, sf, dirs, coeffs, masks, v_colors, v_coeffs, v_dirs)
-  switch (degree) {
-    case 0: if (staged) MGS_SHB(0, true); else MGS_SHB(0, false); break;
-    case 1: if (staged) MGS_SHB(1, true); else MGS_SHB(1, false); break;
-    case 2: if (staged) MGS_SHB(2, true); else MGS_SHB(2, false); break;
-    default: if (staged) MGS_SHB(3, true); else MGS_SHB(3, false); break;
-  }
-#undef MGS_SHB
+  with_sh_degree(degree, [&](auto d) {
+    with_bool(staged, [&](auto st) {
+      hipLaunchKernelGGL((sh_bwd_kernel<decltype(d)::value, decltype(st)::value>), grid, block, 0, s, n, sf, dirs, coeffs,
+                         masks, v_colors, v_coeffs, v_dirs);
+    });
+  });
   return check_launch("sh_bwd");
 }
 
@@ -359,30 +351,21 @@ extern "C" int mgs_project_color_bwd(int n, const float* means, const float* qua
   hipStream_t s = (hipStream_t)stream;
   int sf = coeff_stride * 3;
   bool staged = coeff_stride == 16;
-#define MGS_PCB(D, S, A)                                                                        \
-  if (v_viewmat) MGS_PCB_C(D, S, A, true); else MGS_PCB_C(D, S, A, false)
-#define MGS_PCB_C(D, S, A, V)                                                                   \
-  if (camera_model == MGS_CAMERA_PINHOLE) MGS_PCB_V(D, S, A, V, MGS_CAMERA_PINHOLE);             \
-  else if (camera_model == MGS_CAMERA_ORTHO) MGS_PCB_V(D, S, A, V, MGS_CAMERA_ORTHO);            \
-  else MGS_PCB_V(D, S, A, V, MGS_CAMERA_FISHEYE)
-#define MGS_PCB_V(D, S, A, V, CAM)                                                              \
-  hipLaunchKernelGGL((project_color_bwd_kernel<D, S, A, V, CAM>), grid, block, 0, s, n, means, quats, \
-                     scales, opacities, sf, sh_coeffs, viewmat, K, (float)width, (float)height, \
-                     eps2d, radii, conics, antialiased, feat_stride, feats, v_feats, v_means2d, \
-                     v_conics, v_depths, v_opac_out, v_means, v_quats, v_scales, v_sh_coeffs,   \
-                     v_opacities, v_viewmat)
-#define MGS_PCB_D(D)                                                  \
-  if (staged) { if (accumulate) { MGS_PCB(D, true, true); } else { MGS_PCB(D, true, false); } } \
-  else { if (accumulate) { MGS_PCB(D, false, true); } else { MGS_PCB(D, false, false); } }
-  switch (sh_degree) {
-    case 0: MGS_PCB_D(0) break;
-    case 1: MGS_PCB_D(1) break;
-    case 2: MGS_PCB_D(2) break;
-    default: MGS_PCB_D(3) break;
-  }
-#undef MGS_PCB_D
-#undef MGS_PCB
-#undef MGS_PCB_C
-#undef MGS_PCB_V
+  with_sh_degree(sh_degree, [&](auto d) {
+    with_bool(staged, [&](auto st) {
+      with_bool(accumulate != 0, [&](auto acc) {
+        with_bool(v_viewmat != nullptr, [&](auto vm) {
+          with_camera(camera_model, [&](auto cam) {
+            hipLaunchKernelGGL((project_color_bwd_kernel<decltype(d)::value, decltype(st)::value, decltype(acc)::value,
+                                                         decltype(vm)::value, decltype(cam)::value>),
+                               grid, block, 0, s, n, means, quats, scales, opacities, sf, sh_coeffs, viewmat, K,
+                               (float)width, (float)height, eps2d, radii, conics, antialiased, feat_stride, feats, v_feats,
+                               v_means2d, v_conics, v_depths, v_opac_out, v_means, v_quats, v_scales, v_sh_coeffs,
+                               v_opacities, v_viewmat);
+          });
+        });
+      });
+    });
+  });
   return check_launch("project_color_bwd");
 }

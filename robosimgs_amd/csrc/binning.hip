@@ -709,20 +709,19 @@ struct Workspace {
   size_t total;
   size_t ginfo, blocksums, tile_alt, tile_priv, id_alt, radix, tsort, table, tile_count, group_offsets;
   Workspace(int n, uint32_t cap, int n_tiles) {
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t at = o; o += align_up(bytes, 256); return at; };
+    Bump b(0);           // (an empty field takes no room)
     size_t nn = (size_t)(n > 0 ? n : 1), cc = cap ? cap : 1;
-    ginfo = take(nn * 8);
-    blocksums = take((size_t)div_up((unsigned)nn, kSum) * 4);
-    tile_alt = take(cc * 4); id_alt = take(cc * 4);
-    tile_priv = take(cc * 4);          // stands in for the caller's tile_ids when that is null
-    radix = take(radix_sort_temp_bytes((uint32_t)cc));
-    tsort = take(tile_depth_sort_temp_bytes((uint32_t)cc, n_tiles));
+    ginfo = b.take(nn * 8);
+    blocksums = b.take((size_t)div_up((unsigned)nn, kSum) * 4);
+    tile_alt = b.take(cc * 4); id_alt = b.take(cc * 4);
+    tile_priv = b.take(cc * 4);          // stands in for the caller's tile_ids when that is null
+    radix = b.take(radix_sort_temp_bytes((uint32_t)cc));
+    tsort = b.take(tile_depth_sort_temp_bytes((uint32_t)cc, n_tiles));
     const size_t nt = (size_t)(n_tiles < kDirectMaxTiles ? n_tiles : kDirectMaxTiles);   // bins: tiles or tile groups
-    table = take((size_t)direct_blocks((unsigned)nn) * nt * 4);
-    tile_count = take(nt * 4);
-    group_offsets = take((nt + 1) * 4);
-    total = o;
+    table = b.take((size_t)direct_blocks((unsigned)nn) * nt * 4);
+    tile_count = b.take(nt * 4);
+    group_offsets = b.take((nt + 1) * 4);
+    total = b.total;
   }
 };
 
@@ -730,6 +729,8 @@ struct Workspace {
 }  // namespace mgs
 
 namespace mgs {
+size_t isect_tiles_workspace_bytes(int n, uint32_t capacity, int n_tiles) { return Workspace(n, capacity, n_tiles).total; }
+
 int launch_tile_group_order(int n_tiles, const int32_t* tile_offsets, int32_t* order, hipStream_t stream) {
   hipLaunchKernelGGL(tile_group_order_kernel, dim3(1), dim3(1024), 0, stream, n_tiles, tile_offsets, order);
   return check_launch("tile_group_order");
@@ -752,7 +753,7 @@ extern "C" int mgs_isect_tiles(int n, const float* means2d, const int32_t* radii
   MGS_REQUIRE(tile_w <= 1023 && tile_h <= 1023, "isect_tiles: tile grid %dx%d exceeds 1023x1023", tile_w, tile_h);
   MGS_REQUIRE(workspace_bytes, "isect_tiles: workspace_bytes is null");
   MGS_REQUIRE(cam_id >= 0 && n_cams > cam_id, "isect_tiles: cam_id %d outside 0..%d", cam_id, n_cams);
-  Workspace ws(n, isect_capacity, tile_w * tile_h);
+  const Workspace ws(n, isect_capacity, tile_w * tile_h);
   if (!workspace) {
     *workspace_bytes = ws.total;
     return MGS_OK;
@@ -822,16 +823,14 @@ extern "C" int mgs_isect_tiles(int n, const float* means2d, const int32_t* radii
                            (int)nb, bins, u32(ws.table), u32(ws.tile_count));
       const bool order_in_scatter = tile_group_order && gshift == 2;
       order_done = order_in_scatter;
-#define MGS_SCATTER(P)                                                                                                   \
-      hipLaunchKernelGGL(direct_scatter_kernel<P>, dim3(nb + (order_in_scatter ? 1 : 0)), dim3(kDirectThreads), lds, s, n, \
-                         chunk, ginfo, tile_w, n_tiles, gshift, u32(ws.table), u32(ws.tile_count), cap,                   \
-                         gshift ? u32(ws.id_alt) : reinterpret_cast<uint32_t*>(flatten_ids),                             \
-                         gshift ? reinterpret_cast<int32_t*>(w + ws.group_offsets) : tile_offsets, n_isect, status,      \
-                         order_in_scatter ? tile_group_order : nullptr, sums, reinterpret_cast<int4*>(pair_info),           \
-                         tile_depth_sort_long_list(w + ws.tsort, cap), pair_info ? splat_slots : nullptr, deal_nb)
-      if (pair_info) MGS_SCATTER(true);
-      else MGS_SCATTER(false);
-#undef MGS_SCATTER
+      with_bool(pair_info != nullptr, [&](auto training) {
+        hipLaunchKernelGGL(direct_scatter_kernel<decltype(training)::value>, dim3(nb + (order_in_scatter ? 1 : 0)),
+                           dim3(kDirectThreads), lds, s, n, chunk, ginfo, tile_w, n_tiles, gshift, u32(ws.table),
+                           u32(ws.tile_count), cap, gshift ? u32(ws.id_alt) : reinterpret_cast<uint32_t*>(flatten_ids),
+                           gshift ? reinterpret_cast<int32_t*>(w + ws.group_offsets) : tile_offsets, n_isect, status,
+                           order_in_scatter ? tile_group_order : nullptr, sums, reinterpret_cast<int4*>(pair_info),
+                           tile_depth_sort_long_list(w + ws.tsort, cap), pair_info ? splat_slots : nullptr, deal_nb);
+      });
     } else {
       hipLaunchKernelGGL(scan_blocksums_kernel, dim3(1), dim3(kScanThreads), 0, s, nsum, sums, cap,
                          n_isect, status);

@@ -10,36 +10,56 @@
 #include "mgs_common.h"
 
 namespace {
-// the MGS_FRAMES_CAMERA_* bits of a flags word: at most one, and what they mean to the stage entry points
-bool camera_flags_valid(int flags) {
-  return (flags & (MGS_FRAMES_CAMERA_ORTHO | MGS_FRAMES_CAMERA_FISHEYE)) != (MGS_FRAMES_CAMERA_ORTHO | MGS_FRAMES_CAMERA_FISHEYE);
+// What the three drivers share: the argument checks, the tile grid, and what the frames flags tell the stage entry points.
+struct Frames {
+  int tile_w, tile_h, n_tiles;
+  int bin_flags;       // mgs_project_color_fwd's: tile bounds, radius rule, camera
+  int camera_model;    // MGS_CAMERA_* (mgs_project_color_bwd)
+};
+int frames_prologue(const char* fn, int n, int n_cams, int width, int height, int channels, int flags,
+                    uint32_t isect_capacity, const size_t* workspace_bytes, Frames* f,
+                    const char* channel_rule = "3 (RGB) or 4 (RGB + depth)") {
+  MGS_REQUIRE(n >= 0 && n_cams >= 1 && width > 0 && height > 0, "%s: bad sizes", fn);
+  MGS_REQUIRE(channels == 3 || channels == 4, "%s: channels must be %s, got %d", fn, channel_rule, channels);
+  MGS_REQUIRE(workspace_bytes, "%s: workspace_bytes is null", fn);
+  MGS_REQUIRE(isect_capacity > 0, "%s: zero capacity", fn);
+  MGS_REQUIRE((flags & (MGS_FRAMES_CAMERA_ORTHO | MGS_FRAMES_CAMERA_FISHEYE)) != (MGS_FRAMES_CAMERA_ORTHO | MGS_FRAMES_CAMERA_FISHEYE),
+              "%s: flags set both MGS_FRAMES_CAMERA_ORTHO and MGS_FRAMES_CAMERA_FISHEYE", fn);
+  f->tile_w = (width + MGS_TILE_SIZE - 1) / MGS_TILE_SIZE;
+  f->tile_h = (height + MGS_TILE_SIZE - 1) / MGS_TILE_SIZE;
+  f->n_tiles = f->tile_w * f->tile_h;
+  f->bin_flags = ((flags & MGS_FRAMES_CLASSIC_BOUNDS) ? 0 : MGS_BIN_TIGHT /* same pixels, shorter lists */) |
+                 ((flags & MGS_FRAMES_RADIUS_OPACITY_AWARE) ? MGS_BIN_RADIUS_OPACITY_AWARE : 0) |
+                 ((flags & MGS_FRAMES_CAMERA_ORTHO) ? MGS_BIN_CAMERA_ORTHO : 0) |
+                 ((flags & MGS_FRAMES_CAMERA_FISHEYE) ? MGS_BIN_CAMERA_FISHEYE : 0);
+  f->camera_model = mgs::bin_camera_model(f->bin_flags);
+  return MGS_OK;
 }
-int camera_model_of(int flags) {
-  return (flags & MGS_FRAMES_CAMERA_ORTHO) ? MGS_CAMERA_ORTHO
-         : (flags & MGS_FRAMES_CAMERA_FISHEYE) ? MGS_CAMERA_FISHEYE : MGS_CAMERA_PINHOLE;
-}
-int camera_bin_flags(int flags) {
-  return ((flags & MGS_FRAMES_CAMERA_ORTHO) ? MGS_BIN_CAMERA_ORTHO : 0) | ((flags & MGS_FRAMES_CAMERA_FISHEYE) ? MGS_BIN_CAMERA_FISHEYE : 0);
+// the per-camera binning's workspace, with the tile-grid check of mgs_isect_tiles' size query
+int isect_bytes(int n, uint32_t isect_capacity, const Frames& f, size_t* bytes) {
+  MGS_REQUIRE(f.tile_w <= 1023 && f.tile_h <= 1023, "isect_tiles: tile grid %dx%d exceeds 1023x1023", f.tile_w, f.tile_h);
+  *bytes = mgs::isect_tiles_workspace_bytes(n, isect_capacity, f.n_tiles);
+  return MGS_OK;
 }
 
+// (every field of the frame drivers' layouts, an empty one too, keeps a 256-byte slot of its own)
 struct FrameWs {
   size_t total, depths, opac, splats, bin_info, bin_sums, flatten, offsets, order, isect;
   size_t isect_bytes;
   FrameWs(int n, uint32_t cap, int n_tiles, bool antialiased, size_t isect_ws) {
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t at = o; o += mgs::align_up(bytes ? bytes : 1, 256); return at; };
+    mgs::Bump b(1);
     const size_t nn = (size_t)(n > 0 ? n : 1);
-    depths = take(nn * 4);
-    opac = take(antialiased ? nn * 4 : 0);
-    splats = take(nn * 48);
-    bin_info = take(nn * 8);
-    bin_sums = take(((nn + 63) / 64) * 4);
-    flatten = take((size_t)cap * 4);
-    offsets = take(((size_t)n_tiles + 1) * 4);
-    order = take((((size_t)n_tiles + 3) / 4) * 4);
-    isect = take(isect_ws);
+    depths = b.take(nn * 4);
+    opac = b.take(antialiased ? nn * 4 : 0);
+    splats = b.take(nn * 48);
+    bin_info = b.take(nn * 8);
+    bin_sums = b.take(((nn + 63) / 64) * 4);
+    flatten = b.take((size_t)cap * 4);
+    offsets = b.take(((size_t)n_tiles + 1) * 4);
+    order = b.take((((size_t)n_tiles + 3) / 4) * 4);
+    isect = b.take(isect_ws);
     isect_bytes = isect_ws;
-    total = o;
+    total = b.total;
   }
 };
 }  // namespace
@@ -52,23 +72,18 @@ extern "C" int mgs_render_frames(int n, const float* means, const float* quats, 
                                  uint32_t isect_capacity, float* render, float* alphas, uint32_t* n_isect,
                                  uint32_t* status, uint8_t* ds_rgba, void* ds_distance, int ds_distance_type,
                                  const double* ds_Kinv_host, void* workspace, size_t* workspace_bytes, mgs_stream_t stream) {
-  MGS_REQUIRE(n >= 0 && n_cams >= 1 && width > 0 && height > 0, "render_frames: bad sizes");
-  MGS_REQUIRE(channels == 3 || channels == 4, "render_frames: channels must be 3 (RGB) or 4 (RGB + depth), got %d", channels);
-  MGS_REQUIRE(workspace_bytes, "render_frames: workspace_bytes is null");
-  MGS_REQUIRE(isect_capacity > 0, "render_frames: zero capacity");
-  MGS_REQUIRE(camera_flags_valid(flags), "render_frames: flags set both MGS_FRAMES_CAMERA_ORTHO and MGS_FRAMES_CAMERA_FISHEYE");
-  if ((ds_rgba || ds_distance) && camera_model_of(flags) != MGS_CAMERA_PINHOLE)
+  Frames f;
+  int rc = frames_prologue("render_frames", n, n_cams, width, height, channels, flags, isect_capacity, workspace_bytes, &f);
+  if (rc) return rc;
+  if ((ds_rgba || ds_distance) && f.camera_model != MGS_CAMERA_PINHOLE)
     return mgs::set_error(MGS_ERR_UNSUPPORTED, "render_frames: dataset output (ds_rgba / ds_distance) converts depth to ray "
                                                "distance through a pinhole K^-1; it is not available for an orthographic "
                                                "or fisheye camera");
-  const int tile_w = (width + MGS_TILE_SIZE - 1) / MGS_TILE_SIZE, tile_h = (height + MGS_TILE_SIZE - 1) / MGS_TILE_SIZE;
-  const int n_tiles = tile_w * tile_h;
+  const int tile_w = f.tile_w, tile_h = f.tile_h;
   size_t isect_ws = 0;
-  int rc = mgs_isect_tiles(n, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, MGS_TILE_SIZE, tile_w, tile_h, 0, 1,
-                           isect_capacity, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                           nullptr, nullptr, nullptr, nullptr, nullptr, &isect_ws, stream);
+  rc = isect_bytes(n, isect_capacity, f, &isect_ws);
   if (rc) return rc;
-  const FrameWs ws(n, isect_capacity, n_tiles, antialiased != 0, isect_ws);
+  const FrameWs ws(n, isect_capacity, f.n_tiles, antialiased != 0, isect_ws);
   if (!workspace) {
     *workspace_bytes = ws.total;
     return MGS_OK;
@@ -94,10 +109,7 @@ extern "C" int mgs_render_frames(int n, const float* means, const float* quats, 
   for (int c = 0; c < n_cams; ++c) {
     rc = mgs_project_color_fwd(n, means, quats, scales, opacities, sh_degree, coeff_stride, sh_coeffs,
                                viewmats + 16 * (size_t)c, Ks + 9 * (size_t)c, width, height, eps2d, near_plane, far_plane,
-                               radius_clip, nullptr, nullptr, depths, nullptr, opac_aa, channels, nullptr, splats,
-                               ((flags & MGS_FRAMES_CLASSIC_BOUNDS) ? 0 : MGS_BIN_TIGHT /* same pixels, shorter lists */) |
-                                   ((flags & MGS_FRAMES_RADIUS_OPACITY_AWARE) ? MGS_BIN_RADIUS_OPACITY_AWARE : 0) |
-                                   camera_bin_flags(flags),
+                               radius_clip, nullptr, nullptr, depths, nullptr, opac_aa, channels, nullptr, splats, f.bin_flags,
                                bin_info, bin_sums, nullptr, stream);
     if (rc) return rc;
     size_t iw = ws.isect_bytes;
@@ -133,8 +145,8 @@ struct TrainState {
   TrainState(int n, int width, int height, int channels, uint32_t cap, bool antialiased, int interval) {
     const int tile_w = (width + MGS_TILE_SIZE - 1) / MGS_TILE_SIZE, tile_h = (height + MGS_TILE_SIZE - 1) / MGS_TILE_SIZE;
     const size_t nn = (size_t)(n > 0 ? n : 1), n_tiles = (size_t)tile_w * tile_h, n_px = (size_t)width * height;
-    size_t o = 0;
-    auto take = [&](int f, size_t bytes) { at[f] = o; o += mgs::align_up(bytes ? bytes : 1, 256); };
+    mgs::Bump b(1);
+    auto take = [&](int f, size_t bytes) { at[f] = b.take(bytes); };
     take(TF_RADII, nn * 4);
     take(TF_MEANS2D, nn * 8);
     take(TF_DEPTHS, nn * 4);
@@ -152,34 +164,32 @@ struct TrainState {
     take(TF_CKPT, interval ? mgs_raster_checkpoint_floats(cap, tile_w, tile_h, channels, interval) * 4 : 0);
     take(TF_COUNTS, 8);                      // n_isect, status
     take(TF_RADII_Y, nn * 4);                // written under MGS_FRAMES_RADIUS_OPACITY_AWARE only
-    total = o;
+    total = b.total;
   }
 };
 struct TrainWs {     // shared by the cameras of a call
   size_t bin_info, bin_sums, isect, total;
   TrainWs(int n, size_t isect_ws) {
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t a = o; o += mgs::align_up(bytes ? bytes : 1, 256); return a; };
+    mgs::Bump b(1);
     const size_t nn = (size_t)(n > 0 ? n : 1);
-    bin_info = take(nn * 8);
-    bin_sums = take(((nn + 63) / 64) * 4);
-    isect = take(isect_ws);
-    total = o;
+    bin_info = b.take(nn * 8);
+    bin_sums = b.take(((nn + 63) / 64) * 4);
+    isect = b.take(isect_ws);
+    total = b.total;
   }
 };
 struct BwdWs {
   size_t v_means2d, v_abs, v_conics, v_feats, v_opac, raster, total;
   BwdWs(int n, int channels, size_t raster_ws) {
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t a = o; o += mgs::align_up(bytes ? bytes : 1, 256); return a; };
+    mgs::Bump b(1);
     const size_t nn = (size_t)(n > 0 ? n : 1);
-    v_means2d = take(nn * 8);
-    v_abs = take(nn * 8);
-    v_conics = take(nn * 12);
-    v_feats = take(nn * 4 * channels);
-    v_opac = take(nn * 4);
-    raster = take(raster_ws);
-    total = o;
+    v_means2d = b.take(nn * 8);
+    v_abs = b.take(nn * 8);
+    v_conics = b.take(nn * 12);
+    v_feats = b.take(nn * 4 * channels);
+    v_opac = b.take(nn * 4);
+    raster = b.take(raster_ws);
+    total = b.total;
   }
 };
 __global__ __launch_bounds__(256) void add_rows_kernel(size_t n, const float* __restrict__ src, float* __restrict__ dst, int first) {
@@ -208,17 +218,12 @@ extern "C" int mgs_render_frames_train(int n, const float* means, const float* q
                                        int channels, int flags, const float* backgrounds, uint32_t isect_capacity,
                                        int checkpoint_interval, float* render, float* alphas, void* state, void* workspace,
                                        size_t* workspace_bytes, mgs_stream_t stream) {
-  MGS_REQUIRE(n >= 0 && n_cams >= 1 && width > 0 && height > 0, "render_frames_train: bad sizes");
-  MGS_REQUIRE(channels == 3 || channels == 4, "render_frames_train: channels must be 3 (RGB) or 4 (RGB + depth), got %d", channels);
-  MGS_REQUIRE(workspace_bytes, "render_frames_train: workspace_bytes is null");
-  MGS_REQUIRE(isect_capacity > 0, "render_frames_train: zero capacity");
-  MGS_REQUIRE(camera_flags_valid(flags),
-              "render_frames_train: flags set both MGS_FRAMES_CAMERA_ORTHO and MGS_FRAMES_CAMERA_FISHEYE");
-  const int tile_w = (width + MGS_TILE_SIZE - 1) / MGS_TILE_SIZE, tile_h = (height + MGS_TILE_SIZE - 1) / MGS_TILE_SIZE;
+  Frames f;
+  int rc = frames_prologue("render_frames_train", n, n_cams, width, height, channels, flags, isect_capacity, workspace_bytes, &f);
+  if (rc) return rc;
+  const int tile_w = f.tile_w, tile_h = f.tile_h;
   size_t isect_ws = 0;
-  int rc = mgs_isect_tiles(n, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, MGS_TILE_SIZE, tile_w, tile_h, 0, 1,
-                           isect_capacity, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                           nullptr, nullptr, nullptr, nullptr, nullptr, &isect_ws, stream);
+  rc = isect_bytes(n, isect_capacity, f, &isect_ws);
   if (rc) return rc;
   const TrainWs ws(n, isect_ws);
   if (!workspace) {
@@ -237,8 +242,6 @@ extern "C" int mgs_render_frames_train(int n, const float* means, const float* q
   uint32_t* bin_info = reinterpret_cast<uint32_t*>(w + ws.bin_info);
   uint32_t* bin_sums = reinterpret_cast<uint32_t*>(w + ws.bin_sums);
   const size_t n_px = (size_t)width * height;
-  const int tight = ((flags & MGS_FRAMES_CLASSIC_BOUNDS) ? 0 : MGS_BIN_TIGHT) |
-                    ((flags & MGS_FRAMES_RADIUS_OPACITY_AWARE) ? MGS_BIN_RADIUS_OPACITY_AWARE : 0) | camera_bin_flags(flags);
   for (int c = 0; c < n_cams; ++c) {
     char* s = static_cast<char*>(state) + st.total * (size_t)c;
     auto F = [&](int f) { return reinterpret_cast<float*>(s + st.at[f]); };
@@ -248,7 +251,7 @@ extern "C" int mgs_render_frames_train(int n, const float* means, const float* q
     rc = mgs_project_color_fwd(n, means, quats, scales, opacities, sh_degree, coeff_stride, sh_coeffs,
                                viewmats + 16 * (size_t)c, Ks + 9 * (size_t)c, width, height, eps2d, near_plane, far_plane,
                                radius_clip, I(TF_RADII), F(TF_MEANS2D), F(TF_DEPTHS), F(TF_CONICS), opac_aa, channels,
-                               F(TF_FEATS), F(TF_SPLATS), tight, bin_info, bin_sums, I(TF_RADII_Y), stream);
+                               F(TF_FEATS), F(TF_SPLATS), f.bin_flags, bin_info, bin_sums, I(TF_RADII_Y), stream);
     if (rc) return rc;
     size_t iw = isect_ws;
     rc = mgs_isect_tiles(n, nullptr, nullptr, nullptr, F(TF_DEPTHS), nullptr, nullptr, MGS_TILE_SIZE, tile_w, tile_h, c, n_cams,
@@ -276,29 +279,16 @@ extern "C" int mgs_render_frames_backward(int n, const float* means, const float
                                           float* v_sh_coeffs, float* v_opacities, float* v_viewmats, float* v_means2d,
                                           float* v_means2d_abs, void* workspace, size_t* workspace_bytes,
                                           mgs_stream_t stream) {
-  MGS_REQUIRE(n >= 0 && n_cams >= 1 && width > 0 && height > 0, "render_frames_backward: bad sizes");
-  MGS_REQUIRE(channels == 3 || channels == 4, "render_frames_backward: channels must be 3 or 4, got %d", channels);
-  MGS_REQUIRE(workspace_bytes, "render_frames_backward: workspace_bytes is null");
-  MGS_REQUIRE(isect_capacity > 0, "render_frames_backward: zero capacity");
-  MGS_REQUIRE(camera_flags_valid(flags),
-              "render_frames_backward: flags set both MGS_FRAMES_CAMERA_ORTHO and MGS_FRAMES_CAMERA_FISHEYE");
-  const int tile_w = (width + MGS_TILE_SIZE - 1) / MGS_TILE_SIZE, tile_h = (height + MGS_TILE_SIZE - 1) / MGS_TILE_SIZE;
-  float* const dummy = reinterpret_cast<float*>(16);      // (size query: the absgrad record layout follows this pointer)
-  size_t raster_ws = 0;
-  int rc = mgs_rasterize_bwd_det(0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, channels, width, height, tile_w,
-                                 tile_h, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                 isect_capacity, nullptr, nullptr, 0, 0, nullptr, v_means2d_abs ? dummy : nullptr, nullptr,
-                                 nullptr, nullptr, nullptr, &raster_ws, stream);
+  Frames f;
+  int rc = frames_prologue("render_frames_backward", n, n_cams, width, height, channels, flags, isect_capacity,
+                           workspace_bytes, &f, "3 or 4");
   if (rc) return rc;
-  if (checkpoint_interval) {       // the unit tables of the segmented launch live in the same workspace
-    size_t with_ckpt = 0;
-    rc = mgs_rasterize_bwd_det(0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, channels, width, height, tile_w,
-                               tile_h, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                               isect_capacity, dummy, dummy, checkpoint_interval, 0, nullptr, v_means2d_abs ? dummy : nullptr,
-                               nullptr, nullptr, nullptr, nullptr, &with_ckpt, stream);
-    if (rc) return rc;
-    raster_ws = with_ckpt > raster_ws ? with_ckpt : raster_ws;
-  }
+  const int tile_w = f.tile_w, tile_h = f.tile_h;
+  MGS_REQUIRE(checkpoint_interval == 0 || (checkpoint_interval >= 64 && (checkpoint_interval & (checkpoint_interval - 1)) == 0),
+              "rasterize_bwd_det: checkpoint_interval %d is not a power of two >= 64", checkpoint_interval);
+  // (with checkpoints: the unit tables of the segmented launch live in the same workspace)
+  const size_t raster_ws = mgs::rasterize_bwd_det_workspace_bytes(channels, v_means2d_abs != nullptr, isect_capacity, tile_w,
+                                                                  tile_h, checkpoint_interval);
   const BwdWs ws(n, channels, raster_ws);
   if (!workspace) {
     *workspace_bytes = ws.total;
@@ -341,7 +331,7 @@ extern "C" int mgs_render_frames_backward(int n, const float* means, const float
                                antialiased, channels, F(TF_FEATS), g_feat, g_m2d, g_con, nullptr,
                                antialiased ? g_opac : nullptr, v_means, v_quats, v_scales, v_sh_coeffs,
                                antialiased ? v_opacities : nullptr, v_viewmats ? v_viewmats + 16 * (size_t)c : nullptr,
-                               c > 0 ? 1 : 0, camera_model_of(flags), stream);
+                               c > 0 ? 1 : 0, f.camera_model, stream);
     if (rc) return rc;
     if (!antialiased && n > 0 && c > 0)     // later cameras add theirs
       hipLaunchKernelGGL(add_rows_kernel, dim3(mgs::div_up((unsigned)n, 256u)), dim3(256), 0, hs, (size_t)n, g_opac, v_opacities, 0);

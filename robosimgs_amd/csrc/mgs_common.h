@@ -7,6 +7,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <type_traits>
+
 #include "../../include/mgs.h"
 
 namespace mgs {
@@ -29,6 +31,61 @@ inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
   do {                         \
     if (!(cond)) return ::mgs::set_error(MGS_ERR_INVALID_ARGUMENT, __VA_ARGS__); \
   } while (0)
+
+// Bump allocator of a workspace or state layout: fields in the order taken, each on a 256-byte boundary.
+// min_field: the smallest size a field is given -- 1 keeps a 256-byte slot (and a distinct address) for an empty one.
+struct Bump {
+  size_t total = 0, min_field;
+  explicit Bump(size_t min_field) : min_field(min_field) {}
+  size_t take(size_t bytes) {
+    const size_t at = total;
+    total += align_up(bytes > min_field ? bytes : min_field, 256);
+    return at;
+  }
+};
+
+// ---- typed launch dispatch ----------------------------------------------------------------
+// Each helper maps a (validated) runtime value to a std::integral_constant and calls f with it, so that a generic lambda
+// names its instantiation as kernel<decltype(x)::value>.  Only the values listed are instantiated; a launch that exists
+// for some combinations only says so with `if constexpr`.
+template <int V> using int_c = std::integral_constant<int, V>;
+template <bool V> using bool_c = std::integral_constant<bool, V>;
+
+template <class F> void with_bool(bool b, F&& f) {
+  if (b) f(bool_c<true>{});
+  else f(bool_c<false>{});
+}
+// v in Lo..Hi-1 -> int_c<v>; any other value -> int_c<Hi>
+template <int Lo, int Hi, class F> void with_int(int v, F&& f) {
+  if constexpr (Lo == Hi) f(int_c<Hi>{});
+  else if (v == Lo) f(int_c<Lo>{});
+  else with_int<Lo + 1, Hi>(v, f);
+}
+// MGS_CAMERA_*: anything past MGS_CAMERA_ORTHO is MGS_CAMERA_FISHEYE
+template <class F> void with_camera(int model, F&& f) { with_int<MGS_CAMERA_PINHOLE, MGS_CAMERA_FISHEYE>(model, f); }
+// SH degree 0..3: anything past 2 is 3
+template <class F> void with_sh_degree(int degree, F&& f) { with_int<0, 3>(degree, f); }
+// MGS_RADIUS_OPACITY_AWARE when per_axis, MGS_RADIUS_CLASSIC otherwise
+template <class F> void with_radius_rule(bool per_axis, F&& f) {
+  if (per_axis) f(int_c<MGS_RADIUS_OPACITY_AWARE>{});
+  else f(int_c<MGS_RADIUS_CLASSIC>{});
+}
+// channels 1..MGS_MAX_CHANNELS -> the kernels' channel width: 1, 2, 3, 4, 8, 16 or 32
+template <class F> void with_channels(int channels, F&& f) {
+  if (channels == 1) f(int_c<1>{});
+  else if (channels == 2) f(int_c<2>{});
+  else if (channels == 3) f(int_c<3>{});
+  else if (channels == 4) f(int_c<4>{});
+  else if (channels <= 8) f(int_c<8>{});
+  else if (channels <= 16) f(int_c<16>{});
+  else f(int_c<32>{});
+}
+
+// the camera model the MGS_BIN_CAMERA_* bits of a bin_flags word select (at most one is set: the caller checks)
+inline int bin_camera_model(int bin_flags) {
+  return (bin_flags & MGS_BIN_CAMERA_ORTHO) ? MGS_CAMERA_ORTHO
+         : (bin_flags & MGS_BIN_CAMERA_FISHEYE) ? MGS_CAMERA_FISHEYE : MGS_CAMERA_PINHOLE;
+}
 
 // ---- wave64 helpers -----------------------------------------------------------------
 #if defined(__HIPCC__)
@@ -67,6 +124,13 @@ MGS_WAVE_REDUCE(wave_sum_u32, +, 0u)
 #endif
 
 // ---- internal launchers shared between translation units ---------------------------------
+// Workspace sizes (what the size queries of mgs_isect_tiles and mgs_rasterize_bwd_det report): binning n Gaussians
+// into at most `capacity` pairs on n_tiles tiles; the deterministic raster backward (checkpoint_interval 0: no
+// checkpoints; otherwise a power of two >= 64).  Hidden: they add nothing to the library's exported symbols.
+__attribute__((visibility("hidden"))) size_t isect_tiles_workspace_bytes(int n, uint32_t capacity, int n_tiles);
+__attribute__((visibility("hidden"))) size_t rasterize_bwd_det_workspace_bytes(int channels, bool absgrad, uint32_t capacity,
+                                                                               int tile_w, int tile_h, int checkpoint_interval);
+
 // Radix sort of (key, value) uint32 pairs on bits [0, key_bits) with the element count read
 // from device memory.  Buffers a/b alternate; the sorted result ends in (keys_out, vals_out).
 // temp: radix_sort_temp_bytes(capacity).

@@ -253,17 +253,12 @@ extern "C" int mgs_projection_fwd(int n, const float* means, const float* quats,
   MGS_REQUIRE(radius_rule == MGS_RADIUS_CLASSIC || radius_rule == MGS_RADIUS_OPACITY_AWARE,
               "projection_fwd: radius_rule %d is neither MGS_RADIUS_CLASSIC nor MGS_RADIUS_OPACITY_AWARE", radius_rule);
   MGS_REQUIRE(radius_rule == MGS_RADIUS_CLASSIC || radii_y, "projection_fwd: the per-axis radius rule needs radii_y");
-#define MGS_PF_LAUNCH(CAM)                                                                      \
-  hipLaunchKernelGGL(projection_fwd_kernel<CAM>, dim3(div_up(n, kBlock)), dim3(kBlock), 0,         \
-                     (hipStream_t)stream, n, means, quats, scales, viewmat, K, (float)width,       \
-                     (float)height, eps2d, near_plane, far_plane, radius_clip, radii, means2d,     \
-                     depths, conics, compensations, opacities, radius_rule, radii_y)
-  switch (camera_model) {
-    case MGS_CAMERA_PINHOLE: MGS_PF_LAUNCH(MGS_CAMERA_PINHOLE); break;
-    case MGS_CAMERA_ORTHO: MGS_PF_LAUNCH(MGS_CAMERA_ORTHO); break;
-    default: MGS_PF_LAUNCH(MGS_CAMERA_FISHEYE); break;
-  }
-#undef MGS_PF_LAUNCH
+  with_camera(camera_model, [&](auto cam) {
+    hipLaunchKernelGGL(projection_fwd_kernel<decltype(cam)::value>, dim3(div_up(n, kBlock)), dim3(kBlock), 0,
+                       (hipStream_t)stream, n, means, quats, scales, viewmat, K, (float)width, (float)height, eps2d,
+                       near_plane, far_plane, radius_clip, radii, means2d, depths, conics, compensations, opacities,
+                       radius_rule, radii_y);
+  });
   return check_launch("projection_fwd");
 }
 
@@ -278,15 +273,13 @@ extern "C" int mgs_sh_fwd(int n, int degree, int coeff_stride, const float* dirs
   hipStream_t s = (hipStream_t)stream;
   int sf = coeff_stride * 3;
   bool staged = coeff_stride == 16 && degree >= 2;
-#define MGS_SH_LAUNCH(D, S) \
-  hipLaunchKernelGGL((sh_fwd_kernel<D, S>), grid, block, 0, s, n, sf, dirs, coeffs, masks, colors)
-  switch (degree) {
-    case 0: MGS_SH_LAUNCH(0, false); break;
-    case 1: MGS_SH_LAUNCH(1, false); break;
-    case 2: if (staged) MGS_SH_LAUNCH(2, true); else MGS_SH_LAUNCH(2, false); break;
-    default: if (staged) MGS_SH_LAUNCH(3, true); else MGS_SH_LAUNCH(3, false); break;
-  }
-#undef MGS_SH_LAUNCH
+  with_sh_degree(degree, [&](auto d) {
+    with_bool(staged, [&](auto st) {
+      constexpr int D = decltype(d)::value;
+      if constexpr (D >= 2 || !decltype(st)::value)      // (degrees 0 and 1 are never staged)
+        hipLaunchKernelGGL((sh_fwd_kernel<D, decltype(st)::value>), grid, block, 0, s, n, sf, dirs, coeffs, masks, colors);
+    });
+  });
   return check_launch("sh_fwd");
 }
 
@@ -304,8 +297,7 @@ extern "C" int mgs_project_color_fwd(int n, const float* means, const float* qua
   const bool per_axis = (bin_flags & MGS_BIN_RADIUS_OPACITY_AWARE) != 0;
   MGS_REQUIRE((bin_flags & (MGS_BIN_CAMERA_ORTHO | MGS_BIN_CAMERA_FISHEYE)) != (MGS_BIN_CAMERA_ORTHO | MGS_BIN_CAMERA_FISHEYE),
               "project_color_fwd: bin_flags sets both MGS_BIN_CAMERA_ORTHO and MGS_BIN_CAMERA_FISHEYE");
-  const int cam_model = (bin_flags & MGS_BIN_CAMERA_ORTHO) ? MGS_CAMERA_ORTHO
-                        : (bin_flags & MGS_BIN_CAMERA_FISHEYE) ? MGS_CAMERA_FISHEYE : MGS_CAMERA_PINHOLE;
+  const int cam_model = bin_camera_model(bin_flags);
   MGS_REQUIRE(n >= 0 && width > 0 && height > 0, "project_color_fwd: bad sizes");
   MGS_REQUIRE(sh_degree >= 0 && sh_degree <= 3, "project_color_fwd: sh_degree %d not in 0..3", sh_degree);
   MGS_REQUIRE(coeff_stride >= (sh_degree + 1) * (sh_degree + 1), "project_color_fwd: coeff_stride too small");
@@ -327,27 +319,20 @@ extern "C" int mgs_project_color_fwd(int n, const float* means, const float* qua
   hipStream_t s = (hipStream_t)stream;
   int sf = coeff_stride * 3;
   bool staged = coeff_stride == 16 && sh_degree >= 2;
-#define MGS_PC_LAUNCH(D, S)                                                                   \
-  if (per_axis) MGS_PC_LAUNCH_C(D, S, MGS_RADIUS_OPACITY_AWARE); else MGS_PC_LAUNCH_C(D, S, MGS_RADIUS_CLASSIC)
-#define MGS_PC_LAUNCH_C(D, S, R)                                                              \
-  if (cam_model == MGS_CAMERA_PINHOLE) MGS_PC_LAUNCH_R(D, S, R, MGS_CAMERA_PINHOLE);         \
-  else if (cam_model == MGS_CAMERA_ORTHO) MGS_PC_LAUNCH_R(D, S, R, MGS_CAMERA_ORTHO);        \
-  else MGS_PC_LAUNCH_R(D, S, R, MGS_CAMERA_FISHEYE)
-#define MGS_PC_LAUNCH_R(D, S, R, CAM)                                                         \
-  hipLaunchKernelGGL((project_color_fwd_kernel<D, S, R, CAM>), grid, block, 0, s, n, means, quats, \
-                     scales, opacities, sf, sh_coeffs, viewmat, K, (float)width,              \
-                     (float)height, eps2d, near_plane, far_plane, radius_clip, radii,         \
-                     means2d, depths, conics, opac_out, feat_stride, feats,                    \
-                     reinterpret_cast<float4*>(splats), reinterpret_cast<uint2*>(bin_info),     \
-                     bin_sums, bin_tight, tile_w, tile_h, radii_y)
-  switch (sh_degree) {
-    case 0: MGS_PC_LAUNCH(0, false); break;
-    case 1: MGS_PC_LAUNCH(1, false); break;
-    case 2: if (staged) { MGS_PC_LAUNCH(2, true); } else { MGS_PC_LAUNCH(2, false); } break;
-    default: if (staged) { MGS_PC_LAUNCH(3, true); } else { MGS_PC_LAUNCH(3, false); } break;
-  }
-#undef MGS_PC_LAUNCH
-#undef MGS_PC_LAUNCH_C
-#undef MGS_PC_LAUNCH_R
+  with_sh_degree(sh_degree, [&](auto d) {
+    with_bool(staged, [&](auto st) {
+      with_radius_rule(per_axis, [&](auto rule) {
+        with_camera(cam_model, [&](auto cam) {
+          constexpr int D = decltype(d)::value;
+          if constexpr (D >= 2 || !decltype(st)::value)    // (degrees 0 and 1 are never staged)
+            hipLaunchKernelGGL((project_color_fwd_kernel<D, decltype(st)::value, decltype(rule)::value, decltype(cam)::value>),
+                               grid, block, 0, s, n, means, quats, scales, opacities, sf, sh_coeffs, viewmat, K,
+                               (float)width, (float)height, eps2d, near_plane, far_plane, radius_clip, radii, means2d,
+                               depths, conics, opac_out, feat_stride, feats, reinterpret_cast<float4*>(splats),
+                               reinterpret_cast<uint2*>(bin_info), bin_sums, bin_tight, tile_w, tile_h, radii_y);
+        });
+      });
+    });
+  });
   return check_launch("project_color_fwd");
 }

@@ -1076,7 +1076,34 @@ __global__ __launch_bounds__(256) void reduce_records_rows_kernel(
   if constexpr (ABSGRAD) reinterpret_cast<float2*>(v_means2d_abs)[g] = make_float2(acc[6 + CHT], acc[7 + CHT]);
 }
 
+// mgs_rasterize_bwd_det's workspace: the records, their flags, the header of the big lists' counters (zeroed with the
+// flags), the launch order of the whole-tile walk or the unit tables of the segmented one (their 64 counters first: zeroed
+// together with the flags), and the items of the big lists (reduce_records_rows_kernel, up to 4 channels)
+struct BwdDetWs {
+  size_t cap;                  // isect_capacity, at least 1
+  int ckpt_shift = 0;          // log2 of the checkpoint interval (0: no checkpoints)
+  size_t records, flags, big_counts, order, big_items, total;
+  BwdDetWs(int channels, bool absgrad, uint32_t isect_capacity, int n_tiles, int checkpoint_interval)
+      : cap(isect_capacity ? isect_capacity : 1) {
+    while ((1 << ckpt_shift) < checkpoint_interval) ++ckpt_shift;
+    Bump b(0);
+    records = b.take(cap * record_floats(padded_channels(channels), absgrad) * sizeof(float));
+    flags = b.take(cap);
+    big_counts = b.take(256);
+    static_assert(kBigLists * sizeof(uint32_t) <= 256, "the big lists' counters fit their header");
+    order = b.take(std::max((size_t)n_tiles * sizeof(int32_t),
+                            checkpoint_interval ? unit_tables_bytes(n_tiles, ckpt_shift, (uint32_t)cap) : 0));
+    big_items = b.take(channels <= 4 ? big_lists_bytes((uint32_t)cap) : 0);
+    total = b.total;
+  }
+};
+
 }  // namespace
+
+size_t rasterize_bwd_det_workspace_bytes(int channels, bool absgrad, uint32_t capacity, int tile_w, int tile_h,
+                                         int checkpoint_interval) {
+  return BwdDetWs(channels, absgrad, capacity, tile_w * tile_h, checkpoint_interval).total;
+}
 }  // namespace mgs
 
 using namespace mgs;
@@ -1111,24 +1138,16 @@ extern "C" int mgs_rasterize_bwd(int n, const float* means2d, const float* conic
                   v_opacities, "rasterize_bwd: null pointer");
   const int n_tiles = tile_w * tile_h;
   hipStream_t s = (hipStream_t)stream;
-#define MGS_RB_LAUNCH(C, A)                                                                    \
-  hipLaunchKernelGGL((raster_bwd_kernel<C, A, false>), dim3(div_up(n_tiles, kBwdWgWaves)), dim3(64 * kBwdWgWaves), 0, s, means2d,  \
-                     conics, feats, opacities, (const float4*)nullptr, background, channels,   \
-                     width, height, tile_w,                                                    \
-                     n_tiles, tile_offsets, flatten_ids, alphas, last_ids, v_render, v_alphas, \
-                     v_means2d, v_means2d_abs, v_conics, v_feats, v_opacities,                 \
-                     (const int4*)nullptr, (float*)nullptr, (uint8_t*)nullptr, 0u, (const float*)nullptr, \
-                     (const int32_t*)nullptr, (const float*)nullptr, 0, (const int32_t*)nullptr, (const float*)nullptr, 0)
-#define MGS_RB(C) if (v_means2d_abs) MGS_RB_LAUNCH(C, true); else MGS_RB_LAUNCH(C, false)
-  if (channels == 1) { MGS_RB(1); }
-  else if (channels == 2) { MGS_RB(2); }
-  else if (channels == 3) { MGS_RB(3); }
-  else if (channels == 4) { MGS_RB(4); }
-  else if (channels <= 8) { MGS_RB(8); }
-  else if (channels <= 16) { MGS_RB(16); }
-  else { MGS_RB(32); }
-#undef MGS_RB
-#undef MGS_RB_LAUNCH
+  with_channels(channels, [&](auto cht) {
+    with_bool(v_means2d_abs != nullptr, [&](auto absgrad) {       // (the atomic form: no records)
+      hipLaunchKernelGGL((raster_bwd_kernel<decltype(cht)::value, decltype(absgrad)::value, false>),
+                         dim3(div_up(n_tiles, kBwdWgWaves)), dim3(64 * kBwdWgWaves), 0, s, means2d, conics, feats, opacities,
+                         (const float4*)nullptr, background, channels, width, height, tile_w, n_tiles, tile_offsets,
+                         flatten_ids, alphas, last_ids, v_render, v_alphas, v_means2d, v_means2d_abs, v_conics, v_feats,
+                         v_opacities, (const int4*)nullptr, (float*)nullptr, (uint8_t*)nullptr, 0u, (const float*)nullptr,
+                         (const int32_t*)nullptr, (const float*)nullptr, 0, (const int32_t*)nullptr, (const float*)nullptr, 0);
+    });
+  });
   return check_launch("rasterize_bwd");
 }
 
@@ -1152,32 +1171,19 @@ extern "C" int mgs_rasterize_bwd_det(int n, const float* means2d, const float* c
   MGS_REQUIRE(tile_w == (width + 15) / 16 && tile_h == (height + 15) / 16,
               "rasterize_bwd_det: tile grid does not match the image at tile size 16");
   MGS_REQUIRE(workspace_bytes, "rasterize_bwd_det: workspace_bytes is null");
-  const int rs = record_floats(padded_channels(channels), v_means2d_abs != nullptr);   // floats per record
-  const size_t cap = isect_capacity ? isect_capacity : 1;
-  const size_t rec_bytes = align_up(cap * rs * sizeof(float), 256);
-  const size_t flag_bytes = align_up(cap, 256);
   // segmented walk (checkpoints from mgs_rasterize_fwd): up to 4 channels, whole tiles
-  int ckpt_shift = 0;
   const bool split = checkpoints != nullptr && channels <= 4;
   if (checkpoints) {
     MGS_REQUIRE(checkpoint_interval >= 64 && (checkpoint_interval & (checkpoint_interval - 1)) == 0,
                 "rasterize_bwd_det: checkpoint_interval %d is not a power of two >= 64", checkpoint_interval);
     MGS_REQUIRE(render_out, "rasterize_bwd_det: checkpoints need render_out (the forward's frame)");
     MGS_REQUIRE(!expected_render || expected_render == render_out, "rasterize_bwd_det: expected_render and render_out are the same frame");
-    while ((1 << ckpt_shift) < checkpoint_interval) ++ckpt_shift;
   }
+  const BwdDetWs ws(channels, v_means2d_abs != nullptr, isect_capacity, tile_w * tile_h, checkpoints ? checkpoint_interval : 0);
+  const size_t cap = ws.cap, need = ws.total;
+  const int ckpt_shift = ws.ckpt_shift;
   const size_t n_seg_units = checkpoints ? ckpt_units((uint32_t)cap, tile_w * tile_h, ckpt_shift) : 0;
-  // behind the flags: the launch order of the whole-tile walk, or the unit tables of the segmented one (their 64
-  // counters first: zeroed together with the flags)
-  const size_t order_bytes = align_up(std::max((size_t)tile_w * tile_h * sizeof(int32_t),
-                                               checkpoints ? unit_tables_bytes(tile_w * tile_h, ckpt_shift, (uint32_t)cap) : 0), 256);
-  // the lists of big rectangles (reduce_records_rows_kernel): their kBigLists counters right behind the flags (zeroed with
-  // them), the items at the end
-  constexpr size_t big_hdr = 256;
-  static_assert(kBigLists * sizeof(uint32_t) <= big_hdr, "the big lists' counters fit their header");
   const bool big_path = channels <= 4;
-  const size_t big_bytes = big_path ? align_up(big_lists_bytes((uint32_t)cap), 256) : 0;
-  const size_t need = rec_bytes + flag_bytes + big_hdr + order_bytes + big_bytes;
   if (!workspace) {
     *workspace_bytes = need;
     return MGS_OK;
@@ -1199,17 +1205,18 @@ extern "C" int mgs_rasterize_bwd_det(int n, const float* means2d, const float* c
                   (records_only || (v_means2d && v_conics && v_feats && v_opacities)), "rasterize_bwd_det: null pointer");
   const int n_tiles = tile_w * tile_h;
   hipStream_t s = (hipStream_t)stream;
-  float* records = static_cast<float*>(workspace);
-  uint8_t* flags = static_cast<uint8_t*>(workspace) + rec_bytes;
-  uint32_t* big_counts = reinterpret_cast<uint32_t*>(flags + flag_bytes);
-  uint32_t* big_items = reinterpret_cast<uint32_t*>(flags + flag_bytes + big_hdr + order_bytes);
-  hipError_t e = hipMemsetAsync(flags, 0, flag_bytes + big_hdr + (split ? 256 : 0), s);
+  uint8_t* const w = static_cast<uint8_t*>(workspace);
+  float* records = reinterpret_cast<float*>(w + ws.records);
+  uint8_t* flags = w + ws.flags;
+  uint32_t* big_counts = reinterpret_cast<uint32_t*>(w + ws.big_counts);
+  uint32_t* big_items = reinterpret_cast<uint32_t*>(w + ws.big_items);
+  hipError_t e = hipMemsetAsync(flags, 0, ws.order - ws.flags + (split ? 256 : 0), s);
   if (e != hipSuccess) return set_error((int)e, "rasterize_bwd_det: memset: %s", hipGetErrorString(e));
   const int4* info = reinterpret_cast<const int4*>(pair_info);
   const int32_t* order = nullptr;
   int32_t* seg_table = nullptr;
   if (split) {
-    seg_table = reinterpret_cast<int32_t*>(static_cast<uint8_t*>(workspace) + rec_bytes + flag_bytes + big_hdr);
+    seg_table = reinterpret_cast<int32_t*>(w + ws.order);
     // (+ the workgroups that list the big rectangles for the reduce)
     const unsigned n_disc = big_path && !records_only ? div_up(n, 256 * kDiscoverPerThread) : 0;
     hipLaunchKernelGGL(unit_table_kernel, dim3(div_up(n_tiles, 256) + n_disc), dim3(256), 0, s, n_tiles, tile_offsets,
@@ -1217,7 +1224,7 @@ extern "C" int mgs_rasterize_bwd_det(int n, const float* means2d, const float* c
   } else {
     order = tile_group_order;
     if (!order) {       // the caller's lists came without one (mgs_isect_tiles writes it): compute it here
-      int32_t* mine = reinterpret_cast<int32_t*>(static_cast<uint8_t*>(workspace) + rec_bytes + flag_bytes + big_hdr);
+      int32_t* mine = reinterpret_cast<int32_t*>(w + ws.order);
       const int rc = launch_tile_group_order(n_tiles, tile_offsets, mine, s);
       if (rc) return rc;
       order = mine;
@@ -1228,37 +1235,31 @@ extern "C" int mgs_rasterize_bwd_det(int n, const float* means2d, const float* c
   // (segmented: whole blocks of the XCD-aware unit numbering; units past the live count leave at once)
   const int n_units = split ? (int)((n_seg_units + 8 * kBwdXcdRun - 1) / (8 * kBwdXcdRun)) * 8 * kBwdXcdRun
                             : order ? (n_tiles + 3) / 4 * 4 : n_tiles;
-#define MGS_RD_RASTER(C, A, SP)                                                                 \
-  hipLaunchKernelGGL((raster_bwd_kernel<C, A, true, SP>), dim3(div_up(n_units, kBwdWgWaves)), dim3(64 * kBwdWgWaves), 0, s, means2d, \
-                     conics, feats, opacities, reinterpret_cast<const float4*>(splats),        \
-                     background, channels, width, height, tile_w,                              \
-                     n_tiles, tile_offsets, flatten_ids, alphas, last_ids, v_render, v_alphas, \
-                     (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr,       \
-                     (float*)nullptr, info, records, flags, (uint32_t)cap, expected_render,    \
-                     (const int32_t*)order, checkpoints, ckpt_shift, (const int32_t*)seg_table, render_out, splat_slots)
-#define MGS_RD_LAUNCH(C, A)                                                                     \
-  if (split) MGS_RD_RASTER(C, A, ((C) <= 4)); else MGS_RD_RASTER(C, A, false);                  \
-  if (!records_only) {                                                                          \
-    if constexpr ((C) <= 4)                                                                     \
-      hipLaunchKernelGGL((reduce_records_rows_kernel<((C) <= 4 ? (C) : 4), A>), dim3(kBigWGs + div_up(n, 256)), dim3(256), 0, s, n, \
-                         info, records, flags, (uint32_t)cap, means2d, conics, opacities,      \
-                         reinterpret_cast<const float4*>(splats),                              \
-                         channels, v_means2d, v_means2d_abs, v_conics, v_feats, v_opacities, big_counts, big_items);  \
-    else                                                                                        \
-      hipLaunchKernelGGL((reduce_records_kernel<C, A>), dim3(div_up(n, 256)), dim3(256), 0, s, n,  \
-                         info, records, flags, (uint32_t)cap, means2d, conics, opacities,      \
-                         reinterpret_cast<const float4*>(splats),                              \
-                         channels, v_means2d, v_means2d_abs, v_conics, v_feats, v_opacities); }
-#define MGS_RD(C) if (v_means2d_abs) { MGS_RD_LAUNCH(C, true); } else { MGS_RD_LAUNCH(C, false); }
-  if (channels == 1) { MGS_RD(1) }
-  else if (channels == 2) { MGS_RD(2) }
-  else if (channels == 3) { MGS_RD(3) }
-  else if (channels == 4) { MGS_RD(4) }
-  else if (channels <= 8) { MGS_RD(8) }
-  else if (channels <= 16) { MGS_RD(16) }
-  else { MGS_RD(32) }
-#undef MGS_RD
-#undef MGS_RD_LAUNCH
-#undef MGS_RD_RASTER
+  with_channels(channels, [&](auto cht) {
+    with_bool(v_means2d_abs != nullptr, [&](auto absgrad) {
+      constexpr int C = decltype(cht)::value;
+      constexpr bool A = decltype(absgrad)::value;
+      auto raster = [&](auto seg) {
+        hipLaunchKernelGGL((raster_bwd_kernel<C, A, true, decltype(seg)::value>), dim3(div_up(n_units, kBwdWgWaves)),
+                           dim3(64 * kBwdWgWaves), 0, s, means2d, conics, feats, opacities,
+                           reinterpret_cast<const float4*>(splats), background, channels, width, height, tile_w, n_tiles,
+                           tile_offsets, flatten_ids, alphas, last_ids, v_render, v_alphas, (float*)nullptr, (float*)nullptr,
+                           (float*)nullptr, (float*)nullptr, (float*)nullptr, info, records, flags, (uint32_t)cap,
+                           expected_render, (const int32_t*)order, checkpoints, ckpt_shift, (const int32_t*)seg_table,
+                           render_out, splat_slots);
+      };
+      if constexpr (C <= 4) with_bool(split, raster);       // (the segmented walk exists up to 4 channels)
+      else raster(bool_c<false>{});
+      if (records_only) return;
+      if constexpr (C <= 4)
+        hipLaunchKernelGGL((reduce_records_rows_kernel<C, A>), dim3(kBigWGs + div_up(n, 256)), dim3(256), 0, s, n, info,
+                           records, flags, (uint32_t)cap, means2d, conics, opacities, reinterpret_cast<const float4*>(splats),
+                           channels, v_means2d, v_means2d_abs, v_conics, v_feats, v_opacities, big_counts, big_items);
+      else
+        hipLaunchKernelGGL((reduce_records_kernel<C, A>), dim3(div_up(n, 256)), dim3(256), 0, s, n, info, records, flags,
+                           (uint32_t)cap, means2d, conics, opacities, reinterpret_cast<const float4*>(splats), channels,
+                           v_means2d, v_means2d_abs, v_conics, v_feats, v_opacities);
+    });
+  });
   return check_launch("rasterize_bwd_det");
 }

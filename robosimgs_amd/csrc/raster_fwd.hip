@@ -739,44 +739,27 @@ extern "C" int mgs_rasterize_fwd(int n, const float* means2d, const float* conic
   if (g_raster_opts & 8) tile_group_order = nullptr;
   if ((g_raster_opts & 16) && !per_block && !last_ids) tile_group_order = nullptr;
   const int n_units = tile_group_order ? (n_tiles + 3) / 4 * 4 : n_tiles;       // tile slots of the launch
-#define MGS_RF_LAUNCH_T(C, T)                                                                  \
-  hipLaunchKernelGGL((raster_fwd_kernel<C, T>), dim3(div_up(n_units, (T) ? 1 : kFwdWgWaves)),   \
-                     dim3(64 * ((T) ? 1 : kFwdWgWaves)), (T) ? 0 : (size_t)(g_raster_opts >> 8) * 1024, s, means2d, conics, \
-                     feats, opacities, reinterpret_cast<const float4*>(splats), background,     \
-                     channels, width, height, tile_w, n_tiles,                                 \
-                     tile_offsets, flatten_ids, render, alphas, last_ids, g_raster_cull,            \
-                     (flags & MGS_RASTER_EXPECTED_LAST) ? 1 : 0, g_raster_opts, tile_group_order, checkpoints, ckpt_shift, NoDataset{})
-#define MGS_RQ_LAUNCH_T(C, T)                                                                  \
-  hipLaunchKernelGGL((raster_fwd_q_kernel<C, T>), dim3(n_units), dim3(256), (size_t)(g_raster_opts >> 8) * 1024, s, means2d, conics, feats,  \
-                     opacities, reinterpret_cast<const float4*>(splats), background, channels, width,      \
-                     height, tile_w, n_tiles, tile_offsets, flatten_ids, render, alphas, last_ids,         \
-                     g_raster_cull, (flags & MGS_RASTER_EXPECTED_LAST) ? 1 : 0, tile_group_order, checkpoints, ckpt_shift, NoDataset{})
-#define MGS_RF_LAUNCH(C) do {                                                                      \
-    if (per_block && (C) <= 4) { if (last_ids) MGS_RQ_LAUNCH_T(C, true); else MGS_RQ_LAUNCH_T(C, false); } \
-    else if (last_ids) MGS_RF_LAUNCH_T(C, true); else MGS_RF_LAUNCH_T(C, false); } while (0)
-  if (ds.rgba) {          // 4 channels, inference, "ED": the dataset instantiations of the two schedules
-    if (per_block)
-      hipLaunchKernelGGL((raster_fwd_q_kernel<4, false, true>), dim3(n_units), dim3(256), (size_t)(g_raster_opts >> 8) * 1024, s,
-                         means2d, conics, feats, opacities, reinterpret_cast<const float4*>(splats), background, channels, width,
-                         height, tile_w, n_tiles, tile_offsets, flatten_ids, render, alphas, last_ids, g_raster_cull, 1,
-                         tile_group_order, checkpoints, ckpt_shift, ds);
-    else
-      hipLaunchKernelGGL((raster_fwd_kernel<4, false, true>), dim3(div_up(n_units, kFwdWgWaves)),
-                         dim3(64 * kFwdWgWaves), (size_t)(g_raster_opts >> 8) * 1024, s, means2d, conics, feats, opacities,
-                         reinterpret_cast<const float4*>(splats), background, channels, width, height, tile_w, n_tiles,
-                         tile_offsets, flatten_ids, render, alphas, last_ids, g_raster_cull, 1, g_raster_opts, tile_group_order,
-                         checkpoints, ckpt_shift, ds);
-    return check_launch("rasterize_fwd");
-  }
-  if (channels == 1) MGS_RF_LAUNCH(1);
-  else if (channels == 2) MGS_RF_LAUNCH(2);
-  else if (channels == 3) MGS_RF_LAUNCH(3);
-  else if (channels == 4) MGS_RF_LAUNCH(4);
-  else if (channels <= 8) MGS_RF_LAUNCH(8);
-  else if (channels <= 16) MGS_RF_LAUNCH(16);
-  else MGS_RF_LAUNCH(32);
-#undef MGS_RF_LAUNCH
-#undef MGS_RF_LAUNCH_T
-#undef MGS_RQ_LAUNCH_T
+  const int expected_last = (flags & MGS_RASTER_EXPECTED_LAST) ? 1 : 0;
+  const size_t opts_lds = (size_t)(g_raster_opts >> 8) * 1024;
+  // ds_arg: NoDataset{}, or the DatasetOut of a dataset frame (4 channels, inference, "ED")
+  auto launch = [&](auto cht, auto track_last, auto ds_arg) {
+    constexpr int C = decltype(cht)::value;
+    constexpr bool T = decltype(track_last)::value, DS = std::is_same<decltype(ds_arg), DatasetOut>::value;
+    if (per_block && C <= 4) {    // (a run-time test: the wider instantiations exist, unlaunched)
+      hipLaunchKernelGGL((raster_fwd_q_kernel<C, T, DS>), dim3(n_units), dim3(256), opts_lds, s, means2d, conics, feats,
+                         opacities, reinterpret_cast<const float4*>(splats), background, channels, width, height, tile_w,
+                         n_tiles, tile_offsets, flatten_ids, render, alphas, last_ids, g_raster_cull, expected_last,
+                         tile_group_order, checkpoints, ckpt_shift, ds_arg);
+      return;
+    }
+    hipLaunchKernelGGL((raster_fwd_kernel<C, T, DS>), dim3(div_up(n_units, T ? 1 : kFwdWgWaves)),
+                       dim3(64 * (T ? 1 : kFwdWgWaves)), T ? 0 : opts_lds, s, means2d, conics, feats, opacities,
+                       reinterpret_cast<const float4*>(splats), background, channels, width, height, tile_w, n_tiles,
+                       tile_offsets, flatten_ids, render, alphas, last_ids, g_raster_cull, expected_last, g_raster_opts,
+                       tile_group_order, checkpoints, ckpt_shift, ds_arg);
+  };
+  if (ds.rgba) launch(int_c<4>{}, bool_c<false>{}, ds);
+  else
+    with_channels(channels, [&](auto cht) { with_bool(last_ids != nullptr, [&](auto t) { launch(cht, t, NoDataset{}); }); });
   return check_launch("rasterize_fwd");
 }

@@ -211,21 +211,10 @@ void launch_pass(const uint32_t* n_dev, uint32_t capacity, int shift, int bits, 
                      capacity, shift, mask, keys_a, counts, nblk_cap);
   hipLaunchKernelGGL(radix_rowscan_kernel, dim3(kRadix), dim3(kThreads), 0, stream, n_dev,
                      capacity, (uint32_t)kTile, counts, totals, nblk_cap);
-#define MGS_SCATTER(B)                                                                          \
-  hipLaunchKernelGGL((radix_scatter_kernel<ITEMS, B>), dim3(nblk_cap), dim3(kThreads), 0,      \
-                     stream, n_dev, capacity, shift, mask, keys_a, vals_a, keys_b, vals_b,      \
-                     counts, totals, nblk_cap)
-  switch (bits) {
-    case 1: MGS_SCATTER(1); break;
-    case 2: MGS_SCATTER(2); break;
-    case 3: MGS_SCATTER(3); break;
-    case 4: MGS_SCATTER(4); break;
-    case 5: MGS_SCATTER(5); break;
-    case 6: MGS_SCATTER(6); break;
-    case 7: MGS_SCATTER(7); break;
-    default: MGS_SCATTER(8); break;
-  }
-#undef MGS_SCATTER
+  with_int<1, 8>(bits, [&](auto b) {          // digit width 1..8 (8 unless fewer bits are left)
+    hipLaunchKernelGGL((radix_scatter_kernel<ITEMS, decltype(b)::value>), dim3(nblk_cap), dim3(kThreads), 0, stream, n_dev,
+                       capacity, shift, mask, keys_a, vals_a, keys_b, vals_b, counts, totals, nblk_cap);
+  });
 }
 
 
@@ -449,16 +438,11 @@ int radix_sort_pairs(const uint32_t* n_dev, uint32_t capacity, int key_bits, uin
     int shift = 0;
     for (int p = 0; p < passes; ++p) {
       const uint32_t mask = (1u << bits[p]) - 1u;
-#define MGS_SWEEP(B)                                                                                       \
-      hipLaunchKernelGGL((onesweep_scatter_kernel<IT, B>), dim3(nblk_cap), dim3(kThreads), 0, stream, n_dev, \
-                         capacity, shift, mask, keys_a, vals_a, keys_b, vals_b, ghist + p * kRadix,          \
-                         tickets + p, status + (size_t)p * nblk_cap * kRadix)
-      switch (bits[p]) {
-        case 1: MGS_SWEEP(1); break; case 2: MGS_SWEEP(2); break; case 3: MGS_SWEEP(3); break;
-        case 4: MGS_SWEEP(4); break; case 5: MGS_SWEEP(5); break; case 6: MGS_SWEEP(6); break;
-        case 7: MGS_SWEEP(7); break; default: MGS_SWEEP(8); break;
-      }
-#undef MGS_SWEEP
+      with_int<1, 8>(bits[p], [&](auto b) {
+        hipLaunchKernelGGL((onesweep_scatter_kernel<IT, decltype(b)::value>), dim3(nblk_cap), dim3(kThreads), 0, stream,
+                           n_dev, capacity, shift, mask, keys_a, vals_a, keys_b, vals_b, ghist + p * kRadix, tickets + p,
+                           status + (size_t)p * nblk_cap * kRadix);
+      });
       shift += bits[p];
       uint32_t* t;
       t = keys_a; keys_a = keys_b; keys_b = t;

@@ -1150,20 +1150,20 @@ int tile_depth_sort(int n_tiles, const int32_t* tile_offsets, const float* depth
   const bool mid_lists = !short_lists && (size_t)capacity <= (size_t)n_tiles * 1000;
   // (GROUPED launches are padded to whole blocks of 8 groups: the kernel's XCD-aware tile numbering)
   const int per = 8 << group_shift, n_wg = staging ? (n_tiles + per - 1) / per * per : n_tiles;
-#define MGS_TS_LAUNCH(G, F, D, OFFS, STG, SH, OUT)                                                              \
-  hipLaunchKernelGGL((tile_depth_sort_kernel<G, F, D>), dim3(n_wg), dim3(kTSMain), 0, stream, n_tiles, OFFS,   \
-                     depths, flatten_ids, tile_ids_fill, t, t + stride, t + 2 * stride, t + 3 * stride,    \
-                     STG, SH, OUT, aux)
-  if (staging) {
-    if (short_lists) MGS_TS_LAUNCH(true, kFastShort, false, group_offsets, staging, group_shift, const_cast<int32_t*>(tile_offsets));
-    else if (mid_lists) MGS_TS_LAUNCH(true, kFastMid, true, group_offsets, staging, group_shift, const_cast<int32_t*>(tile_offsets));
-    else MGS_TS_LAUNCH(true, kFastLong, true, group_offsets, staging, group_shift, const_cast<int32_t*>(tile_offsets));
-  } else {
-    if (short_lists) MGS_TS_LAUNCH(false, kFastShort, false, tile_offsets, (const uint32_t*)nullptr, 0, (int32_t*)nullptr);
-    else if (mid_lists) MGS_TS_LAUNCH(false, kFastMid, true, tile_offsets, (const uint32_t*)nullptr, 0, (int32_t*)nullptr);
-    else MGS_TS_LAUNCH(false, kFastLong, true, tile_offsets, (const uint32_t*)nullptr, 0, (int32_t*)nullptr);
-  }
-#undef MGS_TS_LAUNCH
+  // fast: the longest list of the fast path; every form but the short-list one defers longer lists to the units
+  auto launch = [&](auto grouped, auto fast) {
+    constexpr bool G = decltype(grouped)::value;
+    constexpr int F = decltype(fast)::value;
+    hipLaunchKernelGGL((tile_depth_sort_kernel<G, F, F != kFastShort>), dim3(n_wg), dim3(kTSMain), 0, stream, n_tiles,
+                       G ? group_offsets : tile_offsets, depths, flatten_ids, tile_ids_fill, t, t + stride, t + 2 * stride,
+                       t + 3 * stride, G ? staging : nullptr, G ? group_shift : 0,
+                       G ? const_cast<int32_t*>(tile_offsets) : nullptr, aux);
+  };
+  with_bool(staging != nullptr, [&](auto grouped) {
+    if (short_lists) launch(grouped, int_c<kFastShort>{});
+    else if (mid_lists) launch(grouped, int_c<kFastMid>{});
+    else launch(grouped, int_c<kFastLong>{});
+  });
   if (short_lists) return check_launch("tile_depth_sort");
   // the deferred lists: their entries into buffer 0 with the units' counts, then the units (launches that read a zero and
   // leave where no list is long)

@@ -157,15 +157,14 @@ extern "C" int mgs_transform_gaussians(int n, const float* means, const float* q
   dim3 grid(div_up(n, kBlock)), block(kBlock);
   hipStream_t s = (hipStream_t)stream;
   const int stride_f = coeff_stride * 3;
-  if (sh_coeffs && coeff_stride == 16)
-    hipLaunchKernelGGL((transform_kernel<true, true>), grid, block, 0, s, n, means, quats, scales, sh_degree,
-                       stride_f, sh_coeffs, group_ids, n_groups, xforms, sh_rot, out_means, out_quats, out_scales, out_sh);
-  else if (sh_coeffs)
-    hipLaunchKernelGGL((transform_kernel<true, false>), grid, block, 0, s, n, means, quats, scales, sh_degree,
-                       stride_f, sh_coeffs, group_ids, n_groups, xforms, sh_rot, out_means, out_quats, out_scales, out_sh);
-  else
-    hipLaunchKernelGGL((transform_kernel<false, false>), grid, block, 0, s, n, means, quats, scales, 0, 0,
-                       (const float*)nullptr, group_ids, n_groups, xforms, (const float*)nullptr,
-                       out_means, out_quats, out_scales, (float*)nullptr);
+  with_bool(sh_coeffs != nullptr, [&](auto sh) {
+    with_bool(sh_coeffs && coeff_stride == 16, [&](auto staged) {
+      constexpr bool SH = decltype(sh)::value;
+      if constexpr (SH || !decltype(staged)::value)       // (no SH rows: nothing to stage)
+        hipLaunchKernelGGL((transform_kernel<SH, decltype(staged)::value>), grid, block, 0, s, n, means, quats, scales,
+                           SH ? sh_degree : 0, SH ? stride_f : 0, sh_coeffs, group_ids, n_groups, xforms,
+                           SH ? sh_rot : nullptr, out_means, out_quats, out_scales, out_sh);
+    });
+  });
   return check_launch("transform_gaussians");
 }

@@ -45,8 +45,23 @@ def radius_rule_id(radius_rule) -> int:
 
 
 CAMERA_MODELS = {"pinhole": 0, "ortho": 1, "fisheye": 2}    # include/mgs.h MGS_CAMERA_PINHOLE / _ORTHO / _FISHEYE
-CAMERA_BIN_FLAGS = {0: 0, 1: 4, 2: 8}                      # MGS_BIN_CAMERA_ORTHO / _FISHEYE (mgs_project_color_fwd bin_flags)
-CAMERA_FRAME_FLAGS = {0: 0, 1: 16, 2: 32}                  # MGS_FRAMES_CAMERA_ORTHO / _FISHEYE (mgs_render_frames* flags)
+
+# include/mgs.h flag bits, named as there without the MGS_ prefix (tests/test_abi.py checks them against the header)
+RASTER_EXPECTED_LAST, RASTER_LATENCY = 1, 2              # mgs_rasterize_fwd flags (also in the mgs_render_frames* flags)
+FRAMES_CLASSIC_BOUNDS, FRAMES_RADIUS_OPACITY_AWARE = 4, 8  # mgs_render_frames* flags
+FRAMES_CAMERA_ORTHO, FRAMES_CAMERA_FISHEYE = 16, 32
+BIN_TIGHT, BIN_RADIUS_OPACITY_AWARE = 1, 2               # mgs_project_color_fwd bin_flags
+BIN_CAMERA_ORTHO, BIN_CAMERA_FISHEYE = 4, 8
+RASTER_BWD_RECORDS_ONLY, RASTER_BWD_SPLAT_SLOTS = 1, 2   # mgs_rasterize_bwd_det call_flags
+CAMERA_BIN_FLAGS = {0: 0, 1: BIN_CAMERA_ORTHO, 2: BIN_CAMERA_FISHEYE}           # MGS_CAMERA_* -> bin_flags bits
+CAMERA_FRAME_FLAGS = {0: 0, 1: FRAMES_CAMERA_ORTHO, 2: FRAMES_CAMERA_FISHEYE}   # MGS_CAMERA_* -> mgs_render_frames* bits
+
+
+def frames_flags(expected_last, latency, tight, per_axis, camera) -> int:
+    """The flags word of mgs_render_frames / _train / _backward."""
+    return ((RASTER_EXPECTED_LAST if expected_last else 0) | (RASTER_LATENCY if latency else 0)
+            | (0 if tight else FRAMES_CLASSIC_BOUNDS) | (FRAMES_RADIUS_OPACITY_AWARE if per_axis else 0)
+            | CAMERA_FRAME_FLAGS[int(camera)])
 
 
 def camera_model_id(camera_model) -> int:
@@ -121,7 +136,8 @@ def project_color_fwd_raw(means, quats, scales, opacities, sh_degree, sh_coeffs,
         n, ptr(means), ptr(quats), ptr(scales), ptr(opacities), sh_degree, sh_coeffs.shape[1],
         ptr(sh_coeffs), ptr(viewmat), ptr(K), width, height, eps2d, near_plane, far_plane,
         radius_clip, ptr(radii_x(radii)), ptr(means2d), ptr(depths), ptr(conics), ptr(opac), stride,
-        ptr(feats), ptr(splats), int(bin_seed == "tight") | (2 if per_axis else 0) | CAMERA_BIN_FLAGS[int(camera)],
+        ptr(feats), ptr(splats),
+        (BIN_TIGHT if bin_seed == "tight" else 0) | (BIN_RADIUS_OPACITY_AWARE if per_axis else 0) | CAMERA_BIN_FLAGS[int(camera)],
         ptr(seed[0]) if seed else None,
         ptr(seed[1]) if seed else None, ptr(radii[1]) if (per_axis and radii is not None) else None, stream_handle()),
         "mgs_project_color_fwd")
@@ -159,6 +175,13 @@ def _workspace(nbytes: int, device) -> Tensor:
         ws = torch.empty(int(nbytes * 1.25) + 256, dtype=torch.uint8, device=device)
         _workspaces[key] = ws
     return ws
+
+
+def _aligned_ws(nbytes, dev):
+    ws = _workspace(nbytes + 256, dev)
+    base = ws.data_ptr()
+    aligned = (base + 255) // 256 * 256
+    return aligned, ws.numel() - (aligned - base)
 
 
 def isect_tiles_raw(means2d, radii, depths, tile_w, tile_h, capacity: int, cam_id=0, n_cams=1,
@@ -236,19 +259,14 @@ def render_frames_raw(means, quats, scales, opacities, sh_degree, sh_coeffs, vie
     nbytes = ctypes.c_size_t(0)
     args = [n, ptr(means), ptr(quats), ptr(scales), ptr(opacities), int(sh_degree), sh_coeffs.shape[1], ptr(sh_coeffs),
             C, ptr(viewmats), ptr(Ks), int(width), int(height), eps2d, near_plane, far_plane, radius_clip,
-            int(bool(antialiased)), ch,
-            int(bool(expected_last)) | (2 if latency else 0) | (0 if tight else 4) | (8 if per_axis else 0)
-            | CAMERA_FRAME_FLAGS[int(camera)],
-            ptr(backgrounds),
+            int(bool(antialiased)), ch, frames_flags(expected_last, latency, tight, per_axis, camera), ptr(backgrounds),
             int(capacity), ptr(render) if (float_frame or dataset is None) else None,
             ptr(alphas) if (float_frame or dataset is None) else None, ptr(n_isect), ptr(status)]
     ds = dataset_args(dataset, C, height, width, dev)
     args += list(ds[:4])
     check(L.mgs_render_frames(*args, None, ctypes.byref(nbytes), stream_handle()), "mgs_render_frames(size query)")
-    ws = _workspace(nbytes.value + 256, dev)
-    base = ws.data_ptr()
-    aligned = (base + 255) // 256 * 256
-    nbytes = ctypes.c_size_t(ws.numel() - (aligned - base))
+    aligned, room = _aligned_ws(nbytes.value, dev)
+    nbytes = ctypes.c_size_t(room)
     check(L.mgs_render_frames(*args, aligned, ctypes.byref(nbytes), stream_handle()), "mgs_render_frames")
     return render, alphas, n_isect, status
 
@@ -318,13 +336,6 @@ class TrainState:
         return tl
 
 
-def _aligned_ws(nbytes, dev):
-    ws = _workspace(nbytes + 256, dev)
-    base = ws.data_ptr()
-    aligned = (base + 255) // 256 * 256
-    return aligned, ws.numel() - (aligned - base)
-
-
 def render_frames_train_raw(means, quats, scales, opacities, sh_degree, sh_coeffs, viewmats, Ks, width, height, eps2d,
                             near_plane, far_plane, radius_clip, antialiased, with_depth, capacity, interval,
                             backgrounds=None, expected_last=False, latency=True, tight=True, out=None, per_axis=False,
@@ -339,8 +350,7 @@ def render_frames_train_raw(means, quats, scales, opacities, sh_degree, sh_coeff
     else:
         render, alphas = out
     st = TrainState(n, C, width, height, ch, capacity, antialiased, interval, dev)
-    flags = int(bool(expected_last)) | (2 if latency else 0) | (0 if tight else 4) | (8 if per_axis else 0) \
-        | CAMERA_FRAME_FLAGS[int(camera)]
+    flags = frames_flags(expected_last, latency, tight, per_axis, camera)
     L = _lib.lib()
     nbytes = ctypes.c_size_t(0)
     args = [n, ptr(means), ptr(quats), ptr(scales), ptr(opacities), int(sh_degree), sh_coeffs.shape[1], ptr(sh_coeffs), C,
@@ -442,7 +452,7 @@ def rasterize_fwd_raw(means2d, conics, feats, opacities, background, width, heig
     check(_lib.lib().mgs_rasterize_fwd(n, ptr(means2d), ptr(conics), ptr(feats), ptr(opacities),
                                        ptr(splats), ptr(background), ch, width, height, tile_w, tile_h,
                                        ptr(tile_offsets), ptr(flatten_ids), ptr(group_order),
-                                       int(bool(expected_last)) | (2 if latency else 0),
+                                       (RASTER_EXPECTED_LAST if expected_last else 0) | (RASTER_LATENCY if latency else 0),
                                        ptr(render), ptr(alphas), ptr(last_ids), ptr(checkpoints),
                                        int(checkpoint_interval), *ds[:4], stream_handle()),
           "mgs_rasterize_fwd")
@@ -511,7 +521,7 @@ def rasterize_bwd_det_raw(means2d, conics, feats, opacities, background, width, 
             ptr(last_ids), ptr(v_render), ptr(v_alphas), ptr(expected_render), ptr(tl.pair_info),
             ptr(getattr(tl, "group_order", None)), tl.capacity,
             ptr(render_out), ptr(checkpoints), int(checkpoint_interval),
-            int(bool(records_only)) | (2 if _splat_slots_valid(tl, splats) else 0),
+            (RASTER_BWD_RECORDS_ONLY if records_only else 0) | (RASTER_BWD_SPLAT_SLOTS if _splat_slots_valid(tl, splats) else 0),
             ptr(v_means2d), ptr(v_abs), ptr(v_conics), ptr(v_feats), ptr(v_opac)]
     check(L.mgs_rasterize_bwd_det(*args, None, ctypes.byref(nbytes), stream_handle()),
           "mgs_rasterize_bwd_det(size query)")

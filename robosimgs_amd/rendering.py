@@ -56,13 +56,11 @@ class _RenderSH(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means, quats, scales, opacities, sh_coeffs, viewmats, Ks, backgrounds,
                 width, height, sh_degree, eps2d, near_plane, far_plane, radius_clip,
-                antialiased, with_depth, isect_capacity, absgrad, meta_out, tight, expected_depth,
+                antialiased, with_depth, isect_capacity, absgrad, meta_out, tight, per_axis, camera, expected_depth,
                 latency, lean, segment, dataset=None):
+        # tight: tightened tile rectangles; per_axis: the per-axis (gsplat >= 1.5) radius rule; camera: MGS_CAMERA_*
         C = viewmats.shape[0]
         dev = means.device
-        # `tight` carries the binning policy: bit 0 tightened tile rectangles, bit 1 the per-axis (gsplat >= 1.5) radius rule,
-        # bits 2-3 the camera model (MGS_CAMERA_*)
-        per_axis, camera, tight = bool(int(tight) & 2), (int(tight) >> 2) & 3, bool(int(tight) & 1)
         tile_w, tile_h = -(-width // TILE_SIZE), -(-height // TILE_SIZE)
         ch = 4 if with_depth else 3
         render = torch.empty(C, height, width, ch, dtype=torch.float32, device=dev)
@@ -192,7 +190,7 @@ class _RenderSH(torch.autograd.Function):
                 if ctx.expected_depth:
                     vr = torch.cat([vr[..., :-1], (vr[..., -1] / alphas.clamp(min=1e-10)).unsqueeze(-1)], dim=-1)
                 v_bg = (vr * (1.0 - alphas).unsqueeze(-1)).sum(dim=(1, 2))
-            return (v_means, v_quats, v_scales, v_opacities, v_sh, v_viewmats, None, v_bg) + (None,) * 18
+            return (v_means, v_quats, v_scales, v_opacities, v_sh, v_viewmats, None, v_bg) + (None,) * 20
         # "RGB+ED": the raster backward's prologue undoes the divide by max(alpha, 1e-10) itself
         # (expected_render=...); only a background gradient needs the converted cotangent here
         # the first camera overwrites the outputs, later ones accumulate: no zero-fill pass
@@ -248,7 +246,7 @@ class _RenderSH(torch.autograd.Function):
                 v_render = torch.cat([v_render[..., :-1],
                                       (v_render[..., -1] / alphas.clamp(min=1e-10)).unsqueeze(-1)], dim=-1)
             v_bg = (v_render * (1.0 - alphas).unsqueeze(-1)).sum(dim=(1, 2))
-        return (v_means, v_quats, v_scales, v_opacities, v_sh, v_viewmats, None, v_bg) + (None,) * 18
+        return (v_means, v_quats, v_scales, v_opacities, v_sh, v_viewmats, None, v_bg) + (None,) * 20
 
 
 def rasterization(means: Tensor, quats: Tensor, scales: Tensor, opacities: Tensor,
@@ -368,7 +366,7 @@ def rasterization(means: Tensor, quats: Tensor, scales: Tensor, opacities: Tenso
             means, quats, scales, opacities, colors, viewmats, Ks, backgrounds, width, height,
             int(sh_degree), float(eps2d), float(near_plane), float(far_plane),
             float(radius_clip), antialiased, want_depth, isect_capacity, bool(absgrad), store,
-            int(tile_bounds == "tight") | (2 if rule else 0) | (camera << 2), render_mode in ("RGB+ED", "ED"),
+            tile_bounds == "tight", bool(rule), camera, render_mode in ("RGB+ED", "ED"),
             raster_schedule == "latency",
             bool(lean_meta), int(backward_segment), dataset_out)
         if depth_only_via_sh:

@@ -4,7 +4,7 @@
 # (gfx950 tallies 128-byte requests at 64 B), both in KiB.  Writes profiles/pmc_traffic.json keyed to the
 # build stamp of libmgs.so; bench.py prints `roofline.traffic` only when the stamp matches.
 #   gpurun -- bash scripts/pmc_traffic.sh        (results also under gpurun_out/pmc_r6/)
-REPO=${GRAFT_REPO_ROOT:-/root/repo}
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$REPO/gpurun_out/pmc_r6
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
@@ -13,7 +13,9 @@ for stage in raster_inf raster_inf_q raster_bwd_split project binning; do
     tag=$(echo $ctr | cut -d' ' -f1)
     rm -rf $OUT/${stage}_$tag
     # (the backward is measured on the scene in the caller's order, as bench.py's fwd_bwd leg runs it)
-    MORTON=$([ $stage = raster_bwd_split ] && echo 0 || echo 1) SEG=256 timeout 300 rocprofv3 --kernel-trace --pmc $ctr --output-format csv -d $OUT/${stage}_$tag -o pmc -- python $REPO/scripts/run_stage.py $stage 3 > /dev/null 2>&1
+    # (each pass under its own time limit; the first that fails ends the script)
+    MORTON=$([ $stage = raster_bwd_split ] && echo 0 || echo 1) SEG=256 timeout -k 10 300 rocprofv3 --kernel-trace --pmc $ctr --output-format csv -d $OUT/${stage}_$tag -o pmc -- python $REPO/scripts/run_stage.py $stage 3 > $OUT/${stage}_$tag.log 2>&1 \
+      || { rc=$?; echo "pmc_traffic.sh: $stage / $tag failed (exit $rc), see $OUT/${stage}_$tag.log" >&2; exit $rc; }
   done
 done
 python - <<PY

@@ -85,6 +85,28 @@ def test_observation_builds_compile(src, define, symbol, tmp_path):
     assert re.search(r"^\w*" + symbol + r"\w*:", out.read_text(), flags=re.M), f"{define}: {symbol} not defined"
 
 
+def test_flag_constants_match_the_header():
+    """ops' flag bits (MGS_RASTER_*, MGS_FRAMES_*, MGS_BIN_*, MGS_RASTER_BWD_*, named without the prefix) and its camera /
+    radius-rule maps are include/mgs.h's #defines."""
+    from robosimgs_amd import ops
+    defs = {m.group(1): int(m.group(2)) for m in re.finditer(r"^#define\s+MGS_(\w+)\s+(\d+)\b", open(HEADER).read(), flags=re.M)}
+    bits = sorted(k for k in defs if re.match(r"(RASTER|FRAMES|BIN)_", k))
+    assert len(bits) == 12, bits
+    for k in bits:
+        assert getattr(ops, k) == defs[k], k
+    cam = {m: defs["CAMERA_" + m.upper()] for m in ("pinhole", "ortho", "fisheye")}
+    assert ops.CAMERA_MODELS == cam
+    assert ops.CAMERA_BIN_FLAGS == {cam["pinhole"]: 0, cam["ortho"]: defs["BIN_CAMERA_ORTHO"],
+                                    cam["fisheye"]: defs["BIN_CAMERA_FISHEYE"]}
+    assert ops.CAMERA_FRAME_FLAGS == {cam["pinhole"]: 0, cam["ortho"]: defs["FRAMES_CAMERA_ORTHO"],
+                                      cam["fisheye"]: defs["FRAMES_CAMERA_FISHEYE"]}
+    assert ops.RADIUS_RULES == {"classic": defs["RADIUS_CLASSIC"], "opacity_aware": defs["RADIUS_OPACITY_AWARE"]}
+    assert ops.frames_flags(True, True, False, True, cam["fisheye"]) == (
+        defs["RASTER_EXPECTED_LAST"] | defs["RASTER_LATENCY"] | defs["FRAMES_CLASSIC_BOUNDS"]
+        | defs["FRAMES_RADIUS_OPACITY_AWARE"] | defs["FRAMES_CAMERA_FISHEYE"])
+    assert ops.frames_flags(False, False, True, False, cam["pinhole"]) == 0
+
+
 def test_argument_errors_are_reported_without_a_gpu():
     from robosimgs_amd import _lib
     L = _lib.lib()
