@@ -22,6 +22,43 @@ MGS_STATUS_ISECT_OVERFLOW = 1
 MGS_VERSION = 440          # include/mgs.h this binding was written against (parameter lists change with it)
 
 
+# every function include/mgs.h declares: name -> (argtypes, restype)
+p, i, f, u32 = c_void_p, c_int, c_float, c_uint32
+_SIGNATURES = {
+    "mgs_version": ([], c_int),
+    "mgs_last_error_string": ([], c_char_p),
+    "mgs_projection_fwd": ([i, p, p, p, p, p, i, i, f, f, f, f, p, p, p, p, p, p, i, p, i, p], c_int),
+    "mgs_projection_bwd": ([i, p, p, p, p, p, i, i, f, p, p, p, p, p, p, p, p, p, p, p, i, p], c_int),
+    "mgs_sh_fwd": ([i, i, i, p, p, p, p, p], c_int),
+    "mgs_sh_bwd": ([i, i, i, p, p, p, p, p, p, p], c_int),
+    "mgs_project_color_fwd": ([i, p, p, p, p, i, i, p, p, p, i, i, f, f, f, f, p, p, p, p, p, i, p, p, i, p, p, p, p], c_int),
+    "mgs_project_color_bwd": ([i, p, p, p, p, i, i, p, p, p, i, i, f, p, p, i, i, p, p, p, p, p, p, p, p, p, p, p, p, i, i, p], c_int),
+    "mgs_isect_tiles": ([i, p, p, p, p, p, p, i, i, i, i, i, u32, p, p, p, p, p, p, p, p, p, p, p, p, p, POINTER(c_size_t), p], c_int),
+    "mgs_isect_offset_encode": ([u32, p, i, i, i, p, p], c_int),
+    "mgs_render_frames": ([i, p, p, p, p, i, i, p, i, p, p, i, i, f, f, f, f, i, i, i, p, u32, p, p, p, p, p, p, i, p, p, POINTER(c_size_t), p], c_int),
+    "mgs_train_state_layout": ([i, i, i, i, u32, i, i, POINTER(c_size_t), POINTER(c_size_t)], c_int),
+    "mgs_render_frames_train": ([i, p, p, p, p, i, i, p, i, p, p, i, i, f, f, f, f, i, i, i, p, u32, i, p, p, p, p, POINTER(c_size_t), p], c_int),
+    "mgs_render_frames_backward": ([i, p, p, p, p, i, i, p, i, p, p, i, i, f, i, i, i, p, u32, i, p, p, p, p, p, p, p, p, p, p, p, p, p, p, POINTER(c_size_t), p], c_int),
+    "mgs_rasterize_fwd": ([i, p, p, p, p, p, p, i, i, i, i, i, p, p, p, i, p, p, p, p, i, p, p, i, p, p], c_int),
+    "mgs_raster_checkpoint_floats": ([u32, i, i, i, i], c_size_t),
+    "mgs_rasterize_bwd": ([i, p, p, p, p, p, i, i, i, i, i, p, p, p, p, p, p, p, p, p, p, p, p], c_int),
+    "mgs_composite_over": ([i, p, p, p, p, p, p, p, p, p, p], c_int),
+    "mgs_points_project": ([i, p, p, p, p, p, p], c_int),
+    "mgs_points_depth_map": ([i, p, i, p, i, i, i, i, f, f, p, p, p, POINTER(c_size_t), p], c_int),
+    "mgs_points_sample_mask": ([i, p, i, p, i, i, f, p, p, f, p, p], c_int),
+    "mgs_frame_to_u8": ([i, p, i, p, p, p, p], c_int),
+    "mgs_frame_to_dataset": ([i, i, p, i, p, p, p, p, p, i, p], c_int),
+    "mgs_transform_gaussians": ([i, p, p, p, i, i, p, p, i, p, p, p, p, p, p, p], c_int),
+    "mgs_l1_loss_fwd": ([c_size_t, p, p, p, p, POINTER(c_size_t), p], c_int),
+    "mgs_l1_loss_bwd": ([c_size_t, p, p, p, p, p], c_int),
+    "mgs_l1_loss_fwd_grad": ([c_size_t, p, p, p, p, p, POINTER(c_size_t), p], c_int),
+    "mgs_l1_loss_bwd_scale": ([c_size_t, p, p, p], c_int),
+    "mgs_rasterize_bwd_det": ([i, p, p, p, p, p, p, i, i, i, i, i, p, p, p, p, p, p, p, p, p, u32, p, p, i, i, p, p, p, p, p, p, POINTER(c_size_t), p], c_int),
+}
+del p, i, f, u32
+EXPORTS = list(_SIGNATURES)
+
+
 class MgsError(RuntimeError):
     pass
 
@@ -39,39 +76,7 @@ def _load(path: str = None, hooks: bool = False) -> ctypes.CDLL:
     if have != MGS_VERSION:      # shifted parameter lists would end in a GPU fault, not in an error
         raise MgsError(f"{LIB_PATH} reports ABI version {have}, this binding was written for {MGS_VERSION} "
                        "(include/mgs.h): rebuild the library (`python robosimgs_amd/csrc/build.py --force`)")
-    p, i, f, u32 = c_void_p, c_int, c_float, c_uint32
-    sig = {
-        "mgs_version": ([], c_int),
-        "mgs_last_error_string": ([], c_char_p),
-        "mgs_projection_fwd": ([i, p, p, p, p, p, i, i, f, f, f, f, p, p, p, p, p, p, i, p, i, p], c_int),
-        "mgs_projection_bwd": ([i, p, p, p, p, p, i, i, f, p, p, p, p, p, p, p, p, p, p, p, i, p], c_int),
-        "mgs_sh_fwd": ([i, i, i, p, p, p, p, p], c_int),
-        "mgs_sh_bwd": ([i, i, i, p, p, p, p, p, p, p], c_int),
-        "mgs_project_color_fwd": ([i, p, p, p, p, i, i, p, p, p, i, i, f, f, f, f, p, p, p, p, p, i, p, p, i, p, p, p, p], c_int),
-        "mgs_project_color_bwd": ([i, p, p, p, p, i, i, p, p, p, i, i, f, p, p, i, i, p, p, p, p, p, p, p, p, p, p, p, p, i, i, p], c_int),
-        "mgs_isect_tiles": ([i, p, p, p, p, p, p, i, i, i, i, i, u32, p, p, p, p, p, p, p, p, p, p, p, p, p, POINTER(c_size_t), p], c_int),
-        "mgs_isect_offset_encode": ([u32, p, i, i, i, p, p], c_int),
-        "mgs_render_frames": ([i, p, p, p, p, i, i, p, i, p, p, i, i, f, f, f, f, i, i, i, p, u32, p, p, p, p, p, p, i, p, p, POINTER(c_size_t), p], c_int),
-        "mgs_train_state_layout": ([i, i, i, i, u32, i, i, POINTER(c_size_t), POINTER(c_size_t)], c_int),
-        "mgs_render_frames_train": ([i, p, p, p, p, i, i, p, i, p, p, i, i, f, f, f, f, i, i, i, p, u32, i, p, p, p, p, POINTER(c_size_t), p], c_int),
-        "mgs_render_frames_backward": ([i, p, p, p, p, i, i, p, i, p, p, i, i, f, i, i, i, p, u32, i, p, p, p, p, p, p, p, p, p, p, p, p, p, p, POINTER(c_size_t), p], c_int),
-        "mgs_rasterize_fwd": ([i, p, p, p, p, p, p, i, i, i, i, i, p, p, p, i, p, p, p, p, i, p, p, i, p, p], c_int),
-        "mgs_raster_checkpoint_floats": ([u32, i, i, i, i], c_size_t),
-        "mgs_rasterize_bwd": ([i, p, p, p, p, p, i, i, i, i, i, p, p, p, p, p, p, p, p, p, p, p, p], c_int),
-        "mgs_composite_over": ([i, p, p, p, p, p, p, p, p, p, p], c_int),
-        "mgs_points_project": ([i, p, p, p, p, p, p], c_int),
-        "mgs_points_depth_map": ([i, p, i, p, i, i, i, i, f, f, p, p, p, POINTER(c_size_t), p], c_int),
-        "mgs_points_sample_mask": ([i, p, i, p, i, i, f, p, p, f, p, p], c_int),
-        "mgs_frame_to_u8": ([i, p, i, p, p, p, p], c_int),
-        "mgs_frame_to_dataset": ([i, i, p, i, p, p, p, p, p, i, p], c_int),
-        "mgs_transform_gaussians": ([i, p, p, p, i, i, p, p, i, p, p, p, p, p, p, p], c_int),
-        "mgs_l1_loss_fwd": ([c_size_t, p, p, p, p, POINTER(c_size_t), p], c_int),
-        "mgs_l1_loss_bwd": ([c_size_t, p, p, p, p, p], c_int),
-        "mgs_l1_loss_fwd_grad": ([c_size_t, p, p, p, p, p, POINTER(c_size_t), p], c_int),
-        "mgs_l1_loss_bwd_scale": ([c_size_t, p, p, p], c_int),
-        "mgs_rasterize_bwd_det": ([i, p, p, p, p, p, p, i, i, i, i, i, p, p, p, p, p, p, p, p, p, u32, p, p, i, i, p, p, p, p, p, p, POINTER(c_size_t), p], c_int),
-    }
-    for name, (argtypes, restype) in sig.items():
+    for name, (argtypes, restype) in _SIGNATURES.items():
         fn = getattr(lib, name)          # AttributeError here == header/library mismatch
         fn.argtypes = argtypes
         fn.restype = restype
@@ -122,15 +127,6 @@ class use_debug_lib:
         return False
 
 
-EXPORTS = ["mgs_version", "mgs_last_error_string", "mgs_projection_fwd", "mgs_projection_bwd",
-           "mgs_sh_fwd", "mgs_sh_bwd", "mgs_project_color_fwd", "mgs_project_color_bwd",
-           "mgs_isect_tiles", "mgs_isect_offset_encode", "mgs_rasterize_fwd", "mgs_rasterize_bwd",
-           "mgs_rasterize_bwd_det", "mgs_composite_over", "mgs_points_project",
-           "mgs_points_depth_map", "mgs_points_sample_mask", "mgs_l1_loss_fwd", "mgs_l1_loss_bwd", "mgs_l1_loss_fwd_grad", "mgs_l1_loss_bwd_scale",
-           "mgs_transform_gaussians", "mgs_frame_to_u8", "mgs_frame_to_dataset", "mgs_render_frames",
-           "mgs_raster_checkpoint_floats", "mgs_train_state_layout", "mgs_render_frames_train", "mgs_render_frames_backward"]
-
-
 def check(rc: int, what: str) -> None:
     if rc != 0:
         msg = lib().mgs_last_error_string().decode("utf-8", "replace")
@@ -146,6 +142,36 @@ def ptr(t) -> int | None:
 
 def stream_handle() -> int:
     return torch.cuda.current_stream().cuda_stream
+
+
+_workspaces: dict = {}
+
+
+def sized_call(fn, args, device, *, cached: bool, canary_bytes: int = 0):
+    """Two-phase call of an entry point whose parameters end in (workspace, workspace_bytes, stream): a size query (with a
+    null workspace the call only reports the bytes it needs), then the call itself on a 256-byte aligned workspace of
+    exactly that size, both on torch's current stream.  Each call site picks where the workspace comes from:
+      cached=True   one growing scratch tensor per (device, stream, capturing): stream-ordered reuse is safe because
+                    every consumer is enqueued on that stream, and once grown nothing is allocated;
+      cached=False  a tensor of its own, released (stream-ordered) when the call returns.
+    canary_bytes: a fresh workspace followed by that many 0xA5 bytes, returned so that a test can see nothing was
+    written past the workspace.  Returns None otherwise."""
+    stream, nbytes = stream_handle(), ctypes.c_size_t(0)
+    check(fn(*args, None, ctypes.byref(nbytes), stream), f"{fn.__name__}(size query)")
+    size = nbytes.value
+    if canary_bytes:
+        buf = torch.full((size + 256 + canary_bytes,), 0xA5, dtype=torch.uint8, device=device)
+    elif cached:
+        key = (device.index, torch.cuda.current_stream(device).cuda_stream, torch.cuda.is_current_stream_capturing())
+        buf = _workspaces.get(key)
+        if buf is None or buf.numel() < size + 256:
+            buf = _workspaces[key] = torch.empty(int((size + 256) * 1.25) + 256, dtype=torch.uint8, device=device)
+    else:
+        buf = torch.empty(size + 256, dtype=torch.uint8, device=device)
+    pad = -buf.data_ptr() % 256
+    check(fn(*args, buf.data_ptr() + pad, ctypes.byref(nbytes), stream), fn.__name__)
+    if canary_bytes:
+        return buf[pad + size:pad + size + canary_bytes]
 
 
 def require_device(*tensors) -> None:

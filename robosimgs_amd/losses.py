@@ -5,12 +5,10 @@ for the usual grad_output of 1 (mgs_l1_loss_bwd_scale); without a gradient, mgs_
 elementwise / reduction kernels of eager PyTorch; bit-reproducible."""
 from __future__ import annotations
 
-import ctypes
-
 import torch
 
 from . import _lib
-from ._lib import check, ptr, require_device, stream_handle
+from ._lib import check, ptr, require_device, sized_call, stream_handle
 from .ops import _f32c
 
 
@@ -33,19 +31,11 @@ class _L1(torch.autograd.Function):
     def forward(ctx, a, b):
         n = a.numel()
         loss = torch.empty((), dtype=torch.float32, device=a.device)
-        L = _lib.lib()
-        nbytes = ctypes.c_size_t(0)
         if not ctx.needs_input_grad[0]:
-            check(L.mgs_l1_loss_fwd(n, None, None, None, None, ctypes.byref(nbytes), None), "mgs_l1_loss_fwd(size query)")
-            ws = torch.empty(nbytes.value, dtype=torch.uint8, device=a.device)
-            check(L.mgs_l1_loss_fwd(n, ptr(a), ptr(b), ptr(loss), ptr(ws), ctypes.byref(nbytes),
-                                    stream_handle()), "mgs_l1_loss_fwd")
+            sized_call(_lib.lib().mgs_l1_loss_fwd, [n, ptr(a), ptr(b), ptr(loss)], a.device, cached=False)
             return loss
-        check(L.mgs_l1_loss_fwd_grad(n, None, None, None, None, None, ctypes.byref(nbytes), None), "mgs_l1_loss_fwd_grad(size query)")
-        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=a.device)
         v_a = torch.empty_like(a)
-        check(L.mgs_l1_loss_fwd_grad(n, ptr(a), ptr(b), ptr(loss), ptr(v_a), ptr(ws), ctypes.byref(nbytes),
-                                     stream_handle()), "mgs_l1_loss_fwd_grad")
+        sized_call(_lib.lib().mgs_l1_loss_fwd_grad, [n, ptr(a), ptr(b), ptr(loss), ptr(v_a)], a.device, cached=False)
         ctx.save_for_backward(a, b)
         ctx.v_a = v_a
         return loss

@@ -19,7 +19,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from ._lib import check, ptr, require_device, stream_handle
+from ._lib import check, ptr, require_device, sized_call, stream_handle
 
 TILE_SIZE = 16
 
@@ -126,8 +126,6 @@ def project_color_fwd_raw(means, quats, scales, opacities, sh_degree, sh_coeffs,
     depths = torch.empty(n, dtype=torch.float32, device=dev)
     opac = torch.empty(n, dtype=torch.float32, device=dev) if antialiased else None
     splats = torch.empty(n, 12, dtype=torch.float32, device=dev) if want_splats else None
-    if splats is not None:
-        _splat_annotation.pop(splats.data_ptr(), None)     # fresh records: no binning's slot words in them
     seed = None
     if bin_seed is not None and n > 0:
         seed = (torch.empty(n, 2, dtype=torch.int32, device=dev),
@@ -149,39 +147,32 @@ def project_color_fwd_raw(means, quats, scales, opacities, sh_degree, sh_coeffs,
     return out
 
 
+def project_color_bwd_raw(means, quats, scales, opacities, sh_degree, sh_coeffs, viewmat, K, width, height, eps2d,
+                          radii, conics, antialiased, feats, v_feats, v_means2d, v_conics, v_opac_aa, v_means, v_quats,
+                          v_scales, v_sh, v_opacities, v_viewmat=None, accumulate=False, camera=0):
+    """The chain rule of project_color_fwd_raw for one camera.  radii, conics, feats: what the forward returned;
+    v_opac_aa: the cotangent of its opac_aa (antialiased only).  v_means / v_quats / v_scales / v_sh and, antialiased,
+    v_opacities are overwritten, or added to with `accumulate`; v_viewmat [4,4] (optional) is always added to."""
+    check(_lib.lib().mgs_project_color_bwd(
+        means.shape[0], ptr(means), ptr(quats), ptr(scales), ptr(opacities), sh_degree, sh_coeffs.shape[1], ptr(sh_coeffs),
+        ptr(viewmat), ptr(K), width, height, eps2d, ptr(radii_x(radii)), ptr(conics), int(antialiased), feats.shape[1],
+        ptr(feats), ptr(v_feats), ptr(v_means2d), ptr(v_conics), None, ptr(v_opac_aa), ptr(v_means), ptr(v_quats),
+        ptr(v_scales), ptr(v_sh), ptr(v_opacities), ptr(v_viewmat), int(accumulate), int(camera), stream_handle()),
+        "mgs_project_color_bwd")
+
+
 class TileLists:
     """Depth-ordered per-tile lists of one camera (device resident, capacity sized)."""
     __slots__ = ("n_isect", "tile_ids", "flatten_ids", "tile_offsets", "tiles_per_gauss",
                  "isect_ids", "status", "capacity", "pair_info", "group_order", "splat_slots")
 
 
-_workspaces: dict = {}
-
-# mgs_isect_tiles(splat_slots=) writes a binning's record slots into words 10-11 of the caller's splat records IN PLACE:
-# the records then belong to THAT binning.  data_ptr of an annotated record tensor -> the generation of the binning that
-# annotated it last; a TileLists remembers (data_ptr, generation) and rasterize_bwd_det_raw trusts the records' slot words
-# only while the pair still matches (otherwise it gathers pair_info, which every TileLists owns).
-_splat_annotation: dict = {}
-_splat_generation = [0]
-
-
-def _workspace(nbytes: int, device) -> Tensor:
-    """One growing scratch tensor per (device, stream).  Stream-ordered reuse is safe because
-    every consumer is enqueued on the same stream."""
-    key = (device.index, torch.cuda.current_stream(device).cuda_stream,
-           torch.cuda.is_current_stream_capturing())
-    ws = _workspaces.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = torch.empty(int(nbytes * 1.25) + 256, dtype=torch.uint8, device=device)
-        _workspaces[key] = ws
-    return ws
-
-
-def _aligned_ws(nbytes, dev):
-    ws = _workspace(nbytes + 256, dev)
-    base = ws.data_ptr()
-    aligned = (base + 255) // 256 * 256
-    return aligned, ws.numel() - (aligned - base)
+def _tag_splat_slots(tl: TileLists, splats) -> None:
+    """mgs_isect_tiles(splat_slots=) writes the binning's record slots into words 10-11 of `splats` IN PLACE: the records
+    belong to that binning from then on.  The tensor object and `tl` get the same new token; a later binning of the same
+    object replaces the tensor's token, and no other tensor object carries one (_splat_slots_valid)."""
+    tl.splat_slots = object()
+    splats._mgs_splat_slots = tl.splat_slots
 
 
 def isect_tiles_raw(means2d, radii, depths, tile_w, tile_h, capacity: int, cam_id=0, n_cams=1,
@@ -195,11 +186,10 @@ def isect_tiles_raw(means2d, radii, depths, tile_w, tile_h, capacity: int, cam_i
     radii: [N], or planar [2,N] per-axis extents (gsplat >= 1.5's rule).
     splats (with want_pair_info): the packed records [N,12] of project_color_fwd_raw; the pairs' record slots are left in
     their padding words IN PLACE (include/mgs.h: splat_slots) -- the records are tied to this binning from then on -- and the
-    lists remember which tensor they annotated (`splat_slots`): rasterize_bwd_det_raw gathers nothing but the record while
-    that pairing holds, and falls back to pair_info when the records were re-projected or binned again since."""
+    lists remember which tensor object they annotated (_tag_splat_slots): rasterize_bwd_det_raw gathers nothing but the
+    record while that pairing holds, and falls back to pair_info for any other tensor or once the records are binned again."""
     n = depths.shape[0]
     dev = depths.device
-    L = _lib.lib()
     out = TileLists()
     out.capacity = int(capacity)
     out.n_isect = torch.empty(1, dtype=torch.int32, device=dev)
@@ -213,26 +203,34 @@ def isect_tiles_raw(means2d, radii, depths, tile_w, tile_h, capacity: int, cam_i
     out.pair_info = torch.empty(n, 4, dtype=torch.int32, device=dev) if want_pair_info else None
     # launch order of the raster kernels' tiles (groups of four, longest lists first): a schedule, not a result
     out.group_order = (torch.empty((tile_w * tile_h + 3) // 4, dtype=torch.int32, device=dev) if want_group_order else None)
-    nbytes = ctypes.c_size_t(0)
+    annotate = splats is not None and want_pair_info
     args = [n, ptr(means2d), ptr(radii_x(radii)), ptr(radii[1]) if (radii is not None and radii.dim() == 2) else None,
             ptr(depths), ptr(conics), ptr(opacities), TILE_SIZE,
             tile_w, tile_h, cam_id, n_cams,
             capacity, ptr(out.tiles_per_gauss), ptr(out.n_isect), ptr(out.tile_ids),
             ptr(out.flatten_ids), ptr(out.isect_ids), ptr(out.tile_offsets), ptr(out.pair_info),
             ptr(out.group_order), ptr(out.status), ptr(seed[0]) if seed else None, ptr(seed[1]) if seed else None,
-            ptr(splats) if (splats is not None and want_pair_info) else None]
+            ptr(splats) if annotate else None]
     out.splat_slots = False
-    if splats is not None and want_pair_info:
-        _splat_generation[0] += 1
-        _splat_annotation[splats.data_ptr()] = _splat_generation[0]
-        out.splat_slots = (splats.data_ptr(), _splat_generation[0])
-    check(L.mgs_isect_tiles(*args, None, ctypes.byref(nbytes), stream_handle()),
-          "mgs_isect_tiles(size query)")
-    ws = _workspace(nbytes.value, dev)
-    nbytes = ctypes.c_size_t(ws.numel())
-    check(L.mgs_isect_tiles(*args, ptr(ws), ctypes.byref(nbytes), stream_handle()),
-          "mgs_isect_tiles")
+    if annotate:
+        _tag_splat_slots(out, splats)
+    sized_call(_lib.lib().mgs_isect_tiles, args, dev, cached=True)
     return out
+
+
+def _frames_call(means, quats, scales, opacities, sh_degree, sh_coeffs, viewmats, Ks, width, height, eps2d, near_plane,
+                 far_plane, radius_clip, antialiased, with_depth, capacity, backgrounds, flags, out):
+    """The frames mgs_render_frames / mgs_render_frames_train write (`out`, or new [C,H,W,ch] and [C,H,W] tensors) and
+    the arguments both calls begin with."""
+    dev = means.device
+    C, ch = viewmats.shape[0], 4 if with_depth else 3
+    if out is None:
+        out = (torch.empty(C, height, width, ch, dtype=torch.float32, device=dev),
+               torch.empty(C, height, width, dtype=torch.float32, device=dev))
+    args = [means.shape[0], ptr(means), ptr(quats), ptr(scales), ptr(opacities), int(sh_degree), sh_coeffs.shape[1],
+            ptr(sh_coeffs), C, ptr(viewmats), ptr(Ks), int(width), int(height), eps2d, near_plane, far_plane, radius_clip,
+            int(bool(antialiased)), ch, flags, ptr(backgrounds), int(capacity)]
+    return out[0], out[1], args
 
 
 def render_frames_raw(means, quats, scales, opacities, sh_degree, sh_coeffs, viewmats, Ks, width, height,
@@ -246,28 +244,17 @@ def render_frames_raw(means, quats, scales, opacities, sh_degree, sh_coeffs, vie
     dataset = (rgba uint8 [C,H,W,4], distance [C,H,W,1] or None, K): the dataset frames straight out of the raster
     (with_depth and expected_last required); float_frame=False then leaves render / alphas unwritten."""
     dev = means.device
-    C, n = viewmats.shape[0], means.shape[0]
-    ch = 4 if with_depth else 3
-    if out is None:
-        render = torch.empty(C, height, width, ch, dtype=torch.float32, device=dev)
-        alphas = torch.empty(C, height, width, dtype=torch.float32, device=dev)
-    else:
-        render, alphas = out
+    C = viewmats.shape[0]
+    render, alphas, args = _frames_call(means, quats, scales, opacities, sh_degree, sh_coeffs, viewmats, Ks, width, height,
+                                        eps2d, near_plane, far_plane, radius_clip, antialiased, with_depth, capacity,
+                                        backgrounds, frames_flags(expected_last, latency, tight, per_axis, camera), out)
     n_isect = torch.empty(C, dtype=torch.int32, device=dev)
     status = torch.empty(C, dtype=torch.int32, device=dev)
-    L = _lib.lib()
-    nbytes = ctypes.c_size_t(0)
-    args = [n, ptr(means), ptr(quats), ptr(scales), ptr(opacities), int(sh_degree), sh_coeffs.shape[1], ptr(sh_coeffs),
-            C, ptr(viewmats), ptr(Ks), int(width), int(height), eps2d, near_plane, far_plane, radius_clip,
-            int(bool(antialiased)), ch, frames_flags(expected_last, latency, tight, per_axis, camera), ptr(backgrounds),
-            int(capacity), ptr(render) if (float_frame or dataset is None) else None,
-            ptr(alphas) if (float_frame or dataset is None) else None, ptr(n_isect), ptr(status)]
+    args += [ptr(render) if (float_frame or dataset is None) else None,
+             ptr(alphas) if (float_frame or dataset is None) else None, ptr(n_isect), ptr(status)]
     ds = dataset_args(dataset, C, height, width, dev)
     args += list(ds[:4])
-    check(L.mgs_render_frames(*args, None, ctypes.byref(nbytes), stream_handle()), "mgs_render_frames(size query)")
-    aligned, room = _aligned_ws(nbytes.value, dev)
-    nbytes = ctypes.c_size_t(room)
-    check(L.mgs_render_frames(*args, aligned, ctypes.byref(nbytes), stream_handle()), "mgs_render_frames")
+    sized_call(_lib.lib().mgs_render_frames, args, dev, cached=True)
     return render, alphas, n_isect, status
 
 
@@ -286,16 +273,16 @@ TRAIN_FIELDS = ("radii", "means2d", "depths", "conics", "opac_aa", "feats", "spl
 class TrainState:
     """Per-camera state of a batch of training frames (mgs_render_frames_train writes it, mgs_render_frames_backward
     reads it): one device buffer, fields at the offsets mgs_train_state_layout reports; `views(c)` hands them out as
-    tensors without copying."""
+    tensors without copying.  flags: the mgs_render_frames* flags word of the frames (the backward must get the forward's)."""
 
-    def __init__(self, n, n_cams, width, height, channels, capacity, antialiased, interval, device):
+    def __init__(self, n, n_cams, width, height, channels, capacity, antialiased, interval, flags, device):
         offs = (ctypes.c_size_t * len(TRAIN_FIELDS))()
         per = ctypes.c_size_t(0)
         check(_lib.lib().mgs_train_state_layout(n, width, height, channels, int(capacity), int(bool(antialiased)), int(interval),
                                                 offs, ctypes.byref(per)), "mgs_train_state_layout")
         self.offsets, self.per_camera = list(offs), per.value
         self.n, self.n_cams, self.width, self.height, self.channels = n, n_cams, width, height, channels
-        self.capacity, self.antialiased, self.interval = int(capacity), bool(antialiased), int(interval)
+        self.capacity, self.antialiased, self.interval, self.flags = int(capacity), bool(antialiased), int(interval), flags
         self.buf = torch.empty(self.per_camera * n_cams + 256, dtype=torch.uint8, device=device)
         self.pad = (-self.buf.data_ptr()) % 256
         self.n_tiles = (-(-width // TILE_SIZE)) * (-(-height // TILE_SIZE))
@@ -341,26 +328,14 @@ def render_frames_train_raw(means, quats, scales, opacities, sh_degree, sh_coeff
                             backgrounds=None, expected_last=False, latency=True, tight=True, out=None, per_axis=False,
                             camera=0):
     """mgs_render_frames_train: C training frames in one C call.  Returns (render [C,H,W,ch], alphas [C,H,W], TrainState)."""
-    dev = means.device
-    C, n = viewmats.shape[0], means.shape[0]
-    ch = 4 if with_depth else 3
-    if out is None:
-        render = torch.empty(C, height, width, ch, dtype=torch.float32, device=dev)
-        alphas = torch.empty(C, height, width, dtype=torch.float32, device=dev)
-    else:
-        render, alphas = out
-    st = TrainState(n, C, width, height, ch, capacity, antialiased, interval, dev)
     flags = frames_flags(expected_last, latency, tight, per_axis, camera)
-    L = _lib.lib()
-    nbytes = ctypes.c_size_t(0)
-    args = [n, ptr(means), ptr(quats), ptr(scales), ptr(opacities), int(sh_degree), sh_coeffs.shape[1], ptr(sh_coeffs), C,
-            ptr(viewmats), ptr(Ks), int(width), int(height), eps2d, near_plane, far_plane, radius_clip, int(bool(antialiased)),
-            ch, flags, ptr(backgrounds), int(capacity), int(interval), ptr(render), ptr(alphas), st.ptr()]
-    check(L.mgs_render_frames_train(*args, None, ctypes.byref(nbytes), stream_handle()), "mgs_render_frames_train(size query)")
-    aligned, room = _aligned_ws(nbytes.value, dev)
-    nbytes = ctypes.c_size_t(room)
-    check(L.mgs_render_frames_train(*args, aligned, ctypes.byref(nbytes), stream_handle()), "mgs_render_frames_train")
-    st.flags = flags
+    render, alphas, args = _frames_call(means, quats, scales, opacities, sh_degree, sh_coeffs, viewmats, Ks, width, height,
+                                        eps2d, near_plane, far_plane, radius_clip, antialiased, with_depth, capacity,
+                                        backgrounds, flags, out)
+    st = TrainState(means.shape[0], viewmats.shape[0], width, height, 4 if with_depth else 3, capacity, antialiased, interval,
+                    flags, means.device)
+    args += [int(interval), ptr(render), ptr(alphas), st.ptr()]
+    sized_call(_lib.lib().mgs_render_frames_train, args, means.device, cached=True)
     return render, alphas, st
 
 
@@ -375,17 +350,11 @@ def render_frames_backward_raw(means, quats, scales, opacities, sh_degree, sh_co
     v_vm = torch.zeros_like(viewmats) if want_viewmats else None
     v_m2d = torch.empty(C, n, 2, dtype=torch.float32, device=dev)
     v_abs = torch.empty(C, n, 2, dtype=torch.float32, device=dev) if absgrad else None
-    L = _lib.lib()
-    nbytes = ctypes.c_size_t(0)
     args = [n, ptr(means), ptr(quats), ptr(scales), ptr(opacities), int(sh_degree), sh_coeffs.shape[1], ptr(sh_coeffs), C,
             ptr(viewmats), ptr(Ks), st.width, st.height, eps2d, int(st.antialiased), st.channels, st.flags, ptr(backgrounds),
             st.capacity, st.interval, ptr(render), ptr(alphas), ptr(v_render), ptr(v_alphas), st.ptr(), ptr(v_means),
             ptr(v_quats), ptr(v_scales), ptr(v_sh), ptr(v_opac), ptr(v_vm), ptr(v_m2d), ptr(v_abs)]
-    check(L.mgs_render_frames_backward(*args, None, ctypes.byref(nbytes), stream_handle()), "mgs_render_frames_backward(size query)")
-    ws = torch.empty(nbytes.value + 256, dtype=torch.uint8, device=dev)
-    aligned = (ws.data_ptr() + 255) // 256 * 256
-    nbytes = ctypes.c_size_t(ws.numel() - (aligned - ws.data_ptr()))
-    check(L.mgs_render_frames_backward(*args, aligned, ctypes.byref(nbytes), stream_handle()), "mgs_render_frames_backward")
+    sized_call(_lib.lib().mgs_render_frames_backward, args, dev, cached=False)
     return v_means, v_quats, v_scales, v_sh, v_opac, v_vm, v_m2d, v_abs
 
 
@@ -484,15 +453,13 @@ def rasterize_bwd_raw(means2d, conics, feats, opacities, background, width, heig
 
 
 def _splat_slots_valid(tl, splats) -> bool:
-    """The records `splats` carry the record slots of the binning that made `tl` (see _splat_annotation): True for the
-    train-state lists (mgs_render_frames_train annotates its own state), else only when `splats` is the very tensor that
-    binning annotated and no later binning (or projection) has rewritten it."""
+    """The records `splats` carry the record slots of the binning that made `tl` (_tag_splat_slots): True for the
+    train-state lists (mgs_render_frames_train annotates its own state), else only when `splats` is the very tensor
+    object that binning annotated and no later binning has annotated it again."""
     tag = getattr(tl, "splat_slots", False)
     if splats is None or not tag:
         return False
-    if tag is True:
-        return True
-    return tag[0] == splats.data_ptr() and _splat_annotation.get(tag[0]) == tag[1]
+    return tag is True or getattr(splats, "_mgs_splat_slots", None) is tag
 
 
 def rasterize_bwd_det_raw(means2d, conics, feats, opacities, background, width, height, tile_w,
@@ -514,8 +481,6 @@ def rasterize_bwd_det_raw(means2d, conics, feats, opacities, background, width, 
     v_feats = torch.empty(n, ch, dtype=torch.float32, device=dev)
     v_opac = torch.empty(n, dtype=torch.float32, device=dev)
     v_abs = torch.empty(n, 2, dtype=torch.float32, device=dev) if absgrad else None
-    L = _lib.lib()
-    nbytes = ctypes.c_size_t(0)
     args = [n, ptr(means2d), ptr(conics), ptr(feats), ptr(opacities), ptr(splats), ptr(background),
             ch, width, height, tile_w, tile_h, ptr(tl.tile_offsets), ptr(tl.flatten_ids), ptr(alphas),
             ptr(last_ids), ptr(v_render), ptr(v_alphas), ptr(expected_render), ptr(tl.pair_info),
@@ -523,14 +488,9 @@ def rasterize_bwd_det_raw(means2d, conics, feats, opacities, background, width, 
             ptr(render_out), ptr(checkpoints), int(checkpoint_interval),
             (RASTER_BWD_RECORDS_ONLY if records_only else 0) | (RASTER_BWD_SPLAT_SLOTS if _splat_slots_valid(tl, splats) else 0),
             ptr(v_means2d), ptr(v_abs), ptr(v_conics), ptr(v_feats), ptr(v_opac)]
-    check(L.mgs_rasterize_bwd_det(*args, None, ctypes.byref(nbytes), stream_handle()),
-          "mgs_rasterize_bwd_det(size query)")
-    ws = torch.full((nbytes.value + canary_bytes,), 0xA5, dtype=torch.uint8, device=dev) if canary_bytes \
-        else torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
-    check(L.mgs_rasterize_bwd_det(*args, ptr(ws), ctypes.byref(nbytes), stream_handle()),
-          "mgs_rasterize_bwd_det")
+    canary = sized_call(_lib.lib().mgs_rasterize_bwd_det, args, dev, cached=False, canary_bytes=canary_bytes)
     if canary_bytes:
-        return v_means2d, v_conics, v_feats, v_opac, v_abs, ws[nbytes.value:]
+        return v_means2d, v_conics, v_feats, v_opac, v_abs, canary
     return v_means2d, v_conics, v_feats, v_opac, v_abs
 
 

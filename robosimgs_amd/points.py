@@ -7,14 +7,11 @@ on the GPU in -> torch tensors out (no host round trip).  The camera here is the
 `Camera.from_c2w_opengl`."""
 from __future__ import annotations
 
-import ctypes
-from typing import Optional
-
 import numpy as np
 import torch
 
 from . import _lib
-from ._lib import check, ptr, stream_handle
+from ._lib import check, ptr, sized_call, stream_handle
 
 
 def _dev(x, device="cuda") -> torch.Tensor:
@@ -63,15 +60,9 @@ def get_depth_map(uv, depth, h: int, w: int, bg_depth: float = 1e10, scale=2):
         raise ValueError(f"scale {scale} leaves no cells for a {w}x{h} image")
     depth_map = torch.empty(h, w, dtype=torch.float32, device=u.device)
     index = torch.empty(_w * _h, dtype=torch.int64, device=u.device)
-    L = _lib.lib()
-    nbytes = ctypes.c_size_t(0)
     args = [n, ptr(u), u.shape[1], ptr(d), int(h), int(w), _h, _w, float(scale), float(bg_depth),
             ptr(depth_map), ptr(index)]
-    check(L.mgs_points_depth_map(*args, None, ctypes.byref(nbytes), stream_handle()),
-          "mgs_points_depth_map(size query)")
-    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=u.device)
-    check(L.mgs_points_depth_map(*args, ptr(ws), ctypes.byref(nbytes), stream_handle()),
-          "mgs_points_depth_map")
+    sized_call(_lib.lib().mgs_points_depth_map, args, u.device, cached=False)
     return _like(uv, depth_map), _like(uv, index)
 
 

@@ -2,23 +2,26 @@
 splatfacto calls (gsplat 1.x `rasterization`), plus `render(...)`,
 the Camera/Gaussians convenience the data-generation loop would use.
 
-Per camera the frame is four C-ABI calls on torch's current stream:
+Per camera the frame is these C-ABI calls on torch's current stream:
     mgs_project_color_fwd -> mgs_isect_tiles -> mgs_rasterize_fwd        (forward)
-    mgs_rasterize_bwd -> mgs_project_color_bwd                            (backward)
-With `isect_capacity` given nothing is read back from the device, so a frame (or a training
-step) can be captured in a HIP graph.  Without it the intersection bound is read back once
-per camera to size the lists, as the reference operator does.
+    mgs_rasterize_bwd_det -> mgs_project_color_bwd                        (backward)
+With `isect_capacity` given a batch of cameras is one call instead -- mgs_render_frames (inference,
+lean_meta), or mgs_render_frames_train and mgs_render_frames_backward (training) -- and nothing is
+read back from the device, so a frame (or a training step) can be captured in a HIP graph.  Without
+it the intersection bound is read back once per camera to size the lists, as the reference operator
+does.  Features given per Gaussian go through the gsplat-style operators of ops.py instead.
 """
 from __future__ import annotations
 
-from typing import Dict, Optional, Sequence, Tuple
+from dataclasses import dataclass
+from typing import Dict, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 from torch import Tensor
 
-from . import _lib, ops
-from ._lib import check, ptr, require_device, stream_handle
+from . import ops
+from ._lib import MgsError, require_device
 from .ops import TILE_SIZE, _f32c
 
 _MODES = ("RGB", "D", "ED", "RGB+D", "RGB+ED")
@@ -50,203 +53,216 @@ class _Meta(dict):
         return self[key]
 
 
+@dataclass(frozen=True)
+class _RenderConfig:
+    """Everything besides the eight tensors that one rasterization() call hands _RenderSH."""
+    width: int
+    height: int
+    sh_degree: int
+    eps2d: float
+    near: float
+    far: float
+    radius_clip: float
+    antialiased: bool
+    with_depth: bool
+    capacity: Optional[int]     # isect_capacity: fixed list capacity (nothing read back), or None
+    absgrad: bool
+    tight: bool                 # tightened tile rectangles
+    per_axis: bool              # the per-axis (gsplat >= 1.5) radius rule
+    camera: int                 # MGS_CAMERA_*
+    expected_depth: bool        # "ED" modes: the raster divides the depth channel by max(alpha, 1e-10)
+    latency: bool               # raster_schedule "latency"
+    lean: bool                  # lean_meta
+    segment: int                # backward_segment
+    dataset: Optional[tuple]    # dataset_out
+
+    @property
+    def channels(self) -> int:
+        return 4 if self.with_depth else 3
+
+
+class _Camera(NamedTuple):
+    """What the forward keeps of one camera for the backward and the meta dict."""
+    radii: Tensor               # [N], or planar [2,N] under the per-axis rule
+    means2d: Tensor
+    depths: Tensor
+    conics: Tensor
+    opac_aa: Optional[Tensor]   # antialiased only
+    feats: Tensor
+    lists: ops.TileLists
+    splats: Tensor
+    checkpoints: Optional[Tensor]
+
+
+def _stk(xs):
+    """[C,...] of C per-camera tensors (no copy for the common single-camera call)."""
+    return xs[0].unsqueeze(0) if len(xs) == 1 else torch.stack(xs)
+
+
 class _RenderSH(torch.autograd.Function):
     """SH-coloured frames for C cameras: fused projection+colour, binning, raster."""
 
     @staticmethod
-    def forward(ctx, means, quats, scales, opacities, sh_coeffs, viewmats, Ks, backgrounds,
-                width, height, sh_degree, eps2d, near_plane, far_plane, radius_clip,
-                antialiased, with_depth, isect_capacity, absgrad, meta_out, tight, per_axis, camera, expected_depth,
-                latency, lean, segment, dataset=None):
-        # tight: tightened tile rectangles; per_axis: the per-axis (gsplat >= 1.5) radius rule; camera: MGS_CAMERA_*
+    def forward(ctx, means, quats, scales, opacities, sh_coeffs, viewmats, Ks, backgrounds, cfg: _RenderConfig, meta_out):
         C = viewmats.shape[0]
         dev = means.device
+        width, height, ch, cap = cfg.width, cfg.height, cfg.channels, cfg.capacity
         tile_w, tile_h = -(-width // TILE_SIZE), -(-height // TILE_SIZE)
-        ch = 4 if with_depth else 3
         render = torch.empty(C, height, width, ch, dtype=torch.float32, device=dev)
         alphas = torch.empty(C, height, width, dtype=torch.float32, device=dev)
         # last_ids (and the backward's slot map) only when some input wants a gradient
         training = any(ctx.needs_input_grad[:6]) or ctx.needs_input_grad[7]
         last_ids = (torch.empty(C, height, width, dtype=torch.int32, device=dev) if training
                     else None)
+        ctx.cfg, ctx.meta_out = cfg, meta_out
+        ctx.set_materialize_grads(False)       # an unused output's cotangent arrives as None, not as a zero frame
         # lean: an inference frame with a fixed list capacity keeps only what its own kernels read -- the packed
         # records, the binning seed and the depths; radii / means2d / conics / feats / tiles_per_gauss are neither
         # written nor returned (36 + 4 MB of stores per 1 M Gaussians)
-        lean = bool(lean) and not training and isect_capacity is not None
-        if dataset is not None and not lean:
+        lean = cfg.lean and not training and cap is not None
+        if cfg.dataset is not None and not lean:
             raise ValueError("dataset_out needs inference frames through the one-call path: lean_meta=True, isect_capacity "
                              "given, no gradients")
+        args = (means, quats, scales, opacities, cfg.sh_degree, sh_coeffs, viewmats, Ks, width, height, cfg.eps2d, cfg.near,
+                cfg.far, cfg.radius_clip, cfg.antialiased, cfg.with_depth, cap)
         if lean:
             # the whole batch of cameras behind ONE C call (mgs_render_frames): per-camera scratch is reused, nothing
             # per Gaussian is returned
+            ds = cfg.dataset
             _, _, n_isects, status = ops.render_frames_raw(
-                means, quats, scales, opacities, sh_degree, sh_coeffs, viewmats, Ks, width, height, eps2d,
-                near_plane, far_plane, radius_clip, antialiased, with_depth, isect_capacity, backgrounds=backgrounds,
-                expected_last=expected_depth, latency=latency, out=(render, alphas), tight=tight, per_axis=per_axis,
-                camera=camera, dataset=dataset[:3] if dataset is not None else None,
-                float_frame=dataset is None or bool(dataset[3]))
+                *args, backgrounds=backgrounds, expected_last=cfg.expected_depth, latency=cfg.latency, out=(render, alphas),
+                tight=cfg.tight, per_axis=cfg.per_axis, camera=cfg.camera, dataset=ds[:3] if ds is not None else None,
+                float_frame=ds is None or bool(ds[3]))
             meta_out["lean"] = dict(n_isects=n_isects, isect_status=status)
-            ctx.set_materialize_grads(False)
             return render, alphas.unsqueeze(-1)
-        if training and isect_capacity is not None:
+        if training and cap is not None:
             # the whole batch of training cameras behind ONE C call (mgs_render_frames_train): what the backward and the
             # meta dict need stays per camera in one state buffer; no read-back, so the step captures in a HIP graph
             _, _, st = ops.render_frames_train_raw(
-                means, quats, scales, opacities, sh_degree, sh_coeffs, viewmats, Ks, width, height, eps2d, near_plane,
-                far_plane, radius_clip, antialiased, with_depth, isect_capacity, segment, backgrounds=backgrounds,
-                expected_last=expected_depth, latency=latency, tight=tight, out=(render, alphas), per_axis=per_axis,
-                camera=camera)
+                *args, cfg.segment, backgrounds=backgrounds, expected_last=cfg.expected_depth, latency=cfg.latency,
+                tight=cfg.tight, out=(render, alphas), per_axis=cfg.per_axis, camera=cfg.camera)
             per_cam = []
             for c in range(C):
                 v = st.views(c)
-                per_cam.append((torch.stack([v["radii"], v["radii_y"]]) if per_axis else v["radii"], v["means2d"], v["depths"], v["conics"], v["opac_aa"] if antialiased else None,
-                                v["feats"], st.tile_lists(c, v), v["splats"], None))
+                per_cam.append(_Camera(torch.stack([v["radii"], v["radii_y"]]) if cfg.per_axis else v["radii"], v["means2d"],
+                                       v["depths"], v["conics"], v["opac_aa"] if cfg.antialiased else None, v["feats"],
+                                       st.tile_lists(c, v), v["splats"], None))
             ctx.train_state = st
-            ctx.expected_depth = bool(expected_depth)
-            ctx.channels = ch
-            ctx.set_materialize_grads(False)
             ctx.save_for_backward(means, quats, scales, opacities, sh_coeffs, viewmats, Ks, backgrounds, alphas, None, render)
-            ctx.cfg = (width, height, tile_w, tile_h, sh_degree, eps2d, antialiased, with_depth, absgrad)
             meta_out["per_cam"] = per_cam
-            ctx.meta_out = meta_out
             return render, alphas.unsqueeze(-1)
         ctx.train_state = None
         per_cam = []
         for c in range(C):
             # the projection kernel also seeds the binning (tile rectangle + count per Gaussian)
             radii, means2d, depths, conics, opac_aa, feats, splats, seed = ops.project_color_fwd_raw(
-                means, quats, scales, opacities, sh_degree, sh_coeffs, viewmats[c], Ks[c], width,
-                height, eps2d, near_plane, far_plane, radius_clip, antialiased, with_depth,
-                want_splats=True, bin_seed="tight" if tight else "classic", lean=lean, per_axis=per_axis, camera=camera)
-            opac = opac_aa if antialiased else opacities
-            cap = isect_capacity
-            if cap is None:
-                cap = max(1, ops._upper_bound_isects(radii, tile_w, tile_h))
-            tl = ops.isect_tiles_raw(means2d, radii, depths, tile_w, tile_h, cap, c, C,
-                                     want_isect_ids=False, want_tiles_per_gauss=not lean,
-                                     want_pair_info=training, want_tile_ids=not lean,
-                                     conics=conics if tight else None,
-                                     opacities=opac if tight else None, seed=seed, splats=splats if training else None)
+                means, quats, scales, opacities, cfg.sh_degree, sh_coeffs, viewmats[c], Ks[c], width, height, cfg.eps2d,
+                cfg.near, cfg.far, cfg.radius_clip, cfg.antialiased, cfg.with_depth, want_splats=True,
+                bin_seed="tight" if cfg.tight else "classic", per_axis=cfg.per_axis, camera=cfg.camera)
+            opac = opac_aa if cfg.antialiased else opacities
+            cam_cap = cap if cap is not None else max(1, ops._upper_bound_isects(radii, tile_w, tile_h))
+            # training: these records are the ones the backward gets (_Camera.splats), so it may read their slot words
+            tl = ops.isect_tiles_raw(means2d, radii, depths, tile_w, tile_h, cam_cap, c, C, want_pair_info=training,
+                                     conics=conics if cfg.tight else None, opacities=opac if cfg.tight else None,
+                                     seed=seed, splats=splats if training else None)
             # training: the forward leaves per-pixel checkpoints every `segment` list entries, so that the backward
             # can walk a tile's list as independent segments (include/mgs.h: mgs_rasterize_fwd)
-            # (without a fixed capacity `cap` is the loose bound read back above -- several times the lists: the checkpoints
-            #  are then sized by the count the binning has just written, one more read-back on a path that reads back anyway)
-            ckpt_cap = cap if isect_capacity is not None else min(cap, int(tl.n_isect.item()) + 1)
-            ckpt = ops.checkpoint_buffer(ckpt_cap, tile_w, tile_h, ch, segment, dev) if (training and segment) else None
+            # (without a fixed capacity `cam_cap` is the loose bound read back above -- several times the lists: the
+            #  checkpoints are then sized by the count the binning has just written, one more read-back on a path that
+            #  reads back anyway)
+            ckpt = None
+            if training and cfg.segment:
+                ckpt_cap = cam_cap if cap is not None else min(cam_cap, int(tl.n_isect.item()) + 1)
+                ckpt = ops.checkpoint_buffer(ckpt_cap, tile_w, tile_h, ch, cfg.segment, dev)
             ops.rasterize_fwd_raw(means2d, conics, feats, opac,
                                   backgrounds[c] if backgrounds is not None else None, width,
                                   height, tile_w, tile_h, tl.tile_offsets, tl.flatten_ids,
                                   out=(render[c], alphas[c], last_ids[c] if training else None),
-                                  splats=splats, expected_last=expected_depth, latency=latency,
+                                  splats=splats, expected_last=cfg.expected_depth, latency=cfg.latency,
                                   group_order=tl.group_order, channels=ch, checkpoints=ckpt,
-                                  checkpoint_interval=segment if ckpt is not None else 0)
-            per_cam.append((radii, means2d, depths, conics, opac_aa, feats, tl, splats, ckpt))
+                                  checkpoint_interval=cfg.segment if ckpt is not None else 0)
+            per_cam.append(_Camera(radii, means2d, depths, conics, opac_aa, feats, tl, splats, ckpt))
         ctx.per_cam = per_cam
         # "RGB+ED": the kernel's epilogue divided the depth channel by max(alpha, 1e-10); the
         # backward undoes that with the saved frame (an OUTPUT: it must go through
         # save_for_backward -- parked on ctx it forms a reference cycle that crashes HIP graph capture)
-        ctx.expected_depth = bool(expected_depth)
-        ctx.channels = ch
-        ctx.segment = int(segment) if training else 0
-        ctx.set_materialize_grads(False)       # an unused output's cotangent arrives as None, not as a zero frame
         ctx.save_for_backward(means, quats, scales, opacities, sh_coeffs, viewmats, Ks,
                               backgrounds, alphas, last_ids,
-                              render if ((expected_depth or segment) and training) else None)
-        ctx.cfg = (width, height, tile_w, tile_h, sh_degree, eps2d, antialiased, with_depth,
-                   absgrad)
-        ctx.camera = camera
+                              render if ((cfg.expected_depth or cfg.segment) and training) else None)
         meta_out["per_cam"] = per_cam
-        ctx.meta_out = meta_out
         return render, alphas.unsqueeze(-1)
 
     @staticmethod
     def backward(ctx, v_render, v_alphas):
         (means, quats, scales, opacities, sh_coeffs, viewmats, Ks, backgrounds, alphas,
          last_ids, render_out) = ctx.saved_tensors
-        (width, height, tile_w, tile_h, sh_degree, eps2d, antialiased, with_depth,
-         absgrad) = ctx.cfg
-        C, n = viewmats.shape[0], means.shape[0]
+        cfg = ctx.cfg
+        C = viewmats.shape[0]
         # set_materialize_grads(False): an output the loss does not use arrives as None instead of a zero frame
         if v_render is None:
-            v_render = torch.zeros(C, height, width, ctx.channels, dtype=torch.float32, device=means.device)
+            v_render = torch.zeros(C, cfg.height, cfg.width, cfg.channels, dtype=torch.float32, device=means.device)
         v_render = _f32c(v_render)
-        v_alphas = _f32c(v_alphas).reshape(C, height, width) if v_alphas is not None else None
+        v_alphas = _f32c(v_alphas).reshape(C, cfg.height, cfg.width) if v_alphas is not None else None
         if ctx.train_state is not None:
             # the batch's backward behind one C call (mgs_render_frames_backward): same kernels, same order
             v_means, v_quats, v_scales, v_sh, v_opacities, v_viewmats, v_m2d, v_abs = ops.render_frames_backward_raw(
-                means, quats, scales, opacities, sh_degree, sh_coeffs, viewmats, Ks, eps2d, backgrounds, ctx.train_state,
-                render_out, alphas, v_render, v_alphas, absgrad=absgrad, want_viewmats=ctx.needs_input_grad[5])
-            ctx.meta_out["means2d_grad"] = [v_m2d[c] for c in range(C)]
-            if absgrad:
-                ctx.meta_out["means2d_absgrad"] = [v_abs[c] for c in range(C)]
-            m2d = ctx.meta_out.get("means2d")
-            if m2d is not None and m2d.requires_grad:
-                m2d.grad = v_m2d
-                if absgrad:
-                    m2d.absgrad = v_abs
-            v_bg = None
-            if backgrounds is not None and ctx.needs_input_grad[7]:
-                vr = v_render
-                if ctx.expected_depth:
-                    vr = torch.cat([vr[..., :-1], (vr[..., -1] / alphas.clamp(min=1e-10)).unsqueeze(-1)], dim=-1)
-                v_bg = (vr * (1.0 - alphas).unsqueeze(-1)).sum(dim=(1, 2))
-            return (v_means, v_quats, v_scales, v_opacities, v_sh, v_viewmats, None, v_bg) + (None,) * 20
-        # "RGB+ED": the raster backward's prologue undoes the divide by max(alpha, 1e-10) itself
-        # (expected_render=...); only a background gradient needs the converted cotangent here
-        # the first camera overwrites the outputs, later ones accumulate: no zero-fill pass
-        v_means = torch.empty_like(means)
-        v_quats = torch.empty_like(quats)
-        v_scales = torch.empty_like(scales)
-        v_sh = torch.empty_like(sh_coeffs)
-        v_opacities = torch.empty_like(opacities) if antialiased else None
-        # camera-pose gradients only when asked for (float atomics into a zeroed [C,4,4])
-        v_viewmats = torch.zeros_like(viewmats) if ctx.needs_input_grad[5] else None
-        L = _lib.lib()
-        for c in range(C):
-            radii, means2d, depths, conics, opac_aa, feats, tl, splats, ckpt = ctx.per_cam[c]
-            opac = opac_aa if antialiased else opacities
-            bg = backgrounds[c] if backgrounds is not None else None
-            v_means2d, v_conics, v_feats, v_opac, v_abs = ops.rasterize_bwd_det_raw(
-                means2d, conics, feats, opac, bg, width, height, tile_w, tile_h, tl, alphas[c],
-                last_ids[c], v_render[c], v_alphas[c] if v_alphas is not None else None, absgrad, splats=splats,
-                expected_render=render_out[c] if ctx.expected_depth else None,
-                render_out=render_out[c] if ckpt is not None else None, checkpoints=ckpt,
-                checkpoint_interval=ctx.segment if ckpt is not None else 0)
-            # screen-space gradients for densification strategies (gsplat exposes them through
-            # means2d.grad / means2d.absgrad; here they are published in the meta dict)
-            ctx.meta_out.setdefault("means2d_grad", [None] * C)[c] = v_means2d
-            # (all four blend-stage gradients, for tests that gate the raster backward on its own)
-            ctx.meta_out.setdefault("blend_grads", [None] * C)[c] = (v_means2d, v_conics, v_feats, v_opac)
-            if absgrad:
-                ctx.meta_out.setdefault("means2d_absgrad", [None] * C)[c] = v_abs
-            check(L.mgs_project_color_bwd(
-                n, ptr(means), ptr(quats), ptr(scales), ptr(opacities), sh_degree,
-                sh_coeffs.shape[1], ptr(sh_coeffs), ptr(viewmats[c]), ptr(Ks[c]), width, height,
-                eps2d, ptr(ops.radii_x(radii)), ptr(conics), int(antialiased), feats.shape[1], ptr(feats),
-                ptr(v_feats), ptr(v_means2d), ptr(v_conics), None,
-                ptr(v_opac) if antialiased else None, ptr(v_means), ptr(v_quats), ptr(v_scales),
-                ptr(v_sh), ptr(v_opacities),
-                ptr(v_viewmats[c]) if v_viewmats is not None else None, int(c > 0), int(ctx.camera),
-                stream_handle()),
-                "mgs_project_color_bwd")
-            if not antialiased:
-                v_opacities = v_opac if v_opacities is None else v_opacities + v_opac
-        # gsplat users call meta["means2d"].retain_grad() and read .grad / .absgrad after backward
-        # (densification).  meta["means2d"] is handed out as a leaf that receives them here.
-        m2d = ctx.meta_out.get("means2d")
+                means, quats, scales, opacities, cfg.sh_degree, sh_coeffs, viewmats, Ks, cfg.eps2d, backgrounds,
+                ctx.train_state, render_out, alphas, v_render, v_alphas, absgrad=cfg.absgrad,
+                want_viewmats=ctx.needs_input_grad[5])
+        else:
+            tile_w, tile_h = -(-cfg.width // TILE_SIZE), -(-cfg.height // TILE_SIZE)
+            # "RGB+ED": the raster backward's prologue undoes the divide by max(alpha, 1e-10) itself
+            # (expected_render=...); only a background gradient needs the converted cotangent
+            # the first camera overwrites the outputs, later ones accumulate: no zero-fill pass
+            v_means = torch.empty_like(means)
+            v_quats = torch.empty_like(quats)
+            v_scales = torch.empty_like(scales)
+            v_sh = torch.empty_like(sh_coeffs)
+            v_opacities = torch.empty_like(opacities) if cfg.antialiased else None
+            # camera-pose gradients only when asked for (float atomics into a zeroed [C,4,4])
+            v_viewmats = torch.zeros_like(viewmats) if ctx.needs_input_grad[5] else None
+            v_m2d, v_abs, blend = [], [], []
+            for c, cam in enumerate(ctx.per_cam):
+                opac = cam.opac_aa if cfg.antialiased else opacities
+                ckpt = cam.checkpoints
+                v_means2d, v_conics, v_feats, v_opac, v_means2d_abs = ops.rasterize_bwd_det_raw(
+                    cam.means2d, cam.conics, cam.feats, opac, backgrounds[c] if backgrounds is not None else None, cfg.width,
+                    cfg.height, tile_w, tile_h, cam.lists, alphas[c], last_ids[c], v_render[c],
+                    v_alphas[c] if v_alphas is not None else None, cfg.absgrad, splats=cam.splats,
+                    expected_render=render_out[c] if cfg.expected_depth else None,
+                    render_out=render_out[c] if ckpt is not None else None, checkpoints=ckpt,
+                    checkpoint_interval=cfg.segment if ckpt is not None else 0)
+                v_m2d.append(v_means2d)
+                v_abs.append(v_means2d_abs)
+                # (all four blend-stage gradients, for tests that gate the raster backward on its own)
+                blend.append((v_means2d, v_conics, v_feats, v_opac))
+                ops.project_color_bwd_raw(
+                    means, quats, scales, opacities, cfg.sh_degree, sh_coeffs, viewmats[c], Ks[c], cfg.width, cfg.height,
+                    cfg.eps2d, cam.radii, cam.conics, cfg.antialiased, cam.feats, v_feats, v_means2d, v_conics,
+                    v_opac if cfg.antialiased else None, v_means, v_quats, v_scales, v_sh, v_opacities,
+                    v_viewmats[c] if v_viewmats is not None else None, accumulate=c > 0, camera=cfg.camera)
+                if not cfg.antialiased:
+                    v_opacities = v_opac if v_opacities is None else v_opacities + v_opac
+            ctx.meta_out["blend_grads"] = blend
+        # screen-space gradients for densification strategies: published in the meta dict, and gsplat users call
+        # meta["means2d"].retain_grad() and read .grad / .absgrad after backward -- meta["means2d"] is handed out as a
+        # leaf that receives them here.  v_m2d / v_abs: [C,N,2] (one call) or lists of C [N,2] (per camera)
+        meta = ctx.meta_out
+        meta["means2d_grad"] = list(v_m2d)
+        if cfg.absgrad:
+            meta["means2d_absgrad"] = list(v_abs)
+        m2d = meta.get("means2d")
         if m2d is not None and m2d.requires_grad:
-            gl = ctx.meta_out["means2d_grad"]
-            m2d.grad = gl[0].unsqueeze(0) if C == 1 else torch.stack(gl)
-            if absgrad:
-                al = ctx.meta_out["means2d_absgrad"]
-                m2d.absgrad = al[0].unsqueeze(0) if C == 1 else torch.stack(al)
+            m2d.grad = v_m2d if torch.is_tensor(v_m2d) else _stk(v_m2d)
+            if cfg.absgrad:
+                m2d.absgrad = v_abs if torch.is_tensor(v_abs) else _stk(v_abs)
         v_bg = None
         if backgrounds is not None and ctx.needs_input_grad[7]:
-            if ctx.expected_depth:
+            if cfg.expected_depth:
                 v_render = torch.cat([v_render[..., :-1],
                                       (v_render[..., -1] / alphas.clamp(min=1e-10)).unsqueeze(-1)], dim=-1)
             v_bg = (v_render * (1.0 - alphas).unsqueeze(-1)).sum(dim=(1, 2))
-        return (v_means, v_quats, v_scales, v_opacities, v_sh, v_viewmats, None, v_bg) + (None,) * 20
+        return v_means, v_quats, v_scales, v_opacities, v_sh, v_viewmats, None, v_bg, None, None
 
 
 def rasterization(means: Tensor, quats: Tensor, scales: Tensor, opacities: Tensor,
@@ -360,41 +376,35 @@ def rasterization(means: Tensor, quats: Tensor, scales: Tensor, opacities: Tenso
             raise ValueError("sh_degree outside 0..3 or too few coefficients")
         if backgrounds is not None and backgrounds.shape != (C, 4 if want_depth else 3):
             raise ValueError("backgrounds must be [C, channels]")
-        store = meta        # the autograd function publishes per-camera intermediates (and, after
-        #                     backward, "means2d_grad" / "means2d_absgrad" lists) into the meta dict
-        render, alphas = _RenderSH.apply(
-            means, quats, scales, opacities, colors, viewmats, Ks, backgrounds, width, height,
-            int(sh_degree), float(eps2d), float(near_plane), float(far_plane),
-            float(radius_clip), antialiased, want_depth, isect_capacity, bool(absgrad), store,
-            tile_bounds == "tight", bool(rule), camera, render_mode in ("RGB+ED", "ED"),
-            raster_schedule == "latency",
-            bool(lean_meta), int(backward_segment), dataset_out)
+        cfg = _RenderConfig(
+            width, height, int(sh_degree), float(eps2d), float(near_plane), float(far_plane), float(radius_clip),
+            antialiased, want_depth, isect_capacity, bool(absgrad), tight=tile_bounds == "tight", per_axis=bool(rule),
+            camera=camera, expected_depth=render_mode in ("RGB+ED", "ED"), latency=raster_schedule == "latency",
+            lean=bool(lean_meta), segment=int(backward_segment), dataset=dataset_out)
+        # the autograd function publishes per-camera intermediates (and, after backward, "means2d_grad" /
+        # "means2d_absgrad" lists) into the meta dict
+        render, alphas = _RenderSH.apply(means, quats, scales, opacities, colors, viewmats, Ks, backgrounds, cfg, meta)
         if depth_only_via_sh:
             render = render[..., 3:4]
-        if "lean" in store:             # inference frames through mgs_render_frames: counts and status only
-            meta.update(store.pop("lean"))
+        if "lean" in meta:              # inference frames through mgs_render_frames: counts and status only
+            meta.update(meta.pop("lean"))
             return render, alphas, meta
-        per_cam = store.pop("per_cam")
-
-        def _stk(xs):                 # no copy for the common single-camera call
-            return xs[0].unsqueeze(0) if len(xs) == 1 else torch.stack(xs)
+        per_cam = meta.pop("per_cam")
 
         def _cat(xs):
             return xs[0] if len(xs) == 1 else torch.cat(xs)
-        if per_cam[0][0] is not None:        # (a lean frame has none of these)
-            meta.update(
-                radii=_stk([ops.radii_meta(p[0]) for p in per_cam]),
-                means2d=_stk([p[1] for p in per_cam]),
-                conics=_stk([p[3] for p in per_cam]),
-                tiles_per_gauss=_stk([p[6].tiles_per_gauss for p in per_cam]))
         meta.update(
-            depths=_stk([p[2] for p in per_cam]),
-            opacities=(_stk([p[4] for p in per_cam]) if antialiased
+            radii=_stk([ops.radii_meta(p.radii) for p in per_cam]),
+            means2d=_stk([p.means2d for p in per_cam]),
+            conics=_stk([p.conics for p in per_cam]),
+            tiles_per_gauss=_stk([p.lists.tiles_per_gauss for p in per_cam]),
+            depths=_stk([p.depths for p in per_cam]),
+            opacities=(_stk([p.opac_aa for p in per_cam]) if antialiased
                        else opacities.unsqueeze(0).expand(C, N)),
-            n_isects=_cat([p[6].n_isect for p in per_cam]),
-            isect_status=_cat([p[6].status for p in per_cam]),
-            isect_offsets=_stk([p[6].tile_offsets[:-1].view(tile_h, tile_w) for p in per_cam]),
-            tile_lists=[p[6] for p in per_cam])
+            n_isects=_cat([p.lists.n_isect for p in per_cam]),
+            isect_status=_cat([p.lists.status for p in per_cam]),
+            isect_offsets=_stk([p.lists.tile_offsets[:-1].view(tile_h, tile_w) for p in per_cam]),
+            tile_lists=[p.lists for p in per_cam])
         if torch.is_grad_enabled() and render.requires_grad and "means2d" in meta:
             meta["means2d"] = meta["means2d"].detach().requires_grad_(True)   # see _RenderSH.backward
     else:
@@ -440,7 +450,7 @@ def check_isect_status(meta: Dict) -> None:
     """Raise if any camera's intersection list overflowed its capacity (reads one word back)."""
     if "isect_status" in meta and bool((meta["isect_status"] != 0).any().item()):
         need = int(meta["n_isects"].max().item())
-        raise _lib.MgsError(f"tile-intersection capacity exceeded: a camera needs {need} slots; "
+        raise MgsError(f"tile-intersection capacity exceeded: a camera needs {need} slots; "
                             "re-render with a larger isect_capacity")
 
 

@@ -7,6 +7,7 @@ fraction (alpha-threshold flips move a whole Gaussian's contribution at one pixe
 cosine similarity of the full gradient must exceed 0.9999.
 """
 import math
+import warnings
 
 import numpy as np
 import pytest
@@ -692,4 +693,19 @@ def test_splat_slot_words_of_another_binning_are_not_trusted():
     splats2 = ops.project_color_fwd_raw(t["means"], t["quats"], t["scales"], t["opacities"], 1, t["colors"], vm, K, W, H, 0.3, 0.01, 1e10, 0.0, False, True,
                                         want_splats=True)[6]
     assert not ops._splat_slots_valid(tl_classic, splats2)
+    # records freed after their binning: a tensor that is not fresh from a projection (here torch.empty) may be handed the
+    # same address by the caching allocator, and still carries nobody's slots
+    s1 = ops.project_color_fwd_raw(t["means"], t["quats"], t["scales"], t["opacities"], 1, t["colors"], vm, K, W, H, 0.3, 0.01, 1e10, 0.0, False, True,
+                                   want_splats=True)[6]
+    tl_s1 = ops.isect_tiles_raw(m2d, radii, dep, tw, th, cap, want_pair_info=True, splats=s1)
+    assert ops._splat_slots_valid(tl_s1, s1)
+    addr, shape = s1.data_ptr(), s1.shape
+    del s1
+    s3 = torch.empty(shape, dtype=torch.float32, device=DEV)
+    reused = s3.data_ptr() == addr
+    print(f"caching allocator reused the freed records' address: {reused}")
+    if not reused:
+        warnings.warn("the allocator did not reuse the freed records' address: the reuse case went unexercised")
+    assert not ops._splat_slots_valid(tl_s1, s3), f"address reused: {reused}"
+    assert not ops._splat_slots_valid(tl_s1, s3.clone())
 
