@@ -42,8 +42,9 @@ extern "C" {
  * checkpoints + segmented backward, batched training entry points, debug hooks out of the production build);
  * 410 round 4 (the radius rule as a policy: radii_y / radius_rule arguments, MGS_BIN_* / MGS_FRAMES_RADIUS_* flags,
  * one more field in the training state; 420: the dataset frame as an output of the raster forward, ds_* arguments;
- * 440: the camera model as a policy: camera_model arguments, MGS_BIN_CAMERA_* / MGS_FRAMES_CAMERA_* flags). */
-#define MGS_VERSION 440
+ * 440: the camera model as a policy: camera_model arguments, MGS_BIN_CAMERA_* / MGS_FRAMES_CAMERA_* flags;
+ * 450: the image-loss descriptor, a trailing `image` argument of mgs_l1_loss_fwd / _fwd_grad / _bwd). */
+#define MGS_VERSION 450
 
 #define MGS_OK 0
 #define MGS_ERR_INVALID_ARGUMENT (-1)
@@ -521,17 +522,41 @@ int mgs_points_sample_mask(int n, const float *uv, int uv_stride, const float *m
  * Photometric L1 term of the training step (BASELINE configs[2]): loss = mean |a - b| over n
  * floats (a = rendered image, b = target), and its gradient v_a = v_loss * sign(a - b) / n
  * (sign(0) = 0, as torch).  loss, v_loss: device scalars (v_loss NULL = 1).  Fixed summation
- * order: bit-reproducible.  Workspace (forward): two-phase size query.  Buffers 16-byte aligned.
+ * order: bit-reproducible.  Workspace (forward): two-phase size query.
+ *
+ * image (host, nullable): NULL is the plain flat L1 above (buffers 16-byte aligned).  Non-NULL makes the loss
+ * splatfacto's L1 + D-SSIM,
+ *   loss = (1 - ssim_weight) * mean |a - b| + ssim_weight * (1 - SSIM(a, b)),
+ * with a, b laid out [images, height, width, channels] channel-last (n = images * height * width * channels,
+ * channels 1..4, no alignment needed).  SSIM is the mean over positions, channels and images of
+ *   S = (2 mu_a mu_b + C1)(2 sigma_ab + C2) / ((mu_a^2 + mu_b^2 + C1)(sigma_a^2 + sigma_b^2 + C2)),
+ * moments under the separable 11-tap Gaussian window of sigma 1.5, C1 = 0.01^2, C2 = 0.03^2 (data range 1), per
+ * channel.  padding MGS_SSIM_VALID: S where the whole window lies inside the image ((height - 10) x (width - 10)
+ * positions, height and width >= 11; pytorch_msssim / gsplat's trainer); MGS_SSIM_SAME: S at every pixel of the image
+ * zero-padded by 5 (the original 3DGS code's ssim()).  The descriptor is checked before the size query answers.
  * ----------------------------------------------------------------------------------- */
+#define MGS_SSIM_VALID 0
+#define MGS_SSIM_SAME 1
+
+typedef struct mgs_image_loss {
+  int images, height, width, channels;
+  float ssim_weight; /* lambda in [0, 1] */
+  int padding;       /* MGS_SSIM_VALID or MGS_SSIM_SAME */
+} mgs_image_loss;
+
 int mgs_l1_loss_fwd(size_t n, const float *a, const float *b, float *loss, void *workspace,
-                    size_t *workspace_bytes, mgs_stream_t stream);
+                    size_t *workspace_bytes, mgs_stream_t stream, const mgs_image_loss *image);
+/* The gradient for the v_loss that arrived, recomputed from a and b (under a descriptor: the same bits as
+ * mgs_l1_loss_fwd_grad's v_a times *v_loss). */
 int mgs_l1_loss_bwd(size_t n, const float *a, const float *b, const float *v_loss, float *v_a,
-                    mgs_stream_t stream);
-/* The training step's form: loss AND v_a = sign(a - b) / n (the gradient for v_loss = 1) in ONE pass over a and b
- * -- the same bits as the two calls above.  mgs_l1_loss_bwd_scale then turns v_a into the gradient for the v_loss
- * that arrived, in place (v_a <- sign(v_a) * v_loss / n: idempotent), and is a no-op launch when *v_loss == 1. */
+                    mgs_stream_t stream, const mgs_image_loss *image);
+/* The training step's form: loss AND v_a, the gradient for v_loss = 1, in ONE pass over a and b -- the same bits as
+ * the two calls above.  For the plain L1 (image NULL), mgs_l1_loss_bwd_scale then turns v_a into the gradient for the
+ * v_loss that arrived, in place (v_a <- sign(v_a) * v_loss / n: idempotent), and is a no-op launch when *v_loss == 1;
+ * under a descriptor v_a is scaled by the caller (v_a * v_loss). */
 int mgs_l1_loss_fwd_grad(size_t n, const float *a, const float *b, float *loss, float *v_a,
-                         void *workspace, size_t *workspace_bytes, mgs_stream_t stream);
+                         void *workspace, size_t *workspace_bytes, mgs_stream_t stream,
+                         const mgs_image_loss *image);
 int mgs_l1_loss_bwd_scale(size_t n, const float *v_loss, float *v_a, mgs_stream_t stream);
 
 /* -------------------------------------------------------------------------------------

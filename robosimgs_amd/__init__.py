@@ -35,7 +35,7 @@ def __getattr__(name):  # lazy: keeps `import robosimgs_amd` torch-free for host
     if name == "transform_gaussians":
         from . import transform
         return transform.transform_gaussians
-    if name in ("l1_loss", "unit_gradient"):
+    if name in ("l1_loss", "l1_ssim_loss", "ssim", "unit_gradient"):
         from . import losses
         return getattr(losses, name)
     if name in ("FrameRenderer", "locality_order"):

@@ -19,11 +19,19 @@ DEBUG_LIB_PATH = os.path.join(_HERE, "csrc", "libmgs_debug.so")
 DEBUG_HOOKS = ["mgs_debug_set_raster_cull", "mgs_debug_set_raster_opts", "mgs_debug_set_sort_opts"]
 
 MGS_STATUS_ISECT_OVERFLOW = 1
-MGS_VERSION = 440          # include/mgs.h this binding was written against (parameter lists change with it)
+MGS_SSIM_VALID, MGS_SSIM_SAME = 0, 1       # mgs_image_loss.padding
+MGS_VERSION = 450          # include/mgs.h this binding was written against (parameter lists change with it)
+
+
+class ImageLoss(ctypes.Structure):
+    """mgs_image_loss: the image layout and SSIM weight that turn the L1 entry points into L1 + D-SSIM."""
+    _fields_ = [("images", c_int), ("height", c_int), ("width", c_int), ("channels", c_int),
+                ("ssim_weight", c_float), ("padding", c_int)]
 
 
 # every function include/mgs.h declares: name -> (argtypes, restype)
 p, i, f, u32 = c_void_p, c_int, c_float, c_uint32
+img = POINTER(ImageLoss)
 _SIGNATURES = {
     "mgs_version": ([], c_int),
     "mgs_last_error_string": ([], c_char_p),
@@ -49,13 +57,13 @@ _SIGNATURES = {
     "mgs_frame_to_u8": ([i, p, i, p, p, p, p], c_int),
     "mgs_frame_to_dataset": ([i, i, p, i, p, p, p, p, p, i, p], c_int),
     "mgs_transform_gaussians": ([i, p, p, p, i, i, p, p, i, p, p, p, p, p, p, p], c_int),
-    "mgs_l1_loss_fwd": ([c_size_t, p, p, p, p, POINTER(c_size_t), p], c_int),
-    "mgs_l1_loss_bwd": ([c_size_t, p, p, p, p, p], c_int),
-    "mgs_l1_loss_fwd_grad": ([c_size_t, p, p, p, p, p, POINTER(c_size_t), p], c_int),
+    "mgs_l1_loss_fwd": ([c_size_t, p, p, p, p, POINTER(c_size_t), p, img], c_int),
+    "mgs_l1_loss_bwd": ([c_size_t, p, p, p, p, p, img], c_int),
+    "mgs_l1_loss_fwd_grad": ([c_size_t, p, p, p, p, p, POINTER(c_size_t), p, img], c_int),
     "mgs_l1_loss_bwd_scale": ([c_size_t, p, p, p], c_int),
     "mgs_rasterize_bwd_det": ([i, p, p, p, p, p, p, i, i, i, i, i, p, p, p, p, p, p, p, p, p, u32, p, p, i, i, p, p, p, p, p, p, POINTER(c_size_t), p], c_int),
 }
-del p, i, f, u32
+del p, i, f, u32, img
 EXPORTS = list(_SIGNATURES)
 
 
@@ -147,8 +155,8 @@ def stream_handle() -> int:
 _workspaces: dict = {}
 
 
-def sized_call(fn, args, device, *, cached: bool, canary_bytes: int = 0):
-    """Two-phase call of an entry point whose parameters end in (workspace, workspace_bytes, stream): a size query (with a
+def sized_call(fn, args, device, *, cached: bool, canary_bytes: int = 0, trailing=()):
+    """Two-phase call of an entry point whose parameters end in (workspace, workspace_bytes, stream, *trailing): a size query (with a
     null workspace the call only reports the bytes it needs), then the call itself on a 256-byte aligned workspace of
     exactly that size, both on torch's current stream.  Each call site picks where the workspace comes from:
       cached=True   one growing scratch tensor per (device, stream, capturing): stream-ordered reuse is safe because
@@ -157,7 +165,7 @@ def sized_call(fn, args, device, *, cached: bool, canary_bytes: int = 0):
     canary_bytes: a fresh workspace followed by that many 0xA5 bytes, returned so that a test can see nothing was
     written past the workspace.  Returns None otherwise."""
     stream, nbytes = stream_handle(), ctypes.c_size_t(0)
-    check(fn(*args, None, ctypes.byref(nbytes), stream), f"{fn.__name__}(size query)")
+    check(fn(*args, None, ctypes.byref(nbytes), stream, *trailing), f"{fn.__name__}(size query)")
     size = nbytes.value
     if canary_bytes:
         buf = torch.full((size + 256 + canary_bytes,), 0xA5, dtype=torch.uint8, device=device)
@@ -169,7 +177,7 @@ def sized_call(fn, args, device, *, cached: bool, canary_bytes: int = 0):
     else:
         buf = torch.empty(size + 256, dtype=torch.uint8, device=device)
     pad = -buf.data_ptr() % 256
-    check(fn(*args, buf.data_ptr() + pad, ctypes.byref(nbytes), stream), fn.__name__)
+    check(fn(*args, buf.data_ptr() + pad, ctypes.byref(nbytes), stream, *trailing), fn.__name__)
     if canary_bytes:
         return buf[pad + size:pad + size + canary_bytes]
 

@@ -4,7 +4,13 @@
 // 1920x1080x3).  HBM-bound: 8 B read per element forward, 8 B read + 4 B written backward.
 // The sum is taken in a fixed order (per-thread strided partials, wave butterfly, per-block slots,
 // one final block), so the loss is bit-reproducible.
+//
+// Under an image descriptor (mgs_image_loss) the same entry points compute splatfacto's L1 + D-SSIM loss
+// (1 - lambda) mean|a - b| + lambda (1 - SSIM) and its gradient in ONE pass over a and b: ssim_kernel below, then the
+// one-block l1 / ssim final kernel.  Gather form, no atomics: bit-reproducible as well.
 #include <algorithm>
+#include <climits>
+#include <cmath>
 
 #include "mgs_common.h"
 
@@ -121,6 +127,309 @@ __global__ __launch_bounds__(kBlock) void l1_scale_kernel(size_t n, const float*
 
 constexpr unsigned kScaleBlocks = 128;
 
+// ---- L1 + D-SSIM (mgs_image_loss) ----------------------------------------------------------------------------------
+// One workgroup per 32 x 32 output tile of one image, all channels in turn.  Per channel:
+//   stage    x' = x - x(c), y' = y - y(c) on the tile + 10-pixel halo (52 x 52; zeros outside the image, shifted too),
+//            where c is a pixel near the tile's centre: the variances below are differences of two moments, and taking
+//            them about a local value keeps near-constant images from cancelling to nothing in fp32 (SSIM itself is
+//            unchanged: mu = x(c) + g * x', sigma^2 = g * x'^2 - (g * x')^2);
+//   pass 1   the window along rows: the five moments x', y', x'^2, y'^2, x'y' on 52 rows x 42 columns;
+//   pass 2   along columns: the moments at the 42 x 42 window centres q (tile + 5-pixel halo), S(q), and the chained
+//            partials A = dS/dmu_x - 2 mu_x' B - mu_y' C, B = dS/dsigma_x^2, C = dS/dsigma_xy (zero where q is not a
+//            position of the loss: outside the valid region, or outside the image under "same");
+//   pass 3/4 the window's transpose (the window is symmetric: the window itself) over A, B, C along rows, then columns:
+//            dSSIM/dx(p) = (1/M) sum_q g(q - p) [A(q) + 2 x'(p) B(q) + y'(p) C(q)] on the tile.
+// Each thread filters a strip of kP* outputs from kP* + 10 values in registers (2.2-2.6 LDS reads per output instead of
+// 11).  LDS: x', y' (21.1 KiB, reused for A, B, C) + the row-filtered maps (42.7 KiB): 64 KiB, two workgroups per CU.
+constexpr int kSsimTW = 32, kSsimTH = 32;                        // output tile
+constexpr int kR = 5;                                            // window radius: 11 taps
+constexpr int kXW = kSsimTW + 4 * kR, kXH = kSsimTH + 4 * kR;    // staged x', y'
+constexpr int kMW = kSsimTW + 2 * kR, kMH = kSsimTH + 2 * kR;    // window centres whose partials reach the tile
+constexpr int kP1 = 7, kP2 = 7, kP3 = 8, kP4 = 4;                // outputs per thread in passes 1..4
+constexpr int kStage = (kXH * kXW + kBlock - 1) / kBlock;        // staged pixels per thread
+static_assert(kMW % kP1 == 0 && kMH % kP2 == 0 && kSsimTW % kP3 == 0 && kSsimTH % kP4 == 0, "strips tile the passes");
+constexpr int kLdsA = 2 * kXH * kXW;                             // x', y'; then A, B, C [3][kMH][kMW]
+constexpr int kLdsB = 5 * kXH * kMW;                             // row-filtered moments; then row-filtered A, B, C
+static_assert(3 * kMH * kMW <= kLdsA && 3 * kMH * kSsimTW <= kLdsB, "overlays fit");
+constexpr float kC1 = 0.01f * 0.01f, kC2 = 0.03f * 0.03f;
+
+struct SsimArgs {
+  const float* a;
+  const float* b;
+  int height, width, channels, tiles_x, tiles_per_image, valid;
+  float l1_scale;          // (1 - lambda) / n
+  float s_scale;           // lambda / M
+  const float* v_loss;     // nullable: 1
+  float* partial;          // [2 * blocks]: per block sum |a - b|, then sum S; nullable (the backward)
+  float* v_a;              // the gradient (kGrad)
+  float g[2 * kR + 1];     // the normalised window
+};
+
+template <int K>
+__device__ __forceinline__ void filter_strip(const float* v, const float* g, float* out) {
+#pragma unroll
+  for (int m = 0; m < K; ++m) {
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k <= 2 * kR; ++k) s += g[k] * v[m + k];
+    out[m] = s;
+  }
+}
+
+template <bool kGrad>
+__global__ __launch_bounds__(kBlock) void ssim_kernel(const SsimArgs p) {
+  __shared__ float lds_a[kLdsA];
+  __shared__ float lds_b[kLdsB];
+  __shared__ float red[2 * (kBlock / 64)];
+  const int tid = threadIdx.x;
+  const int img = blockIdx.x / p.tiles_per_image, t = blockIdx.x - img * p.tiles_per_image;
+  const int ty0 = (t / p.tiles_x) * kSsimTH, tx0 = (t - (t / p.tiles_x) * p.tiles_x) * kSsimTW;
+  const int H = p.height, W = p.width, C = p.channels;
+  const size_t base = (size_t)img * H * W * C;
+  const float* __restrict__ A = p.a + base;
+  const float* __restrict__ B = p.b + base;
+  const int qy_lo = p.valid ? kR : 0, qy_hi = p.valid ? H - kR : H;     // window centres that are loss positions
+  const int qx_lo = p.valid ? kR : 0, qx_hi = p.valid ? W - kR : W;
+  float g[2 * kR + 1];
+#pragma unroll
+  for (int k = 0; k <= 2 * kR; ++k) g[k] = p.g[k];
+  const float vl = p.v_loss ? *p.v_loss : 1.f;
+  const size_t centre = ((size_t)min(ty0 + kSsimTH / 2, H - 1) * W + min(tx0 + kSsimTW / 2, W - 1)) * C;
+  float* X = lds_a;
+  float* Y = lds_a + kXH * kXW;
+  float* Hm = lds_b;                 // [5][kXH][kMW]
+  float* Abc = lds_a;                // [3][kMH][kMW]
+  float* Habc = lds_b;               // [3][kMH][kSsimTW]
+  float acc_l1 = 0.f, acc_s = 0.f;
+
+  for (int c = 0; c < C; ++c) {
+    const float sx = A[centre + c], sy = B[centre + c];
+    // (no barrier needed here: lds_a was last read in pass 1 / pass 3 of the previous channel, behind a barrier since)
+    // All of a thread's loads first, from clamped addresses, so that they are in flight together; zeros outside after.
+    float xl[kStage], yl[kStage];
+#pragma unroll
+    for (int s = 0; s < kStage; ++s) {
+      const int i = min(tid + s * kBlock, kXH * kXW - 1);
+      const int r = i / kXW, col = i - r * kXW;
+      const int gy = min(max(ty0 - 2 * kR + r, 0), H - 1), gx = min(max(tx0 - 2 * kR + col, 0), W - 1);
+      const size_t o = ((size_t)gy * W + gx) * C + c;
+      xl[s] = A[o];
+      yl[s] = B[o];
+    }
+#pragma unroll
+    for (int s = 0; s < kStage; ++s) {
+      const int i = tid + s * kBlock;
+      if (i < kXH * kXW) {
+        const int r = i / kXW, col = i - r * kXW;
+        const int gy = ty0 - 2 * kR + r, gx = tx0 - 2 * kR + col;
+        const bool inside = gy >= 0 && gy < H && gx >= 0 && gx < W;
+        const float xv = inside ? xl[s] : 0.f, yv = inside ? yl[s] : 0.f;
+        if (inside && r >= 2 * kR && r < 2 * kR + kSsimTH && col >= 2 * kR && col < 2 * kR + kSsimTW)
+          acc_l1 += fabsf(xv - yv);
+        X[i] = xv - sx;
+        Y[i] = yv - sy;
+      }
+    }
+    __syncthreads();
+
+    // pass 1: rows
+    for (int it = tid; it < kXH * (kMW / kP1); it += kBlock) {
+      const int r = it / (kMW / kP1), j0 = (it - r * (kMW / kP1)) * kP1;
+      float xs[kP1 + 2 * kR], ys[kP1 + 2 * kR], prod[kP1 + 2 * kR], out[kP1];
+#pragma unroll
+      for (int k = 0; k < kP1 + 2 * kR; ++k) {
+        xs[k] = X[r * kXW + j0 + k];
+        ys[k] = Y[r * kXW + j0 + k];
+      }
+      float* h = Hm + r * kMW + j0;
+      filter_strip<kP1>(xs, g, out);
+#pragma unroll
+      for (int m = 0; m < kP1; ++m) h[m] = out[m];
+      filter_strip<kP1>(ys, g, out);
+#pragma unroll
+      for (int m = 0; m < kP1; ++m) h[kXH * kMW + m] = out[m];
+#pragma unroll
+      for (int k = 0; k < kP1 + 2 * kR; ++k) prod[k] = xs[k] * xs[k];
+      filter_strip<kP1>(prod, g, out);
+#pragma unroll
+      for (int m = 0; m < kP1; ++m) h[2 * kXH * kMW + m] = out[m];
+#pragma unroll
+      for (int k = 0; k < kP1 + 2 * kR; ++k) prod[k] = ys[k] * ys[k];
+      filter_strip<kP1>(prod, g, out);
+#pragma unroll
+      for (int m = 0; m < kP1; ++m) h[3 * kXH * kMW + m] = out[m];
+#pragma unroll
+      for (int k = 0; k < kP1 + 2 * kR; ++k) prod[k] = xs[k] * ys[k];
+      filter_strip<kP1>(prod, g, out);
+#pragma unroll
+      for (int m = 0; m < kP1; ++m) h[4 * kXH * kMW + m] = out[m];
+    }
+    __syncthreads();
+
+    // pass 2: columns -> S and the partials at the window centres
+    for (int it = tid; it < kMW * (kMH / kP2); it += kBlock) {
+      const int col = it % kMW, i0 = (it / kMW) * kP2;
+      float mo[5][kP2];
+#pragma unroll
+      for (int q = 0; q < 5; ++q) {
+        float v[kP2 + 2 * kR];
+#pragma unroll
+        for (int k = 0; k < kP2 + 2 * kR; ++k) v[k] = Hm[(q * kXH + i0 + k) * kMW + col];
+        filter_strip<kP2>(v, g, mo[q]);
+      }
+      const int qx = tx0 - kR + col;
+      const bool own_x = col >= kR && col < kR + kSsimTW;
+#pragma unroll
+      for (int m = 0; m < kP2; ++m) {
+        const int qy = ty0 - kR + i0 + m;
+        const bool in = qy >= qy_lo && qy < qy_hi && qx >= qx_lo && qx < qx_hi;
+        const float mx = mo[0][m], my = mo[1][m];
+        const float mux = sx + mx, muy = sy + my;
+        const float vxx = mo[2][m] - mx * mx, vyy = mo[3][m] - my * my, vxy = mo[4][m] - mx * my;
+        const float n1 = 2.f * mux * muy + kC1, n2 = 2.f * vxy + kC2;
+        const float d1 = mux * mux + muy * muy + kC1, d2 = vxx + vyy + kC2;
+        const float inv = 1.f / (d1 * d2);
+        const float S = n1 * n2 * inv;
+        if (in && own_x && i0 + m >= kR && i0 + m < kR + kSsimTH) acc_s += S;
+        if (kGrad) {
+          float pa = 0.f, pb = 0.f, pc = 0.f;
+          if (in) {
+            pb = -S / d2;
+            pc = 2.f * n1 * inv;
+            pa = 2.f * muy * n2 * inv - 2.f * mux * S / d1 - 2.f * mx * pb - my * pc;
+          }
+          Abc[(i0 + m) * kMW + col] = pa;
+          Abc[(kMH + i0 + m) * kMW + col] = pb;
+          Abc[(2 * kMH + i0 + m) * kMW + col] = pc;
+        }
+      }
+    }
+    if (!kGrad) continue;        // the next channel's staging writes lds_a, which pass 2 did not touch
+    __syncthreads();
+
+    // pass 3: the transposed window along rows
+    for (int it = tid; it < kMH * (kSsimTW / kP3); it += kBlock) {
+      const int r = it / (kSsimTW / kP3), j0 = (it - r * (kSsimTW / kP3)) * kP3;
+#pragma unroll
+      for (int q = 0; q < 3; ++q) {
+        float v[kP3 + 2 * kR], out[kP3];
+#pragma unroll
+        for (int k = 0; k < kP3 + 2 * kR; ++k) v[k] = Abc[(q * kMH + r) * kMW + j0 + k];
+        filter_strip<kP3>(v, g, out);
+#pragma unroll
+        for (int m = 0; m < kP3; ++m) Habc[(q * kMH + r) * kSsimTW + j0 + m] = out[m];
+      }
+    }
+    __syncthreads();
+
+    // pass 4: along columns, and the gradient on the tile
+    for (int it = tid; it < kSsimTW * (kSsimTH / kP4); it += kBlock) {
+      const int col = it % kSsimTW, i0 = (it / kSsimTW) * kP4;
+      float f[3][kP4];
+#pragma unroll
+      for (int q = 0; q < 3; ++q) {
+        float v[kP4 + 2 * kR];
+#pragma unroll
+        for (int k = 0; k < kP4 + 2 * kR; ++k) v[k] = Habc[(q * kMH + i0 + k) * kSsimTW + col];
+        filter_strip<kP4>(v, g, f[q]);
+      }
+      const int px = tx0 + col;
+#pragma unroll
+      for (int m = 0; m < kP4; ++m) {
+        const int py = ty0 + i0 + m;
+        if (py < H && px < W) {
+          const size_t o = ((size_t)py * W + px) * C + c;
+          const float xv = A[o], yv = B[o], d = xv - yv;
+          const float sg = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
+          const float ds = f[0][m] + 2.f * (xv - sx) * f[1][m] + (yv - sy) * f[2][m];
+          p.v_a[base + o] = (p.l1_scale * sg - p.s_scale * ds) * vl;
+        }
+      }
+    }
+    // (the next channel's staging writes lds_a, last read in pass 3; pass 1 writes lds_b after the staging barrier)
+  }
+  if (p.partial) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+      acc_l1 += __shfl_xor(acc_l1, d);
+      acc_s += __shfl_xor(acc_s, d);
+    }
+    if ((tid & 63) == 0) {
+      red[tid >> 6] = acc_l1;
+      red[kBlock / 64 + (tid >> 6)] = acc_s;
+    }
+    __syncthreads();
+    if (tid == 0) {
+      p.partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+      p.partial[gridDim.x + blockIdx.x] = (red[4] + red[5]) + (red[6] + red[7]);
+    }
+  }
+}
+static_assert(kBlock == 256, "ssim_kernel's reduction assumes four waves");
+
+// loss = (1 - lambda) * sum|a - b| / n + lambda * (1 - sum S / M), the per-block sums added in a fixed order
+__global__ __launch_bounds__(kBlock) void ssim_final_kernel(int n_partial, const float* __restrict__ partial,
+                                                            float inv_n, float inv_m, float lambda,
+                                                            float* __restrict__ loss) {
+  __shared__ float lds[kBlock / 64];
+  float acc = 0.f;
+  for (int i = threadIdx.x; i < n_partial; i += kBlock) acc += partial[i];
+  const float l1 = block_sum(acc, lds);
+  __syncthreads();
+  acc = 0.f;
+  for (int i = threadIdx.x; i < n_partial; i += kBlock) acc += partial[n_partial + i];
+  const float s = block_sum(acc, lds);
+  if (threadIdx.x == 0) *loss = (1.f - lambda) * (l1 * inv_n) + lambda * (1.f - s * inv_m);
+}
+
+// The descriptor checked against n, the grid and the scales.  Host only: runs before any size query answers.
+struct SsimPlan {
+  SsimArgs args;
+  unsigned blocks;
+  float inv_n, inv_m, lambda;
+};
+
+int ssim_plan(size_t n, const mgs_image_loss* d, const char* what, SsimPlan* plan) {
+  MGS_REQUIRE(d->images >= 1 && d->height >= 1 && d->width >= 1, "%s: images %d, height %d, width %d must be positive",
+              what, d->images, d->height, d->width);
+  MGS_REQUIRE(d->channels >= 1 && d->channels <= 4, "%s: channels %d not in 1..4", what, d->channels);
+  MGS_REQUIRE(d->padding == MGS_SSIM_VALID || d->padding == MGS_SSIM_SAME,
+              "%s: padding %d is neither MGS_SSIM_VALID nor MGS_SSIM_SAME", what, d->padding);
+  MGS_REQUIRE(d->padding == MGS_SSIM_SAME || (d->height >= 2 * kR + 1 && d->width >= 2 * kR + 1),
+              "%s: padding MGS_SSIM_VALID needs height and width >= 11 (got %d x %d)", what, d->height, d->width);
+  MGS_REQUIRE(d->ssim_weight >= 0.f && d->ssim_weight <= 1.f, "%s: ssim_weight %g not in [0, 1]", what,
+              (double)d->ssim_weight);
+  const size_t elems = (size_t)d->images * d->height * d->width * d->channels;
+  MGS_REQUIRE(n == elems, "%s: n %zu != images x height x width x channels = %zu", what, n, elems);
+  const size_t tiles_x = div_up(d->width, kSsimTW), tiles_y = div_up(d->height, kSsimTH);
+  const size_t blocks = tiles_x * tiles_y * d->images;
+  MGS_REQUIRE(blocks <= (size_t)INT_MAX / 2, "%s: %zu tiles exceed the grid", what, blocks);
+  const bool valid = d->padding == MGS_SSIM_VALID;
+  const double positions = valid ? (double)(d->height - 2 * kR) * (d->width - 2 * kR) : (double)d->height * d->width;
+  const double m = positions * d->channels * d->images;
+  SsimArgs& a = plan->args;
+  a = SsimArgs{};
+  a.height = d->height;
+  a.width = d->width;
+  a.channels = d->channels;
+  a.tiles_x = (int)tiles_x;
+  a.tiles_per_image = (int)(tiles_x * tiles_y);
+  a.valid = valid ? 1 : 0;
+  a.l1_scale = (float)((1.0 - d->ssim_weight) / (double)n);
+  a.s_scale = (float)(d->ssim_weight / m);
+  double w[2 * kR + 1], sum = 0.0;
+  for (int i = 0; i <= 2 * kR; ++i) sum += (w[i] = std::exp(-(double)((i - kR) * (i - kR)) / (2.0 * 1.5 * 1.5)));
+  for (int i = 0; i <= 2 * kR; ++i) a.g[i] = (float)(w[i] / sum);
+  plan->blocks = (unsigned)blocks;
+  plan->inv_n = (float)(1.0 / (double)n);
+  plan->inv_m = (float)(1.0 / m);
+  plan->lambda = d->ssim_weight;
+  return MGS_OK;
+}
+
+size_t ssim_workspace_bytes(const SsimPlan& plan) { return 2 * (size_t)plan.blocks * sizeof(float); }
+
+
 unsigned grid_for(size_t n) {
   size_t blocks = (n / 4 + kBlock - 1) / kBlock;
   return (unsigned)(blocks < 1 ? 1 : (blocks > kMaxBlocks ? kMaxBlocks : blocks));
@@ -131,9 +440,44 @@ unsigned grid_for(size_t n) {
 
 using namespace mgs;
 
+namespace {
+
+// the L1 + D-SSIM forms of the three entry points below (image != NULL); the descriptor is already planned
+int ssim_fwd(const SsimPlan& plan, const float* a, const float* b, float* loss, float* v_a, void* workspace,
+             size_t* workspace_bytes, hipStream_t s, const char* what) {
+  const size_t need = ssim_workspace_bytes(plan);
+  if (!workspace) {
+    *workspace_bytes = need;
+    return MGS_OK;
+  }
+  if (*workspace_bytes < need)
+    return set_error(MGS_ERR_WORKSPACE_TOO_SMALL, "%s: workspace %zu < %zu bytes", what, *workspace_bytes, need);
+  MGS_REQUIRE(a && b && loss, "%s: null pointer", what);
+  SsimArgs args = plan.args;
+  args.a = a;
+  args.b = b;
+  args.partial = static_cast<float*>(workspace);
+  args.v_a = v_a;
+  if (v_a)
+    hipLaunchKernelGGL(ssim_kernel<true>, dim3(plan.blocks), dim3(kBlock), 0, s, args);
+  else
+    hipLaunchKernelGGL(ssim_kernel<false>, dim3(plan.blocks), dim3(kBlock), 0, s, args);
+  hipLaunchKernelGGL(ssim_final_kernel, dim3(1), dim3(kBlock), 0, s, (int)plan.blocks, args.partial, plan.inv_n,
+                     plan.inv_m, plan.lambda, loss);
+  return check_launch(what);
+}
+
+}  // namespace
+
 extern "C" int mgs_l1_loss_fwd(size_t n, const float* a, const float* b, float* loss,
-                               void* workspace, size_t* workspace_bytes, mgs_stream_t stream) {
+                               void* workspace, size_t* workspace_bytes, mgs_stream_t stream,
+                               const mgs_image_loss* image) {
   MGS_REQUIRE(workspace_bytes, "l1_loss_fwd: workspace_bytes is null");
+  if (image) {
+    SsimPlan plan;
+    if (int rc = ssim_plan(n, image, "l1_loss_fwd", &plan)) return rc;
+    return ssim_fwd(plan, a, b, loss, nullptr, workspace, workspace_bytes, (hipStream_t)stream, "l1_loss_fwd");
+  }
   const size_t need = kMaxBlocks * sizeof(float);
   if (!workspace) {
     *workspace_bytes = need;
@@ -154,7 +498,19 @@ extern "C" int mgs_l1_loss_fwd(size_t n, const float* a, const float* b, float* 
 }
 
 extern "C" int mgs_l1_loss_bwd(size_t n, const float* a, const float* b, const float* v_loss,
-                               float* v_a, mgs_stream_t stream) {
+                               float* v_a, mgs_stream_t stream, const mgs_image_loss* image) {
+  if (image) {
+    SsimPlan plan;
+    if (int rc = ssim_plan(n, image, "l1_loss_bwd", &plan)) return rc;
+    MGS_REQUIRE(a && b && v_a, "l1_loss_bwd: null pointer");
+    SsimArgs args = plan.args;
+    args.a = a;
+    args.b = b;
+    args.v_loss = v_loss;
+    args.v_a = v_a;
+    hipLaunchKernelGGL(ssim_kernel<true>, dim3(plan.blocks), dim3(kBlock), 0, (hipStream_t)stream, args);
+    return check_launch("l1_loss_bwd");
+  }
   MGS_REQUIRE(n > 0 && a && b && v_a, "l1_loss_bwd: empty input or null pointer");
   MGS_REQUIRE(((uintptr_t)a & 15) == 0 && ((uintptr_t)b & 15) == 0 && ((uintptr_t)v_a & 15) == 0,
               "l1_loss_bwd: buffers must be 16-byte aligned");
@@ -164,8 +520,15 @@ extern "C" int mgs_l1_loss_bwd(size_t n, const float* a, const float* b, const f
 }
 
 extern "C" int mgs_l1_loss_fwd_grad(size_t n, const float* a, const float* b, float* loss, float* v_a,
-                                    void* workspace, size_t* workspace_bytes, mgs_stream_t stream) {
+                                    void* workspace, size_t* workspace_bytes, mgs_stream_t stream,
+                                    const mgs_image_loss* image) {
   MGS_REQUIRE(workspace_bytes, "l1_loss_fwd_grad: workspace_bytes is null");
+  if (image) {
+    SsimPlan plan;
+    if (int rc = ssim_plan(n, image, "l1_loss_fwd_grad", &plan)) return rc;
+    MGS_REQUIRE(v_a || !workspace, "l1_loss_fwd_grad: v_a is null");
+    return ssim_fwd(plan, a, b, loss, v_a, workspace, workspace_bytes, (hipStream_t)stream, "l1_loss_fwd_grad");
+  }
   const size_t need = kMaxBlocks * sizeof(float);
   if (!workspace) {
     *workspace_bytes = need;

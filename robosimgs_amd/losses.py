@@ -2,8 +2,22 @@
 `(render - target).abs().mean()` with its gradient.  Where the render wants a gradient the forward is ONE streaming
 launch that also leaves sign(render - target) / n (mgs_l1_loss_fwd_grad) and the backward a launch that does nothing
 for the usual grad_output of 1 (mgs_l1_loss_bwd_scale); without a gradient, mgs_l1_loss_fwd alone.  Instead of six
-elementwise / reduction kernels of eager PyTorch; bit-reproducible."""
+elementwise / reduction kernels of eager PyTorch; bit-reproducible.
+
+`l1_ssim_loss(render, target)` is splatfacto's photometric loss (1 - lambda) L1 + lambda (1 - SSIM) and `ssim(render,
+target)` the SSIM term alone, both over images laid out [..., H, W, ch] as the renderer returns them.  The same pattern:
+one pass over render and target that leaves the loss's per-tile sums and the complete gradient for a cotangent of 1
+(loss.hip: ssim_kernel), one block that adds the sums up; the backward launches nothing for `unit_gradient(loss)`.
+
+SSIM is pytorch_msssim's `SSIM(data_range=1.0, size_average=True)`: an 11-tap Gaussian window of sigma 1.5, applied
+separably per channel, C1 = 0.01^2, C2 = 0.03^2, the mean over positions, channels and leading dimensions.
+padding="valid" (default; pytorch_msssim and gsplat's simple_trainer) takes S where the whole window lies inside the image,
+(H - 10) x (W - 10) positions, and raises ValueError below 11 pixels (pytorch_msssim instead skips filtering along such an
+axis, with a warning); padding="same" (the original 3DGS code's `ssim()`) zero-pads by 5 pixels and takes S at every pixel."""
 from __future__ import annotations
+
+import ctypes
+import math
 
 import torch
 
@@ -26,16 +40,23 @@ def unit_gradient(loss: torch.Tensor) -> torch.Tensor:
     return one
 
 
+def _is_unit(g: torch.Tensor) -> bool:
+    """g is unit_gradient's tensor: the cotangent is 1 (known without reading it)."""
+    one = _ONES.get((g.device.type, g.device.index))
+    return one is not None and g.data_ptr() == one.data_ptr()
+
+
 class _L1(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, b):
         n = a.numel()
         loss = torch.empty((), dtype=torch.float32, device=a.device)
         if not ctx.needs_input_grad[0]:
-            sized_call(_lib.lib().mgs_l1_loss_fwd, [n, ptr(a), ptr(b), ptr(loss)], a.device, cached=False)
+            sized_call(_lib.lib().mgs_l1_loss_fwd, [n, ptr(a), ptr(b), ptr(loss)], a.device, cached=False, trailing=(None,))
             return loss
         v_a = torch.empty_like(a)
-        sized_call(_lib.lib().mgs_l1_loss_fwd_grad, [n, ptr(a), ptr(b), ptr(loss), ptr(v_a)], a.device, cached=False)
+        sized_call(_lib.lib().mgs_l1_loss_fwd_grad, [n, ptr(a), ptr(b), ptr(loss), ptr(v_a)], a.device, cached=False,
+                   trailing=(None,))
         ctx.save_for_backward(a, b)
         ctx.v_a = v_a
         return loss
@@ -45,14 +66,13 @@ class _L1(torch.autograd.Function):
         g = _f32c(v_loss)
         v_a, ctx.v_a = ctx.v_a, None
         if v_a is not None:
-            one = _ONES.get((g.device.type, g.device.index))
-            if one is None or g.data_ptr() != one.data_ptr():      # (unit_gradient's tensor: the cotangent is 1, nothing to scale)
+            if not _is_unit(g):          # (unit_gradient's tensor: the cotangent is 1, nothing to scale)
                 check(_lib.lib().mgs_l1_loss_bwd_scale(v_a.numel(), ptr(g), ptr(v_a), stream_handle()), "mgs_l1_loss_bwd_scale")
             return v_a, None
         # a second backward through a retained graph: autograd owns the first buffer by now
         a, b = ctx.saved_tensors
         v_a = torch.empty_like(a)
-        check(_lib.lib().mgs_l1_loss_bwd(a.numel(), ptr(a), ptr(b), ptr(g), ptr(v_a), stream_handle()), "mgs_l1_loss_bwd")
+        check(_lib.lib().mgs_l1_loss_bwd(a.numel(), ptr(a), ptr(b), ptr(g), ptr(v_a), stream_handle(), None), "mgs_l1_loss_bwd")
         return v_a, None
 
 
@@ -67,3 +87,76 @@ def l1_loss(render: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
     if b.data_ptr() % 16:
         b = b.clone()
     return _L1.apply(a, b)
+
+
+class _L1SSIM(torch.autograd.Function):
+    """_L1 under an mgs_image_loss descriptor: the forward leaves the gradient for a cotangent of 1 (mgs_l1_loss_fwd_grad),
+    any other cotangent scales it once, a second backward recomputes it (mgs_l1_loss_bwd)."""
+
+    @staticmethod
+    def forward(ctx, a, b, desc):
+        n = a.numel()
+        loss = torch.empty((), dtype=torch.float32, device=a.device)
+        if not ctx.needs_input_grad[0]:
+            sized_call(_lib.lib().mgs_l1_loss_fwd, [n, ptr(a), ptr(b), ptr(loss)], a.device, cached=False,
+                       trailing=(ctypes.byref(desc),))
+            return loss
+        v_a = torch.empty_like(a)
+        sized_call(_lib.lib().mgs_l1_loss_fwd_grad, [n, ptr(a), ptr(b), ptr(loss), ptr(v_a)], a.device, cached=False,
+                   trailing=(ctypes.byref(desc),))
+        ctx.save_for_backward(a, b)
+        ctx.v_a, ctx.desc = v_a, desc
+        return loss
+
+    @staticmethod
+    def backward(ctx, v_loss):
+        g = _f32c(v_loss)
+        v_a, ctx.v_a = ctx.v_a, None
+        if v_a is not None:
+            if not _is_unit(g):
+                v_a.mul_(g)
+            return v_a, None, None
+        a, b = ctx.saved_tensors
+        v_a = torch.empty_like(a)
+        check(_lib.lib().mgs_l1_loss_bwd(a.numel(), ptr(a), ptr(b), ptr(g), ptr(v_a), stream_handle(), ctypes.byref(ctx.desc)),
+              "mgs_l1_loss_bwd")
+        return v_a, None, None
+
+
+_PADDING = {"valid": _lib.MGS_SSIM_VALID, "same": _lib.MGS_SSIM_SAME}
+
+
+def _image_loss(shape, ssim_lambda: float, padding: str) -> "_lib.ImageLoss":
+    if padding not in _PADDING:
+        raise ValueError(f"padding must be 'valid' or 'same', got {padding!r}")
+    if len(shape) < 3:
+        raise ValueError(f"expected images [..., H, W, ch], got shape {tuple(shape)}")
+    h, w, ch = (int(v) for v in shape[-3:])
+    images = math.prod(int(v) for v in shape[:-3])
+    if not 1 <= ch <= 4:
+        raise ValueError(f"ch = {ch}: 1 to 4 channels (the last dimension)")
+    if images < 1 or h < 1 or w < 1:
+        raise ValueError(f"empty images {tuple(shape)}")
+    if padding == "valid" and (h < 11 or w < 11):
+        raise ValueError(f'padding="valid" needs H and W >= 11 (the window), got {h} x {w}; padding="same" takes any size')
+    if not 0.0 <= float(ssim_lambda) <= 1.0:
+        raise ValueError(f"ssim_lambda = {ssim_lambda} not in [0, 1]")
+    return _lib.ImageLoss(images, h, w, ch, float(ssim_lambda), _PADDING[padding])
+
+
+def l1_ssim_loss(render: torch.Tensor, target: torch.Tensor, ssim_lambda: float = 0.2, padding: str = "valid") -> torch.Tensor:
+    """(1 - ssim_lambda) * mean|render - target| + ssim_lambda * (1 - ssim(render, target, padding)) (scalar tensor), the
+    loss of splatfacto and gsplat's simple_trainer; render, target [..., H, W, ch] (ch 1..4).  The L1 term is the mean over
+    every element, as l1_loss; SSIM as `ssim`.  Gradient flows to `render` only."""
+    if render.shape != target.shape:
+        raise ValueError(f"shape mismatch {tuple(render.shape)} vs {tuple(target.shape)}")
+    desc = _image_loss(render.shape, ssim_lambda, padding)
+    require_device(render, target)
+    return _L1SSIM.apply(_f32c(render), _f32c(target.detach()), desc)
+
+
+def ssim(render: torch.Tensor, target: torch.Tensor, padding: str = "valid") -> torch.Tensor:
+    """Mean SSIM of render against target (scalar tensor), images [..., H, W, ch] (ch 1..4): pytorch_msssim's
+    SSIM(data_range=1.0, size_average=True) for padding="valid", the original 3DGS `ssim()` for "same" (module docstring).
+    Computed as 1 - l1_ssim_loss(render, target, ssim_lambda=1); gradient flows to `render` only."""
+    return 1.0 - l1_ssim_loss(render, target, 1.0, padding)
