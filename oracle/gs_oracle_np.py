@@ -18,10 +18,20 @@ module.  The product package (robosimgs_amd/) never does.
 
 All functions take a `dtype` (np.float64 for the reference answer, np.float32 to mimic
 device rounding op-by-op without FMA contraction).
+
+`project` and `render` take a camera_model (include/mgs.h MGS_CAMERA_*).  Pinhole is A.2 step 3; ortho and fisheye
+change the mean and the Jacobian J of that step only (oracle/camera_models.py):
+  ortho    mean (fx x + cx, fy y + cy), J = [[fx, 0, 0], [0, fy, 0]]
+  fisheye  rho = |(x, y)|, theta = atan2(rho, z), s = theta / rho, mean (fx s x + cx, fy s y + cy),
+           J = [[fx (s + x^2 a), fx x y a, -fx x / r2], [fy x y a, fy (s + y^2 a), -fy y / r2]],
+           r2 = rho^2 + z^2, a = (z / r2 - s) / rho^2
+with no frustum clamp; depth is z and near / far cull on it as for pinhole.
 """
 from __future__ import annotations
 
 import numpy as np
+
+from .camera_models import CAMERA_MODELS, mean_and_J
 
 ALPHA_MIN = 1.0 / 255.0
 ALPHA_MAX = 0.999
@@ -89,8 +99,8 @@ EXTENT_MAX = 3.33     # gsplat >= 1.5: the per-axis extent is ca
 
 def project(means, quats, scales, viewmat, K, width, height, eps2d=0.3,
             near_plane=0.01, far_plane=1e10, radius_clip=0.0, dtype=np.float64,
-            radius_rule="classic", opacities=None, antialiased=False):
-    """A.2 steps 1-5 for one camera.
+            radius_rule="classic", opacities=None, antialiased=False, camera_model="pinhole"):
+    """A.2 steps 1-5 for one camera; camera_model (one of CAMERA_MODELS) selects the mean and the Jacobian of step 3.
 
     Returns dict(radii[N] int32, means2d[N,2], depths[N], conics[N,3],
     compensations[N]); culled Gaussians have radii 0 and zeros elsewhere.
@@ -100,6 +110,8 @@ def project(means, quats, scales, viewmat, K, width, height, eps2d=0.3,
     e = min(3.33, sqrt(2 ln(255 o))), o = opacity (x compensation when antialiased; e = 3.33 without opacities);
     culled: o < 1/255, both extents <= radius_clip, the box mean +- extents wholly off screen.
     """
+    if camera_model not in CAMERA_MODELS:
+        raise ValueError(camera_model)
     means = np.asarray(means, dtype=dtype)
     viewmat = np.asarray(viewmat, dtype=dtype)
     K = np.asarray(K, dtype=dtype)
@@ -116,21 +128,26 @@ def project(means, quats, scales, viewmat, K, width, height, eps2d=0.3,
     cov = covar_world(quats, scales, dtype)
     cov_c = Rcw[None] @ cov @ Rcw.T[None]
 
-    tanx, tany = dtype(0.5) * W / fx, dtype(0.5) * H / fy        # step 3
-    k03 = dtype(0.3)
-    lim_xp, lim_xn = (W - cx) / fx + k03 * tanx, cx / fx + k03 * tanx
-    lim_yp, lim_yn = (H - cy) / fy + k03 * tany, cy / fy + k03 * tany
-    rz = dtype(1.0) / zs
-    rz2 = rz * rz
-    tx = zs * np.minimum(lim_xp, np.maximum(-lim_xn, x * rz))
-    ty = zs * np.minimum(lim_yp, np.maximum(-lim_yn, y * rz))
-    J = np.zeros((N, 2, 3), dtype=dtype)
-    J[:, 0, 0] = fx * rz
-    J[:, 0, 2] = -fx * tx * rz2
-    J[:, 1, 1] = fy * rz
-    J[:, 1, 2] = -fy * ty * rz2
+    if camera_model == "pinhole":                                # step 3: the only one that knows the model
+        tanx, tany = dtype(0.5) * W / fx, dtype(0.5) * H / fy
+        k03 = dtype(0.3)
+        lim_xp, lim_xn = (W - cx) / fx + k03 * tanx, cx / fx + k03 * tanx
+        lim_yp, lim_yn = (H - cy) / fy + k03 * tany, cy / fy + k03 * tany
+        rz = dtype(1.0) / zs
+        rz2 = rz * rz
+        tx = zs * np.minimum(lim_xp, np.maximum(-lim_xn, x * rz))
+        ty = zs * np.minimum(lim_yp, np.maximum(-lim_yn, y * rz))
+        J = np.zeros((N, 2, 3), dtype=dtype)
+        J[:, 0, 0] = fx * rz
+        J[:, 0, 2] = -fx * tx * rz2
+        J[:, 1, 1] = fy * rz
+        J[:, 1, 2] = -fy * ty * rz2
+        mu = np.stack([fx * x * rz + cx, fy * y * rz + cy], axis=-1)
+    else:
+        (mx, my), Jt = mean_and_J(x, y, zs, fx, fy, cx, cy, camera_model, np)
+        J = np.stack(Jt, axis=-1).reshape(N, 2, 3)
+        mu = np.stack([mx, my], axis=-1)
     cov2 = J @ cov_c @ np.swapaxes(J, 1, 2)
-    mu = np.stack([fx * x * rz + cx, fy * y * rz + cy], axis=-1)
 
     a, b, c = cov2[:, 0, 0], cov2[:, 0, 1], cov2[:, 1, 1]       # step 4
     det0 = a * c - b * b
@@ -718,8 +735,9 @@ def gaussian_edge_mask(p, opacities, width, height, tile_size=16, eps_radius=3e-
 def render(means, quats, scales, opacities, sh_or_colors, viewmat, K, width, height,
            sh_degree=None, tile_size=16, render_mode="RGB", eps2d=0.3,
            near_plane=0.01, far_plane=1e10, radius_clip=0.0, background=None,
-           rasterize_mode="classic", dtype=np.float64, margins=False, flip_eps=None, radius_rule="classic"):
-    """Full single-camera frame following SURVEY.md A.1/A.2.  Inputs are post-activation
+           rasterize_mode="classic", dtype=np.float64, margins=False, flip_eps=None, radius_rule="classic",
+           camera_model="pinhole"):
+    """Full single-camera frame following SURVEY.md A.1/A.2 under `camera_model` (see `project`).  Inputs are post-activation
     (scales = exp(log_s), opacities = sigmoid(logit)).  Returns (colors[H,W,D],
     alpha[H,W,1], meta).  margins=True adds meta["margins"] (see `rasterize`) and
     meta["edge_mask"] / meta["n_edge_gaussians"] (see `gaussian_edge_mask`); flip_eps (an EPS_* dict) also
@@ -728,7 +746,7 @@ def render(means, quats, scales, opacities, sh_or_colors, viewmat, K, width, hei
     tile_h = -(-height // tile_size)
     p = project(means, quats, scales, viewmat, K, width, height, eps2d, near_plane,
                 far_plane, radius_clip, dtype, radius_rule=radius_rule, opacities=opacities,
-                antialiased=rasterize_mode == "antialiased")
+                antialiased=rasterize_mode == "antialiased", camera_model=camera_model)
     opac = np.asarray(opacities, dtype=dtype)
     if rasterize_mode == "antialiased":
         opac = opac * p["compensations"]

@@ -15,6 +15,7 @@ from __future__ import annotations
 import torch
 
 from . import gs_oracle_np as O
+from .camera_models import CAMERA_MODELS, mean_and_J
 
 DT = torch.float64
 
@@ -30,10 +31,13 @@ def quat_to_rotmat(q):
 
 
 def project(means, quats, scales, viewmat, K, width, height, eps2d=0.3, near_plane=0.01,
-            far_plane=1e10, radius_clip=0.0, radius_rule="classic", opacities=None, antialiased=False):
+            far_plane=1e10, radius_clip=0.0, radius_rule="classic", opacities=None, antialiased=False,
+            camera_model="pinhole"):
     """A.2 steps 1-5; differentiable in means/quats/scales/viewmat.  Returns dict with
     radii (int, no grad), means2d, depths, conics, compensations (zeros where culled).
-    radius_rule / opacities / antialiased: as gs_oracle_np.project (radii [N,2] under "opacity_aware")."""
+    radius_rule / opacities / antialiased / camera_model: as gs_oracle_np.project (radii [N,2] under "opacity_aware")."""
+    if camera_model not in CAMERA_MODELS:
+        raise ValueError(camera_model)
     Rcw, tcw = viewmat[:3, :3], viewmat[:3, 3]
     fx, fy, cx, cy = K[0, 0], K[1, 1], K[0, 2], K[1, 2]
     pc = means @ Rcw.T + tcw
@@ -43,17 +47,23 @@ def project(means, quats, scales, viewmat, K, width, height, eps2d=0.3, near_pla
     M = quat_to_rotmat(quats) * scales[:, None, :]
     cov = M @ M.transpose(1, 2)
     cov_c = Rcw @ cov @ Rcw.T
-    tanx, tany = 0.5 * width / fx, 0.5 * height / fy
-    lim_xp, lim_xn = (width - cx) / fx + 0.3 * tanx, cx / fx + 0.3 * tanx
-    lim_yp, lim_yn = (height - cy) / fy + 0.3 * tany, cy / fy + 0.3 * tany
-    rz = 1.0 / zs
-    tx = zs * torch.minimum(lim_xp, torch.maximum(-lim_xn, x * rz))
-    ty = zs * torch.minimum(lim_yp, torch.maximum(-lim_yn, y * rz))
-    zero = torch.zeros_like(rz)
-    J = torch.stack([fx * rz, zero, -fx * tx * rz * rz,
-                     zero, fy * rz, -fy * ty * rz * rz], dim=-1).reshape(-1, 2, 3)
+    if camera_model == "pinhole":           # step 3: the only one that knows the model
+        tanx, tany = 0.5 * width / fx, 0.5 * height / fy
+        lim_xp, lim_xn = (width - cx) / fx + 0.3 * tanx, cx / fx + 0.3 * tanx
+        lim_yp, lim_yn = (height - cy) / fy + 0.3 * tany, cy / fy + 0.3 * tany
+        rz = 1.0 / zs
+        tx = zs * torch.minimum(lim_xp, torch.maximum(-lim_xn, x * rz))
+        ty = zs * torch.minimum(lim_yp, torch.maximum(-lim_yn, y * rz))
+        zero = torch.zeros_like(rz)
+        # (J before the mean: autograd sums the contributions to x, y, 1/z in an order set by the order their consumers
+        #  were created in, and the last bits of the gradients of means and viewmat follow it)
+        Jt = (fx * rz, zero, -fx * tx * rz * rz, zero, fy * rz, -fy * ty * rz * rz)
+        mu = (fx * x * rz + cx, fy * y * rz + cy)
+    else:
+        mu, Jt = mean_and_J(x, y, zs, fx, fy, cx, cy, camera_model, torch)
+    J = torch.stack(Jt, dim=-1).reshape(-1, 2, 3)
     cov2 = J @ cov_c @ J.transpose(1, 2)
-    mu = torch.stack([fx * x * rz + cx, fy * y * rz + cy], dim=-1)
+    mu = torch.stack(mu, dim=-1)
     a, b, c = cov2[:, 0, 0], cov2[:, 0, 1], cov2[:, 1, 1]
     det0 = a * c - b * b
     a = a + eps2d
@@ -172,11 +182,13 @@ def rasterize(means2d, conics, colors, opacities, flatten_ids, offsets, width, h
 
 def render(means, quats, scales, opacities, sh_or_colors, viewmat, K, width, height,
            sh_degree=None, tile_size=16, render_mode="RGB", eps2d=0.3, near_plane=0.01,
-           far_plane=1e10, radius_clip=0.0, background=None, rasterize_mode="classic", radius_rule="classic"):
+           far_plane=1e10, radius_clip=0.0, background=None, rasterize_mode="classic", radius_rule="classic",
+           camera_model="pinhole"):
     """Whole frame, differentiable w.r.t. means/quats/scales/opacities/colours/viewmat.
     The (integer) tile lists come from the NumPy oracle evaluated at the current values."""
     p = project(means, quats, scales, viewmat, K, width, height, eps2d, near_plane, far_plane,
-                radius_clip, radius_rule=radius_rule, opacities=opacities, antialiased=rasterize_mode == "antialiased")
+                radius_clip, radius_rule=radius_rule, opacities=opacities, antialiased=rasterize_mode == "antialiased",
+                camera_model=camera_model)
     opac = opacities * p["compensations"] if rasterize_mode == "antialiased" else opacities
     vis = p["radii"] > 0 if p["radii"].dim() == 1 else p["radii"][:, 0] > 0
     if sh_degree is None:

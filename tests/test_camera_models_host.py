@@ -7,7 +7,7 @@ import math
 import numpy as np
 import pytest
 
-import camera_models_ref as CM
+from oracle import gs_oracle_np as O
 from robosimgs_amd import Camera
 from robosimgs_amd.camera import cameras_from_transforms_json
 
@@ -48,8 +48,8 @@ def test_project_follows_the_model(model):
         want = np.stack([c.fx * s * x + c.cx, c.fy * s * y + c.cy], -1)
     np.testing.assert_allclose(uv, want, rtol=1e-12, atol=1e-9)
     # the renderer's projected means are the same map
-    ref = CM.project(pts, np.tile([1.0, 0, 0, 0], (len(pts), 1)), np.full((len(pts), 3), 1e-3), vm, c.K, c.width,
-                     c.height, camera_model=model)
+    ref = O.project(pts, np.tile([1.0, 0, 0, 0], (len(pts), 1)), np.full((len(pts), 3), 1e-3), vm, c.K, c.width,
+                    c.height, camera_model=model)
     np.testing.assert_allclose(ref["mu"], want, rtol=1e-12, atol=1e-9)
     uv2, d = c.project(pts, return_dists=True)
     np.testing.assert_allclose(d, np.linalg.norm(pc, axis=-1))

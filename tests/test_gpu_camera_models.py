@@ -1,16 +1,16 @@
 """Camera models as a policy of the projection (include/mgs.h MGS_CAMERA_*): camera_model="ortho" / "fisheye" through
 every entry point that projects (the operator, the per-camera SH path, the one-call inference path, FrameRenderer, the
-batched training path, Trainer), against the fp64 restatement of tests/camera_models_ref.py composed with the oracle's
-stages.  "pinhole" (the default) is what every other test file exercises; here it is checked to be the default bit for
-bit."""
+batched training path, Trainer), against the fp64 oracle under the same model (oracle/gs_oracle_np.py and
+oracle/gs_oracle_torch.py, camera_model=).  "pinhole" (the default) is what every other test file exercises; here it is
+checked to be the default bit for bit."""
 import math
 
 import numpy as np
 import pytest
 import torch
 
-import camera_models_ref as CM
 from oracle import gs_oracle_np as O
+from oracle import gs_oracle_torch as OT
 from robosimgs_amd import camera_ring, synthetic_scene
 
 pytestmark = pytest.mark.gpu
@@ -52,8 +52,8 @@ def test_projection_operator_matches_fp64(model, rule, aa):
     g, vm = _scene(n, 0.05, 0, w, h)
     K = _K(model, w, h)
     op = np.asarray(g.opacities, dtype=np.float32)
-    ref = CM.project(_f32(g.means), _f32(g.quats), _f32(g.scales), _f32(vm), _f32(K), w, h, radius_rule=rule,
-                     opacities=op.astype(np.float64) if rule != "classic" else None, antialiased=aa, camera_model=model)
+    ref = O.project(_f32(g.means), _f32(g.quats), _f32(g.scales), _f32(vm), _f32(K), w, h, radius_rule=rule,
+                    opacities=op.astype(np.float64) if rule != "classic" else None, antialiased=aa, camera_model=model)
     radii, means2d, depths, conics, comps = ops.fully_fused_projection(
         _t(g.means), None, _t(g.quats), _t(g.scales), _t(vm)[None], _t(K)[None], w, h, calc_compensations=aa,
         opacities=_t(op) if rule != "classic" else None, radius_rule=rule, camera_model=model)
@@ -82,9 +82,9 @@ def _check_path(model, g, vm, K, w, h, deg, mode, aa, what, **kw):
     colors, alphas, meta = rasterization(t["means"], t["quats"], t["scales"], t["opacities"], t["colors"], _t(vm)[None],
                                          _t(K)[None], w, h, sh_degree=deg, render_mode=mode, rasterize_mode=rm,
                                          tile_bounds="classic", camera_model=model, **kw)
-    ref, ref_alpha, rmeta = CM.render_model(g.means, g.quats, g.scales, g.opacities, g.sh_coeffs[:, :(deg + 1) ** 2],
-                                            _f32(vm), _f32(K), w, h, sh_degree=deg, render_mode=mode, rasterize_mode=rm,
-                                            margins=True, flip_eps=O.EPS_PATH, camera_model=model, **kw)
+    ref, ref_alpha, rmeta = O.render(g.means, g.quats, g.scales, g.opacities, g.sh_coeffs[:, :(deg + 1) ** 2],
+                                     _f32(vm), _f32(K), w, h, sh_degree=deg, render_mode=mode, rasterize_mode=rm,
+                                     margins=True, flip_eps=O.EPS_PATH, camera_model=model, **kw)
     assert abs(int(meta["radii"][0].gt(0).sum()) - rmeta["n_vis"]) <= 1
     assert torch.isfinite(colors).all() and torch.isfinite(alphas).all()
     st = O.check_frame(colors[0].cpu().numpy(), alphas[0].cpu().numpy(), ref, ref_alpha, rmeta["margins"], O.EPS_PATH,
@@ -174,9 +174,9 @@ def _ref_grads(model, g, vm, K, w, h, deg, mode, aa, wr, wa):
     r = {k: _d(v, True) for k, v in (("means", g.means), ("quats", g.quats), ("scales", g.scales),
                                       ("opacities", g.opacities), ("colors", g.sh_coeffs[:, :(deg + 1) ** 2]))}
     vmd = _d(_f32(vm), True)
-    img, al, p = CM.render_model_torch(r["means"], r["quats"], r["scales"], r["opacities"], r["colors"], vmd,
-                                       _d(_f32(K)), w, h, sh_degree=deg, render_mode=mode,
-                                       rasterize_mode="antialiased" if aa else "classic", camera_model=model)
+    img, al, p = OT.render(r["means"], r["quats"], r["scales"], r["opacities"], r["colors"], vmd,
+                           _d(_f32(K)), w, h, sh_degree=deg, render_mode=mode,
+                           rasterize_mode="antialiased" if aa else "classic", camera_model=model)
     ((img * _d(wr)).sum() + (al[..., 0] * _d(wa)).sum()).backward()
     return {k: v.grad.numpy() for k, v in r.items()}, vmd.grad.numpy(), p
 

@@ -1,7 +1,7 @@
 """CPU test of the orthographic and fisheye camera models in the per-Gaussian DEVICE math (robosimgs_amd/csrc/mgs_math.h,
-project_gaussian<CAM> / project_gaussian_vjp<CAM>, compiled with g++) against the fp64 restatement of
-tests/camera_models_ref.py: forward values, backward against autograd, the fisheye's optical axis and wide angles, the
-pinhole default call, and the -DMGS_PROJ_FACTORED=1 build."""
+project_gaussian<CAM> / project_gaussian_vjp<CAM>, compiled with g++) against the fp64 oracle under the same model
+(oracle/gs_oracle_np.py and oracle/gs_oracle_torch.py, camera_model=): forward values, backward against autograd, the
+fisheye's optical axis and wide angles, the pinhole default call, and the -DMGS_PROJ_FACTORED=1 build."""
 import ctypes
 import math
 import os
@@ -11,7 +11,8 @@ import numpy as np
 import pytest
 import torch
 
-import camera_models_ref as CM
+from oracle import gs_oracle_np as O
+from oracle import gs_oracle_torch as OT
 from robosimgs_amd import camera_ring, synthetic_scene
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -106,15 +107,15 @@ def test_forward_matches_fp64_reference(hh, model, rule, aa):
     op = _f(g.opacities) if rule == "opacity_aware" else None
     got = project(hh, model, g.means, g.quats, g.scales, vm, K, w, h, rule, op, aa)
     f64 = lambda a: _f(a).astype(np.float64)          # what the device is given
-    ref = CM.project(f64(g.means), f64(g.quats), f64(g.scales), f64(vm), f64(K), w, h, radius_rule=rule,
-                     opacities=None if op is None else op.astype(np.float64), antialiased=aa, camera_model=model)
+    ref = O.project(f64(g.means), f64(g.quats), f64(g.scales), f64(vm), f64(K), w, h, radius_rule=rule,
+                    opacities=None if op is None else op.astype(np.float64), antialiased=aa, camera_model=model)
     _check_forward(got, ref, rule, min_vis=1000)
 
 
 def _autograd(model, means, quats, scales, vm, K, w, h, vis, cot):
     t = lambda a: torch.tensor(_f(a).astype(np.float64), requires_grad=True)
     tm, tq, ts, tv = t(means), t(quats), t(scales), t(vm)
-    p = CM.project_torch(tm, tq, ts, tv, torch.tensor(_f(K).astype(np.float64)), w, h, camera_model=model)
+    p = OT.project(tm, tq, ts, tv, torch.tensor(_f(K).astype(np.float64)), w, h, camera_model=model)
     mask = torch.tensor(vis.astype(np.float64))
     v_m2d, v_dep, v_con, v_comp = (torch.tensor(c.astype(np.float64)) for c in cot)
     loss = (((p["means2d"] * v_m2d).sum(-1) + p["depths"] * v_dep + (p["conics"] * v_con).sum(-1)
@@ -140,8 +141,8 @@ def test_backward_matches_fp64_autograd(hh, model, aa):
     rng = np.random.default_rng(1)
     cot = [rng.normal(size=(n, 2)), rng.normal(size=n), rng.normal(size=(n, 3)),
            rng.normal(size=n) if aa else np.zeros(n)]
-    ref_vis = CM.project(_f(g.means).astype(np.float64), _f(g.quats).astype(np.float64), _f(g.scales).astype(np.float64),
-                         _f(vm).astype(np.float64), _f(K).astype(np.float64), w, h, camera_model=model)["radii"] > 0
+    ref_vis = O.project(_f(g.means).astype(np.float64), _f(g.quats).astype(np.float64), _f(g.scales).astype(np.float64),
+                        _f(vm).astype(np.float64), _f(K).astype(np.float64), w, h, camera_model=model)["radii"] > 0
     vis = ref_vis & (fw["radii"] > 0)
     assert vis.sum() > 500
     fw["radii"] = np.where(vis, fw["radii"], 0).astype(np.int32)
@@ -184,8 +185,8 @@ def test_fisheye_from_the_axis_to_85_degrees(hh):
     assert (fw["radii"] > 0).all(), "every test point is in front of the lens and on the image"
     for k, v in fw.items():
         assert np.isfinite(v).all(), k
-    ref = CM.project(_f(means).astype(np.float64), _f(quats).astype(np.float64), _f(scales).astype(np.float64), vm,
-                     _f(K).astype(np.float64), w, h, camera_model="fisheye")
+    ref = O.project(_f(means).astype(np.float64), _f(quats).astype(np.float64), _f(scales).astype(np.float64), vm,
+                    _f(K).astype(np.float64), w, h, camera_model="fisheye")
     _check_forward(fw, ref, "classic", min_vis=n)
     rng = np.random.default_rng(2)
     cot = [rng.normal(size=(n, 2)), rng.normal(size=n), rng.normal(size=(n, 3)), rng.normal(size=n)]
@@ -257,6 +258,6 @@ def test_factored_build_matches_reference(hh_factored, model):
     for rule in ("classic", "opacity_aware"):
         op = _f(g.opacities) if rule == "opacity_aware" else None
         got = project(hh_factored, model, g.means, g.quats, g.scales, vm, K, w, h, rule, op, True)
-        ref = CM.project(f64(g.means), f64(g.quats), f64(g.scales), f64(vm), f64(K), w, h, radius_rule=rule,
-                         opacities=None if op is None else op.astype(np.float64), antialiased=True, camera_model=model)
+        ref = O.project(f64(g.means), f64(g.quats), f64(g.scales), f64(vm), f64(K), w, h, radius_rule=rule,
+                        opacities=None if op is None else op.astype(np.float64), antialiased=True, camera_model=model)
         _check_forward(got, ref, rule, min_vis=1000)

@@ -54,6 +54,44 @@ def test_single_isotropic_gaussian_closed_form():
     assert abs(alpha[c[0], c[1], 0] - o) < 0.02          # centre pixel ~ opacity
 
 
+def test_single_isotropic_gaussian_closed_form_ortho():
+    """The case above under camera_model="ortho": J = [[fx,0,0],[0,fy,0]] is constant, so on an isotropic Sigma = s^2 I the
+    conic is inv(diag(fx^2 s^2, fy^2 s^2) + eps2d I) whatever the depth."""
+    W = H = 64
+    fx, fy, z, s, o = 25.0, 30.0, 4.0, 0.2, 0.7
+    K = np.array([[fx, 0, W / 2], [0, fy, H / 2], [0, 0, 1.0]])
+    means = np.array([[0.013, -0.021, z]])
+    img, alpha, meta = O.render(means, np.array([[1.0, 0, 0, 0]]), np.full((1, 3), s), np.array([o]),
+                                np.array([[0.3, 0.6, 0.9]]), EYE_VIEW, K, W, H, sh_degree=None, camera_model="ortho")
+    mu = np.array([fx * means[0, 0] + W / 2, fy * means[0, 1] + H / 2])
+    np.testing.assert_allclose(meta["means2d"][0], mu, rtol=1e-12)
+    assert meta["depths"][0] == z
+    cov2 = np.diag([fx * fx * s * s, fy * fy * s * s]) + 0.3 * np.eye(2)
+    conic = np.linalg.inv(cov2)
+    np.testing.assert_allclose(meta["conics"][0], [conic[0, 0], conic[0, 1], conic[1, 1]], rtol=1e-10)
+    lam = np.linalg.eigvalsh(cov2).max()
+    assert meta["radii"][0] == math.ceil(3 * math.sqrt(lam))
+    py, px = np.meshgrid(np.arange(H) + 0.5, np.arange(W) + 0.5, indexing="ij")
+    d = np.stack([mu[0] - px, mu[1] - py], -1)
+    sigma = 0.5 * np.einsum("hwi,ij,hwj->hw", d, conic, d)
+    a = np.minimum(0.999, o * np.exp(-sigma))
+    a = np.where(a >= 1 / 255, a, 0.0)
+    # pixels outside the Gaussian's tile rectangle receive nothing
+    r = meta["radii"][0]
+    x0, x1 = math.floor((mu[0] - r) / 16) * 16, math.ceil((mu[0] + r) / 16) * 16
+    y0, y1 = math.floor((mu[1] - r) / 16) * 16, math.ceil((mu[1] + r) / 16) * 16
+    box = (px > x0) & (px < x1) & (py > y0) & (py < y1)
+    a = np.where(box, a, 0.0)
+    np.testing.assert_allclose(alpha[..., 0], a, atol=1e-13)
+    np.testing.assert_allclose(img, a[..., None] * np.array([0.3, 0.6, 0.9]), atol=1e-13)
+    c = int(mu[1]), int(mu[0])
+    assert abs(alpha[c[0], c[1], 0] - o) < 0.02          # centre pixel ~ opacity
+    # the depth does not enter: the same Gaussian farther away is the same frame
+    img2, alpha2, _ = O.render(means + [0, 0, 5.0], np.array([[1.0, 0, 0, 0]]), np.full((1, 3), s), np.array([o]),
+                               np.array([[0.3, 0.6, 0.9]]), EYE_VIEW, K, W, H, sh_degree=None, camera_model="ortho")
+    assert np.array_equal(img2, img) and np.array_equal(alpha2, alpha)
+
+
 @pytest.mark.parametrize("o", [0.9, 0.05, 0.0041, 0.0039])
 def test_opacity_aware_radius_rule_closed_form(o):
     """SURVEY.md A.4 (gsplat >= 1.5): per-axis extents ceil(e sqrt(Sigma_ii)), e = min(3.33, sqrt(2 ln(255 o))) -- on an
@@ -156,6 +194,70 @@ def test_projection_identities():
     assert (vis != (q["radii"] > 0)).sum() <= 1
     np.testing.assert_allclose(q["means2d"][both], p["means2d"][both], rtol=3e-5, atol=3e-3)
     np.testing.assert_allclose(q["conics"][both], p["conics"][both], rtol=5e-4, atol=1e-6)
+
+
+def _fisheye_axis_scene():
+    """Camera-space points of an identity camera for the fisheye's two seams: exactly on the optical axis, rho / z from
+    1e-7 up to either side of the series threshold (rho^2 / z^2 = 1e-3, rho / z = 0.0316...), and directions 86 to 89
+    degrees off axis (the wide-angle end; z stays in front of the near plane)."""
+    pts = []
+    for z in (0.5, 2.0, 7.0):
+        pts.append((0.0, 0.0, z))
+        for r in (1e-7, 1e-6, 1e-3, 0.031, 0.0316, 0.0317, 0.033):
+            for phi in (0.3, 2.0, 4.4):
+                pts.append((r * z * math.cos(phi), r * z * math.sin(phi), z))
+    for deg in (30, 60, 86, 88, 89):
+        for phi in np.linspace(0.2, 0.2 + 2 * math.pi, 5, endpoint=False):
+            th = math.radians(deg)
+            pts.append((3.0 * math.sin(th) * math.cos(phi), 3.0 * math.sin(th) * math.sin(phi), 3.0 * math.cos(th)))
+    means = np.array(pts)
+    rng = np.random.default_rng(7)
+    quats = rng.normal(size=(len(means), 4))
+    scales = np.exp(rng.uniform(math.log(0.02), math.log(0.1), size=(len(means), 3)))
+    return means, quats, scales
+
+
+@pytest.mark.parametrize("model", ["ortho", "fisheye"])
+def test_projection_identities_ortho_fisheye(model):
+    """test_projection_identities' conic identity under the other two camera models, through a mean map written here
+    (closed form only: no series) and its finite-difference Jacobian.  Neither model clamps, so no point is skipped."""
+    w, h = 160, 120
+    g = synthetic_scene(3000, math.log(0.1), 0, 3)
+    cam = camera_ring(1, w, h, thetas=[1.1])[0]
+    f = {"ortho": w / 5.0, "fisheye": w / math.pi}[model]           # most of the scene on screen
+    cases = [(g.means, g.quats, g.scales, cam.viewmat(), np.array([[f, 0, cam.cx], [0, 1.05 * f, cam.cy], [0, 0, 1.0]]),
+              w, h, 40)]
+    if model == "fisheye":
+        means, quats, scales = _fisheye_axis_scene()
+        t = (means[:, 0] ** 2 + means[:, 1] ** 2) / means[:, 2] ** 2
+        off = np.degrees(np.arctan2(np.hypot(means[:, 0], means[:, 1]), means[:, 2]))
+        assert (t == 0).sum() == 3 and ((t > 0) & (t < 1e-3)).sum() >= 20 and ((t > 1e-3) & (t < 1.2e-3)).sum() >= 6
+        assert (off > 85).sum() >= 15
+        cases.append((means, quats, scales, EYE_VIEW, np.array([[512 / math.pi, 0, 256.0], [0, 500 / math.pi, 256.0], [0, 0, 1.0]]),
+                      512, 512, len(means)))                        # 180 degrees across: every point is on the image
+
+    for means, quats, scales, vm, K, W, H, n_check in cases:
+        fx, fy, cx, cy = K[0, 0], K[1, 1], K[0, 2], K[1, 2]
+        p = O.project(means, quats, scales, vm, K, W, H, camera_model=model)
+        vis = np.nonzero(p["radii"] > 0)[0]
+        assert len(vis) >= n_check
+        Rcw, t = vm[:3, :3], vm[:3, 3]
+        cov = O.covar_world(quats, scales)
+
+        def proj(q):
+            if model == "ortho":
+                return np.array([fx * q[0] + cx, fy * q[1] + cy])
+            rho = math.hypot(q[0], q[1])
+            s = math.atan2(rho, q[2]) / rho if rho > 0 else 1.0 / q[2]
+            return np.array([fx * s * q[0] + cx, fy * s * q[1] + cy])
+        for i in vis[:n_check]:
+            pc = Rcw @ means[i].astype(np.float64) + t
+            np.testing.assert_allclose(p["means2d"][i], proj(pc), rtol=1e-12, atol=1e-9)
+            np.testing.assert_allclose(p["depths"][i], pc[2], rtol=1e-12)
+            J = np.stack([(proj(pc + 1e-6 * e) - proj(pc - 1e-6 * e)) / 2e-6 for e in np.eye(3)], 1)
+            cov2 = J @ Rcw @ cov[i] @ Rcw.T @ J.T + 0.3 * np.eye(2)
+            C = np.array([[p["conics"][i, 0], p["conics"][i, 1]], [p["conics"][i, 1], p["conics"][i, 2]]])
+            np.testing.assert_allclose(C @ cov2, np.eye(2), atol=1e-6)
 
 
 def test_tile_lists_are_sorted_and_complete():
