@@ -43,7 +43,10 @@ extern "C" {
  * 410 round 4 (the radius rule as a policy: radii_y / radius_rule arguments, MGS_BIN_* / MGS_FRAMES_RADIUS_* flags,
  * one more field in the training state; 420: the dataset frame as an output of the raster forward, ds_* arguments;
  * 440: the camera model as a policy: camera_model arguments, MGS_BIN_CAMERA_* / MGS_FRAMES_CAMERA_* flags;
- * 450: the image-loss descriptor, a trailing `image` argument of mgs_l1_loss_fwd / _fwd_grad / _bwd). */
+ * 450: the image-loss descriptor, a trailing `image` argument of mgs_l1_loss_fwd / _fwd_grad / _bwd).
+ * Not a bump, no parameter list changed: the parameter form as a policy, MGS_PARAMS_RAW -- a new bit of bin_flags, of the
+ * mgs_render_frames* flags and of mgs_project_color_bwd's camera_model word; a caller that never sets it sees 450's
+ * behaviour. */
 #define MGS_VERSION 450
 
 #define MGS_OK 0
@@ -103,6 +106,23 @@ extern "C" {
 #define MGS_BIN_RADIUS_OPACITY_AWARE 2  /* MGS_RADIUS_OPACITY_AWARE instead of MGS_RADIUS_CLASSIC */
 #define MGS_BIN_CAMERA_ORTHO 4          /* MGS_CAMERA_ORTHO instead of MGS_CAMERA_PINHOLE */
 #define MGS_BIN_CAMERA_FISHEYE 8        /* MGS_CAMERA_FISHEYE instead of MGS_CAMERA_PINHOLE (at most one MGS_BIN_CAMERA_* bit) */
+
+/* The parameter form.  Default (no bit): `scales` and `opacities` are ACTIVATED, exp(log-scale) and sigmoid(logit), as
+ * gsplat's operators take them.  MGS_PARAMS_RAW: they hold what a .ply stores and an optimiser owns, log-scales and
+ * opacity logits; the project-colour kernels apply s = exp(log_s) and o = 1 / (1 + exp(-x)) in registers right after
+ * the load (accurate expf), so every later stage -- radius rule, tile rectangles, compensation, packed records,
+ * opac_out, the raster -- sees activated values and means what it means without the bit, and the backward returns
+ * v_scales = d loss / d log_s and v_opacities = d loss / d x.  Quaternions need nothing: they are normalised inside.
+ * Valid in mgs_project_color_fwd's bin_flags and in the flags word of mgs_render_frames, mgs_render_frames_train and
+ * mgs_render_frames_backward (which forward it; the backward must be given the forward's bit, like the camera bits),
+ * and OR-ed into mgs_project_color_bwd's camera_model (the one word that carries the forward's policies there).  Needs opacities != NULL (MGS_ERR_INVALID_ARGUMENT otherwise).
+ * mgs_projection_fwd / _bwd (gsplat's fully_fused_projection, post-activation by contract) do not take it. */
+#define MGS_PARAMS_RAW 64
+/* mgs_project_color_fwd's bin_flags only, with MGS_PARAMS_RAW and opac_out: opac_out receives the plain activated
+ * opacity, no compensation is applied anywhere (a raw-form TRAINING frame that is not anti-aliased: the backward and
+ * gsplat's meta["opacities"] need sigmoid(logit) kept; mgs_render_frames_train sets it by itself).  Without this bit
+ * a non-NULL opac_out means "anti-aliased", as in the activated form. */
+#define MGS_PARAMS_OPAC_PLAIN 128
 
 /* mgs_rasterize_bwd_det flags */
 #define MGS_RASTER_BWD_SPLAT_SLOTS 2  /* the splat records carry the pairs' record slots (mgs_isect_tiles: splat_slots): pair_info is
@@ -202,6 +222,8 @@ int mgs_sh_bwd(int n, int degree, int coeff_stride, const float *dirs, const flo
  * 36 of 84 MB of stores per 1 M Gaussians fall away).  depths is always written.
  * bin_flags & MGS_BIN_RADIUS_OPACITY_AWARE: project with that radius rule (opacity x compensation when opac_out is
  * given); radii_y[N] then receives the extents along y beside radii (x) -- required whenever radii is given, else NULL.
+ * bin_flags & MGS_PARAMS_RAW: scales[N,3] are log-scales and opacities[N] logits (above); every output is what the
+ * activated form gives for exp / sigmoid of them.
  * ----------------------------------------------------------------------------------- */
 int mgs_project_color_fwd(int n, const float *means, const float *quats, const float *scales,
                           const float *opacities, int sh_degree, int coeff_stride,
@@ -273,7 +295,8 @@ int mgs_isect_tiles(int n, const float *means2d, const int32_t *radii, const int
  * per camera mgs_project_color_fwd -> mgs_isect_tiles -> mgs_rasterize_fwd in their inference-frame form
  * (packed records + binning seed, tightened tile rectangles unless MGS_FRAMES_CLASSIC_BOUNDS, no per-Gaussian
  * outputs), enqueued back to back on `stream`.  viewmats[C,4,4], Ks[C,3,3]; channels 3 (RGB) or 4 (RGB + camera-space depth as the last
- * channel); flags as mgs_rasterize_fwd (MGS_RASTER_EXPECTED_LAST turns that channel into "ED");
+ * channel); flags as mgs_rasterize_fwd (MGS_RASTER_EXPECTED_LAST turns that channel into "ED"), the MGS_FRAMES_* bits
+ * and MGS_PARAMS_RAW (scales / opacities are log-scales / logits);
  * backgrounds[C,channels] nullable; antialiased != 0 = rasterize_mode "antialiased".
  * out: render[C,H,W,channels], alphas[C,H,W], n_isect[C], status[C] (as mgs_isect_tiles, per camera).
  * The per-camera intermediates live in `workspace` (two-phase size query; 256-byte aligned) and are reused
@@ -303,7 +326,11 @@ int mgs_render_frames(int n, const float *means, const float *quats, const float
  *   flatten_ids[cap] i32 | tile_offsets[n_tiles+1] i32 | tile_group_order[ceil(n_tiles/4)] i32 | last_ids[H,W] i32 |
  *   checkpoints | {n_isect, status} u32 | radii_y[N] i32 (written under MGS_FRAMES_RADIUS_OPACITY_AWARE only)
  * flags: MGS_RASTER_EXPECTED_LAST, MGS_RASTER_LATENCY, MGS_FRAMES_CLASSIC_BOUNDS, MGS_FRAMES_RADIUS_OPACITY_AWARE,
- * MGS_FRAMES_CAMERA_ORTHO / _FISHEYE (the backward must get the forward's).  Workspace (shared by the cameras):
+ * MGS_FRAMES_CAMERA_ORTHO / _FISHEYE, MGS_PARAMS_RAW (the backward must get the forward's).  Under MGS_PARAMS_RAW the
+ * opacity field is kept whether anti-aliased or not (sigmoid(logit), x compensation when anti-aliased) and the raster
+ * backward's opacity gradient goes through mgs_project_color_bwd, as in the anti-aliased case: v_scales / v_opacities
+ * are then gradients of the log-scales / logits.  mgs_train_state_layout's `antialiased` argument means "the opacity
+ * field is kept": pass antialiased || raw.  Workspace (shared by the cameras):
  * two-phase size query, 256-byte aligned.
  * mgs_render_frames_backward: per camera mgs_rasterize_bwd_det (segmented when checkpoint_interval != 0) ->
  * mgs_project_color_bwd; v_means / v_quats / v_scales / v_sh_coeffs / v_opacities are OVERWRITTEN by the first camera
@@ -436,7 +463,11 @@ int mgs_rasterize_bwd_det(int n, const float *means2d, const float *conics, cons
  *   so the cameras of a batch can be summed without a separate zero-fill pass.
  *   v_viewmat[4,4] (nullable): gradient of the world-to-camera matrix (projection and the SH
  *   view direction, dir = mean + R^T t), ALWAYS accumulated with one float atomic per entry
- *   per wave: zero it first.  Camera-pose optimisation only.  camera_model: MGS_CAMERA_*, the forward's (its bin_flags). */
+ *   per wave: zero it first.  Camera-pose optimisation only.  camera_model: MGS_CAMERA_*, the forward's (its bin_flags).
+ *   camera_model | MGS_PARAMS_RAW when the forward ran with that bit: scales / opacities are log-scales / logits, the kernel
+ *   recomputes s and o from them, v_opac_out (then needed with AND without anti-aliasing: the cotangent of
+ *   o, or of o x compensation) is the blend's opacity gradient, and v_scales = v_s * s, v_opacities = v_o * o (1 - o)
+ *   are written (or added to) in both cases. */
 int mgs_project_color_bwd(int n, const float *means, const float *quats, const float *scales,
                           const float *opacities, int sh_degree, int coeff_stride,
                           const float *sh_coeffs, const float *viewmat, const float *K,

@@ -171,7 +171,9 @@ __global__ __launch_bounds__(kBlock) void sh_bwd_kernel(
   }
 }
 
-template <int DEG, bool STAGED, bool ACCUM, bool VIEWGRAD, int CAM>
+// RAW (include/mgs.h MGS_PARAMS_RAW) is a template constant, not a kernel argument: as a wave-uniform argument it cost
+// 15 of the 96 activated-form instantiations a step of occupancy ("Raw parameter form").
+template <int DEG, bool STAGED, bool ACCUM, bool VIEWGRAD, int CAM, bool RAW>
 __global__ __launch_bounds__(kBlock) void project_color_bwd_kernel(
     int n, const float* __restrict__ means, const float* __restrict__ quats,
     const float* __restrict__ scales, const float* __restrict__ opacities, int stride_f,
@@ -186,6 +188,9 @@ __global__ __launch_bounds__(kBlock) void project_color_bwd_kernel(
   __shared__ float4 lds[STAGED ? (kBlock / kWave) * kWave * kShPitchF4 : 1];
   int g = blockIdx.x * kBlock + threadIdx.x;
   bool active = g < n && radii[g] > 0;
+  // v_opacities is this kernel's to write when the opacity the raster saw is not the parameter: anti-aliased
+  // (opacity x compensation) or raw (sigmoid of the logit); v_opac_out is then the blend's opacity gradient
+  const bool own_opac = antialiased || RAW;
   CameraParams cam = load_camera(viewmat, Kmat);
   float m[3] = {0.f, 0.f, 0.f}, dir[3] = {0.f, 0.f, 1.f}, v_rgb[3] = {0.f, 0.f, 0.f};
   float v_depth = 0.f;
@@ -217,6 +222,13 @@ __global__ __launch_bounds__(kBlock) void project_color_bwd_kernel(
     q[0] = qq.x; q[1] = qq.y; q[2] = qq.z; q[3] = qq.w;
     float2 v2 = reinterpret_cast<const float2*>(v_means2d)[g];
     vm2[0] = v2.x; vm2[1] = v2.y;
+    float o = 0.f;                                // the ACTIVATED opacity, as the forward saw it
+    if constexpr (RAW) {                          // recompute the forward's activations
+      o = opacities[g];
+      s[0] = activate_scale(s[0]); s[1] = activate_scale(s[1]); s[2] = activate_scale(s[2]);
+      o = activate_opacity(o);
+      v_opac = v_opac_out[g];                     // not anti-aliased: the raster saw o itself
+    }
     float comp = 0.f, v_comp = 0.f;
     if (antialiased && v_opac_out) {
       // compensation from the blurred conic: det(C)/det(C + eps I)
@@ -225,10 +237,14 @@ __global__ __launch_bounds__(kBlock) void project_color_bwd_kernel(
       float a00 = con[2] * inv_dc - eps2d, a11 = con[0] * inv_dc - eps2d, a01 = -con[1] * inv_dc;
       comp = sqrtf(fmaxf(0.f, (a00 * a11 - a01 * a01) * det_conic));
       float vo = v_opac_out[g];
-      v_comp = vo * opacities[g];
+      v_comp = vo * (RAW ? o : opacities[g]);
       v_opac = vo * comp;
     }
     r = project_gaussian_vjp<CAM>(m, q, s, cam, W, H, eps2d, con, comp, vm2, v_depth, vcon, v_comp);
+    if constexpr (RAW) {     // chain rule of the activations: the outputs are gradients of the log-scales and the logit
+      r.v_scale[0] *= s[0]; r.v_scale[1] *= s[1]; r.v_scale[2] *= s[2];
+      v_opac *= activate_opacity_grad(o);
+    }
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
       om[k] = r.v_mean[k] + v_dir[k];
@@ -263,7 +279,7 @@ __global__ __launch_bounds__(kBlock) void project_color_bwd_kernel(
       float4 o = *vq;
       o.x += oq[0]; o.y += oq[1]; o.z += oq[2]; o.w += oq[3];
       *vq = o;
-      if (v_opacities && antialiased) v_opacities[g] += v_opac;
+      if (v_opacities && own_opac) v_opacities[g] += v_opac;
     }
   } else {
 #pragma unroll
@@ -272,7 +288,7 @@ __global__ __launch_bounds__(kBlock) void project_color_bwd_kernel(
       v_scales[3 * (size_t)g + k] = os[k];
     }
     *vq = make_float4(oq[0], oq[1], oq[2], oq[3]);
-    if (v_opacities && antialiased) v_opacities[g] = v_opac;
+    if (v_opacities && own_opac) v_opacities[g] = v_opac;
   }
 }
 
@@ -335,9 +351,15 @@ extern "C" int mgs_project_color_bwd(int n, const float* means, const float* qua
                                      const float* v_opac_out, float* v_means, float* v_quats,
                                      float* v_scales, float* v_sh_coeffs, float* v_opacities,
                                      float* v_viewmat, int accumulate, int camera_model, mgs_stream_t stream) {
+  // camera_model carries the forward's policies: MGS_CAMERA_* and, OR-ed in, its MGS_PARAMS_RAW bit
+  const int raw = (camera_model & MGS_PARAMS_RAW) ? 1 : 0;
+  camera_model &= ~MGS_PARAMS_RAW;
   MGS_REQUIRE(n >= 0 && width > 0 && height > 0, "project_color_bwd: bad sizes");
   MGS_REQUIRE(camera_model >= MGS_CAMERA_PINHOLE && camera_model <= MGS_CAMERA_FISHEYE,
-              "project_color_bwd: camera_model %d is not MGS_CAMERA_PINHOLE, _ORTHO or _FISHEYE", camera_model);
+              "project_color_bwd: camera_model %d is not MGS_CAMERA_PINHOLE, _ORTHO or _FISHEYE (optionally | MGS_PARAMS_RAW)",
+              camera_model);
+  MGS_REQUIRE(!raw || (opacities && v_opac_out && v_opacities),
+              "project_color_bwd: MGS_PARAMS_RAW needs opacities (the logits), v_opac_out and v_opacities");
   MGS_REQUIRE(sh_degree >= 0 && sh_degree <= 3, "project_color_bwd: sh_degree %d not in 0..3", sh_degree);
   MGS_REQUIRE(coeff_stride >= (sh_degree + 1) * (sh_degree + 1), "project_color_bwd: coeff_stride too small");
   MGS_REQUIRE(feat_stride == 3 || feat_stride == 4, "project_color_bwd: feat_stride must be 3 or 4");
@@ -356,12 +378,14 @@ extern "C" int mgs_project_color_bwd(int n, const float* means, const float* qua
       with_bool(accumulate != 0, [&](auto acc) {
         with_bool(v_viewmat != nullptr, [&](auto vm) {
           with_camera(camera_model, [&](auto cam) {
-            hipLaunchKernelGGL((project_color_bwd_kernel<decltype(d)::value, decltype(st)::value, decltype(acc)::value,
-                                                         decltype(vm)::value, decltype(cam)::value>),
-                               grid, block, 0, s, n, means, quats, scales, opacities, sf, sh_coeffs, viewmat, K,
-                               (float)width, (float)height, eps2d, radii, conics, antialiased, feat_stride, feats, v_feats,
-                               v_means2d, v_conics, v_depths, v_opac_out, v_means, v_quats, v_scales, v_sh_coeffs,
-                               v_opacities, v_viewmat);
+            with_bool(raw != 0, [&](auto rw) {
+              hipLaunchKernelGGL((project_color_bwd_kernel<decltype(d)::value, decltype(st)::value, decltype(acc)::value,
+                                                           decltype(vm)::value, decltype(cam)::value, decltype(rw)::value>),
+                                 grid, block, 0, s, n, means, quats, scales, opacities, sf, sh_coeffs, viewmat, K,
+                                 (float)width, (float)height, eps2d, radii, conics, antialiased, feat_stride, feats, v_feats,
+                                 v_means2d, v_conics, v_depths, v_opac_out, v_means, v_quats, v_scales, v_sh_coeffs,
+                                 v_opacities, v_viewmat);
+            });
           });
         });
       });

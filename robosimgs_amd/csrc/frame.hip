@@ -15,8 +15,9 @@ struct Frames {
   int tile_w, tile_h, n_tiles;
   int bin_flags;       // mgs_project_color_fwd's: tile bounds, radius rule, camera
   int camera_model;    // MGS_CAMERA_* (mgs_project_color_bwd)
+  bool raw;            // MGS_PARAMS_RAW: `scales` holds log-scales, `opacities` logits
 };
-int frames_prologue(const char* fn, int n, int n_cams, int width, int height, int channels, int flags,
+int frames_prologue(const char* fn, int n, int n_cams, int width, int height, int channels, int flags, const float* opacities,
                     uint32_t isect_capacity, const size_t* workspace_bytes, Frames* f,
                     const char* channel_rule = "3 (RGB) or 4 (RGB + depth)") {
   MGS_REQUIRE(n >= 0 && n_cams >= 1 && width > 0 && height > 0, "%s: bad sizes", fn);
@@ -25,13 +26,15 @@ int frames_prologue(const char* fn, int n, int n_cams, int width, int height, in
   MGS_REQUIRE(isect_capacity > 0, "%s: zero capacity", fn);
   MGS_REQUIRE((flags & (MGS_FRAMES_CAMERA_ORTHO | MGS_FRAMES_CAMERA_FISHEYE)) != (MGS_FRAMES_CAMERA_ORTHO | MGS_FRAMES_CAMERA_FISHEYE),
               "%s: flags set both MGS_FRAMES_CAMERA_ORTHO and MGS_FRAMES_CAMERA_FISHEYE", fn);
+  f->raw = (flags & MGS_PARAMS_RAW) != 0;
+  MGS_REQUIRE(!f->raw || opacities, "%s: MGS_PARAMS_RAW needs opacities (the logits), got NULL", fn);
   f->tile_w = (width + MGS_TILE_SIZE - 1) / MGS_TILE_SIZE;
   f->tile_h = (height + MGS_TILE_SIZE - 1) / MGS_TILE_SIZE;
   f->n_tiles = f->tile_w * f->tile_h;
   f->bin_flags = ((flags & MGS_FRAMES_CLASSIC_BOUNDS) ? 0 : MGS_BIN_TIGHT /* same pixels, shorter lists */) |
                  ((flags & MGS_FRAMES_RADIUS_OPACITY_AWARE) ? MGS_BIN_RADIUS_OPACITY_AWARE : 0) |
                  ((flags & MGS_FRAMES_CAMERA_ORTHO) ? MGS_BIN_CAMERA_ORTHO : 0) |
-                 ((flags & MGS_FRAMES_CAMERA_FISHEYE) ? MGS_BIN_CAMERA_FISHEYE : 0);
+                 ((flags & MGS_FRAMES_CAMERA_FISHEYE) ? MGS_BIN_CAMERA_FISHEYE : 0) | (f->raw ? MGS_PARAMS_RAW : 0);
   f->camera_model = mgs::bin_camera_model(f->bin_flags);
   return MGS_OK;
 }
@@ -73,7 +76,7 @@ extern "C" int mgs_render_frames(int n, const float* means, const float* quats, 
                                  uint32_t* status, uint8_t* ds_rgba, void* ds_distance, int ds_distance_type,
                                  const double* ds_Kinv_host, void* workspace, size_t* workspace_bytes, mgs_stream_t stream) {
   Frames f;
-  int rc = frames_prologue("render_frames", n, n_cams, width, height, channels, flags, isect_capacity, workspace_bytes, &f);
+  int rc = frames_prologue("render_frames", n, n_cams, width, height, channels, flags, opacities, isect_capacity, workspace_bytes, &f);
   if (rc) return rc;
   if ((ds_rgba || ds_distance) && f.camera_model != MGS_CAMERA_PINHOLE)
     return mgs::set_error(MGS_ERR_UNSUPPORTED, "render_frames: dataset output (ds_rgba / ds_distance) converts depth to ray "
@@ -219,7 +222,8 @@ extern "C" int mgs_render_frames_train(int n, const float* means, const float* q
                                        int checkpoint_interval, float* render, float* alphas, void* state, void* workspace,
                                        size_t* workspace_bytes, mgs_stream_t stream) {
   Frames f;
-  int rc = frames_prologue("render_frames_train", n, n_cams, width, height, channels, flags, isect_capacity, workspace_bytes, &f);
+  int rc = frames_prologue("render_frames_train", n, n_cams, width, height, channels, flags, opacities, isect_capacity, workspace_bytes,
+                           &f);
   if (rc) return rc;
   const int tile_w = f.tile_w, tile_h = f.tile_h;
   size_t isect_ws = 0;
@@ -237,7 +241,10 @@ extern "C" int mgs_render_frames_train(int n, const float* means, const float* q
               "render_frames_train: workspace and state must be 256-byte aligned");
   MGS_REQUIRE(checkpoint_interval == 0 || (checkpoint_interval >= 64 && (checkpoint_interval & (checkpoint_interval - 1)) == 0),
               "render_frames_train: checkpoint_interval %d is not 0 or a power of two >= 64", checkpoint_interval);
-  const TrainState st(n, width, height, channels, isect_capacity, antialiased != 0, checkpoint_interval);
+  // raw form keeps the activated opacity per camera like the anti-aliased one (meta["opacities"], the raster backward)
+  const bool keep_opac = antialiased != 0 || f.raw;
+  const TrainState st(n, width, height, channels, isect_capacity, keep_opac, checkpoint_interval);
+  const int bin_flags = f.bin_flags | ((f.raw && !antialiased) ? MGS_PARAMS_OPAC_PLAIN : 0);
   char* w = static_cast<char*>(workspace);
   uint32_t* bin_info = reinterpret_cast<uint32_t*>(w + ws.bin_info);
   uint32_t* bin_sums = reinterpret_cast<uint32_t*>(w + ws.bin_sums);
@@ -247,11 +254,11 @@ extern "C" int mgs_render_frames_train(int n, const float* means, const float* q
     auto F = [&](int f) { return reinterpret_cast<float*>(s + st.at[f]); };
     auto I = [&](int f) { return reinterpret_cast<int32_t*>(s + st.at[f]); };
     auto U = [&](int f) { return reinterpret_cast<uint32_t*>(s + st.at[f]); };
-    float* opac_aa = antialiased ? F(TF_OPAC) : nullptr;
+    float* opac_aa = keep_opac ? F(TF_OPAC) : nullptr;
     rc = mgs_project_color_fwd(n, means, quats, scales, opacities, sh_degree, coeff_stride, sh_coeffs,
                                viewmats + 16 * (size_t)c, Ks + 9 * (size_t)c, width, height, eps2d, near_plane, far_plane,
                                radius_clip, I(TF_RADII), F(TF_MEANS2D), F(TF_DEPTHS), F(TF_CONICS), opac_aa, channels,
-                               F(TF_FEATS), F(TF_SPLATS), f.bin_flags, bin_info, bin_sums, I(TF_RADII_Y), stream);
+                               F(TF_FEATS), F(TF_SPLATS), bin_flags, bin_info, bin_sums, I(TF_RADII_Y), stream);
     if (rc) return rc;
     size_t iw = isect_ws;
     rc = mgs_isect_tiles(n, nullptr, nullptr, nullptr, F(TF_DEPTHS), nullptr, nullptr, MGS_TILE_SIZE, tile_w, tile_h, c, n_cams,
@@ -280,7 +287,7 @@ extern "C" int mgs_render_frames_backward(int n, const float* means, const float
                                           float* v_means2d_abs, void* workspace, size_t* workspace_bytes,
                                           mgs_stream_t stream) {
   Frames f;
-  int rc = frames_prologue("render_frames_backward", n, n_cams, width, height, channels, flags, isect_capacity,
+  int rc = frames_prologue("render_frames_backward", n, n_cams, width, height, channels, flags, opacities, isect_capacity,
                            workspace_bytes, &f, "3 or 4");
   if (rc) return rc;
   const int tile_w = f.tile_w, tile_h = f.tile_h;
@@ -300,7 +307,10 @@ extern "C" int mgs_render_frames_backward(int n, const float* means, const float
                   v_opacities, "render_frames_backward: null pointer");
   MGS_REQUIRE(((reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(state)) & 255u) == 0,
               "render_frames_backward: workspace and state must be 256-byte aligned");
-  const TrainState st(n, width, height, channels, isect_capacity, antialiased != 0, checkpoint_interval);
+  // the opacity the raster saw is not the parameter (x compensation, or the sigmoid of a logit): it was kept per camera,
+  // and the blend's opacity gradient goes through mgs_project_color_bwd instead of straight into v_opacities
+  const bool own_opac = antialiased != 0 || f.raw;
+  const TrainState st(n, width, height, channels, isect_capacity, own_opac, checkpoint_interval);
   char* w = static_cast<char*>(workspace);
   const size_t n_px = (size_t)width * height;
   hipStream_t hs = (hipStream_t)stream;
@@ -308,13 +318,14 @@ extern "C" int mgs_render_frames_backward(int n, const float* means, const float
     const char* s = static_cast<const char*>(state) + st.total * (size_t)c;
     auto F = [&](int f) { return reinterpret_cast<const float*>(s + st.at[f]); };
     auto I = [&](int f) { return reinterpret_cast<const int32_t*>(s + st.at[f]); };
-    const float* opac = antialiased ? F(TF_OPAC) : opacities;
+    const float* opac = own_opac ? F(TF_OPAC) : opacities;
     float* g_m2d = v_means2d ? v_means2d + 2 * (size_t)n * c : reinterpret_cast<float*>(w + ws.v_means2d);
     float* g_abs = v_means2d_abs ? v_means2d_abs + 2 * (size_t)n * c : nullptr;
     float* g_con = reinterpret_cast<float*>(w + ws.v_conics);
     float* g_feat = reinterpret_cast<float*>(w + ws.v_feats);
-    // (not anti-aliased: the blend's opacity gradient IS the parameter's -- the first camera's reduce writes it in place)
-    float* g_opac = (!antialiased && c == 0) ? v_opacities : reinterpret_cast<float*>(w + ws.v_opac);
+    // (activated and not anti-aliased: the blend's opacity gradient IS the parameter's -- the first camera's reduce writes it
+    //  in place)
+    float* g_opac = (!own_opac && c == 0) ? v_opacities : reinterpret_cast<float*>(w + ws.v_opac);
     const float* frame = render + n_px * channels * c;
     const bool ed = (flags & MGS_RASTER_EXPECTED_LAST) != 0;
     size_t rw = raster_ws;
@@ -329,11 +340,11 @@ extern "C" int mgs_render_frames_backward(int n, const float* means, const float
     rc = mgs_project_color_bwd(n, means, quats, scales, opacities, sh_degree, coeff_stride, sh_coeffs,
                                viewmats + 16 * (size_t)c, Ks + 9 * (size_t)c, width, height, eps2d, I(TF_RADII), F(TF_CONICS),
                                antialiased, channels, F(TF_FEATS), g_feat, g_m2d, g_con, nullptr,
-                               antialiased ? g_opac : nullptr, v_means, v_quats, v_scales, v_sh_coeffs,
-                               antialiased ? v_opacities : nullptr, v_viewmats ? v_viewmats + 16 * (size_t)c : nullptr,
-                               c > 0 ? 1 : 0, f.camera_model, stream);
+                               own_opac ? g_opac : nullptr, v_means, v_quats, v_scales, v_sh_coeffs,
+                               own_opac ? v_opacities : nullptr, v_viewmats ? v_viewmats + 16 * (size_t)c : nullptr,
+                               c > 0 ? 1 : 0, f.camera_model | (f.raw ? MGS_PARAMS_RAW : 0), stream);
     if (rc) return rc;
-    if (!antialiased && n > 0 && c > 0)     // later cameras add theirs
+    if (!own_opac && n > 0 && c > 0)     // later cameras add theirs
       hipLaunchKernelGGL(add_rows_kernel, dim3(mgs::div_up((unsigned)n, 256u)), dim3(256), 0, hs, (size_t)n, g_opac, v_opacities, 0);
   }
   return mgs::check_launch("render_frames_backward");

@@ -41,6 +41,14 @@ MGS_HD void camera_position(const CameraParams& c, float pos[3]) {
   pos[2] = -(c.R[2] * c.t[0] + c.R[5] * c.t[1] + c.R[8] * c.t[2]);
 }
 
+// The raw parameter form (include/mgs.h MGS_PARAMS_RAW): what an optimiser owns are log-scales and opacity logits;
+// the project-colour kernels activate them in registers right after the load, s = exp(log_s), o = 1 / (1 + exp(-x)),
+// with the accurate expf (about 1 ulp; the forward gate's margins are made for exactly rounded activations, not for
+// the fast intrinsic's).  Backward: d s / d log_s = s, d o / d x = o (1 - o).
+MGS_HD float activate_scale(float log_s) { return expf(log_s); }
+MGS_HD float activate_opacity(float logit) { return 1.0f / (1.0f + expf(-logit)); }
+MGS_HD float activate_opacity_grad(float o) { return o * (1.0f - o); }
+
 #ifndef MGS_PROJ_FACTORED
 // project_gaussian: 0 = cov2d in the textbook order of A.2 steps 2-4 (the reference's, and what every parity statement is made
 // on); 1 = from the 2 x 3 factor J R Rq S (measurement, MGS_EXTRA_FLAGS=-DMGS_PROJ_FACTORED=1: profiles/r6/00_experiments.md 9)

@@ -146,24 +146,33 @@ __global__ __launch_bounds__(kBlock) void project_color_fwd_kernel(
     float* __restrict__ means2d, float* __restrict__ depths, float* __restrict__ conics,
     float* __restrict__ opac_out, int feat_stride, float* __restrict__ feats,
     float4* __restrict__ splats, uint2* __restrict__ bin_info, uint32_t* __restrict__ bin_sums,
-    int bin_tight, int tile_w, int tile_h, int32_t* __restrict__ radii_y) {
+    int bin_tight, int tile_w, int tile_h, int32_t* __restrict__ radii_y, int params) {
   __shared__ float4 lds[STAGED ? (kBlock / kWave) * kWave * kShPitchF4 : 1];
   int g = blockIdx.x * kBlock + threadIdx.x;
   CameraParams cam = load_camera(viewmat, Kmat);
   float m[3] = {0.f, 0.f, 0.f};
+  float o = 1.f;       // the ACTIVATED opacity: every use below sees it, whichever form `opacities` holds
+  // params: bin_flags' MGS_PARAMS_* bits.  anti-aliased <=> opac_out receives opacity x compensation
+  // (MGS_PARAMS_OPAC_PLAIN: the plain opacity, kept for the backward)
+  const bool aa = opac_out != nullptr && !(params & MGS_PARAMS_OPAC_PLAIN);
   Projected p;
   p.radius = 0;
   if (g < n) {
     float s[3], q[4];
     load3(means + 3 * (size_t)g, m);
     load3(scales + 3 * (size_t)g, s);
+    if (opacities) o = opacities[g];
+    if (params & MGS_PARAMS_RAW) {   // wave-uniform: log-scales and a logit were loaded
+      s[0] = activate_scale(s[0]); s[1] = activate_scale(s[1]); s[2] = activate_scale(s[2]);
+      o = activate_opacity(o);
+    }
     float4 qq = reinterpret_cast<const float4*>(quats)[g];
     q[0] = qq.x; q[1] = qq.y; q[2] = qq.z; q[3] = qq.w;
     if (RULE == MGS_RADIUS_CLASSIC)
       p = project_gaussian<CAM>(m, q, s, cam, W, H, eps2d, near_plane, far_plane, radius_clip);
     else
       p = project_gaussian<CAM>(m, q, s, cam, W, H, eps2d, near_plane, far_plane, radius_clip, RULE, opacities != nullptr,
-                                opacities ? opacities[g] : 1.f, opac_out != nullptr);
+                                o, aa);
     // radii / means2d / conics (and feats below) are null in an inference frame: the raster reads the packed
     // records, the seeded binning reads bin_info + depths -- 36 MB of stores per 1 M Gaussians nobody would read
     if (radii) radii[g] = p.radius;
@@ -175,7 +184,7 @@ __global__ __launch_bounds__(kBlock) void project_color_fwd_kernel(
       conics[3 * (size_t)g + 1] = p.conic[1];
       conics[3 * (size_t)g + 2] = p.conic[2];
     }
-    if (opac_out) opac_out[g] = opacities[g] * p.compensation;
+    if (opac_out) opac_out[g] = aa ? o * p.compensation : o;
   }
   bool active = p.radius > 0;
   // seed of the binning (mgs_isect_tiles seed_info / seed_sums): this Gaussian's tile rectangle and
@@ -189,7 +198,7 @@ __global__ __launch_bounds__(kBlock) void project_color_fwd_kernel(
                        : tile_rect(p.mean2d[0], p.mean2d[1], p.radius, p.radius_y, (float)MGS_TILE_SIZE, tile_w, tile_h);
       if (bin_tight)
         r = tighten_rect(r, p.mean2d[0], p.mean2d[1], p.conic[0], p.conic[1], p.conic[2],
-                         opacities[g] * (opac_out ? p.compensation : 1.f), (float)MGS_TILE_SIZE);
+                         o * (aa ? p.compensation : 1.f), (float)MGS_TILE_SIZE);
       info = pack_tile_rect(r);
     }
     if (g < n) bin_info[g] = info;
@@ -217,7 +226,7 @@ __global__ __launch_bounds__(kBlock) void project_color_fwd_kernel(
   // one 48-byte record per visible Gaussian for the raster kernels' list gathers (culled
   // Gaussians never enter a tile list: their records are left unwritten)
   if (splats && active) {
-    float op = opacities ? opacities[g] * (opac_out ? p.compensation : 1.f) : 0.f;
+    float op = opacities ? o * (aa ? p.compensation : 1.f) : 0.f;
     splats[3 * (size_t)g + 0] = make_float4(p.mean2d[0], p.mean2d[1], p.conic[0], p.conic[1]);
     splats[3 * (size_t)g + 1] = make_float4(p.conic[2], op, rgb[0], rgb[1]);
     splats[3 * (size_t)g + 2] = make_float4(rgb[2], feat_stride == 4 ? p.depth : 0.f, 0.f, 0.f);
@@ -298,6 +307,11 @@ extern "C" int mgs_project_color_fwd(int n, const float* means, const float* qua
   MGS_REQUIRE((bin_flags & (MGS_BIN_CAMERA_ORTHO | MGS_BIN_CAMERA_FISHEYE)) != (MGS_BIN_CAMERA_ORTHO | MGS_BIN_CAMERA_FISHEYE),
               "project_color_fwd: bin_flags sets both MGS_BIN_CAMERA_ORTHO and MGS_BIN_CAMERA_FISHEYE");
   const int cam_model = bin_camera_model(bin_flags);
+  const int params = bin_flags & (MGS_PARAMS_RAW | MGS_PARAMS_OPAC_PLAIN);
+  MGS_REQUIRE(!(params & MGS_PARAMS_RAW) || opacities,
+              "project_color_fwd: MGS_PARAMS_RAW needs opacities (the logits), got NULL");
+  MGS_REQUIRE(!(params & MGS_PARAMS_OPAC_PLAIN) || ((params & MGS_PARAMS_RAW) && opac_out),
+              "project_color_fwd: MGS_PARAMS_OPAC_PLAIN comes with MGS_PARAMS_RAW and opac_out");
   MGS_REQUIRE(n >= 0 && width > 0 && height > 0, "project_color_fwd: bad sizes");
   MGS_REQUIRE(sh_degree >= 0 && sh_degree <= 3, "project_color_fwd: sh_degree %d not in 0..3", sh_degree);
   MGS_REQUIRE(coeff_stride >= (sh_degree + 1) * (sh_degree + 1), "project_color_fwd: coeff_stride too small");
@@ -329,7 +343,7 @@ extern "C" int mgs_project_color_fwd(int n, const float* means, const float* qua
                                grid, block, 0, s, n, means, quats, scales, opacities, sf, sh_coeffs, viewmat, K,
                                (float)width, (float)height, eps2d, near_plane, far_plane, radius_clip, radii, means2d,
                                depths, conics, opac_out, feat_stride, feats, reinterpret_cast<float4*>(splats),
-                               reinterpret_cast<uint2*>(bin_info), bin_sums, bin_tight, tile_w, tile_h, radii_y);
+                               reinterpret_cast<uint2*>(bin_info), bin_sums, bin_tight, tile_w, tile_h, radii_y, params);
         });
       });
     });

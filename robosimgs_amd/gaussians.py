@@ -94,14 +94,15 @@ class Gaussians:
         """[N,K,3] = cat(f_dc[:,None], f_rest)."""
         return np.concatenate([self.sh_dc[:, None, :], self.sh_rest], axis=1)
 
-    def to_torch(self, device="cuda", sh_degree: Optional[int] = None):
-        """Post-activation tensors in `rasterization(...)` argument order."""
+    def to_torch(self, device="cuda", sh_degree: Optional[int] = None, raw: bool = False):
+        """Post-activation tensors in `rasterization(...)` argument order.  raw=True: the `scales` / `opacities` entries are
+        `log_scales` / `opacity_logits` as stored, for `rasterization(..., raw_params=True)`."""
         import torch
         deg = self.sh_degree if sh_degree is None else sh_degree
         k = (deg + 1) ** 2
         t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(device)
-        return dict(means=t(self.means), quats=t(self.quats), scales=t(self.scales),
-                    opacities=t(self.opacities), colors=t(self.sh_coeffs[:, :k]),
+        return dict(means=t(self.means), quats=t(self.quats), scales=t(self.log_scales if raw else self.scales),
+                    opacities=t(self.opacity_logits if raw else self.opacities), colors=t(self.sh_coeffs[:, :k]),
                     sh_degree=deg)
 
     # -- world-frame alignment ---------------------------------------------------------

@@ -7,7 +7,8 @@ Appendix A.1), each a thin torch wrapper over one C-ABI entry point of libmgs.so
     isect_offset_encode      -> mgs_isect_offset_encode
     rasterize_to_pixels      -> mgs_rasterize_fwd / mgs_rasterize_bwd
 
-Inputs are post-activation fp32 CUDA(HIP) tensors; ids are int32, keys int64.  All kernels
+Inputs are post-activation fp32 CUDA(HIP) tensors (the render-path calls also take the raw form, log-scales and
+opacity logits, with raw=True: include/mgs.h MGS_PARAMS_RAW); ids are int32, keys int64.  All kernels
 are enqueued on torch's current stream.  Nothing here computes on the CPU.
 """
 from __future__ import annotations
@@ -53,15 +54,17 @@ FRAMES_CAMERA_ORTHO, FRAMES_CAMERA_FISHEYE = 16, 32
 BIN_TIGHT, BIN_RADIUS_OPACITY_AWARE = 1, 2               # mgs_project_color_fwd bin_flags
 BIN_CAMERA_ORTHO, BIN_CAMERA_FISHEYE = 4, 8
 RASTER_BWD_RECORDS_ONLY, RASTER_BWD_SPLAT_SLOTS = 1, 2   # mgs_rasterize_bwd_det call_flags
+PARAMS_RAW = 64          # the parameter form: bin_flags, the mgs_render_frames* flags, mgs_project_color_bwd's camera word
+PARAMS_OPAC_PLAIN = 128  # bin_flags, with PARAMS_RAW: opac_out keeps the plain activated opacity (not anti-aliased)
 CAMERA_BIN_FLAGS = {0: 0, 1: BIN_CAMERA_ORTHO, 2: BIN_CAMERA_FISHEYE}           # MGS_CAMERA_* -> bin_flags bits
 CAMERA_FRAME_FLAGS = {0: 0, 1: FRAMES_CAMERA_ORTHO, 2: FRAMES_CAMERA_FISHEYE}   # MGS_CAMERA_* -> mgs_render_frames* bits
 
 
-def frames_flags(expected_last, latency, tight, per_axis, camera) -> int:
+def frames_flags(expected_last, latency, tight, per_axis, camera, raw=False) -> int:
     """The flags word of mgs_render_frames / _train / _backward."""
     return ((RASTER_EXPECTED_LAST if expected_last else 0) | (RASTER_LATENCY if latency else 0)
             | (0 if tight else FRAMES_CLASSIC_BOUNDS) | (FRAMES_RADIUS_OPACITY_AWARE if per_axis else 0)
-            | CAMERA_FRAME_FLAGS[int(camera)])
+            | CAMERA_FRAME_FLAGS[int(camera)] | (PARAMS_RAW if raw else 0))
 
 
 def camera_model_id(camera_model) -> int:
@@ -104,14 +107,18 @@ def projection_fwd_raw(means, quats, scales, viewmat, K, width, height, eps2d, n
 
 def project_color_fwd_raw(means, quats, scales, opacities, sh_degree, sh_coeffs, viewmat, K,
                           width, height, eps2d, near_plane, far_plane, radius_clip,
-                          antialiased, with_depth, want_splats=False, bin_seed=None, lean=False, per_axis=False, camera=0):
+                          antialiased, with_depth, want_splats=False, bin_seed=None, lean=False, per_axis=False, camera=0,
+                          raw=False):
     """Returns (radii, means2d, depths, conics, opac_aa|None, feats) and, with want_splats, a 7th
     item: the packed [N,12] records the raster kernels gather from.  bin_seed = "tight" | "classic":
     an 8th item (seed_info [N,2] i32, seed_sums [ceil(N/64)] i32) for isect_tiles_raw(seed=...).
     lean (needs want_splats and bin_seed): radii / means2d / conics / feats are not written and come back
     as None -- an inference frame, whose raster reads the records and whose binning reads the seed.
     per_axis: project with MGS_RADIUS_OPACITY_AWARE; radii is then planar [2,N] (radii_x / radii_meta).
-    camera: the camera model, MGS_CAMERA_* (camera_model_id)."""
+    camera: the camera model, MGS_CAMERA_* (camera_model_id).
+    raw: scales are log-scales and opacities logits (MGS_PARAMS_RAW); every output is the activated form's.  Unless
+    lean, the 5th item is then kept whether anti-aliased or not: the activated opacity (x compensation when
+    anti-aliased), which the raster and project_color_bwd_raw need."""
     n = means.shape[0]
     dev = means.device
     if lean and not (want_splats and bin_seed is not None):
@@ -124,7 +131,8 @@ def project_color_fwd_raw(means, quats, scales, opacities, sh_degree, sh_coeffs,
         conics = torch.empty(n, 3, dtype=torch.float32, device=dev)
         feats = torch.empty(n, stride, dtype=torch.float32, device=dev)
     depths = torch.empty(n, dtype=torch.float32, device=dev)
-    opac = torch.empty(n, dtype=torch.float32, device=dev) if antialiased else None
+    keep_plain = bool(raw) and not antialiased and not lean
+    opac = torch.empty(n, dtype=torch.float32, device=dev) if (antialiased or keep_plain) else None
     splats = torch.empty(n, 12, dtype=torch.float32, device=dev) if want_splats else None
     seed = None
     if bin_seed is not None and n > 0:
@@ -135,7 +143,8 @@ def project_color_fwd_raw(means, quats, scales, opacities, sh_degree, sh_coeffs,
         ptr(sh_coeffs), ptr(viewmat), ptr(K), width, height, eps2d, near_plane, far_plane,
         radius_clip, ptr(radii_x(radii)), ptr(means2d), ptr(depths), ptr(conics), ptr(opac), stride,
         ptr(feats), ptr(splats),
-        (BIN_TIGHT if bin_seed == "tight" else 0) | (BIN_RADIUS_OPACITY_AWARE if per_axis else 0) | CAMERA_BIN_FLAGS[int(camera)],
+        (BIN_TIGHT if bin_seed == "tight" else 0) | (BIN_RADIUS_OPACITY_AWARE if per_axis else 0) | CAMERA_BIN_FLAGS[int(camera)]
+        | (PARAMS_RAW if raw else 0) | (PARAMS_OPAC_PLAIN if keep_plain else 0),
         ptr(seed[0]) if seed else None,
         ptr(seed[1]) if seed else None, ptr(radii[1]) if (per_axis and radii is not None) else None, stream_handle()),
         "mgs_project_color_fwd")
@@ -149,16 +158,18 @@ def project_color_fwd_raw(means, quats, scales, opacities, sh_degree, sh_coeffs,
 
 def project_color_bwd_raw(means, quats, scales, opacities, sh_degree, sh_coeffs, viewmat, K, width, height, eps2d,
                           radii, conics, antialiased, feats, v_feats, v_means2d, v_conics, v_opac_aa, v_means, v_quats,
-                          v_scales, v_sh, v_opacities, v_viewmat=None, accumulate=False, camera=0):
+                          v_scales, v_sh, v_opacities, v_viewmat=None, accumulate=False, camera=0, raw=False):
     """The chain rule of project_color_fwd_raw for one camera.  radii, conics, feats: what the forward returned;
     v_opac_aa: the cotangent of its opac_aa (antialiased only).  v_means / v_quats / v_scales / v_sh and, antialiased,
-    v_opacities are overwritten, or added to with `accumulate`; v_viewmat [4,4] (optional) is always added to."""
+    v_opacities are overwritten, or added to with `accumulate`; v_viewmat [4,4] (optional) is always added to.
+    raw (the forward's): scales / opacities are log-scales / logits; v_opac_aa -- the blend's opacity gradient -- and
+    v_opacities are then needed anti-aliased or not, and v_scales / v_opacities are the gradients of the raw tensors."""
     check(_lib.lib().mgs_project_color_bwd(
         means.shape[0], ptr(means), ptr(quats), ptr(scales), ptr(opacities), sh_degree, sh_coeffs.shape[1], ptr(sh_coeffs),
         ptr(viewmat), ptr(K), width, height, eps2d, ptr(radii_x(radii)), ptr(conics), int(antialiased), feats.shape[1],
         ptr(feats), ptr(v_feats), ptr(v_means2d), ptr(v_conics), None, ptr(v_opac_aa), ptr(v_means), ptr(v_quats),
-        ptr(v_scales), ptr(v_sh), ptr(v_opacities), ptr(v_viewmat), int(accumulate), int(camera), stream_handle()),
-        "mgs_project_color_bwd")
+        ptr(v_scales), ptr(v_sh), ptr(v_opacities), ptr(v_viewmat), int(accumulate),
+        int(camera) | (PARAMS_RAW if raw else 0), stream_handle()), "mgs_project_color_bwd")
 
 
 class TileLists:
@@ -236,18 +247,19 @@ def _frames_call(means, quats, scales, opacities, sh_degree, sh_coeffs, viewmats
 def render_frames_raw(means, quats, scales, opacities, sh_degree, sh_coeffs, viewmats, Ks, width, height,
                       eps2d, near_plane, far_plane, radius_clip, antialiased, with_depth, capacity,
                       backgrounds=None, expected_last=False, latency=False, out=None, tight=True, per_axis=False,
-                      dataset=None, float_frame=True, camera=0):
+                      dataset=None, float_frame=True, camera=0, raw=False):
     """mgs_render_frames: C inference frames in one C call (no per-Gaussian outputs, scratch reused from camera to
     camera).  viewmats [C,4,4], Ks [C,3,3], backgrounds [C,ch] or None.  Returns (render [C,H,W,ch], alphas [C,H,W],
     n_isects [C] i32, isect_status [C] i32); out = (render, alphas) to write into existing buffers.
     tight=False: gsplat's classic tile rectangles (MGS_FRAMES_CLASSIC_BOUNDS; same pixels, classic counts).
     dataset = (rgba uint8 [C,H,W,4], distance [C,H,W,1] or None, K): the dataset frames straight out of the raster
-    (with_depth and expected_last required); float_frame=False then leaves render / alphas unwritten."""
+    (with_depth and expected_last required); float_frame=False then leaves render / alphas unwritten.
+    raw: scales are log-scales and opacities logits (MGS_PARAMS_RAW)."""
     dev = means.device
     C = viewmats.shape[0]
     render, alphas, args = _frames_call(means, quats, scales, opacities, sh_degree, sh_coeffs, viewmats, Ks, width, height,
                                         eps2d, near_plane, far_plane, radius_clip, antialiased, with_depth, capacity,
-                                        backgrounds, frames_flags(expected_last, latency, tight, per_axis, camera), out)
+                                        backgrounds, frames_flags(expected_last, latency, tight, per_axis, camera, raw), out)
     n_isect = torch.empty(C, dtype=torch.int32, device=dev)
     status = torch.empty(C, dtype=torch.int32, device=dev)
     args += [ptr(render) if (float_frame or dataset is None) else None,
@@ -273,12 +285,16 @@ TRAIN_FIELDS = ("radii", "means2d", "depths", "conics", "opac_aa", "feats", "spl
 class TrainState:
     """Per-camera state of a batch of training frames (mgs_render_frames_train writes it, mgs_render_frames_backward
     reads it): one device buffer, fields at the offsets mgs_train_state_layout reports; `views(c)` hands them out as
-    tensors without copying.  flags: the mgs_render_frames* flags word of the frames (the backward must get the forward's)."""
+    tensors without copying.  flags: the mgs_render_frames* flags word of the frames (the backward must get the forward's).
+    raw: the frames are rendered from raw parameters (flags has PARAMS_RAW); the "opac_aa" field -- the opacity the raster
+    saw -- is then kept whether anti-aliased or not."""
 
-    def __init__(self, n, n_cams, width, height, channels, capacity, antialiased, interval, flags, device):
+    def __init__(self, n, n_cams, width, height, channels, capacity, antialiased, interval, flags, device, raw=False):
         offs = (ctypes.c_size_t * len(TRAIN_FIELDS))()
         per = ctypes.c_size_t(0)
-        check(_lib.lib().mgs_train_state_layout(n, width, height, channels, int(capacity), int(bool(antialiased)), int(interval),
+        self.raw = bool(raw)
+        self.keep_opac = bool(antialiased) or self.raw
+        check(_lib.lib().mgs_train_state_layout(n, width, height, channels, int(capacity), int(self.keep_opac), int(interval),
                                                 offs, ctypes.byref(per)), "mgs_train_state_layout")
         self.offsets, self.per_camera = list(offs), per.value
         self.n, self.n_cams, self.width, self.height, self.channels = n, n_cams, width, height, channels
@@ -293,7 +309,7 @@ class TrainState:
     def views(self, c: int) -> dict:
         n, cap, nt = self.n, self.capacity, self.n_tiles
         shapes = {"radii": (torch.int32, (n,)), "means2d": (torch.float32, (n, 2)), "depths": (torch.float32, (n,)),
-                  "conics": (torch.float32, (n, 3)), "opac_aa": (torch.float32, (n,) if self.antialiased else (0,)),
+                  "conics": (torch.float32, (n, 3)), "opac_aa": (torch.float32, (n,) if self.keep_opac else (0,)),
                   "feats": (torch.float32, (n, self.channels)), "splats": (torch.float32, (n, 12)),
                   "tiles_per_gauss": (torch.int32, (n,)), "pair_info": (torch.int32, (n, 4)), "tile_ids": (torch.int32, (cap,)),
                   "flatten_ids": (torch.int32, (cap,)), "tile_offsets": (torch.int32, (nt + 1,)),
@@ -326,23 +342,27 @@ class TrainState:
 def render_frames_train_raw(means, quats, scales, opacities, sh_degree, sh_coeffs, viewmats, Ks, width, height, eps2d,
                             near_plane, far_plane, radius_clip, antialiased, with_depth, capacity, interval,
                             backgrounds=None, expected_last=False, latency=True, tight=True, out=None, per_axis=False,
-                            camera=0):
-    """mgs_render_frames_train: C training frames in one C call.  Returns (render [C,H,W,ch], alphas [C,H,W], TrainState)."""
-    flags = frames_flags(expected_last, latency, tight, per_axis, camera)
+                            camera=0, raw=False):
+    """mgs_render_frames_train: C training frames in one C call.  Returns (render [C,H,W,ch], alphas [C,H,W], TrainState).
+    raw: scales are log-scales and opacities logits (MGS_PARAMS_RAW; the state remembers it for the backward)."""
+    flags = frames_flags(expected_last, latency, tight, per_axis, camera, raw)
     render, alphas, args = _frames_call(means, quats, scales, opacities, sh_degree, sh_coeffs, viewmats, Ks, width, height,
                                         eps2d, near_plane, far_plane, radius_clip, antialiased, with_depth, capacity,
                                         backgrounds, flags, out)
     st = TrainState(means.shape[0], viewmats.shape[0], width, height, 4 if with_depth else 3, capacity, antialiased, interval,
-                    flags, means.device)
+                    flags, means.device, raw=raw)
     args += [int(interval), ptr(render), ptr(alphas), st.ptr()]
     sized_call(_lib.lib().mgs_render_frames_train, args, means.device, cached=True)
     return render, alphas, st
 
 
 def render_frames_backward_raw(means, quats, scales, opacities, sh_degree, sh_coeffs, viewmats, Ks, eps2d, backgrounds, st,
-                               render, alphas, v_render, v_alphas, absgrad=False, want_viewmats=False):
+                               render, alphas, v_render, v_alphas, absgrad=False, want_viewmats=False, raw=False):
     """mgs_render_frames_backward on a TrainState.  Returns (v_means, v_quats, v_scales, v_sh, v_opacities, v_viewmats|None,
-    v_means2d [C,N,2], v_means2d_abs [C,N,2]|None)."""
+    v_means2d [C,N,2], v_means2d_abs [C,N,2]|None).  raw must be the forward's (it travels in st.flags; the keyword is
+    checked against it): v_scales / v_opacities are then the gradients of the log-scales / logits."""
+    if bool(raw) != bool(st.flags & PARAMS_RAW):
+        raise ValueError(f"raw={bool(raw)} but the TrainState was rendered with raw={bool(st.flags & PARAMS_RAW)}")
     dev = means.device
     C, n = viewmats.shape[0], means.shape[0]
     v_means, v_quats, v_scales = torch.empty_like(means), torch.empty_like(quats), torch.empty_like(scales)

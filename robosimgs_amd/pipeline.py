@@ -123,7 +123,14 @@ class FrameRenderer:
         -1 = static) and n_groups; submit(..., rotations=, translations=[, scales=]) then poses
         the groups for that frame.  Every slot owns a posed copy of the Gaussians and its graph
         starts with mgs_transform_gaussians(rest pose -> copy) reading the slot's transform buffer,
-        so a posed frame costs one small upload and 14-97 us of GPU time more than a static one."""
+        so a posed frame costs one small upload and 14-97 us of GPU time more than a static one.
+
+        raw_params=True (forwarded to rasterization like every raster_kw): `tensors` hold log-scales and opacity logits
+        (Gaussians.to_torch(raw=True)), so a loaded .ply renders without an activation pass on the host.  Static scenes
+        only: the group transform multiplies activated scales by the group's s."""
+        if group_ids is not None and raster_kw.get("raw_params"):
+            raise ValueError("raw_params=True is not available with group_ids: mgs_transform_gaussians scales activated "
+                             "extents (scales' = s scales), it does not add log s to log-scales")
         # reorder="morton" (default): the renderer keeps ITS OWN copy of the scene in Morton order of the means -- a
         # one-off at construction, like any acceleration structure of a static scene.  Frames carry nothing per
         # Gaussian, so nothing has to be mapped back; the image is the one the caller's order gives except where two

@@ -75,6 +75,7 @@ class _RenderConfig:
     lean: bool                  # lean_meta
     segment: int                # backward_segment
     dataset: Optional[tuple]    # dataset_out
+    raw: bool = False           # raw_params: scales are log-scales, opacities logits (MGS_PARAMS_RAW)
 
     @property
     def channels(self) -> int:
@@ -87,7 +88,7 @@ class _Camera(NamedTuple):
     means2d: Tensor
     depths: Tensor
     conics: Tensor
-    opac_aa: Optional[Tensor]   # antialiased only
+    opac_aa: Optional[Tensor]   # the opacity the raster saw, when it is not the parameter: antialiased, or raw form
     feats: Tensor
     lists: ops.TileLists
     splats: Tensor
@@ -132,7 +133,7 @@ class _RenderSH(torch.autograd.Function):
             _, _, n_isects, status = ops.render_frames_raw(
                 *args, backgrounds=backgrounds, expected_last=cfg.expected_depth, latency=cfg.latency, out=(render, alphas),
                 tight=cfg.tight, per_axis=cfg.per_axis, camera=cfg.camera, dataset=ds[:3] if ds is not None else None,
-                float_frame=ds is None or bool(ds[3]))
+                float_frame=ds is None or bool(ds[3]), raw=cfg.raw)
             meta_out["lean"] = dict(n_isects=n_isects, isect_status=status)
             return render, alphas.unsqueeze(-1)
         if training and cap is not None:
@@ -140,12 +141,12 @@ class _RenderSH(torch.autograd.Function):
             # meta dict need stays per camera in one state buffer; no read-back, so the step captures in a HIP graph
             _, _, st = ops.render_frames_train_raw(
                 *args, cfg.segment, backgrounds=backgrounds, expected_last=cfg.expected_depth, latency=cfg.latency,
-                tight=cfg.tight, out=(render, alphas), per_axis=cfg.per_axis, camera=cfg.camera)
+                tight=cfg.tight, out=(render, alphas), per_axis=cfg.per_axis, camera=cfg.camera, raw=cfg.raw)
             per_cam = []
             for c in range(C):
                 v = st.views(c)
                 per_cam.append(_Camera(torch.stack([v["radii"], v["radii_y"]]) if cfg.per_axis else v["radii"], v["means2d"],
-                                       v["depths"], v["conics"], v["opac_aa"] if cfg.antialiased else None, v["feats"],
+                                       v["depths"], v["conics"], v["opac_aa"] if (cfg.antialiased or cfg.raw) else None, v["feats"],
                                        st.tile_lists(c, v), v["splats"], None))
             ctx.train_state = st
             ctx.save_for_backward(means, quats, scales, opacities, sh_coeffs, viewmats, Ks, backgrounds, alphas, None, render)
@@ -158,8 +159,8 @@ class _RenderSH(torch.autograd.Function):
             radii, means2d, depths, conics, opac_aa, feats, splats, seed = ops.project_color_fwd_raw(
                 means, quats, scales, opacities, cfg.sh_degree, sh_coeffs, viewmats[c], Ks[c], width, height, cfg.eps2d,
                 cfg.near, cfg.far, cfg.radius_clip, cfg.antialiased, cfg.with_depth, want_splats=True,
-                bin_seed="tight" if cfg.tight else "classic", per_axis=cfg.per_axis, camera=cfg.camera)
-            opac = opac_aa if cfg.antialiased else opacities
+                bin_seed="tight" if cfg.tight else "classic", per_axis=cfg.per_axis, camera=cfg.camera, raw=cfg.raw)
+            opac = opac_aa if (cfg.antialiased or cfg.raw) else opacities
             cam_cap = cap if cap is not None else max(1, ops._upper_bound_isects(radii, tile_w, tile_h))
             # training: these records are the ones the backward gets (_Camera.splats), so it may read their slot words
             tl = ops.isect_tiles_raw(means2d, radii, depths, tile_w, tile_h, cam_cap, c, C, want_pair_info=training,
@@ -208,7 +209,7 @@ class _RenderSH(torch.autograd.Function):
             v_means, v_quats, v_scales, v_sh, v_opacities, v_viewmats, v_m2d, v_abs = ops.render_frames_backward_raw(
                 means, quats, scales, opacities, cfg.sh_degree, sh_coeffs, viewmats, Ks, cfg.eps2d, backgrounds,
                 ctx.train_state, render_out, alphas, v_render, v_alphas, absgrad=cfg.absgrad,
-                want_viewmats=ctx.needs_input_grad[5])
+                want_viewmats=ctx.needs_input_grad[5], raw=cfg.raw)
         else:
             tile_w, tile_h = -(-cfg.width // TILE_SIZE), -(-cfg.height // TILE_SIZE)
             # "RGB+ED": the raster backward's prologue undoes the divide by max(alpha, 1e-10) itself
@@ -218,12 +219,14 @@ class _RenderSH(torch.autograd.Function):
             v_quats = torch.empty_like(quats)
             v_scales = torch.empty_like(scales)
             v_sh = torch.empty_like(sh_coeffs)
-            v_opacities = torch.empty_like(opacities) if cfg.antialiased else None
+            # (the opacity the raster saw is not the parameter: the blend's gradient goes through project_color_bwd_raw)
+            own_opac = cfg.antialiased or cfg.raw
+            v_opacities = torch.empty_like(opacities) if own_opac else None
             # camera-pose gradients only when asked for (float atomics into a zeroed [C,4,4])
             v_viewmats = torch.zeros_like(viewmats) if ctx.needs_input_grad[5] else None
             v_m2d, v_abs, blend = [], [], []
             for c, cam in enumerate(ctx.per_cam):
-                opac = cam.opac_aa if cfg.antialiased else opacities
+                opac = cam.opac_aa if own_opac else opacities
                 ckpt = cam.checkpoints
                 v_means2d, v_conics, v_feats, v_opac, v_means2d_abs = ops.rasterize_bwd_det_raw(
                     cam.means2d, cam.conics, cam.feats, opac, backgrounds[c] if backgrounds is not None else None, cfg.width,
@@ -239,9 +242,9 @@ class _RenderSH(torch.autograd.Function):
                 ops.project_color_bwd_raw(
                     means, quats, scales, opacities, cfg.sh_degree, sh_coeffs, viewmats[c], Ks[c], cfg.width, cfg.height,
                     cfg.eps2d, cam.radii, cam.conics, cfg.antialiased, cam.feats, v_feats, v_means2d, v_conics,
-                    v_opac if cfg.antialiased else None, v_means, v_quats, v_scales, v_sh, v_opacities,
-                    v_viewmats[c] if v_viewmats is not None else None, accumulate=c > 0, camera=cfg.camera)
-                if not cfg.antialiased:
+                    v_opac if own_opac else None, v_means, v_quats, v_scales, v_sh, v_opacities,
+                    v_viewmats[c] if v_viewmats is not None else None, accumulate=c > 0, camera=cfg.camera, raw=cfg.raw)
+                if not own_opac:
                     v_opacities = v_opac if v_opacities is None else v_opacities + v_opac
             ctx.meta_out["blend_grads"] = blend
         # screen-space gradients for densification strategies: published in the meta dict, and gsplat users call
@@ -279,8 +282,15 @@ def rasterization(means: Tensor, quats: Tensor, scales: Tensor, opacities: Tenso
                   backward_segment: int = 256,
                   radius_rule: str = "classic",
                   dataset_out=None,
-                  camera_model: str = "pinhole") -> Tuple[Tensor, Tensor, Dict]:
+                  camera_model: str = "pinhole",
+                  raw_params: bool = False) -> Tuple[Tensor, Tensor, Dict]:
     """Render N Gaussians from C cameras.
+
+    raw_params (SH path): `scales` hold log-scales and `opacities` logits -- what a nerfstudio .ply stores and
+    splatfacto's optimiser steps on -- and the returned gradients are with respect to those tensors.  The projection
+    kernels apply exp / sigmoid in registers (include/mgs.h MGS_PARAMS_RAW) and their backward applies the two chain-rule
+    factors: no activation launches, no activated copies, no autograd nodes between the optimiser's leaves and the
+    renderer.  Everything else is as in the activated form; meta["opacities"] stays post-activation [C,N].
 
     dataset_out = (rgba uint8 [C,H,W,4], distance [C,H,W,1] float16 / 32 / 64 or None, K [3,3], keep_float_frame):
     inference frames ("RGB+ED", lean_meta=True, isect_capacity given) leave the raster as the dataset frames the
@@ -332,6 +342,8 @@ def rasterization(means: Tensor, quats: Tensor, scales: Tensor, opacities: Tenso
         raise NotImplementedError("packed / sparse_grad are not supported")
     if tile_size != TILE_SIZE:
         raise NotImplementedError(f"tile_size must be {TILE_SIZE}")
+    if raw_params and sh_degree is None:
+        raise NotImplementedError("raw_params needs sh_degree: per-Gaussian features run gsplat's post-activation operators")
     if tile_bounds not in ("tight", "classic"):
         raise ValueError(f"tile_bounds {tile_bounds!r} not in ('tight', 'classic')")
     rule = ops.radius_rule_id(radius_rule)
@@ -380,7 +392,7 @@ def rasterization(means: Tensor, quats: Tensor, scales: Tensor, opacities: Tenso
             width, height, int(sh_degree), float(eps2d), float(near_plane), float(far_plane), float(radius_clip),
             antialiased, want_depth, isect_capacity, bool(absgrad), tight=tile_bounds == "tight", per_axis=bool(rule),
             camera=camera, expected_depth=render_mode in ("RGB+ED", "ED"), latency=raster_schedule == "latency",
-            lean=bool(lean_meta), segment=int(backward_segment), dataset=dataset_out)
+            lean=bool(lean_meta), segment=int(backward_segment), dataset=dataset_out, raw=bool(raw_params))
         # the autograd function publishes per-camera intermediates (and, after backward, "means2d_grad" /
         # "means2d_absgrad" lists) into the meta dict
         render, alphas = _RenderSH.apply(means, quats, scales, opacities, colors, viewmats, Ks, backgrounds, cfg, meta)
@@ -399,7 +411,7 @@ def rasterization(means: Tensor, quats: Tensor, scales: Tensor, opacities: Tenso
             conics=_stk([p.conics for p in per_cam]),
             tiles_per_gauss=_stk([p.lists.tiles_per_gauss for p in per_cam]),
             depths=_stk([p.depths for p in per_cam]),
-            opacities=(_stk([p.opac_aa for p in per_cam]) if antialiased
+            opacities=(_stk([p.opac_aa for p in per_cam]) if (antialiased or raw_params)
                        else opacities.unsqueeze(0).expand(C, N)),
             n_isects=_cat([p.lists.n_isect for p in per_cam]),
             isect_status=_cat([p.lists.status for p in per_cam]),
@@ -409,6 +421,9 @@ def rasterization(means: Tensor, quats: Tensor, scales: Tensor, opacities: Tenso
             meta["means2d"] = meta["means2d"].detach().requires_grad_(True)   # see _RenderSH.backward
     else:
         # feature path: colours are given per Gaussian (or evaluated from SH for "D"/"ED")
+        if raw_params:
+            raise NotImplementedError("raw_params needs the fused SH colour path (an RGB mode, or isect_capacity for 'D' / 'ED'): "
+                                      "this path runs gsplat's post-activation operators")
         if isect_capacity is not None:
             # this path sizes its lists by reading the intersection count back (as the reference
             # operator does), so it can neither honour a fixed capacity nor be captured in a graph

@@ -86,17 +86,23 @@ class Trainer:
     with the new ones; the next render reorders them.  A strategy that keeps per-Gaussian accumulators (gsplat's `grad2d`,
     `count`, `radii`) hands them over as `extra_state` so that they follow; anything not handed over keeps the old order.
     render_fn: the render call (default robosimgs_amd.rasterization) -- (means, quats, scales, opacities, colors, viewmats,
-    Ks, width, height, **kw) -> (colors, alphas, meta)."""
+    Ks, width, height, **kw) -> (colors, alphas, meta).
+
+    raw_params=True: params["scales"] / params["opacities"] hold log-scales / opacity logits, as splatfacto keeps them, and
+    the render call gets raw_params=True (rasterization activates them inside its projection kernels).  The optimiser's
+    leaves are then the very tensors handed in, with no activation graph in between: their .grad comes straight out of the
+    library's backward.  KEYS, reorder_parameters and rebind work as in the activated form."""
 
     KEYS = ("means", "quats", "scales", "opacities", "colors")
 
     def __init__(self, params: Dict[str, torch.Tensor], optimizer: Optional[torch.optim.Optimizer], width: int, height: int,
                  auto_reorder_every: int = 500, extra_state: Iterable[torch.Tensor] = (), render_fn=None, bits: int = 10,
-                 **raster_kwargs):
+                 raw_params: bool = False, **raster_kwargs):
         self.width, self.height = int(width), int(height)
         self.auto_reorder_every = int(auto_reorder_every)
         self.bits = int(bits)
-        self.raster_kwargs = dict(raster_kwargs)
+        self.raw_params = bool(raw_params)
+        self.raster_kwargs = dict(raster_kwargs, raw_params=True) if self.raw_params else dict(raster_kwargs)
         self._render_fn = render_fn
         self.it = 0
         self.reorders = 0
