@@ -44,6 +44,9 @@ def __getattr__(name):  # lazy: keeps `import robosimgs_amd` torch-free for host
     if name in ("reorder_parameters", "Trainer"):
         from . import training
         return getattr(training, name)
+    if name in ("GaussianAdam", "splatfacto_groups"):
+        from . import optim
+        return getattr(optim, name)
     if name in ("render_sharded", "gather_frames", "shard_cameras"):
         from . import distributed
         return getattr(distributed, name)

@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import c_char_p, c_float, c_int, c_size_t, c_uint32, c_void_p, POINTER
+from ctypes import c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_uint32, c_void_p, POINTER
 
 import torch  # noqa: F401  (must precede the dlopen below)
 
@@ -28,6 +28,15 @@ class ImageLoss(ctypes.Structure):
     _fields_ = [("images", c_int), ("height", c_int), ("width", c_int), ("channels", c_int),
                 ("ssim_weight", c_float), ("padding", c_int)]
 
+
+class AdamGroup(ctypes.Structure):
+    """mgs_adam_group (include/mgs_optim.h): one parameter group of mgs_adam_step, n rows of row_floats floats."""
+    _fields_ = [("param", c_void_p), ("grad", c_void_p), ("exp_avg", c_void_p), ("exp_avg_sq", c_void_p),
+                ("n", c_int64), ("row_floats", c_int32), ("head_floats", c_int32), ("lr", c_double),
+                ("lr_final", c_double), ("decay_steps", c_int32), ("rest_lr_scale", c_double)]
+
+
+ADAM_MAX_GROUPS = 8        # MGS_ADAM_MAX_GROUPS
 
 # every function include/mgs.h declares: name -> (argtypes, restype)
 p, i, f, u32 = c_void_p, c_int, c_float, c_uint32
@@ -63,8 +72,13 @@ _SIGNATURES = {
     "mgs_l1_loss_bwd_scale": ([c_size_t, p, p, p], c_int),
     "mgs_rasterize_bwd_det": ([i, p, p, p, p, p, p, i, i, i, i, i, p, p, p, p, p, p, p, p, p, u32, p, p, i, i, p, p, p, p, p, p, POINTER(c_size_t), p], c_int),
 }
+# every function include/mgs_optim.h declares (the same libraries; EXPORTS stays include/mgs.h's table)
+_OPTIM_SIGNATURES = {
+    "mgs_adam_step": ([i, POINTER(AdamGroup), c_double, c_double, c_double, p, p, p, i, c_size_t, p, p], c_int),
+}
 del p, i, f, u32, img
 EXPORTS = list(_SIGNATURES)
+OPTIM_EXPORTS = list(_OPTIM_SIGNATURES)
 
 
 class MgsError(RuntimeError):
@@ -84,7 +98,7 @@ def _load(path: str = None, hooks: bool = False) -> ctypes.CDLL:
     if have != MGS_VERSION:      # shifted parameter lists would end in a GPU fault, not in an error
         raise MgsError(f"{LIB_PATH} reports ABI version {have}, this binding was written for {MGS_VERSION} "
                        "(include/mgs.h): rebuild the library (`python robosimgs_amd/csrc/build.py --force`)")
-    for name, (argtypes, restype) in _SIGNATURES.items():
+    for name, (argtypes, restype) in (*_SIGNATURES.items(), *_OPTIM_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here == header/library mismatch
         fn.argtypes = argtypes
         fn.restype = restype

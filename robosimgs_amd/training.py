@@ -14,6 +14,7 @@ from typing import Dict, Iterable, Optional
 
 import torch
 
+from .optim import GaussianAdam
 from .pipeline import locality_order
 
 
@@ -91,7 +92,11 @@ class Trainer:
     raw_params=True: params["scales"] / params["opacities"] hold log-scales / opacity logits, as splatfacto keeps them, and
     the render call gets raw_params=True (rasterization activates them inside its projection kernels).  The optimiser's
     leaves are then the very tensors handed in, with no activation graph in between: their .grad comes straight out of the
-    library's backward.  KEYS, reorder_parameters and rebind work as in the activated form."""
+    library's backward.  KEYS, reorder_parameters and rebind work as in the activated form.
+
+    optimizer = robosimgs_amd.GaussianAdam(..., selective=True): `step` hands it the radii of the last `render` as the
+    visibility mask, so the Gaussians that render did not see keep their parameters and moments (gsplat's SelectiveAdam).
+    Every other optimiser is stepped with no arguments."""
 
     KEYS = ("means", "quats", "scales", "opacities", "colors")
 
@@ -107,6 +112,7 @@ class Trainer:
         self.it = 0
         self.reorders = 0
         self.last_order: Optional[torch.Tensor] = None
+        self.last_meta: Optional[dict] = None          # meta of the last render() under a selective GaussianAdam: its visibility
         self.rebind(params, optimizer, extra_state)
 
     def rebind(self, params: Dict[str, torch.Tensor], optimizer: Optional[torch.optim.Optimizer],
@@ -116,6 +122,7 @@ class Trainer:
         if missing:
             raise KeyError(f"params lacks {missing} (needs {self.KEYS})")
         self.params, self.optimizer, self.extra_state = params, optimizer, list(extra_state)
+        self.last_meta = None
         n = params["means"].shape[0]
         self.original_index = torch.arange(n, device=params["means"].device)
         self._due = self.auto_reorder_every > 0
@@ -136,8 +143,14 @@ class Trainer:
         if fn is None:
             from .rendering import rasterization as fn
         p = self.params
-        return fn(p["means"], p["quats"], p["scales"], p["opacities"], p["colors"], viewmats, Ks, self.width, self.height,
-                  **{**self.raster_kwargs, **kw})
+        out = fn(p["means"], p["quats"], p["scales"], p["opacities"], p["colors"], viewmats, Ks, self.width, self.height,
+                 **{**self.raster_kwargs, **kw})
+        if self._selective():           # only then: a kept meta keeps the frame's per-camera state alive until the next render
+            self.last_meta = out[2]
+        return out
+
+    def _selective(self) -> bool:
+        return isinstance(self.optimizer, GaussianAdam) and self.optimizer.selective
 
     def step(self, loss: torch.Tensor) -> None:
         """loss.backward(), optimiser step, zero_grad(set_to_none=True); counts the step towards the next reorder.  A scalar loss
@@ -148,7 +161,12 @@ class Trainer:
         else:
             loss.backward()
         if self.optimizer is not None:
-            self.optimizer.step()
+            if self._selective():
+                if self.last_meta is None or self.last_meta.get("radii") is None:
+                    raise RuntimeError("a selective GaussianAdam steps on the radii of Trainer.render(): render first")
+                self.optimizer.step(visibility=self.last_meta["radii"])
+            else:
+                self.optimizer.step()
             self.optimizer.zero_grad(set_to_none=True)
         self.it += 1
         self._since = getattr(self, "_since", 0) + 1
