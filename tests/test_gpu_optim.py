@@ -12,10 +12,12 @@ import torch
 
 from robosimgs_amd import GaussianAdam, Trainer, camera_ring, reorder_parameters, splatfacto_groups, synthetic_scene
 
+# tests/adam_ref.py: the fp64 update and the per-element bounds, shared with test_gpu_training_loop.py
+from adam_ref import B1, B2, EPS, U, first_moment_bound, param_bound, second_moment_bound
+from adam_ref import update64 as _update64
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-U = 2.0 ** -24
-B1, B2, EPS = 0.9, 0.999, 1e-8
 SHAPES = {1: lambda n: (n,), 3: lambda n: (n, 3), 4: lambda n: (n, 4), 48: lambda n: (n, 16, 3)}
 
 
@@ -56,12 +58,6 @@ def _snapshot(opt, ps):
     return [x.detach().clone() for x in (*ps, *m, *v)]
 
 
-def _update64(m, v, t, lr):
-    """The step of update number t in fp64 from given moments: (lr / (1 - b1^t)) m / (sqrt(v) / sqrt(1 - b2^t) + eps)."""
-    bc1, bc2 = -math.expm1(t * math.log(B1)), -math.expm1(t * math.log(B2))
-    return (lr / bc1) * m.double() / (v.double().sqrt() / math.sqrt(bc2) + EPS)
-
-
 @pytest.mark.parametrize("t", [1, 2, 1000])
 @pytest.mark.parametrize("n", [1, 5, 257, 4099])
 def test_one_step_matches_fp64_adam(n, t):
@@ -95,11 +91,11 @@ def test_one_step_matches_fp64_adam(n, t):
         d_ref = _update64(m64, v64, t, lr)
         assert bool((((p.double() - d_ref) - q.detach()).abs() <= 1e-12 * (d_ref.abs() + p.double().abs())).all())
         gm, gv, gp = ms[k].cpu(), vs[k].cpu(), ps[k].detach().cpu()
-        err_m = (gm.double() - m64).abs() - 4 * U * (B1 * m.double().abs() + (1 - B1) * g.double().abs())
-        err_v = (gv.double() - v64).abs() - 4 * U * v64
+        err_m = (gm.double() - m64).abs() - first_moment_bound(m, g)
+        err_v = (gv.double() - v64).abs() - second_moment_bound(v64)
         d64 = _update64(gm, gv, t, lr)
         p64 = p.double() - d64
-        err_p = (gp.double() - p64).abs() - (U * p64.abs() + 16 * U * d64.abs())
+        err_p = (gp.double() - p64).abs() - param_bound(p64, d64)
         what = f"n={n} t={t} row={list(SHAPES)[k]}"
         print(f"{what}: worst excess over the bound m {float(err_m.max()):.3e} v {float(err_v.max()):.3e} p {float(err_p.max()):.3e}")
         assert int((err_m > 0).sum()) == 0, what
