@@ -47,6 +47,9 @@ def __getattr__(name):  # lazy: keeps `import robosimgs_amd` torch-free for host
     if name in ("GaussianAdam", "splatfacto_groups"):
         from . import optim
         return getattr(optim, name)
+    if name == "MCMCStrategy":
+        from . import strategy
+        return strategy.MCMCStrategy
     if name in ("render_sharded", "gather_frames", "shard_cameras"):
         from . import distributed
         return getattr(distributed, name)

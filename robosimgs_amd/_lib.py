@@ -38,6 +38,21 @@ class AdamGroup(ctypes.Structure):
 
 ADAM_MAX_GROUPS = 8        # MGS_ADAM_MAX_GROUPS
 
+
+class RefineGroup(ctypes.Structure):
+    """mgs_refine_group (include/mgs_refine.h): one parameter group of mgs_mcmc_relocate, rows of row_floats floats."""
+    _fields_ = [("param", c_void_p), ("exp_avg", c_void_p), ("exp_avg_sq", c_void_p), ("row_floats", c_int32)]
+
+
+class McmcStats(ctypes.Structure):
+    """mgs_mcmc_stats: what the weights pass leaves on the device (the layout of a 16-byte device buffer)."""
+    _fields_ = [("total", c_double), ("n_dead", c_int32), ("n_live", c_int32)]
+
+
+MCMC_RELOCATE, MCMC_ADD = 0, 1             # mgs_mcmc_relocate.mode
+MCMC_MAX_RATIO = 51                        # MGS_MCMC_MAX_RATIO
+REFINE_MAX_GROUPS = 8                      # MGS_REFINE_MAX_GROUPS
+
 # every function include/mgs.h declares: name -> (argtypes, restype)
 p, i, f, u32 = c_void_p, c_int, c_float, c_uint32
 img = POINTER(ImageLoss)
@@ -76,9 +91,17 @@ _SIGNATURES = {
 _OPTIM_SIGNATURES = {
     "mgs_adam_step": ([i, POINTER(AdamGroup), c_double, c_double, c_double, p, p, p, i, c_size_t, p, p], c_int),
 }
+# every function include/mgs_refine.h declares (the same libraries again)
+_REFINE_SIGNATURES = {
+    "mgs_mcmc_weights": ([c_int64, p, f, i, p, p, p, p, POINTER(c_size_t), p], c_int),
+    "mgs_mcmc_relocate": ([i, c_int64, c_int64, c_int64, p, p, i, POINTER(RefineGroup), f, p, p, p, p, p, p,
+                           POINTER(c_size_t), p], c_int),
+    "mgs_mcmc_noise": ([c_int64, p, p, p, p, p, c_double, c_double, c_double, c_int32, p, p], c_int),
+}
 del p, i, f, u32, img
 EXPORTS = list(_SIGNATURES)
 OPTIM_EXPORTS = list(_OPTIM_SIGNATURES)
+REFINE_EXPORTS = list(_REFINE_SIGNATURES)
 
 
 class MgsError(RuntimeError):
@@ -98,7 +121,7 @@ def _load(path: str = None, hooks: bool = False) -> ctypes.CDLL:
     if have != MGS_VERSION:      # shifted parameter lists would end in a GPU fault, not in an error
         raise MgsError(f"{LIB_PATH} reports ABI version {have}, this binding was written for {MGS_VERSION} "
                        "(include/mgs.h): rebuild the library (`python robosimgs_amd/csrc/build.py --force`)")
-    for name, (argtypes, restype) in (*_SIGNATURES.items(), *_OPTIM_SIGNATURES.items()):
+    for name, (argtypes, restype) in (*_SIGNATURES.items(), *_OPTIM_SIGNATURES.items(), *_REFINE_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here == header/library mismatch
         fn.argtypes = argtypes
         fn.restype = restype

@@ -96,19 +96,24 @@ class Trainer:
 
     optimizer = robosimgs_amd.GaussianAdam(..., selective=True): `step` hands it the radii of the last `render` as the
     visibility mask, so the Gaussians that render did not see keep their parameters and moments (gsplat's SelectiveAdam).
-    Every other optimiser is stepped with no arguments."""
+    Every other optimiser is stepped with no arguments.
+
+    strategy = robosimgs_amd.MCMCStrategy(...): `step` ends with strategy.step(self) -- splatfacto-mcmc's relocation and
+    growth when due (the strategy rebinds the trainer to the grown views of its storage) and its noise every step.
+    None (default): nothing is called."""
 
     KEYS = ("means", "quats", "scales", "opacities", "colors")
 
     def __init__(self, params: Dict[str, torch.Tensor], optimizer: Optional[torch.optim.Optimizer], width: int, height: int,
                  auto_reorder_every: int = 500, extra_state: Iterable[torch.Tensor] = (), render_fn=None, bits: int = 10,
-                 raw_params: bool = False, **raster_kwargs):
+                 raw_params: bool = False, strategy=None, **raster_kwargs):
         self.width, self.height = int(width), int(height)
         self.auto_reorder_every = int(auto_reorder_every)
         self.bits = int(bits)
         self.raw_params = bool(raw_params)
         self.raster_kwargs = dict(raster_kwargs, raw_params=True) if self.raw_params else dict(raster_kwargs)
         self._render_fn = render_fn
+        self.strategy = strategy
         self.it = 0
         self.reorders = 0
         self.last_order: Optional[torch.Tensor] = None
@@ -170,6 +175,8 @@ class Trainer:
             self.optimizer.zero_grad(set_to_none=True)
         self.it += 1
         self._since = getattr(self, "_since", 0) + 1
+        if self.strategy is not None:
+            self.strategy.step(self)
 
     def in_original_order(self, x: torch.Tensor) -> torch.Tensor:
         """A per-Gaussian tensor in the trainer's current order -> the order the trainer was built (or last rebound) with."""
