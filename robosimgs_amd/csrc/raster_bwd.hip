@@ -428,8 +428,7 @@ __device__ __forceinline__ void raster_bwd_unit(const int unit,
         cc = conics[3 * (size_t)g + 2];
         op = opacities[g];
       }
-      qmask = quadrant_mask(xy.x, xy.y, ca, cb, cc, op, tile_x, tile_y);
-      qmask &= live;
+      qmask = quadrant_mask(xy.x, xy.y, ca, cb, cc, op, tile_x, tile_y, live);
     }
     const unsigned long long keep = ballot(qmask != 0u);
     const int count = __popcll(keep);

@@ -12,7 +12,8 @@
 // the conic's quadratic form over the quadrant's pixel-centre rectangle; Gaussians that
 // cannot reach alpha >= 1/255 anywhere in the tile are dropped, survivors are compacted
 // into a wave-private LDS queue with ballot + mbcnt, and the wave then walks the queue with
-// broadcast ds_read_b128.  Dropping a Gaussian never changes a pixel: every pixel it would
+// broadcast ds_read_b128 (the forward keeps the four quadrants' lane masks in SGPRs and tests them at the entry's lane;
+// the backward reads the entry's own mask).  Dropping a Gaussian never changes a pixel: every pixel it would
 // have evaluated fails the alpha >= 1/255 test of A.2 step 9.  No workgroup barrier exists
 // anywhere in the kernel.
 #ifndef MGS_RASTER_COMMON_H_
@@ -29,13 +30,21 @@ constexpr int kQueue = 64;
 
 struct QuadRect { float x0, x1, y0, y1; };   // pixel-centre extents of an 8x8 quadrant
 
-// 1D clamped minimum of the quadratic along one rectangle edge.
-//   fixed offset e (edge coordinate - mean) on the "u" axis with weight wu,
-//   free offset in [lo, hi] on the "v" axis with weight wv, cross term b.
-__device__ __forceinline__ float edge_min_sigma(float e, float wu, float wv, float b,
-                                                float inv_wv, float lo, float hi) {
-  float v = fminf(fmaxf(-b * e * inv_wv, lo), hi);
-  return 0.5f * (wu * e * e + wv * v * v) + b * e * v;
+// ---- the cull: exact minimum of the conic's quadratic form over a rectangle of pixel centres ---------------
+// Off the rectangle's interior the minimum lies on one of its four edges.  An edge lies on a LINE: a fixed offset e
+// (line coordinate - mean) on the "u" axis with weight w_u, a free offset v in [lo, hi] on the "v" axis with weight
+// w_v, cross term b.  Along the line sigma(v) = 0.5 w_u e^2 + v (0.5 w_v v + b e), smallest at v = k e with
+// k = -b / w_v, clamped to the edge.  What depends on the line alone is computed once per line -- b e, k e and
+// E = 0.5 w_u e^2 -- and an edge then costs one v_med3_f32 and two FMAs.  The 16 edges of a tile's four quadrants lie
+// on only 8 lines.  (v_med3_f32 returns min3 when an operand is NaN and needs no canonicalising v_max of its inputs;
+// a NaN mean or conic still makes every edge value NaN through b e or E, and NaN keeps the quadrant.)
+struct EdgeLine { float be, ke, E; };
+__device__ __forceinline__ EdgeLine edge_line(float e, float b, float k, float half_wu) {
+  return EdgeLine{b * e, k * e, (half_wu * e) * e};
+}
+__device__ __forceinline__ float edge_min_sigma(const EdgeLine& l, float half_wv, float lo, float hi) {
+  const float v = __builtin_amdgcn_fmed3f(l.ke, lo, hi);
+  return fmaf(v, fmaf(half_wv, v, l.be), l.E);
 }
 
 // min over the rectangle of 0.5*(a dx^2 + c dy^2) + b dx dy, (dx,dy) = p - mean.
@@ -43,40 +52,92 @@ __device__ __forceinline__ float rect_min_sigma(float mx, float my, float a, flo
                                                 float inv_a, float inv_c, const QuadRect& r) {
   float lx = r.x0 - mx, hx = r.x1 - mx, ly = r.y0 - my, hy = r.y1 - my;
   if (lx <= 0.f && hx >= 0.f && ly <= 0.f && hy >= 0.f) return 0.f;
-  float s0 = edge_min_sigma(lx, a, c, b, inv_c, ly, hy);
-  float s1 = edge_min_sigma(hx, a, c, b, inv_c, ly, hy);
-  float s2 = edge_min_sigma(ly, c, a, b, inv_a, lx, hx);
-  float s3 = edge_min_sigma(hy, c, a, b, inv_a, lx, hx);
+  const float ha = 0.5f * a, hc = 0.5f * c, kx = -b * inv_c, ky = -b * inv_a;
+  float s0 = edge_min_sigma(edge_line(lx, b, kx, ha), hc, ly, hy);
+  float s1 = edge_min_sigma(edge_line(hx, b, kx, ha), hc, ly, hy);
+  float s2 = edge_min_sigma(edge_line(ly, b, ky, hc), ha, lx, hx);
+  float s3 = edge_min_sigma(edge_line(hy, b, ky, hc), ha, lx, hx);
   return fminf(fminf(s0, s1), fminf(s2, s3));
 }
 
-// Bit k set <=> the Gaussian may reach alpha >= 1/255 at some pixel centre of quadrant k.
-// Conservative by `slack` (fp32 rounding of both this test and the per-pixel sigma).
-__device__ __forceinline__ unsigned quadrant_mask(float mx, float my, float a, float b, float c,
-                                                  float opac, float tile_x, float tile_y) {
-  if (!(opac >= kAlphaMin)) return 0u;           // alpha <= opac < 1/255 everywhere
-  // (one v_log_f32: __logf compiles to the denormal-safe sequence of fourteen; 255 opac >= 1 here, and the slack below
-  //  is five orders above the instruction's error)
-  float thr = 0.6931471805599453f * __builtin_amdgcn_logf(255.0f * opac);
+// The cull's opacity gate.  alpha <= opacity, but only in exact arithmetic: log2(opacity) and the exponent's polynomial
+// round, and the blend's fp32 alpha does come out at 1/255 at the mean of a Gaussian whose opacity is an ulp short of
+// it (tests/test_cull_host.py).  The polynomial's terms reach |A| m^2 ~ 2e4 for a mean 60 px from the tile centre, five
+// roundings of that are 6e-3 in the exponent, 0.4 % in alpha: the gate sits 5 % below 1/255 -- the constant part of
+// the cull's slack -- and opacities between there and 1/255 are judged like any other, by lim.  False for NaN.
+__device__ __forceinline__ bool cull_opacity_ok(float opac) { return opac >= 0.95f * kAlphaMin; }
+
+// reach[k] = the lanes of the wave whose Gaussian (`valid`: the lane holds one) may reach alpha >= 1/255 at some pixel
+// centre of quadrant k, for the quadrants that still have an open pixel (bit k of the wave-uniform `live`; 0 for the
+// others).  Conservative by `slack` (fp32 rounding of both this test and the per-pixel sigma).  Lane masks, not a
+// per-lane bit mask: the compares leave them in SGPRs, where the forward's walk tests them at an entry's lane.
+// The line offsets are d + 0.5, 7.5, 8.5, 15.5 with d = tile corner - mean: two roundings instead of the one of
+// (corner + offset) - mean, each at most half an ulp of an offset no larger than f = max(|d|, |d + 16|), so sigma
+// moves by at most (|a| + |b|) f * 1.2e-7 f -- a thirtieth of the slack's relative term.  (f as |d + 8| + 8: the same
+// number without fmaxf's canonicalising v_max of an operand from another basic block.)
+// The two lines of a tile column (row) serve the two quadrants of that column (row): the columns come first and
+// leave each live quadrant's smaller edge value in s_k, the rows finish it.  The arithmetic of a quadrant that is not
+// live is skipped with scalar branches (s_k is read only under the bit it was written under).  No lane leaves EXEC.
+__device__ __forceinline__ void quadrant_reach(float mx, float my, float a, float b, float c, float opac, bool valid,
+                                               float tile_x, float tile_y, unsigned live,
+                                               unsigned long long (&reach)[4]) {
+  // (Every condition below is the ballot of ONE compare, combined as 64-bit integers: a ballot of a combined condition
+  //  costs a v_cndmask and a v_cmp to rebuild the lane mask, and as a condition of the quadrants' arithmetic `ok`
+  //  would put it behind a divergent branch.)
+  const unsigned long long ok = ballot(valid) & ballot(cull_opacity_ok(opac));
+  // (one v_log_f32: __logf compiles to the denormal-safe sequence of fourteen; 255 opac >= 0.95 where it counts, and
+  //  the slack below is five orders above the instruction's error)
+  const float thr = 0.6931471805599453f * __builtin_amdgcn_logf(255.0f * opac);
   // (v_rcp_f32, not the IEEE divide's eleven instructions each: the reciprocals only place the clamped minimiser on an
   //  edge, where the quadratic is flat to second order -- a 1-ulp reciprocal moves sigma by ~1e-13 relative, the test
   //  below carries a slack of 0.05; profiles/r5/00_experiments.md section 21)
-  float inv_a = __builtin_amdgcn_rcpf(a), inv_c = __builtin_amdgcn_rcpf(c);
-  float fx = fmaxf(fabsf(tile_x - mx), fabsf(tile_x + 16.f - mx));
-  float fy = fmaxf(fabsf(tile_y - my), fabsf(tile_y + 16.f - my));
-  float slack = 0.05f + 4e-6f * (fabsf(a) + fabsf(c) + 2.f * fabsf(b)) * (fx * fx + fy * fy);
-  float lim = thr + slack;
+  const float kx = -b * __builtin_amdgcn_rcpf(c), ky = -b * __builtin_amdgcn_rcpf(a);
+  const float ha = 0.5f * a, hc = 0.5f * c;
+  const float dx = tile_x - mx, dy = tile_y - my;
+  const float fx = fabsf(dx + 8.f) + 8.f, fy = fabsf(dy + 8.f) + 8.f;
+  const float slack = 0.05f + 4e-6f * (fabsf(a) + fabsf(c) + 2.f * fabsf(b)) * (fx * fx + fy * fy);
+  const float lim = thr + slack;
+  const float ex[4] = {dx + 0.5f, dx + 7.5f, dx + 8.5f, dx + 15.5f};
+  const float ey[4] = {dy + 0.5f, dy + 7.5f, dy + 8.5f, dy + 15.5f};
+  // the mean lies between the two lines of column g / row g: with both, inside the rectangle, where the minimum is 0
+  const unsigned long long in_x[2] = {ballot(ex[0] <= 0.f) & ballot(ex[1] >= 0.f), ballot(ex[2] <= 0.f) & ballot(ex[3] >= 0.f)};
+  const unsigned long long in_y[2] = {ballot(ey[0] <= 0.f) & ballot(ey[1] >= 0.f), ballot(ey[2] <= 0.f) & ballot(ey[3] >= 0.f)};
+  float s0, s1, s2, s3;
+  auto column = [&](int g, float& s_top, float& s_bottom) {      // quadrants g and g + 2
+    if (live & (5u << g)) {
+      const EdgeLine l0 = edge_line(ex[2 * g], b, kx, ha), l1 = edge_line(ex[2 * g + 1], b, kx, ha);
+      if (live & (1u << g)) s_top = fminf(edge_min_sigma(l0, hc, ey[0], ey[1]), edge_min_sigma(l1, hc, ey[0], ey[1]));
+      if (live & (4u << g)) s_bottom = fminf(edge_min_sigma(l0, hc, ey[2], ey[3]), edge_min_sigma(l1, hc, ey[2], ey[3]));
+    }
+  };
+  auto row = [&](int g, float s_left, float s_right, unsigned long long& r_left, unsigned long long& r_right) {   // 2 g, 2 g + 1
+    r_left = r_right = 0ull;
+    if (live & (3u << (2 * g))) {
+      const EdgeLine l0 = edge_line(ey[2 * g], b, ky, hc), l1 = edge_line(ey[2 * g + 1], b, ky, hc);
+      if (live & (1u << (2 * g))) {
+        const float s = fminf(s_left, fminf(edge_min_sigma(l0, ha, ex[0], ex[1]), edge_min_sigma(l1, ha, ex[0], ex[1])));
+        r_left = ok & ((in_x[0] & in_y[g]) | ~ballot(s > lim));           // NaN keeps the quadrant
+      }
+      if (live & (2u << (2 * g))) {
+        const float s = fminf(s_right, fminf(edge_min_sigma(l0, ha, ex[2], ex[3]), edge_min_sigma(l1, ha, ex[2], ex[3])));
+        r_right = ok & ((in_x[1] & in_y[g]) | ~ballot(s > lim));
+      }
+    }
+  };
+  column(0, s0, s2);
+  column(1, s1, s3);
+  row(0, s0, s1, reach[0], reach[1]);
+  row(1, s2, s3, reach[2], reach[3]);
+}
+
+// the same for one lane: bit k <=> this lane's Gaussian reaches (live) quadrant k
+__device__ __forceinline__ unsigned quadrant_mask(float mx, float my, float a, float b, float c, float opac,
+                                                  float tile_x, float tile_y, unsigned live = 0xfu) {
+  unsigned long long reach[4];
+  quadrant_reach(mx, my, a, b, c, opac, true, tile_x, tile_y, live, reach);
   unsigned m = 0;
 #pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    QuadRect r;
-    r.x0 = tile_x + 8.f * (k & 1) + 0.5f;
-    r.x1 = r.x0 + 7.f;
-    r.y0 = tile_y + 8.f * (k >> 1) + 0.5f;
-    r.y1 = r.y0 + 7.f;
-    float s = rect_min_sigma(mx, my, a, b, c, inv_a, inv_c, r);
-    if (!(s > lim)) m |= 1u << k;                // NaN keeps the quadrant
-  }
+  for (int k = 0; k < 4; ++k) m |= __builtin_amdgcn_inverse_ballot_w64(reach[k]) ? 1u << k : 0u;
   return m;
 }
 
@@ -161,6 +222,7 @@ __device__ __forceinline__ size_t ckpt_unit(int start, int tile, int seg, int sh
   return (size_t)(start >> shift) + (size_t)tile + (size_t)seg;
 }
 
+#if defined(__HIPCC__)     // (below: wave-level helpers; the geometry above also compiles for the host, tests/test_cull_host.py)
 // A queue entry part is read from LDS as ONE ds_read_b128: an empty asm that "uses" all four lanes of the register
 // tuple keeps the compiler from narrowing the load to the components the caller happens to touch (it split a 16-byte
 // read into b64 + b32 + 2 x read2_b32: five LDS instructions per entry instead of three).
@@ -252,6 +314,8 @@ __device__ __forceinline__ int wave_reduce_scatter_index(unsigned lane) {
   if (V == 2) return (b3 || b1) ? -1 : b0;
   return lane == 0 ? 0 : -1;
 }
+
+#endif  // __HIPCC__
 
 }  // namespace mgs
 #endif

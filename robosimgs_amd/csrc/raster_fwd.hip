@@ -118,12 +118,13 @@ constexpr bool kMasks = CHT == 3 || CHT == 4;
 // leave `alive`).  15 vector instructions per 64 pairs -- 12 FMA-class, two compares, one v_exp: 45 cycles by
 // scripts/ubench/valu_issue.hip; the round-3 form with the sign of T as the flag had two selects more (16, 51 cycles).
 // gfx940+ needs one wait state after a transcendental before its result is read.
-// LIVE_BIT >= 0 (one wave per tile): bit LIVE_BIT of `live` is cleared the moment the quadrant's last pixel closes, so
-// that the rest of the batch skips the quadrant (the caller ands every entry's quadrant mask with `live`: scalar
-// instructions only; re-deriving the live quadrants with ballots every 8 / 16 / 32 entries was a loss in round 3).
-template <int CHT, bool TRACK_LAST, int LIVE_BIT = -1>
-__device__ __forceinline__ void blend_pixel_safe_asm(PixelState<CHT>& px, unsigned long long& alive, unsigned& live,
-                                                     const PixelPoly& pp,
+// WALK (one wave per tile): `quad` holds the lanes of the batch whose Gaussian reaches this quadrant and `at` the lane
+// that queued this entry.  The body runs only if bit `at` of `quad` is set (s_bitcmp1_b64 and a branch over it), and
+// `quad` is emptied the moment the quadrant's last pixel closes, so that the rest of the batch skips the quadrant:
+// scalar instructions only (re-deriving the live quadrants with ballots every 8 / 16 / 32 entries was a loss in round 3).
+template <int CHT, bool TRACK_LAST, bool WALK = false>
+__device__ __forceinline__ void blend_pixel_safe_asm(PixelState<CHT>& px, unsigned long long& alive,
+                                                     unsigned long long& quad, int at, const PixelPoly& pp,
                                                      float q0, float q1, float q2, float A, float B, float C,
                                                      const float* feat, int idx) {
   static_assert(CHT == 3 || CHT == 4, "hand-written blend: 3 or 4 channels");
@@ -133,6 +134,10 @@ __device__ __forceinline__ void blend_pixel_safe_asm(PixelState<CHT>& px, unsign
   float c3 = CHT == 4 ? px.C[CHT - 1] : 0.f;
   const float f3 = CHT == 4 ? feat[CHT - 1] : 0.f;
   asm volatile(
+      ".if %[walk]\n"
+      "s_bitcmp1_b64 %[quad], %[at]\n"
+      "s_cbranch_scc0 .Lmgs_next_quadrant_%=\n"
+      ".endif\n"
       "s_mov_b64 exec, %[alive]\n"
       "v_fma_f32 %[t1], %[q1], %[x], %[q0]\n"          // pair_power_poly, same order
       "v_fmac_f32 %[t1], %[q2], %[y]\n"
@@ -157,18 +162,18 @@ __device__ __forceinline__ void blend_pixel_safe_asm(PixelState<CHT>& px, unsign
       ".endif\n"
       "s_xor_b64 vcc, vcc, %[acc]\n"                   // counted but not accumulated: the pixels this Gaussian closes
       "s_andn2_b64 %[alive], %[alive], vcc\n"          // (SCC = some pixel of the quadrant is still open)
-      ".if %[livebit] >= 0\n"
-      "s_cselect_b32 vcc_lo, -1, %[clr]\n"
-      "s_and_b32 %[live], %[live], vcc_lo\n"
+      ".if %[walk]\n"
+      "s_cselect_b64 vcc, -1, 0\n"
+      "s_and_b64 %[quad], %[quad], vcc\n"
       ".endif\n"
       "s_mov_b64 exec, -1\n"
-      : [dx] "=&v"(dx), [t0] "=&v"(t0), [t1] "=&v"(t1), [acc] "=&s"(acc), [alive] "+s"(alive), [live] "+s"(live),
+      ".Lmgs_next_quadrant_%=:\n"
+      : [dx] "=&v"(dx), [t0] "=&v"(t0), [t1] "=&v"(t1), [acc] "=&s"(acc), [alive] "+s"(alive), [quad] "+s"(quad),
         [T] "+v"(px.T), [c0] "+v"(px.C[0]), [c1] "+v"(px.C[1]), [c2] "+v"(px.C[2]), [c3] "+v"(c3), [last] "+v"(px.last)
       : [q0] "v"(q0), [q1] "v"(q1), [q2] "v"(q2), [x] "v"(pp.x), [y] "v"(pp.y), [xx] "v"(pp.xx), [xy] "v"(pp.xy),
         [yy] "v"(pp.yy), [A] "v"(A), [B] "v"(B), [C] "v"(C),
         [f0] "v"(feat[0]), [f1] "v"(feat[1]), [f2] "v"(feat[2]), [f3] "v"(f3), [amin] "s"(amin), [tstop] "s"(tstop),
-        [four] "n"(CHT == 4 ? 1 : 0), [track] "n"(TRACK_LAST ? 1 : 0), [idx] "v"(idx), [livebit] "n"(LIVE_BIT),
-        [clr] "n"(LIVE_BIT >= 0 ? ~(1 << LIVE_BIT) : -1)
+        [four] "n"(CHT == 4 ? 1 : 0), [track] "n"(TRACK_LAST ? 1 : 0), [idx] "v"(idx), [walk] "n"(WALK ? 1 : 0), [at] "s"(at)
       : "vcc", "scc");            // (s_xor / s_andn2 write SCC: the loop counter's compare must not straddle the body)
   if (CHT == 4) px.C[CHT - 1] = c3;
 }
@@ -294,18 +299,28 @@ __global__ __launch_bounds__(64 * (TRACK_LAST ? 1 : kFwdWgWaves), (CHT <= 4 ? kF
 #pragma unroll
     for (int c = 0; c < CHT; ++c) c_feat[c] = r_feat[c];
 
-    unsigned qmask = 0;
-    if (c_ok) qmask = (cull ? quadrant_mask(c_xy.x, c_xy.y, c_ca, c_cb, c_cc, c_op, tile_x, tile_y) : 0xfu) & live;
-    const unsigned long long keep = ballot(qmask != 0u);
+    // the cull leaves lane masks: reach[k] = the lanes whose Gaussian reaches (live) quadrant k.  They stay in SGPRs
+    // for the walk, which tests them at the entry's lane instead of reading the entry's mask back from LDS.
+    unsigned long long reach[4];
+    if (cull) {
+      quadrant_reach(c_xy.x, c_xy.y, c_ca, c_cb, c_cc, c_op, c_ok, tile_x, tile_y, live, reach);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) reach[k] = ((live >> k) & 1u) ? ballot(c_ok) : 0ull;
+    }
+    const unsigned long long keep = reach[0] | reach[1] | reach[2] | reach[3];
+    const bool queued = __builtin_amdgcn_inverse_ballot_w64(keep);
     // every queued Gaussian of this batch has a well conditioned conic and an opacity <= 0.999 (nearly
     // always): the sigma >= 0 test and the 0.999 clamp are dead for the whole batch and the walk below runs
     // without them (raster_common.h: sigma_sign_is_safe) -- two compare / min class instructions less per 64 pairs
-    const bool all_safe = ballot(qmask != 0u && !entry_is_safe(c_ca, c_cb, c_cc, c_op)) == 0ull;
-    const int count = __popcll(keep);
+    const bool all_safe = ballot(queued && !entry_is_safe(c_ca, c_cb, c_cc, c_op)) == 0ull;
     MGS_STAT(0, __popcll(ballot(c_ok)));
-    MGS_STAT(1, count);
+    MGS_STAT(1, __popcll(keep));
     MGS_STAT(5, 1);
-    if (qmask != 0u) {
+    if (queued) {
+      unsigned qmask = 0;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) qmask |= __builtin_amdgcn_inverse_ballot_w64(reach[k]) ? 1u << k : 0u;
       QueueEntry<CHT>& e = queue[mask_rank(keep)];
       const float sA = -0.5f * kLog2e * c_ca, sB = -kLog2e * c_cb, sC = -0.5f * kLog2e * c_cc;
       const float m_x = c_xy.x - ctr_x, m_y = c_xy.y - ctr_y;
@@ -327,9 +342,11 @@ __global__ __launch_bounds__(64 * (TRACK_LAST ? 1 : kFwdWgWaves), (CHT <= 4 ? kF
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 
-    // (measured and rejected: reading entry j+1 while blending entry j, 307 vs 292 us; two
-    //  entries per loop trip, 291 vs 288 us)
-    auto blend_entry = [&](auto safe_tag, const float4& g0, const float4& g1, const float4* ef, const float4& g3) {
+    // (measured and rejected in round 1: reading entry j+1 while blending entry j, 307 vs 292 us; two entries per trip
+    //  of the counted loop, 291 vs 288 us.  The four-entry trip of the walk below is about the queue pointer's v_add.)
+    // `at`: the lane that queued this entry
+    auto blend_entry = [&](auto safe_tag, int at, const float4& g0, const float4& g1, const float4* ef,
+                           const float4& g3) {
       constexpr bool SAFE = decltype(safe_tag)::value;
       float feat[CHT];
 #pragma unroll
@@ -339,21 +356,21 @@ __global__ __launch_bounds__(64 * (TRACK_LAST ? 1 : kFwdWgWaves), (CHT <= 4 ? kF
         if (4 * f + 2 < CHT) feat[4 * f + 2] = ef[f].z;
         if (4 * f + 3 < CHT) feat[4 * f + 3] = ef[f].w;
       }
-      // (kMasks: `live` loses a quadrant's bit the moment its last pixel closes, blend_pixel_safe_asm)
-      const unsigned m = __builtin_amdgcn_readfirstlane(__float_as_uint(g1.z)) & (kMasks<CHT> ? live : 0xfu);
       const int idx = __float_as_int(g1.w);
-      MGS_STAT(2, __popc(m));
       // (measured and rejected, profiles/r3/00_experiments.md: one straight-line body per quadrant SET behind a
       //  switch on the mask, 268-278 us against 197; the live quadrants re-derived every 8 / 16 / 32 entries, +2 %)
       auto quad = [&](auto kc) {
         constexpr int k = decltype(kc)::value;
-        if (m & (1u << k)) {
-          if constexpr (kMasks<CHT> && SAFE)
-            blend_pixel_safe_asm<CHT, TRACK_LAST, k>(st[k], alive[k], live, pq[k], g0.x, g0.y, g0.z, g0.w, g1.x, g1.y,
-                                                     feat, idx);
-          else
-            blend_pixel<CHT, TRACK_LAST, SAFE, kMasks<CHT>>(st[k], alive[k], pq[k], g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g3.x,
-                                                             g3.y, feat, idx);
+        // (kMasks: reach[k] is emptied the moment the quadrant's last pixel closes, blend_pixel_safe_asm)
+        MGS_STAT(2, (unsigned)((reach[k] >> at) & 1ull));
+        if constexpr (kMasks<CHT> && SAFE) {
+          // (the body tests reach[k] at `at` itself, s_bitcmp1_b64 and a branch: the compiler's own test of a
+          //  variable bit of a 64-bit mask is a shift, an AND and a compare on top of the branch)
+          blend_pixel_safe_asm<CHT, TRACK_LAST, true>(st[k], alive[k], reach[k], at, pq[k], g0.x, g0.y, g0.z, g0.w, g1.x,
+                                                      g1.y, feat, idx);
+        } else if ((reach[k] >> at) & 1ull) {
+          blend_pixel<CHT, TRACK_LAST, SAFE, kMasks<CHT>>(st[k], alive[k], pq[k], g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g3.x,
+                                                           g3.y, feat, idx);
         }
       };
       quad(std::integral_constant<int, 0>{});
@@ -363,8 +380,11 @@ __global__ __launch_bounds__(64 * (TRACK_LAST ? 1 : kFwdWgWaves), (CHT <= 4 ? kF
     };
     auto walk = [&](auto safe_tag) {
       constexpr bool SAFE = decltype(safe_tag)::value;
-      for (int j = 0; j < count; ++j) {
-        const QueueEntry<CHT>& e = queue[j];
+      // entry j was queued by the lane of the j-th set bit of `keep`: the walk scans those bits (s_ff1 / s_bitset0)
+      unsigned long long rest = keep;
+      auto entry = [&](const QueueEntry<CHT>& e) {
+        const int at = __builtin_ctzll(rest);
+        asm("s_bitset0_b64 %0, %1" : "+s"(rest) : "s"(at));
         float4 g0, g1, ef[(CHT + 3) / 4];
         if constexpr (CHT <= 4) {
           lds_read_3f4(&e.geo0, &e.geo1, &e.feat[0], g0, g1, ef[0]);
@@ -375,7 +395,25 @@ __global__ __launch_bounds__(64 * (TRACK_LAST ? 1 : kFwdWgWaves), (CHT <= 4 ? kF
         }
         float4 g3 = make_float4(0.f, 0.f, 0.f, 0.f);
         if constexpr (!SAFE) g3 = e.geo3;            // the mean's offset: only the sigma >= 0 test reads it
-        blend_entry(safe_tag, g0, g1, ef, g3);
+        blend_entry(safe_tag, at, g0, g1, ef, g3);
+      };
+      if (rest == 0ull) return;
+      const QueueEntry<CHT>* e = queue;
+      if constexpr (kMasks<CHT> && SAFE) {
+        // four entries per trip, each leaving the moment the queue is empty: the LDS address advances through the
+        // reads' immediate offsets, one v_add per four entries (no remainder loop: the exits are the loop test)
+        for (;; e += 4) {
+          entry(e[0]);
+          if (rest == 0ull) break;
+          entry(e[1]);
+          if (rest == 0ull) break;
+          entry(e[2]);
+          if (rest == 0ull) break;
+          entry(e[3]);
+          if (rest == 0ull) break;
+        }
+      } else {
+        do entry(*e++); while (rest != 0ull);
       }
     };
     if (all_safe) walk(std::true_type{}); else walk(std::false_type{});
@@ -537,7 +575,7 @@ __global__ __launch_bounds__(256) void raster_fwd_q_kernel(    // (bounded to 64
       keep_me = true;
       if (cull) {
         keep_me = false;
-        if (c_op >= kAlphaMin) {
+        if (cull_opacity_ok(c_op)) {
           // (single v_log_f32 / v_rcp_f32, as in quadrant_mask: the slack is orders above their error)
           const float thr = 0.6931471805599453f * __builtin_amdgcn_logf(255.0f * c_op);
           const float fx = fmaxf(fabsf(tile_x - c_xy.x), fabsf(tile_x + 16.f - c_xy.x));
@@ -596,8 +634,8 @@ __global__ __launch_bounds__(256) void raster_fwd_q_kernel(    // (bounded to 64
           if (4 * f + 3 < CHT) feat[4 * f + 3] = v.w;
         }
         if constexpr (kMasks<CHT> && SAFE) {
-          unsigned unused = 0;
-          blend_pixel_safe_asm<CHT, TRACK_LAST>(st, alive, unused, pp, g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, feat, __float_as_int(g1.w));
+          unsigned long long unused = 0;
+          blend_pixel_safe_asm<CHT, TRACK_LAST>(st, alive, unused, 0, pp, g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, feat, __float_as_int(g1.w));
         } else {
           float4 g3 = make_float4(0.f, 0.f, 0.f, 0.f);
           if constexpr (!SAFE) g3 = e.geo3;
