@@ -15,7 +15,7 @@ __version__ = "0.1.0"
 
 _DEVICE_API = {"rasterization", "render", "check_isect_status", "fully_fused_projection",
                "spherical_harmonics", "isect_tiles", "isect_offset_encode",
-               "rasterize_to_pixels", "render_sharded", "gather_frames"}
+               "rasterize_to_pixels", "rasterize_labels", "render_sharded", "gather_frames"}
 
 
 def __getattr__(name):  # lazy: keeps `import robosimgs_amd` torch-free for host-only use
@@ -23,7 +23,7 @@ def __getattr__(name):  # lazy: keeps `import robosimgs_amd` torch-free for host
         from . import rendering
         return getattr(rendering, name)
     if name in ("fully_fused_projection", "spherical_harmonics", "isect_tiles",
-                "isect_offset_encode", "rasterize_to_pixels"):
+                "isect_offset_encode", "rasterize_to_pixels", "rasterize_labels"):
         from . import ops
         return getattr(ops, name)
     if name in ("composite_over", "frame_to_u8"):

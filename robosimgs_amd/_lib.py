@@ -98,10 +98,19 @@ _REFINE_SIGNATURES = {
                            POINTER(c_size_t), p], c_int),
     "mgs_mcmc_noise": ([c_int64, p, p, p, p, p, c_double, c_double, c_double, c_int32, p, p], c_int),
 }
+# every function include/mgs_labels.h declares (the same libraries again): mgs_render_frames_labeled is
+# mgs_render_frames with (class_ids, n_classes, labels, label_weights) in front of the workspace
+_LABEL_SIGNATURES = {
+    "mgs_raster_labels": ([i, p, p, p, p, p, i, i, i, i, i, p, p, p, p, p, p], c_int),
+    "mgs_render_frames_labeled": (_SIGNATURES["mgs_render_frames"][0][:-3] + [p, i, p, p]
+                                  + _SIGNATURES["mgs_render_frames"][0][-3:], c_int),
+}
 del p, i, f, u32, img
 EXPORTS = list(_SIGNATURES)
 OPTIM_EXPORTS = list(_OPTIM_SIGNATURES)
 REFINE_EXPORTS = list(_REFINE_SIGNATURES)
+LABEL_EXPORTS = list(_LABEL_SIGNATURES)
+LABEL_NONE, LABELS_MAX_CLASSES = 255, 32    # MGS_LABEL_NONE, MGS_LABELS_MAX_CLASSES
 
 
 class MgsError(RuntimeError):
@@ -121,7 +130,8 @@ def _load(path: str = None, hooks: bool = False) -> ctypes.CDLL:
     if have != MGS_VERSION:      # shifted parameter lists would end in a GPU fault, not in an error
         raise MgsError(f"{LIB_PATH} reports ABI version {have}, this binding was written for {MGS_VERSION} "
                        "(include/mgs.h): rebuild the library (`python robosimgs_amd/csrc/build.py --force`)")
-    for name, (argtypes, restype) in (*_SIGNATURES.items(), *_OPTIM_SIGNATURES.items(), *_REFINE_SIGNATURES.items()):
+    for name, (argtypes, restype) in (*_SIGNATURES.items(), *_OPTIM_SIGNATURES.items(), *_REFINE_SIGNATURES.items(),
+                                      *_LABEL_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here == header/library mismatch
         fn.argtypes = argtypes
         fn.restype = restype

@@ -8,6 +8,7 @@
 // allocation: a batch is capturable in a hipGraph like a single frame.  What a non-Python host calls to "render these
 // cameras", and what rasterization(C > 1) uses instead of 3 C ctypes calls with their tensor bookkeeping.
 #include "mgs_common.h"
+#include "../../include/mgs_labels.h"
 
 namespace {
 // What the three drivers share: the argument checks, the tile grid, and what the frames flags tell the stage entry points.
@@ -65,16 +66,25 @@ struct FrameWs {
     total = b.total;
   }
 };
-}  // namespace
 
-extern "C" int mgs_render_frames(int n, const float* means, const float* quats, const float* scales,
-                                 const float* opacities, int sh_degree, int coeff_stride, const float* sh_coeffs,
-                                 int n_cams, const float* viewmats, const float* Ks, int width, int height,
-                                 float eps2d, float near_plane, float far_plane, float radius_clip,
-                                 int antialiased, int channels, int flags, const float* backgrounds,
-                                 uint32_t isect_capacity, float* render, float* alphas, uint32_t* n_isect,
-                                 uint32_t* status, uint8_t* ds_rgba, void* ds_distance, int ds_distance_type,
-                                 const double* ds_Kinv_host, void* workspace, size_t* workspace_bytes, mgs_stream_t stream) {
+// What mgs_render_frames_labeled adds to a camera's launches (include/mgs_labels.h); class_ids == nullptr: nothing.
+struct LabelOut {
+  const int32_t* class_ids;
+  int n_classes;
+  uint8_t* labels;
+  float* weights;
+};
+
+// The body of mgs_render_frames and mgs_render_frames_labeled.
+int render_frames_impl(int n, const float* means, const float* quats, const float* scales,
+                       const float* opacities, int sh_degree, int coeff_stride, const float* sh_coeffs,
+                       int n_cams, const float* viewmats, const float* Ks, int width, int height,
+                       float eps2d, float near_plane, float far_plane, float radius_clip,
+                       int antialiased, int channels, int flags, const float* backgrounds,
+                       uint32_t isect_capacity, float* render, float* alphas, uint32_t* n_isect,
+                       uint32_t* status, uint8_t* ds_rgba, void* ds_distance, int ds_distance_type,
+                       const double* ds_Kinv_host, const LabelOut& lab, void* workspace, size_t* workspace_bytes,
+                       mgs_stream_t stream) {
   Frames f;
   int rc = frames_prologue("render_frames", n, n_cams, width, height, channels, flags, opacities, isect_capacity, workspace_bytes, &f);
   if (rc) return rc;
@@ -128,8 +138,46 @@ extern "C" int mgs_render_frames(int n, const float* means, const float* quats, 
                            ds_distance ? static_cast<char*>(ds_distance) + n_px * ds_dist_bytes * c : nullptr, ds_distance_type,
                            ds_Kinv_host, stream);
     if (rc) return rc;
+    if (lab.class_ids) {
+      rc = mgs_raster_labels(n, nullptr, nullptr, nullptr, splats, lab.class_ids, lab.n_classes, width, height, tile_w, tile_h,
+                             offsets, flatten, order, lab.labels + n_px * c, lab.weights ? lab.weights + n_px * c : nullptr, stream);
+      if (rc) return rc;
+    }
   }
   return MGS_OK;
+}
+}  // namespace
+
+extern "C" int mgs_render_frames(int n, const float* means, const float* quats, const float* scales,
+                                 const float* opacities, int sh_degree, int coeff_stride, const float* sh_coeffs,
+                                 int n_cams, const float* viewmats, const float* Ks, int width, int height,
+                                 float eps2d, float near_plane, float far_plane, float radius_clip,
+                                 int antialiased, int channels, int flags, const float* backgrounds,
+                                 uint32_t isect_capacity, float* render, float* alphas, uint32_t* n_isect,
+                                 uint32_t* status, uint8_t* ds_rgba, void* ds_distance, int ds_distance_type,
+                                 const double* ds_Kinv_host, void* workspace, size_t* workspace_bytes, mgs_stream_t stream) {
+  return render_frames_impl(n, means, quats, scales, opacities, sh_degree, coeff_stride, sh_coeffs, n_cams, viewmats, Ks, width,
+                            height, eps2d, near_plane, far_plane, radius_clip, antialiased, channels, flags, backgrounds,
+                            isect_capacity, render, alphas, n_isect, status, ds_rgba, ds_distance, ds_distance_type,
+                            ds_Kinv_host, LabelOut{nullptr, 0, nullptr, nullptr}, workspace, workspace_bytes, stream);
+}
+
+extern "C" int mgs_render_frames_labeled(int n, const float* means, const float* quats, const float* scales,
+                                         const float* opacities, int sh_degree, int coeff_stride, const float* sh_coeffs,
+                                         int n_cams, const float* viewmats, const float* Ks, int width, int height,
+                                         float eps2d, float near_plane, float far_plane, float radius_clip,
+                                         int antialiased, int channels, int flags, const float* backgrounds,
+                                         uint32_t isect_capacity, float* render, float* alphas, uint32_t* n_isect,
+                                         uint32_t* status, uint8_t* ds_rgba, void* ds_distance, int ds_distance_type,
+                                         const double* ds_Kinv_host, const int32_t* class_ids, int n_classes,
+                                         uint8_t* labels, float* label_weights, void* workspace, size_t* workspace_bytes,
+                                         mgs_stream_t stream) {
+  const int rc = mgs::check_label_args("render_frames_labeled", class_ids, n_classes, labels);
+  if (rc) return rc;
+  return render_frames_impl(n, means, quats, scales, opacities, sh_degree, coeff_stride, sh_coeffs, n_cams, viewmats, Ks, width,
+                            height, eps2d, near_plane, far_plane, radius_clip, antialiased, channels, flags, backgrounds,
+                            isect_capacity, render, alphas, n_isect, status, ds_rgba, ds_distance, ds_distance_type,
+                            ds_Kinv_host, LabelOut{class_ids, n_classes, labels, label_weights}, workspace, workspace_bytes, stream);
 }
 
 // ---- a batch of TRAINING frames behind two C calls ----------------------------------------------------------------

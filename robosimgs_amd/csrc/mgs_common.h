@@ -131,6 +131,11 @@ __attribute__((visibility("hidden"))) size_t isect_tiles_workspace_bytes(int n, 
 __attribute__((visibility("hidden"))) size_t rasterize_bwd_det_workspace_bytes(int channels, bool absgrad, uint32_t capacity,
                                                                                int tile_w, int tile_h, int checkpoint_interval);
 
+// The label arguments mgs_raster_labels and mgs_render_frames_labeled share (labels.hip; include/mgs_labels.h): checked
+// under the caller's name `fn` before anything is enqueued.
+__attribute__((visibility("hidden"))) int check_label_args(const char* fn, const int32_t* class_ids, int n_classes,
+                                                           const uint8_t* labels);
+
 // Radix sort of (key, value) uint32 pairs on bits [0, key_bits) with the element count read
 // from device memory.  Buffers a/b alternate; the sorted result ends in (keys_out, vals_out).
 // temp: radix_sort_temp_bytes(capacity).

@@ -6,6 +6,7 @@ Appendix A.1), each a thin torch wrapper over one C-ABI entry point of libmgs.so
     isect_tiles              -> mgs_isect_tiles
     isect_offset_encode      -> mgs_isect_offset_encode
     rasterize_to_pixels      -> mgs_rasterize_fwd / mgs_rasterize_bwd
+    rasterize_labels         -> mgs_raster_labels (include/mgs_labels.h; no gsplat counterpart, no backward)
 
 Inputs are post-activation fp32 CUDA(HIP) tensors (the render-path calls also take the raw form, log-scales and
 opacity logits, with raw=True: include/mgs.h MGS_PARAMS_RAW); ids are int32, keys int64.  All kernels
@@ -247,14 +248,16 @@ def _frames_call(means, quats, scales, opacities, sh_degree, sh_coeffs, viewmats
 def render_frames_raw(means, quats, scales, opacities, sh_degree, sh_coeffs, viewmats, Ks, width, height,
                       eps2d, near_plane, far_plane, radius_clip, antialiased, with_depth, capacity,
                       backgrounds=None, expected_last=False, latency=False, out=None, tight=True, per_axis=False,
-                      dataset=None, float_frame=True, camera=0, raw=False):
+                      dataset=None, float_frame=True, camera=0, labels=None, raw=False):
     """mgs_render_frames: C inference frames in one C call (no per-Gaussian outputs, scratch reused from camera to
     camera).  viewmats [C,4,4], Ks [C,3,3], backgrounds [C,ch] or None.  Returns (render [C,H,W,ch], alphas [C,H,W],
     n_isects [C] i32, isect_status [C] i32); out = (render, alphas) to write into existing buffers.
     tight=False: gsplat's classic tile rectangles (MGS_FRAMES_CLASSIC_BOUNDS; same pixels, classic counts).
     dataset = (rgba uint8 [C,H,W,4], distance [C,H,W,1] or None, K): the dataset frames straight out of the raster
     (with_depth and expected_last required); float_frame=False then leaves render / alphas unwritten.
-    raw: scales are log-scales and opacities logits (MGS_PARAMS_RAW)."""
+    raw: scales are log-scales and opacities logits (MGS_PARAMS_RAW).
+    labels = (class_ids int32 [N], n_classes, labels uint8 [C,H,W], label_weights [C,H,W] or None): the call is
+    mgs_render_frames_labeled, which also writes every camera's label frame (include/mgs_labels.h)."""
     dev = means.device
     C = viewmats.shape[0]
     render, alphas, args = _frames_call(means, quats, scales, opacities, sh_degree, sh_coeffs, viewmats, Ks, width, height,
@@ -266,7 +269,13 @@ def render_frames_raw(means, quats, scales, opacities, sh_degree, sh_coeffs, vie
              ptr(alphas) if (float_frame or dataset is None) else None, ptr(n_isect), ptr(status)]
     ds = dataset_args(dataset, C, height, width, dev)
     args += list(ds[:4])
-    sized_call(_lib.lib().mgs_render_frames, args, dev, cached=True)
+    if labels is not None:
+        class_ids, n_classes, lab, lab_w = labels
+        check_label_buffers(class_ids, means.shape[0], n_classes, lab, lab_w, (C, height, width))
+        args += [ptr(class_ids), int(n_classes), ptr(lab), ptr(lab_w)]
+        sized_call(_lib.lib().mgs_render_frames_labeled, args, dev, cached=True)
+    else:
+        sized_call(_lib.lib().mgs_render_frames, args, dev, cached=True)
     return render, alphas, n_isect, status
 
 
@@ -446,6 +455,65 @@ def rasterize_fwd_raw(means2d, conics, feats, opacities, background, width, heig
                                        int(checkpoint_interval), *ds[:4], stream_handle()),
           "mgs_rasterize_fwd")
     return render, alphas, last_ids
+
+
+def class_ids_i32(class_ids, n: int) -> Tensor:
+    """class_ids as the kernels read them: any integer tensor [n] on the device -> contiguous int32."""
+    require_device(class_ids)
+    if class_ids.dtype in (torch.float16, torch.bfloat16, torch.float32, torch.float64, torch.bool) or class_ids.is_complex():
+        raise ValueError(f"class_ids must be an integer tensor, got {class_ids.dtype}")
+    if tuple(class_ids.shape) != (n,):
+        raise ValueError(f"class_ids shape {tuple(class_ids.shape)} != ({n},): one class per Gaussian")
+    return class_ids.to(torch.int32).contiguous()
+
+
+def check_n_classes(n_classes) -> int:
+    n_classes = int(n_classes)
+    if not 1 <= n_classes <= _lib.LABELS_MAX_CLASSES:
+        raise ValueError(f"n_classes {n_classes} outside 1..{_lib.LABELS_MAX_CLASSES}")
+    return n_classes
+
+
+def check_label_buffers(class_ids, n, n_classes, labels, weights, shape) -> None:
+    """The kernels write prod(shape) label bytes (and as many floats) through raw pointers and gather class_ids at every
+    listed Gaussian: the buffers must hold exactly that."""
+    check_n_classes(n_classes)
+    if class_ids.dtype != torch.int32 or not class_ids.is_contiguous() or class_ids.numel() != n:
+        raise ValueError(f"class_ids must be a contiguous int32 tensor of {n} entries (class_ids_i32)")
+    if labels.dtype != torch.uint8 or not labels.is_contiguous() or tuple(labels.shape) != tuple(shape):
+        raise ValueError(f"labels must be a contiguous uint8 tensor {tuple(shape)}")
+    if weights is not None and (weights.dtype != torch.float32 or not weights.is_contiguous()
+                                or tuple(weights.shape) != tuple(shape)):
+        raise ValueError(f"label_weights must be a contiguous float32 tensor {tuple(shape)}")
+    require_device(class_ids, labels, weights)
+
+
+def raster_labels_raw(tl: "TileLists", class_ids, n_classes, width, height, means2d=None, conics=None, opacities=None,
+                      splats=None, out=None, return_weights=True, use_group_order=True, tile_offsets=None):
+    """mgs_raster_labels on one camera's lists: labels uint8 [H,W] and (return_weights) label_weights [H,W], the class
+    with the largest share of each pixel's blend weights and that share (include/mgs_labels.h).  class_ids: int32 [n]
+    (class_ids_i32), n the rows of `splats` -- the packed records the frame's raster read -- or of means2d / conics /
+    opacities.  out = (labels, label_weights|None) to write into existing buffers.  use_group_order: start the tiles in
+    tl.group_order where the lists have one (a schedule, never a result); tile_offsets: another offset table than
+    tl.tile_offsets (a camera's slice of a concatenated one)."""
+    src = splats if splats is not None else means2d
+    if src is None or (splats is None and (conics is None or opacities is None)):
+        raise ValueError("raster_labels_raw needs splats, or means2d, conics and opacities")
+    n, dev = src.shape[0], src.device
+    if out is None:
+        labels = torch.empty(height, width, dtype=torch.uint8, device=dev)
+        weights = torch.empty(height, width, dtype=torch.float32, device=dev) if return_weights else None
+    else:
+        labels, weights = out
+    check_label_buffers(class_ids, n, n_classes, labels, weights, (height, width))
+    tile_w, tile_h = -(-width // TILE_SIZE), -(-height // TILE_SIZE)
+    order = getattr(tl, "group_order", None) if use_group_order else None
+    check(_lib.lib().mgs_raster_labels(n, ptr(means2d), ptr(conics), ptr(opacities), ptr(splats), ptr(class_ids),
+                                       int(n_classes), width, height, tile_w, tile_h,
+                                       ptr(tile_offsets if tile_offsets is not None else tl.tile_offsets),
+                                       ptr(tl.flatten_ids), ptr(order), ptr(labels), ptr(weights), stream_handle()),
+          "mgs_raster_labels")
+    return labels, weights
 
 
 def rasterize_bwd_raw(means2d, conics, feats, opacities, background, width, height, tile_w,
@@ -782,3 +850,42 @@ def rasterize_to_pixels(means2d: Tensor, conics: Tensor, colors: Tensor, opaciti
     return _RasterizeToPixels.apply(_f32c(means2d), _f32c(conics), _f32c(colors),
                                     _f32c(opacities), _f32c(backgrounds), int(image_width),
                                     int(image_height), offsets_ext, flatten_ids, bool(absgrad))
+
+
+@torch.no_grad()
+def rasterize_labels(means2d: Tensor, conics: Tensor, opacities: Tensor, class_ids: Tensor, n_classes: int,
+                     image_width: int, image_height: int, tile_size: int, isect_offsets: Tensor, flatten_ids: Tensor,
+                     return_weights: bool = False):
+    """Per-pixel part labels of the frames rasterize_to_pixels blends from the same arguments: means2d [C,N,2], conics
+    [C,N,3], opacities [C,N], class_ids [N] (any integer type), isect_offsets [C,th,tw], flatten_ids [n_isects] ->
+    labels [C,H,W] uint8, the class k in 0..n_classes-1 (n_classes <= 32) with the largest sum of blend weights at the
+    pixel, ties to the lowest k, 255 where no counted Gaussian has such a class; with return_weights also that sum,
+    [C,H,W] float32.  A Gaussian whose class is outside 0..n_classes-1 occludes and is never reported.  The weights are
+    the blend's own bit for bit.  Not differentiable."""
+    if tile_size != TILE_SIZE:
+        raise NotImplementedError(f"tile_size must be {TILE_SIZE}")
+    require_device(means2d, conics, opacities, isect_offsets, flatten_ids)
+    C, N = means2d.shape[0], means2d.shape[1]
+    if conics.shape != (C, N, 3) or opacities.shape != (C, N) or means2d.shape != (C, N, 2):
+        raise ValueError("expected means2d [C,N,2], conics [C,N,3], opacities [C,N]")
+    n_classes = check_n_classes(n_classes)
+    width, height = int(image_width), int(image_height)
+    tile_w, tile_h = -(-width // TILE_SIZE), -(-height // TILE_SIZE)
+    if tuple(isect_offsets.shape) != (C, tile_h, tile_w):
+        raise ValueError(f"isect_offsets shape {tuple(isect_offsets.shape)} != {(C, tile_h, tile_w)}")
+    n_tiles = tile_w * tile_h
+    dev = means2d.device
+    # ids in flatten_ids are cam*N + gaussian: the kernel gets the flat [C*N,...] views and the classes once per camera
+    cls = class_ids_i32(class_ids, N).repeat(C)
+    means2d, conics, opacities = _f32c(means2d.detach()), _f32c(conics.detach()), _f32c(opacities.detach())
+    tl = TileLists()
+    tl.flatten_ids = flatten_ids.to(torch.int32).contiguous()
+    end = torch.full((1,), tl.flatten_ids.numel(), dtype=torch.int32, device=dev)
+    offsets_ext = torch.cat([isect_offsets.reshape(-1).to(torch.int32), end])
+    labels = torch.empty(C, height, width, dtype=torch.uint8, device=dev)
+    weights = torch.empty(C, height, width, dtype=torch.float32, device=dev) if return_weights else None
+    for c in range(C):
+        raster_labels_raw(tl, cls, n_classes, width, height, means2d.view(C * N, 2), conics.view(C * N, 3),
+                          opacities.view(C * N), out=(labels[c], weights[c] if return_weights else None), use_group_order=False,
+                          tile_offsets=offsets_ext[c * n_tiles:])
+    return (labels, weights) if return_weights else labels

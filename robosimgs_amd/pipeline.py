@@ -105,7 +105,8 @@ class FrameRenderer:
                  capacity_margin: float = 1.5, background: Optional[torch.Tensor] = None,
                  sizing_camera=None, group_ids: Optional[torch.Tensor] = None, n_groups: int = 0,
                  rotate_sh: bool = True, reorder: Optional[str] = "morton", dataset_output=None, dataset_K=None,
-                 dataset_keep_float: bool = False, **raster_kw):
+                 dataset_keep_float: bool = False, class_ids: Optional[torch.Tensor] = None, n_classes: Optional[int] = None,
+                 labels: bool = False, **raster_kw):
         """tensors: dict(means, quats, scales, opacities, colors, sh_degree) on the GPU
         (Gaussians.to_torch()); `self.t` is the renderer's own (by default Morton-ordered) copy.  isect_capacity: slots reserved for tile intersections per
         frame; if None it is measured once with `sizing_camera` = (viewmat, K) (required then)
@@ -125,6 +126,12 @@ class FrameRenderer:
         starts with mgs_transform_gaussians(rest pose -> copy) reading the slot's transform buffer,
         so a posed frame costs one small upload and 14-97 us of GPU time more than a static one.
 
+        Part labels (rasterization's class_ids / n_classes): class_ids -- any integer tensor [N] on the GPU,
+        in the order of `tensors` (the renderer permutes it along with its Morton copy), with n_classes beside it -- or
+        labels=True with group_ids: class = group id + 1, the static Gaussians class 0, n_classes = n_groups + 1.  Every
+        slot's graphs then hold the label launch, and fetch() / render() also return "labels" [H,W] uint8 (255: no part)
+        and "label_weights" [H,W] float32, the slot's own buffers like the frame.
+
         raw_params=True (forwarded to rasterization like every raster_kw): `tensors` hold log-scales and opacity logits
         (Gaussians.to_torch(raw=True)), so a loaded .ply renders without an activation pass on the host.  Static scenes
         only: the group transform multiplies activated scales by the group's s."""
@@ -141,6 +148,20 @@ class FrameRenderer:
         if reorder not in (None, "morton"):
             raise ValueError(f"reorder {reorder!r} not in (None, 'morton')")
         self.order = None
+        n_all = tensors["means"].shape[0]
+        if class_ids is not None:
+            if labels and group_ids is not None:
+                raise ValueError("give class_ids or labels=True (classes from group_ids), not both")
+            if tuple(class_ids.shape) != (n_all,) or not class_ids.is_cuda:
+                raise ValueError(f"class_ids must be an integer tensor [{n_all}] on the GPU")
+            if n_classes is None:
+                n_classes = int(class_ids.max().item()) + 1
+        elif labels:
+            if group_ids is None:
+                raise ValueError("labels=True takes its classes from group_ids: give group_ids / n_groups, or class_ids")
+            class_ids, n_classes = group_ids.to(torch.int32) + 1, int(n_groups) + 1
+        elif n_classes is not None:
+            raise ValueError("n_classes given without class_ids")
         if reorder == "morton" and tensors["means"].shape[0] > 1:
             self.order = locality_order(tensors["means"])
             n = tensors["means"].shape[0]
@@ -148,7 +169,12 @@ class FrameRenderer:
                            if torch.is_tensor(v) and v.dim() >= 1 and v.shape[0] == n else v) for k, v in tensors.items()}
             if group_ids is not None:
                 group_ids = group_ids.index_select(0, self.order)
+            if class_ids is not None:
+                class_ids = class_ids.index_select(0, self.order)
         self.t = tensors
+        # the classes in the renderer's own index order (None: no label frames)
+        self.class_ids = class_ids.to(torch.int32).contiguous() if class_ids is not None else None
+        self.n_classes = int(n_classes) if class_ids is not None else None
         self.group_ids = group_ids.to(torch.int32).contiguous() if group_ids is not None else None
         self.n_groups = int(n_groups)
         self.rotate_sh = bool(rotate_sh) and int(tensors.get("sh_degree") or 0) >= 1
@@ -180,7 +206,7 @@ class FrameRenderer:
             if sizing_camera is None:
                 raise ValueError("give isect_capacity or a sizing_camera=(viewmat, K)")
             vm, K = self._cam_tensors(*sizing_camera)
-            _, _, meta = self._raster(vm, K, None)
+            _, _, meta = self._raster(vm, K, None, labels=False)
             isect_capacity = int(int(meta["n_isects"].max().item()) * capacity_margin) + 4096
         self.capacity = int(isect_capacity)
         self.n_slots = max(1, int(frames_in_flight))
@@ -196,9 +222,11 @@ class FrameRenderer:
         Kt = torch.as_tensor(np.asarray(K, dtype=np.float32)).reshape(1, 3, 3).to(self.dev)
         return vm, Kt
 
-    def _raster(self, vm, K, cap, t=None, dataset_out=None, schedule=None):
+    def _raster(self, vm, K, cap, t=None, dataset_out=None, schedule=None, labels=True):
         t = self.t if t is None else t
         kw = self.kw if schedule is None else dict(self.kw, raster_schedule=schedule)
+        if labels and self.class_ids is not None:
+            kw = dict(kw, class_ids=self.class_ids, n_classes=self.n_classes)
         return rasterization(t["means"], t["quats"], t["scales"], t["opacities"], t["colors"], vm,
                              K, self.width, self.height, sh_degree=t.get("sh_degree"),
                              render_mode=self.mode, backgrounds=self.bg, isect_capacity=cap,
@@ -346,6 +374,8 @@ class FrameRenderer:
                                 f"{self.capacity}: build the FrameRenderer with a larger "
                                 "isect_capacity / capacity_margin")
         out = {"colors": s["colors"][0], "alphas": s["alphas"][0], "meta": s["meta"]}
+        if self.class_ids is not None:
+            out["labels"], out["label_weights"] = s["meta"]["labels"][0], s["meta"]["label_weights"][0]
         if s["ds"] is not None:
             out.update(s["ds"])
             if not self.dataset_keep_float:          # the float frame was never written

@@ -76,6 +76,7 @@ class _RenderConfig:
     segment: int                # backward_segment
     dataset: Optional[tuple]    # dataset_out
     raw: bool = False           # raw_params: scales are log-scales, opacities logits (MGS_PARAMS_RAW)
+    labels: Optional[tuple] = None   # (class_ids int32 [N], n_classes): a label frame per camera (include/mgs_labels.h)
 
     @property
     def channels(self) -> int:
@@ -116,6 +117,11 @@ class _RenderSH(torch.autograd.Function):
         last_ids = (torch.empty(C, height, width, dtype=torch.int32, device=dev) if training
                     else None)
         ctx.cfg, ctx.meta_out = cfg, meta_out
+        lab = lab_w = None
+        if cfg.labels is not None:          # the label frames: outputs that carry no gradient, published in the meta dict
+            lab = torch.empty(C, height, width, dtype=torch.uint8, device=dev)
+            lab_w = torch.empty(C, height, width, dtype=torch.float32, device=dev)
+            meta_out["label_frames"] = dict(labels=lab, label_weights=lab_w)
         ctx.set_materialize_grads(False)       # an unused output's cotangent arrives as None, not as a zero frame
         # lean: an inference frame with a fixed list capacity keeps only what its own kernels read -- the packed
         # records, the binning seed and the depths; radii / means2d / conics / feats / tiles_per_gauss are neither
@@ -133,7 +139,8 @@ class _RenderSH(torch.autograd.Function):
             _, _, n_isects, status = ops.render_frames_raw(
                 *args, backgrounds=backgrounds, expected_last=cfg.expected_depth, latency=cfg.latency, out=(render, alphas),
                 tight=cfg.tight, per_axis=cfg.per_axis, camera=cfg.camera, dataset=ds[:3] if ds is not None else None,
-                float_frame=ds is None or bool(ds[3]), raw=cfg.raw)
+                float_frame=ds is None or bool(ds[3]), raw=cfg.raw,
+                labels=cfg.labels + (lab, lab_w) if cfg.labels is not None else None)
             meta_out["lean"] = dict(n_isects=n_isects, isect_status=status)
             return render, alphas.unsqueeze(-1)
         if training and cap is not None:
@@ -148,6 +155,8 @@ class _RenderSH(torch.autograd.Function):
                 per_cam.append(_Camera(torch.stack([v["radii"], v["radii_y"]]) if cfg.per_axis else v["radii"], v["means2d"],
                                        v["depths"], v["conics"], v["opac_aa"] if (cfg.antialiased or cfg.raw) else None, v["feats"],
                                        st.tile_lists(c, v), v["splats"], None))
+                if lab is not None:         # on the camera's own records and lists, kept in the state
+                    ops.raster_labels_raw(per_cam[c].lists, *cfg.labels, width, height, splats=v["splats"], out=(lab[c], lab_w[c]))
             ctx.train_state = st
             ctx.save_for_backward(means, quats, scales, opacities, sh_coeffs, viewmats, Ks, backgrounds, alphas, None, render)
             meta_out["per_cam"] = per_cam
@@ -182,6 +191,8 @@ class _RenderSH(torch.autograd.Function):
                                   splats=splats, expected_last=cfg.expected_depth, latency=cfg.latency,
                                   group_order=tl.group_order, channels=ch, checkpoints=ckpt,
                                   checkpoint_interval=cfg.segment if ckpt is not None else 0)
+            if lab is not None:             # the records the raster has just read: its opacity, its lists, its launch order
+                ops.raster_labels_raw(tl, *cfg.labels, width, height, splats=splats, out=(lab[c], lab_w[c]))
             per_cam.append(_Camera(radii, means2d, depths, conics, opac_aa, feats, tl, splats, ckpt))
         ctx.per_cam = per_cam
         # "RGB+ED": the kernel's epilogue divided the depth channel by max(alpha, 1e-10); the
@@ -283,8 +294,19 @@ def rasterization(means: Tensor, quats: Tensor, scales: Tensor, opacities: Tenso
                   radius_rule: str = "classic",
                   dataset_out=None,
                   camera_model: str = "pinhole",
-                  raw_params: bool = False) -> Tuple[Tensor, Tensor, Dict]:
+                  raw_params: bool = False,
+                  class_ids: Optional[Tensor] = None,
+                  n_classes: Optional[int] = None) -> Tuple[Tensor, Tensor, Dict]:
     """Render N Gaussians from C cameras.
+
+    class_ids (any integer tensor [N] on the device) with n_classes = K <= 32: every frame also gets a part-label frame,
+    meta["labels"] [C,H,W] uint8 -- the class whose Gaussians hold the largest share of the pixel's blend weights, ties to
+    the lowest class, 255 where no counted Gaussian has a class in 0..K-1 -- and meta["label_weights"] [C,H,W] float32,
+    that share (threshold it against alpha to decide how much coverage counts as "this part").  A class outside 0..K-1
+    (-1, say) occludes and is never reported.  The weights are the frame's own blend weights bit for bit (DESIGN.md 4.11);
+    colours, alphas and every other meta entry are what they are without class_ids.  On every path: per-Gaussian features,
+    SH with per-camera intermediates, and lean_meta, where the label launch sits inside the one C call (graph-capturable).
+    n_classes=None reads class_ids.max() back once -- not under graph capture.  Labels carry no gradient.
 
     raw_params (SH path): `scales` hold log-scales and `opacities` logits -- what a nerfstudio .ply stores and
     splatfacto's optimiser steps on -- and the returned gradients are with respect to those tensors.  The projection
@@ -357,6 +379,17 @@ def rasterization(means: Tensor, quats: Tensor, scales: Tensor, opacities: Tenso
         raise ValueError(f"raster_schedule {raster_schedule!r} not in ('latency', 'throughput')")
     require_device(means, quats, scales, opacities, colors, viewmats, Ks, backgrounds)
     N, C = means.shape[0], viewmats.shape[0]
+    labels = None
+    if class_ids is not None:
+        cls = ops.class_ids_i32(class_ids, N)
+        if n_classes is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise ValueError("n_classes=None reads class_ids.max() back to the host, which a graph capture cannot do: "
+                                 "give n_classes")
+            n_classes = int(cls.max().item()) + 1 if N > 0 else 1
+        labels = (cls, ops.check_n_classes(n_classes))
+    elif n_classes is not None:
+        raise ValueError("n_classes given without class_ids")
     if means.shape != (N, 3) or quats.shape != (N, 4) or scales.shape != (N, 3) \
             or opacities.shape != (N,):
         raise ValueError("expected means [N,3], quats [N,4], scales [N,3], opacities [N]")
@@ -392,12 +425,15 @@ def rasterization(means: Tensor, quats: Tensor, scales: Tensor, opacities: Tenso
             width, height, int(sh_degree), float(eps2d), float(near_plane), float(far_plane), float(radius_clip),
             antialiased, want_depth, isect_capacity, bool(absgrad), tight=tile_bounds == "tight", per_axis=bool(rule),
             camera=camera, expected_depth=render_mode in ("RGB+ED", "ED"), latency=raster_schedule == "latency",
-            lean=bool(lean_meta), segment=int(backward_segment), dataset=dataset_out, raw=bool(raw_params))
+            lean=bool(lean_meta), segment=int(backward_segment), dataset=dataset_out, raw=bool(raw_params),
+            labels=labels)
         # the autograd function publishes per-camera intermediates (and, after backward, "means2d_grad" /
         # "means2d_absgrad" lists) into the meta dict
         render, alphas = _RenderSH.apply(means, quats, scales, opacities, colors, viewmats, Ks, backgrounds, cfg, meta)
         if depth_only_via_sh:
             render = render[..., 3:4]
+        if "label_frames" in meta:
+            meta.update(meta.pop("label_frames"))
         if "lean" in meta:              # inference frames through mgs_render_frames: counts and status only
             meta.update(meta.pop("lean"))
             return render, alphas, meta
@@ -455,6 +491,10 @@ def rasterization(means: Tensor, quats: Tensor, scales: Tensor, opacities: Tenso
         meta.update(radii=radii, means2d=means2d, depths=depths, conics=conics, opacities=opac,
                     tiles_per_gauss=tpg, isect_ids=isect_ids, flatten_ids=flatten_ids,
                     isect_offsets=offsets)
+        if labels is not None:
+            meta["labels"], meta["label_weights"] = ops.rasterize_labels(
+                means2d, conics, opac.contiguous(), labels[0], labels[1], width, height, TILE_SIZE, offsets, flatten_ids,
+                return_weights=True)
         if render_mode in ("ED", "RGB+ED"):      # operator path (explicit features): divide here
             render = torch.cat([render[..., :-1],
                                 render[..., -1:] / alphas.clamp(min=1e-10)], dim=-1)
@@ -474,7 +514,8 @@ def render(gaussians, cameras: Sequence, sh_degree: Optional[int] = None,
            device: str = "cuda", tensors: Optional[Dict] = None, **kw):
     """Render a `Gaussians` scene from `Camera`s (the Python-side API that stays, per the
     north star).  Applies splatfacto's post-processing: rgb = clamp(rgb + (1-alpha)*bg, 0, 1),
-    depth = where(alpha > 0, depth, max depth).  Returns dict(rgb, depth, alpha, meta)."""
+    depth = where(alpha > 0, depth, max depth).  Returns dict(rgb, depth, alpha, meta), and with class_ids= / n_classes=
+    (rasterization's keywords) also labels [C,H,W] uint8 and label_weights [C,H,W]."""
     cams = list(cameras)
     w, h = cams[0].width, cams[0].height
     if any(c.width != w or c.height != h for c in cams):
@@ -490,6 +531,8 @@ def render(gaussians, cameras: Sequence, sh_degree: Optional[int] = None,
                                          near_plane=cams[0].near, far_plane=cams[0].far,
                                          sh_degree=t["sh_degree"], render_mode=render_mode, **kw)
     out = {"alpha": alphas, "meta": meta}
+    if "labels" in meta:             # class_ids= / n_classes= (forwarded through **kw): the part-label frames
+        out["labels"], out["label_weights"] = meta["labels"], meta["label_weights"]
     if render_mode.startswith("RGB"):
         rgb = colors[..., :3]
         if background is not None:
