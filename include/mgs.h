@@ -46,7 +46,8 @@ extern "C" {
  * 450: the image-loss descriptor, a trailing `image` argument of mgs_l1_loss_fwd / _fwd_grad / _bwd).
  * Not a bump, no parameter list changed: the parameter form as a policy, MGS_PARAMS_RAW -- a new bit of bin_flags, of the
  * mgs_render_frames* flags and of mgs_project_color_bwd's camera_model word; a caller that never sets it sees 450's
- * behaviour. */
+ * behaviour.  Likewise the fourth camera model, MGS_CAMERA_FISHEYE_KB: a new camera_model value and new flag bits
+ * (include/mgs_lens.h); no parameter list changed, the `K` / `Ks` rows grow to 16 floats under that model only. */
 #define MGS_VERSION 450
 
 #define MGS_OK 0
@@ -74,17 +75,29 @@ extern "C" {
                                              backward must be given the forward's bit.  Dataset output (ds_rgba /
                                              ds_distance) is pinhole-only: MGS_ERR_UNSUPPORTED otherwise */
 
-/* The camera model, a compile-time policy of the projection kernels like the radius rule (all three instantiations ship,
+/* The camera model, a compile-time policy of the projection kernels like the radius rule (every instantiation ships,
  * the caller picks one per call).  Camera point p = (x, y, z) in OpenCV axes, K = [[fx, 0, cx], [0, fy, cy], [0, 0, 1]]:
  *   MGS_CAMERA_PINHOLE  (fx x/z + cx, fy y/z + cy); the EWA Jacobian with x/z, y/z clamped to 1.3 x the half field of view.
  *   MGS_CAMERA_ORTHO    (fx x + cx, fy y + cy); J = [[fx, 0, 0], [0, fy, 0]]; no frustum clamp.
  *   MGS_CAMERA_FISHEYE  ideal equidistant lens (r = f theta, no distortion coefficients): rho = |(x, y)|,
  *                       theta = atan2(rho, z), (fx x theta/rho + cx, fy y theta/rho + cy); J the dense Jacobian of that
  *                       map; no frustum clamp.
+ *   MGS_CAMERA_FISHEYE_KB  the equidistant lens with OpenCV's fisheye (Kannala-Brandt) polynomial, cv2.fisheye /
+ *                       nerfstudio OPENCV_FISHEYE: theta_d = theta P(theta^2), P(u) = 1 + k1 u + k2 u^2 + k3 u^3 + k4 u^4,
+ *                       (fx x theta_d/rho + cx, fy y theta_d/rho + cy); J the dense Jacobian of that map; no frustum clamp.
+ *                       The coefficients travel with the intrinsics: under this model every `K` / `Ks` pointer addresses
+ *                       rows of 16 floats per camera instead of 9 -- K row-major in 0..8, k1..k4 in 9..12, u_max in 13,
+ *                       zero in 14..15.  u_max = theta_max^2 ends the lens's valid range: theta_max is the smallest
+ *                       positive root of d theta_d / d theta = 1 + 3 k1 theta^2 + 5 k2 theta^4 + 7 k3 theta^6 + 9 k4 theta^8
+ *                       (where the polynomial folds back), or pi/2 without one; the caller computes it (the kernels
+ *                       solve nothing).  A Gaussian with theta^2 >= u_max is culled like one behind the near plane.
+ *                       All k zero gives MGS_CAMERA_FISHEYE's numbers.  A fourth instantiation; its flag bits
+ *                       (MGS_BIN_CAMERA_FISHEYE_KB, MGS_FRAMES_CAMERA_FISHEYE_KB) are in include/mgs_lens.h.
  * Depth is camera z under every model (near / far cull, sort key, "D" / "ED"); the SH view direction is mean - campos. */
 #define MGS_CAMERA_PINHOLE 0
 #define MGS_CAMERA_ORTHO 1
 #define MGS_CAMERA_FISHEYE 2
+#define MGS_CAMERA_FISHEYE_KB 3
 
 /* The radius rule ("make the radius rule a compile-time policy so the tighter one can be benchmarked").
  * Inside the library the rule is a template constant of the projection kernels; both instantiations ship and the
@@ -163,7 +176,8 @@ void mgs_debug_set_sort_opts(int opts);
  *   radius_rule: MGS_RADIUS_CLASSIC (opacities / radii_y not read or written, may be NULL) or
  *   MGS_RADIUS_OPACITY_AWARE: opacities[N] nullable (as gsplat >= 1.5's optional argument; multiplied by the compensation
  *   iff compensations is given, gsplat's calc_compensations), radii = extent along x, radii_y[N] = extent along y.
- *   camera_model: MGS_CAMERA_PINHOLE, MGS_CAMERA_ORTHO or MGS_CAMERA_FISHEYE (anything else: MGS_ERR_INVALID_ARGUMENT).
+ *   camera_model: MGS_CAMERA_PINHOLE, MGS_CAMERA_ORTHO, MGS_CAMERA_FISHEYE or MGS_CAMERA_FISHEYE_KB (K then addresses the
+ *   16-float row described at MGS_CAMERA_*); anything else: MGS_ERR_INVALID_ARGUMENT.
  * ----------------------------------------------------------------------------------- */
 int mgs_projection_fwd(int n, const float *means, const float *quats, const float *scales,
                        const float *viewmat, const float *K, int width, int height,

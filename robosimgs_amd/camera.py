@@ -1,4 +1,4 @@
-"""Cameras in the conventions RoboSimGS uses (pinhole, orthographic or ideal equidistant fisheye).
+"""Cameras in the conventions RoboSimGS uses (pinhole, orthographic or equidistant fisheye, ideal or with OpenCV's k1..k4).
 
 The reference stores cameras as OpenGL camera-to-world matrices (+X right, +Y up, camera
 looks down -Z) plus a 3x3 intrinsic matrix:
@@ -14,8 +14,8 @@ from __future__ import annotations
 
 import json
 import math
-from dataclasses import dataclass
-from typing import Dict, List, Sequence
+from dataclasses import dataclass, field
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -23,11 +23,27 @@ _FLIP_YZ = np.diag([1.0, -1.0, -1.0, 1.0])
 CAMERA_MODELS = ("pinhole", "ortho", "fisheye")      # rasterization(camera_model=...); include/mgs.h MGS_CAMERA_*
 
 
+def lens_theta_max(k) -> float:
+    """Where the fisheye polynomial theta_d = theta (1 + k1 theta^2 + k2 theta^4 + k3 theta^6 + k4 theta^8) stops being
+    monotonic: the smallest positive root of d theta_d / d theta = 1 + 3 k1 u + 5 k2 u^2 + 7 k3 u^3 + 9 k4 u^4, u = theta^2,
+    or pi/2 (the near plane's limit) when there is none below it.  fp64; the renderer culls theta >= theta_max."""
+    k1, k2, k3, k4 = (float(v) for v in k)
+    coeffs = np.trim_zeros(np.array([9.0 * k4, 7.0 * k3, 5.0 * k2, 3.0 * k1, 1.0]), "f")
+    best = 0.5 * math.pi
+    if len(coeffs) > 1:
+        for r in np.roots(coeffs):
+            if abs(r.imag) <= 1e-12 * max(1.0, abs(r.real)) and r.real > 0.0:
+                best = min(best, math.sqrt(r.real))
+    return best
+
+
 @dataclass
 class Camera:
     """One camera.  `c2w` is OpenGL camera-to-world (4x4, float64).  `model`: "pinhole", "ortho" (pixel =
     (fx x + cx, fy y + cy) in camera space: fx is pixels per world unit) or "fisheye" (ideal equidistant lens,
-    pixel radius = f theta, theta the angle off the optical axis)."""
+    pixel radius = f theta, theta the angle off the optical axis).  `distortion` (meaningful for "fisheye"): OpenCV fisheye
+    coefficients (k1, k2, k3, k4), pixel radius = f theta (1 + k1 theta^2 + k2 theta^4 + k3 theta^6 + k4 theta^8) -- what
+    cv2.fisheye.calibrate and nerfstudio's OPENCV_FISHEYE store; None: the ideal lens."""
 
     c2w: np.ndarray
     fx: float
@@ -38,11 +54,19 @@ class Camera:
     height: int
     near: float = 0.01
     far: float = 1e10
+    # keyword-only (Camera(..., distortion=(k1, k2, k3, k4))), so that `model` stays the last positional field
+    distortion: Optional[Tuple[float, float, float, float]] = field(default=None, kw_only=True)
     model: str = "pinhole"
 
     def __post_init__(self):
         if self.model not in CAMERA_MODELS:
             raise ValueError(f"camera model {self.model!r} not in {CAMERA_MODELS}")
+        if self.distortion is not None:
+            if self.model != "fisheye":
+                raise ValueError(f"distortion (fisheye k1..k4) needs model='fisheye', got {self.model!r}")
+            self.distortion = tuple(float(v) for v in self.distortion)
+            if len(self.distortion) != 4:
+                raise ValueError("distortion must be (k1, k2, k3, k4)")
         self.c2w = np.asarray(self.c2w, dtype=np.float64).reshape(4, 4)
         self.width = int(self.width)
         self.height = int(self.height)
@@ -112,7 +136,13 @@ class Camera:
                 rho = np.linalg.norm(xy, axis=-1)
                 theta = np.arctan2(rho, pc[:, 2])
                 safe = np.where(rho > 0, rho, 1.0)
-                xy = xy * np.where(rho > 0, theta / safe, 0.0)[:, None]
+                theta_d = theta
+                if self.distortion is not None and any(self.distortion):
+                    k1, k2, k3, k4 = self.distortion
+                    u = theta * theta
+                    theta_d = theta * (1.0 + u * (k1 + u * (k2 + u * (k3 + u * k4))))
+                    theta_d = np.where(theta < lens_theta_max(self.distortion), theta_d, np.nan)   # past the fold
+                xy = xy * np.where(rho > 0, theta_d / safe, 0.0 * theta_d)[:, None]
             uv = xy * np.array([self.fx, self.fy]) + np.array([self.cx, self.cy])
         if return_dists:
             return uv, np.linalg.norm(pc, axis=-1)
@@ -123,17 +153,18 @@ class Camera:
         return Camera(self.c2w.copy(), self.fx * factor, self.fy * factor,
                       self.cx * factor, self.cy * factor,
                       int(round(self.width * factor)), int(round(self.height * factor)),
-                      self.near, self.far, self.model)
+                      self.near, self.far, self.model, distortion=self.distortion)
 
 
 def cameras_from_transforms_json(path: str, width: int | None = None,
-                                 height: int | None = None) -> List[Camera]:
+                                 height: int | None = None, lens_distortion: bool = False) -> List[Camera]:
     """nerfstudio `transforms.json` -> cameras.  Accepts global or per-frame intrinsics,
     the two layouts `parse_transforms_json` reads (nerf2physic_utils.py:30-45).
 
     nerfstudio's `camera_model` key (top level or per frame): "OPENCV_FISHEYE" is read as the ideal equidistant
-    fisheye when its distortion coefficients k1..k4 are absent or zero, and raises ValueError otherwise (lens distortion
-    is not modelled); every other value loads as a pinhole camera, as before."""
+    fisheye when its distortion coefficients k1..k4 are absent or zero; non-zero coefficients raise ValueError unless
+    lens_distortion=True, which loads them into Camera.distortion (the renderer then applies the lens).  Every other value
+    -- "OPENCV" with its radial / tangential terms included -- loads as a pinhole camera, as before."""
     with open(path, "rb") as f:
         t = json.load(f)
     cams = []
@@ -141,22 +172,24 @@ def cameras_from_transforms_json(path: str, width: int | None = None,
         src = fr if "fl_x" in fr else t
         w = int(src.get("w", t.get("w", width or round(2 * src["cx"]))))
         h = int(src.get("h", t.get("h", height or round(2 * src["cy"]))))
+        model, dist = _transforms_camera_model(fr, t, lens_distortion)
         cams.append(Camera(fr["transform_matrix"], src["fl_x"], src["fl_y"], src["cx"],
-                           src["cy"], w, h, model=_transforms_camera_model(fr, t)))
+                           src["cy"], w, h, model=model, distortion=dist))
     return cams
 
 
-def _transforms_camera_model(frame: Dict, top: Dict) -> str:
-    """The Camera.model of one transforms.json frame (per-frame keys override top-level ones)."""
+def _transforms_camera_model(frame: Dict, top: Dict, lens_distortion: bool = False):
+    """(Camera.model, Camera.distortion) of one transforms.json frame (per-frame keys override top-level ones)."""
     name = frame.get("camera_model", top.get("camera_model", "OPENCV"))
     if name != "OPENCV_FISHEYE":
-        return "pinhole"
+        return "pinhole", None
     ks = {k: float(frame.get(k, top.get(k, 0.0))) for k in ("k1", "k2", "k3", "k4")}
     nonzero = {k: v for k, v in ks.items() if v != 0.0}
-    if nonzero:
+    if nonzero and not lens_distortion:
         raise ValueError(f"OPENCV_FISHEYE with distortion coefficients {nonzero}: fisheye lens distortion (k1..k4) is "
-                         "not supported; only the ideal equidistant fisheye (all k zero) is")
-    return "fisheye"
+                         "not supported by default; pass lens_distortion=True to load it into Camera.distortion (without "
+                         "it only the ideal equidistant fisheye, all k zero, is read)")
+    return "fisheye", (tuple(ks.values()) if nonzero else None)
 
 
 def cameras_from_camera_params_json(path: str) -> Dict[str, Camera]:

@@ -49,7 +49,7 @@ __global__ __launch_bounds__(kBlock) void projection_bwd_kernel(
   bool active = g < n && radii[g] > 0;
   ProjectedGrad r;
   if (active) {
-    CameraParams cam = load_camera(viewmat, Kmat);
+    CameraParams cam = load_camera<CAM>(viewmat, Kmat);
     float m[3], s[3], q[4], con[3], vm2[2], vcon[3];
     load3(means + 3 * (size_t)g, m);
     load3(scales + 3 * (size_t)g, s);
@@ -191,7 +191,7 @@ __global__ __launch_bounds__(kBlock) void project_color_bwd_kernel(
   // v_opacities is this kernel's to write when the opacity the raster saw is not the parameter: anti-aliased
   // (opacity x compensation) or raw (sigmoid of the logit); v_opac_out is then the blend's opacity gradient
   const bool own_opac = antialiased || RAW;
-  CameraParams cam = load_camera(viewmat, Kmat);
+  CameraParams cam = load_camera<CAM>(viewmat, Kmat);
   float m[3] = {0.f, 0.f, 0.f}, dir[3] = {0.f, 0.f, 1.f}, v_rgb[3] = {0.f, 0.f, 0.f};
   float v_depth = 0.f;
   if (active) {
@@ -306,8 +306,8 @@ extern "C" int mgs_projection_bwd(int n, const float* means, const float* quats,
                                   float* v_means, float* v_quats, float* v_scales,
                                   float* v_viewmat, int camera_model, mgs_stream_t stream) {
   MGS_REQUIRE(n >= 0 && width > 0 && height > 0, "projection_bwd: bad sizes");
-  MGS_REQUIRE(camera_model >= MGS_CAMERA_PINHOLE && camera_model <= MGS_CAMERA_FISHEYE,
-              "projection_bwd: camera_model %d is not MGS_CAMERA_PINHOLE, _ORTHO or _FISHEYE", camera_model);
+  MGS_REQUIRE(is_camera_model(camera_model),
+              "projection_bwd: camera_model %d is not MGS_CAMERA_PINHOLE, _ORTHO, _FISHEYE or _FISHEYE_KB", camera_model);
   if (n == 0) return MGS_OK;
   MGS_REQUIRE(means && quats && scales && viewmat && K && radii && conics && v_means2d &&
                   v_conics && v_means && v_quats && v_scales, "projection_bwd: null pointer");
@@ -355,11 +355,11 @@ extern "C" int mgs_project_color_bwd(int n, const float* means, const float* qua
   const int raw = (camera_model & MGS_PARAMS_RAW) ? 1 : 0;
   camera_model &= ~MGS_PARAMS_RAW;
   MGS_REQUIRE(n >= 0 && width > 0 && height > 0, "project_color_bwd: bad sizes");
-  MGS_REQUIRE(camera_model >= MGS_CAMERA_PINHOLE && camera_model <= MGS_CAMERA_FISHEYE,
-              "project_color_bwd: camera_model %d is not MGS_CAMERA_PINHOLE, _ORTHO or _FISHEYE (optionally | MGS_PARAMS_RAW)",
-              camera_model);
+  MGS_REQUIRE(is_camera_model(camera_model),
+              "project_color_bwd: camera_model %d is not MGS_CAMERA_PINHOLE, _ORTHO, _FISHEYE or _FISHEYE_KB (optionally | "
+              "MGS_PARAMS_RAW)", camera_model);
   MGS_REQUIRE(!raw || (opacities && v_opac_out && v_opacities),
-              "project_color_bwd: MGS_PARAMS_RAW needs opacities (the logits), v_opac_out and v_opacities");
+              "project_color_bwd: camera_model carries MGS_PARAMS_RAW, which needs opacities (the logits), v_opac_out and v_opacities");
   MGS_REQUIRE(sh_degree >= 0 && sh_degree <= 3, "project_color_bwd: sh_degree %d not in 0..3", sh_degree);
   MGS_REQUIRE(coeff_stride >= (sh_degree + 1) * (sh_degree + 1), "project_color_bwd: coeff_stride too small");
   MGS_REQUIRE(feat_stride == 3 || feat_stride == 4, "project_color_bwd: feat_stride must be 3 or 4");

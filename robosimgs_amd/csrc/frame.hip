@@ -17,6 +17,7 @@ struct Frames {
   int bin_flags;       // mgs_project_color_fwd's: tile bounds, radius rule, camera
   int camera_model;    // MGS_CAMERA_* (mgs_project_color_bwd)
   bool raw;            // MGS_PARAMS_RAW: `scales` holds log-scales, `opacities` logits
+  size_t k_row;        // floats per camera in `Ks`: 9, or 16 under MGS_CAMERA_FISHEYE_KB
 };
 int frames_prologue(const char* fn, int n, int n_cams, int width, int height, int channels, int flags, const float* opacities,
                     uint32_t isect_capacity, const size_t* workspace_bytes, Frames* f,
@@ -27,6 +28,8 @@ int frames_prologue(const char* fn, int n, int n_cams, int width, int height, in
   MGS_REQUIRE(isect_capacity > 0, "%s: zero capacity", fn);
   MGS_REQUIRE((flags & (MGS_FRAMES_CAMERA_ORTHO | MGS_FRAMES_CAMERA_FISHEYE)) != (MGS_FRAMES_CAMERA_ORTHO | MGS_FRAMES_CAMERA_FISHEYE),
               "%s: flags set both MGS_FRAMES_CAMERA_ORTHO and MGS_FRAMES_CAMERA_FISHEYE", fn);
+  MGS_REQUIRE(!mgs::several_camera_bits(flags, MGS_FRAMES_CAMERA_ORTHO | MGS_FRAMES_CAMERA_FISHEYE | MGS_FRAMES_CAMERA_FISHEYE_KB),
+              "%s: flags set more than one MGS_FRAMES_CAMERA_* bit", fn);
   f->raw = (flags & MGS_PARAMS_RAW) != 0;
   MGS_REQUIRE(!f->raw || opacities, "%s: MGS_PARAMS_RAW needs opacities (the logits), got NULL", fn);
   f->tile_w = (width + MGS_TILE_SIZE - 1) / MGS_TILE_SIZE;
@@ -35,8 +38,10 @@ int frames_prologue(const char* fn, int n, int n_cams, int width, int height, in
   f->bin_flags = ((flags & MGS_FRAMES_CLASSIC_BOUNDS) ? 0 : MGS_BIN_TIGHT /* same pixels, shorter lists */) |
                  ((flags & MGS_FRAMES_RADIUS_OPACITY_AWARE) ? MGS_BIN_RADIUS_OPACITY_AWARE : 0) |
                  ((flags & MGS_FRAMES_CAMERA_ORTHO) ? MGS_BIN_CAMERA_ORTHO : 0) |
-                 ((flags & MGS_FRAMES_CAMERA_FISHEYE) ? MGS_BIN_CAMERA_FISHEYE : 0) | (f->raw ? MGS_PARAMS_RAW : 0);
+                 ((flags & MGS_FRAMES_CAMERA_FISHEYE) ? MGS_BIN_CAMERA_FISHEYE : 0) |
+                 ((flags & MGS_FRAMES_CAMERA_FISHEYE_KB) ? MGS_BIN_CAMERA_FISHEYE_KB : 0) | (f->raw ? MGS_PARAMS_RAW : 0);
   f->camera_model = mgs::bin_camera_model(f->bin_flags);
+  f->k_row = mgs::camera_row_floats(f->camera_model);
   return MGS_OK;
 }
 // the per-camera binning's workspace, with the tile-grid check of mgs_isect_tiles' size query
@@ -91,7 +96,7 @@ int render_frames_impl(int n, const float* means, const float* quats, const floa
   if ((ds_rgba || ds_distance) && f.camera_model != MGS_CAMERA_PINHOLE)
     return mgs::set_error(MGS_ERR_UNSUPPORTED, "render_frames: dataset output (ds_rgba / ds_distance) converts depth to ray "
                                                "distance through a pinhole K^-1; it is not available for an orthographic "
-                                               "or fisheye camera");
+                                               "or fisheye camera (with or without lens distortion)");
   const int tile_w = f.tile_w, tile_h = f.tile_h;
   size_t isect_ws = 0;
   rc = isect_bytes(n, isect_capacity, f, &isect_ws);
@@ -121,7 +126,7 @@ int render_frames_impl(int n, const float* means, const float* quats, const floa
   const size_t n_px = (size_t)width * height;
   for (int c = 0; c < n_cams; ++c) {
     rc = mgs_project_color_fwd(n, means, quats, scales, opacities, sh_degree, coeff_stride, sh_coeffs,
-                               viewmats + 16 * (size_t)c, Ks + 9 * (size_t)c, width, height, eps2d, near_plane, far_plane,
+                               viewmats + 16 * (size_t)c, Ks + f.k_row * (size_t)c, width, height, eps2d, near_plane, far_plane,
                                radius_clip, nullptr, nullptr, depths, nullptr, opac_aa, channels, nullptr, splats, f.bin_flags,
                                bin_info, bin_sums, nullptr, stream);
     if (rc) return rc;
@@ -304,7 +309,7 @@ extern "C" int mgs_render_frames_train(int n, const float* means, const float* q
     auto U = [&](int f) { return reinterpret_cast<uint32_t*>(s + st.at[f]); };
     float* opac_aa = keep_opac ? F(TF_OPAC) : nullptr;
     rc = mgs_project_color_fwd(n, means, quats, scales, opacities, sh_degree, coeff_stride, sh_coeffs,
-                               viewmats + 16 * (size_t)c, Ks + 9 * (size_t)c, width, height, eps2d, near_plane, far_plane,
+                               viewmats + 16 * (size_t)c, Ks + f.k_row * (size_t)c, width, height, eps2d, near_plane, far_plane,
                                radius_clip, I(TF_RADII), F(TF_MEANS2D), F(TF_DEPTHS), F(TF_CONICS), opac_aa, channels,
                                F(TF_FEATS), F(TF_SPLATS), bin_flags, bin_info, bin_sums, I(TF_RADII_Y), stream);
     if (rc) return rc;
@@ -386,7 +391,7 @@ extern "C" int mgs_render_frames_backward(int n, const float* means, const float
                                g_opac, w + ws.raster, &rw, stream);
     if (rc) return rc;
     rc = mgs_project_color_bwd(n, means, quats, scales, opacities, sh_degree, coeff_stride, sh_coeffs,
-                               viewmats + 16 * (size_t)c, Ks + 9 * (size_t)c, width, height, eps2d, I(TF_RADII), F(TF_CONICS),
+                               viewmats + 16 * (size_t)c, Ks + f.k_row * (size_t)c, width, height, eps2d, I(TF_RADII), F(TF_CONICS),
                                antialiased, channels, F(TF_FEATS), g_feat, g_m2d, g_con, nullptr,
                                own_opac ? g_opac : nullptr, v_means, v_quats, v_scales, v_sh_coeffs,
                                own_opac ? v_opacities : nullptr, v_viewmats ? v_viewmats + 16 * (size_t)c : nullptr,

@@ -10,6 +10,7 @@
 #include <type_traits>
 
 #include "../../include/mgs.h"
+#include "../../include/mgs_lens.h"
 
 namespace mgs {
 
@@ -61,8 +62,11 @@ template <int Lo, int Hi, class F> void with_int(int v, F&& f) {
   else if (v == Lo) f(int_c<Lo>{});
   else with_int<Lo + 1, Hi>(v, f);
 }
-// MGS_CAMERA_*: anything past MGS_CAMERA_ORTHO is MGS_CAMERA_FISHEYE
-template <class F> void with_camera(int model, F&& f) { with_int<MGS_CAMERA_PINHOLE, MGS_CAMERA_FISHEYE>(model, f); }
+// MGS_CAMERA_*: anything past MGS_CAMERA_FISHEYE is MGS_CAMERA_FISHEYE_KB
+template <class F> void with_camera(int model, F&& f) { with_int<MGS_CAMERA_PINHOLE, MGS_CAMERA_FISHEYE_KB>(model, f); }
+inline bool is_camera_model(int model) { return model >= MGS_CAMERA_PINHOLE && model <= MGS_CAMERA_FISHEYE_KB; }
+// floats per camera behind a `K` / `Ks` pointer (include/mgs.h at MGS_CAMERA_*)
+inline size_t camera_row_floats(int model) { return model == MGS_CAMERA_FISHEYE_KB ? MGS_LENS_ROW_FLOATS : 9; }
 // SH degree 0..3: anything past 2 is 3
 template <class F> void with_sh_degree(int degree, F&& f) { with_int<0, 3>(degree, f); }
 // MGS_RADIUS_OPACITY_AWARE when per_axis, MGS_RADIUS_CLASSIC otherwise
@@ -84,8 +88,11 @@ template <class F> void with_channels(int channels, F&& f) {
 // the camera model the MGS_BIN_CAMERA_* bits of a bin_flags word select (at most one is set: the caller checks)
 inline int bin_camera_model(int bin_flags) {
   return (bin_flags & MGS_BIN_CAMERA_ORTHO) ? MGS_CAMERA_ORTHO
-         : (bin_flags & MGS_BIN_CAMERA_FISHEYE) ? MGS_CAMERA_FISHEYE : MGS_CAMERA_PINHOLE;
+         : (bin_flags & MGS_BIN_CAMERA_FISHEYE) ? MGS_CAMERA_FISHEYE
+         : (bin_flags & MGS_BIN_CAMERA_FISHEYE_KB) ? MGS_CAMERA_FISHEYE_KB : MGS_CAMERA_PINHOLE;
 }
+// more than one of the camera bits `bits` set in `flags`
+inline bool several_camera_bits(int flags, int bits) { const int c = flags & bits; return (c & (c - 1)) != 0; }
 
 // ---- wave64 helpers -----------------------------------------------------------------
 #if defined(__HIPCC__)

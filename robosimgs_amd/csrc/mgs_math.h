@@ -23,14 +23,22 @@ struct CameraParams {  // one camera, row-major viewmat (OpenCV world-to-camera)
   float R[9];
   float t[3];
   float fx, fy, cx, cy;
+  float k[4], u_max;   // MGS_CAMERA_FISHEYE_KB only: k1..k4 and theta_max^2 (floats 9..13 of the camera's 16-float row)
 };
 
+// CAM: the camera model of the caller's instantiation -- only MGS_CAMERA_FISHEYE_KB reads past K[8]
+template <int CAM = 0>
 MGS_HD CameraParams load_camera(const float* viewmat, const float* K) {
   CameraParams c;
   c.R[0] = viewmat[0]; c.R[1] = viewmat[1]; c.R[2] = viewmat[2];  c.t[0] = viewmat[3];
   c.R[3] = viewmat[4]; c.R[4] = viewmat[5]; c.R[5] = viewmat[6];  c.t[1] = viewmat[7];
   c.R[6] = viewmat[8]; c.R[7] = viewmat[9]; c.R[8] = viewmat[10]; c.t[2] = viewmat[11];
   c.fx = K[0]; c.cx = K[2]; c.fy = K[4]; c.cy = K[5];
+  if constexpr (CAM == 3) {   // MGS_CAMERA_FISHEYE_KB
+    c.k[0] = K[9]; c.k[1] = K[10]; c.k[2] = K[11]; c.k[3] = K[12]; c.u_max = K[13];
+  } else {
+    c.k[0] = c.k[1] = c.k[2] = c.k[3] = 0.f; c.u_max = 0.f;
+  }
   return c;
 }
 
@@ -120,11 +128,16 @@ struct Projected {
 //   MGS_CAMERA_ORTHO    mean (fx x + cx, fy y + cy); J = [[fx, 0, 0], [0, fy, 0]]; no clamp
 //   MGS_CAMERA_FISHEYE  ideal equidistant lens, r = f theta: rho = |(x, y)|, theta = atan2(rho, z), s = theta / rho,
 //                       mean (fx s x + cx, fy s y + cy); J is the (dense) Jacobian of that map; no clamp
+//   MGS_CAMERA_FISHEYE_KB  that lens with OpenCV's fisheye polynomial: theta_d = theta P(theta^2) (fisheye_kb_terms below);
+//                       culled where theta^2 >= cam.u_max, the end of the polynomial's monotonic range
 // Depth is camera z and near / far cull on it under every model.
 #ifndef MGS_CAMERA_PINHOLE
 #define MGS_CAMERA_PINHOLE 0
 #define MGS_CAMERA_ORTHO 1
 #define MGS_CAMERA_FISHEYE 2
+#endif
+#ifndef MGS_CAMERA_FISHEYE_KB
+#define MGS_CAMERA_FISHEYE_KB 3
 #endif
 
 // Below t = rho^2 / z^2 = 0.1 the fisheye terms come from their series in t (nine terms: truncation < 1e-8 relative):
@@ -156,6 +169,31 @@ MGS_HD void fisheye_terms(float x, float y, float z, float& s, float& a, float& 
     a = (z * ir2 - s) / q;
     if (WITH_B) b = (-z * ir2 * ir2 - 1.5f * a) / q;
   }
+}
+
+// The Kannala-Brandt polynomial on top of the equidistant terms (s, a, ir2 of fisheye_terms at the same point; q = rho^2):
+//   u = theta^2 = s^2 q,  P(u) = 1 + k1 u + k2 u^2 + k3 u^3 + k4 u^4,  theta_d = theta P
+//   S = s P                       (the mean is (fx S x + cx, fy S y + cy))
+//   A = a P + 2 s^2 z P' / r2     (dS/dx = A x, dS/dy = A y)
+//   D = P + 2 u P' = d theta_d / d theta     (dS/dz = -D / r2)
+// so J is the equidistant J with s -> S, a -> A and its third column times D.  No new singularity on the axis: u, P, P'
+// are polynomials in what the series branch yields.  du/d(x, y, z) = (2 s z x, 2 s z y, -2 s q) / r2.
+struct FisheyeKb {
+  float u, P, P1, P2;   // P1 = P', P2 = P''
+  float S, A, D;
+};
+template <bool WITH_P2>
+MGS_HD FisheyeKb fisheye_kb_terms(const float k[4], float q, float z, float s, float a, float ir2) {
+  FisheyeKb t;
+  const float u = s * s * q;
+  t.u = u;
+  t.P = 1.f + u * (k[0] + u * (k[1] + u * (k[2] + u * k[3])));
+  t.P1 = k[0] + u * (2.f * k[1] + u * (3.f * k[2] + u * (4.f * k[3])));
+  t.P2 = WITH_P2 ? 2.f * k[1] + u * (6.f * k[2] + u * (12.f * k[3])) : 0.f;
+  t.S = s * t.P;
+  t.A = a * t.P + 2.f * s * s * z * t.P1 * ir2;
+  t.D = t.P + 2.f * u * t.P1;
+  return t;
 }
 
 // A.2 steps 1-5.  Returns radius == 0 for culled Gaussians (all other fields zeroed).
@@ -194,14 +232,24 @@ MGS_HD Projected project_gaussian(const float mean[3], const float quat[4],
     rz = 1.f;
     j00 = cam.fx; j02 = 0.f;
     j11 = cam.fy; j12 = 0.f;
-  } else {
-    static_assert(CAM == MGS_CAMERA_FISHEYE, "camera model");
+  } else if constexpr (CAM == MGS_CAMERA_FISHEYE) {
     float fa, fb, ir2;
     fisheye_terms<false>(x, y, z, fs, fa, fb, ir2);
     rz = 1.f;
     const float xya = x * y * fa;
     j00 = cam.fx * (fs + x * x * fa); j01 = cam.fx * xya; j02 = -cam.fx * x * ir2;
     j10 = cam.fy * xya; j11 = cam.fy * (fs + y * y * fa); j12 = -cam.fy * y * ir2;
+  } else {
+    static_assert(CAM == MGS_CAMERA_FISHEYE_KB, "camera model");
+    float es, ea, eb, ir2;
+    fisheye_terms<false>(x, y, z, es, ea, eb, ir2);
+    const FisheyeKb kb = fisheye_kb_terms<false>(cam.k, x * x + y * y, z, es, ea, ir2);
+    if (!(kb.u < cam.u_max)) return out;      // past the lens's monotonic range: culled like the near plane
+    rz = 1.f;
+    fs = kb.S;
+    const float xya = x * y * kb.A, dr = kb.D * ir2;
+    j00 = cam.fx * (fs + x * x * kb.A); j01 = cam.fx * xya; j02 = -cam.fx * x * dr;
+    j10 = cam.fy * xya; j11 = cam.fy * (fs + y * y * kb.A); j12 = -cam.fy * y * dr;
   }
   float Rq[9];
   quat_to_rotmat(quat, Rq);
@@ -216,7 +264,7 @@ MGS_HD Projected project_gaussian(const float mean[3], const float quat[4],
   mat3_mul(R, Rq, RR);
   float m0[3], m1[3];
   for (int k = 0; k < 3; ++k) {
-    if constexpr (CAM == MGS_CAMERA_FISHEYE) {
+    if constexpr (CAM == MGS_CAMERA_FISHEYE || CAM == MGS_CAMERA_FISHEYE_KB) {
       m0[k] = (j00 * RR[k] + j01 * RR[3 + k] + j02 * RR[6 + k]) * scale[k];
       m1[k] = (j10 * RR[k] + j11 * RR[3 + k] + j12 * RR[6 + k]) * scale[k];
     } else {
@@ -242,7 +290,7 @@ MGS_HD Projected project_gaussian(const float mean[3], const float quat[4],
   mat3_mul(R, cov, tmp);        // R Sigma
   mat3_mul_bt(tmp, R, covc);    // R Sigma R^T
   float a, b, c;
-  if constexpr (CAM == MGS_CAMERA_FISHEYE) {
+  if constexpr (CAM == MGS_CAMERA_FISHEYE || CAM == MGS_CAMERA_FISHEYE_KB) {
     // cov2d = J covc J^T with a dense J: T = J covc (2 x 3), then T J^T
     float t0[3], t1[3];
     for (int k = 0; k < 3; ++k) {
@@ -262,6 +310,23 @@ MGS_HD Projected project_gaussian(const float mean[3], const float quat[4],
   a += eps2d;
   c += eps2d;
   float det = a * c - b * b;
+  if constexpr (CAM == MGS_CAMERA_FISHEYE_KB) {
+    // Towards theta_max the lens squashes a splat radially by D -> 0: cov2d turns needle-like whatever the Gaussian's own
+    // shape, and a c - b^2 cancels (the compensation factor was off by 3e-3 relative within a few degrees of the fold).
+    // So this model alone takes det(cov2d) as the sum of the squared 2 x 2 minors of M2 = J R Rq S (Cauchy-Binet, positive
+    // terms only, as under MGS_PROJ_FACTORED) and the blurred determinant from it; a, b, c keep the textbook order.
+    float RR[9], m0[3], m1[3];
+    mat3_mul(R, Rq, RR);
+    for (int k = 0; k < 3; ++k) {
+      m0[k] = (j00 * RR[k] + j01 * RR[3 + k] + j02 * RR[6 + k]) * scale[k];
+      m1[k] = (j10 * RR[k] + j11 * RR[3 + k] + j12 * RR[6 + k]) * scale[k];
+    }
+    const float d01 = diff_of_products(m0[0], m1[1], m0[1], m1[0]);
+    const float d02 = diff_of_products(m0[0], m1[2], m0[2], m1[0]);
+    const float d12 = diff_of_products(m0[1], m1[2], m0[2], m1[1]);
+    det0 = d01 * d01 + d02 * d02 + d12 * d12;
+    det = det0 + eps2d * (a + c) - eps2d * eps2d;        // det(cov2d + eps2d I), a and c already blurred
+  }
 #endif
   float mx, my;
   if constexpr (CAM == MGS_CAMERA_PINHOLE) {
@@ -447,7 +512,16 @@ MGS_HD ProjectedGrad project_gaussian_vjp(const float mean[3], const float quat[
     j00 = cam.fx * (fs + x * x * fa); j01 = cam.fx * xya; j02 = -cam.fx * x * ir2;
     j10 = cam.fy * xya; j11 = cam.fy * (fs + y * y * fa); j12 = -cam.fy * y * ir2;
   }
-  static_assert(CAM == MGS_CAMERA_PINHOLE || CAM == MGS_CAMERA_ORTHO || CAM == MGS_CAMERA_FISHEYE, "camera model");
+  [[maybe_unused]] FisheyeKb kb;
+  if constexpr (CAM == MGS_CAMERA_FISHEYE_KB) {
+    fisheye_terms<true>(x, y, z, fs, fa, fb, ir2);     // the equidistant s, a, b; the lens's S, A, D in kb
+    kb = fisheye_kb_terms<true>(cam.k, x * x + y * y, z, fs, fa, ir2);
+    const float xya = x * y * kb.A, dr = kb.D * ir2;
+    j00 = cam.fx * (kb.S + x * x * kb.A); j01 = cam.fx * xya; j02 = -cam.fx * x * dr;
+    j10 = cam.fy * xya; j11 = cam.fy * (kb.S + y * y * kb.A); j12 = -cam.fy * y * dr;
+  }
+  static_assert(CAM == MGS_CAMERA_PINHOLE || CAM == MGS_CAMERA_ORTHO || CAM == MGS_CAMERA_FISHEYE ||
+                    CAM == MGS_CAMERA_FISHEYE_KB, "camera model");
 
   // conic = inv(cov2d + eps I):  G2 = -conic * Vc * conic, Vc = [[va, vb/2],[vb/2, vc]]
   float ca = conic[0], cb = conic[1], cc = conic[2];
@@ -504,6 +578,44 @@ MGS_HD ProjectedGrad project_gaussian_vjp(const float mean[3], const float quat[
     vx = cam.fx * v_mean2d[0];
     vy = cam.fy * v_mean2d[1];
     vz = v_depth;
+  } else if constexpr (CAM == MGS_CAMERA_FISHEYE_KB) {
+    // as the equidistant branch below, with S, A, D for s, a, 1.  With c = 2 s z / r2 (du/dx = c x, du/dy = c y) and
+    // uz = du/dz = -2 s q / r2:
+    //   dA/dx = x B, dA/dy = y B,  B = 2 b P + a P' c + (2 z / r2) (2 s a P' + s^2 P'' c - 2 s^2 P' / r2)
+    //   dA/dz = Az = 2 P / r2^2 + a P' uz + (2 s^2 / r2) (P' (1 - 2 z^2 / r2) + z P'' uz) - 4 s z P' / r2^2
+    //   dD/du = Du = 3 P' + 2 u P''
+    vx = j00 * v_mean2d[0] + j10 * v_mean2d[1];
+    vy = j01 * v_mean2d[0] + j11 * v_mean2d[1];
+    vz = j02 * v_mean2d[0] + j12 * v_mean2d[1] + v_depth;
+    float vJ[6];
+    for (int r = 0; r < 2; ++r)
+      for (int c = 0; c < 3; ++c)
+        vJ[r * 3 + c] = GsJ[r * 3] * covc[c] + GsJ[r * 3 + 1] * covc[3 + c] + GsJ[r * 3 + 2] * covc[6 + c];
+    const float ir4 = ir2 * ir2, xx = x * x, yy = y * y, xy = x * y, q = xx + yy;
+    const float ss = fs * fs, cz = 2.f * fs * z * ir2, uz = -2.f * fs * q * ir2;
+    const float B = 2.f * fb * kb.P + fa * kb.P1 * cz +
+                    2.f * z * ir2 * (2.f * fs * fa * kb.P1 + ss * kb.P2 * cz - 2.f * ss * kb.P1 * ir2);
+    const float Az = 2.f * ir4 * kb.P + fa * kb.P1 * uz +
+                     2.f * ss * ir2 * (kb.P1 * (1.f - 2.f * z * z * ir2) + z * kb.P2 * uz) - 4.f * fs * z * kb.P1 * ir4;
+    const float Du = 3.f * kb.P1 + 2.f * kb.u * kb.P2;
+    const float A = kb.A, dr = kb.D * ir2;
+    const float E = 2.f * kb.D * ir4 - Du * cz * ir2;              // d(D / r2): -(x, y) E in x, y
+    const float Fz = 2.f * z * kb.D * ir4 - Du * uz * ir2;         //            -Fz in z
+    const float wx = cam.fx * vJ[0], w01 = cam.fx * vJ[1], w02 = cam.fx * vJ[2];
+    const float w10 = cam.fy * vJ[3], wy = cam.fy * vJ[4], w12 = cam.fy * vJ[5];
+    const float wxy = w01 + w10;
+    // J00 = fx (S + x^2 A),  J11 = fy (S + y^2 A)
+    vx += wx * x * (3.f * A + xx * B) + wy * x * (A + yy * B);
+    vy += wx * y * (A + xx * B) + wy * y * (3.f * A + yy * B);
+    vz += wx * (xx * Az - dr) + wy * (yy * Az - dr);
+    // J01 = fx x y A,  J10 = fy x y A
+    vx += wxy * y * (A + xx * B);
+    vy += wxy * x * (A + yy * B);
+    vz += wxy * xy * Az;
+    // J02 = -fx x D / r2,  J12 = -fy y D / r2
+    vx += w02 * (xx * E - dr) + w12 * xy * E;
+    vy += w02 * xy * E + w12 * (yy * E - dr);
+    vz += (w02 * x + w12 * y) * Fz;
   } else {
     // J is the Jacobian of the mean map: the mean's share is J^T v_mean2d
     vx = j00 * v_mean2d[0] + j10 * v_mean2d[1];

@@ -38,7 +38,7 @@ __global__ __launch_bounds__(kBlock) void projection_fwd_kernel(
     int32_t* __restrict__ radii_y) {
   int g = blockIdx.x * kBlock + threadIdx.x;
   if (g >= n) return;
-  CameraParams cam = load_camera(viewmat, Kmat);
+  CameraParams cam = load_camera<CAM>(viewmat, Kmat);
   float m[3], s[3], q[4];
   load3(means + 3 * (size_t)g, m);
   load3(scales + 3 * (size_t)g, s);
@@ -149,7 +149,7 @@ __global__ __launch_bounds__(kBlock) void project_color_fwd_kernel(
     int bin_tight, int tile_w, int tile_h, int32_t* __restrict__ radii_y, int params) {
   __shared__ float4 lds[STAGED ? (kBlock / kWave) * kWave * kShPitchF4 : 1];
   int g = blockIdx.x * kBlock + threadIdx.x;
-  CameraParams cam = load_camera(viewmat, Kmat);
+  CameraParams cam = load_camera<CAM>(viewmat, Kmat);
   float m[3] = {0.f, 0.f, 0.f};
   float o = 1.f;       // the ACTIVATED opacity: every use below sees it, whichever form `opacities` holds
   // params: bin_flags' MGS_PARAMS_* bits.  anti-aliased <=> opac_out receives opacity x compensation
@@ -254,8 +254,8 @@ extern "C" int mgs_projection_fwd(int n, const float* means, const float* quats,
                                   float* compensations, const float* opacities, int radius_rule,
                                   int32_t* radii_y, int camera_model, mgs_stream_t stream) {
   MGS_REQUIRE(n >= 0 && width > 0 && height > 0, "projection_fwd: bad sizes n=%d %dx%d", n, width, height);
-  MGS_REQUIRE(camera_model >= MGS_CAMERA_PINHOLE && camera_model <= MGS_CAMERA_FISHEYE,
-              "projection_fwd: camera_model %d is not MGS_CAMERA_PINHOLE, _ORTHO or _FISHEYE", camera_model);
+  MGS_REQUIRE(is_camera_model(camera_model),
+              "projection_fwd: camera_model %d is not MGS_CAMERA_PINHOLE, _ORTHO, _FISHEYE or _FISHEYE_KB", camera_model);
   if (n == 0) return MGS_OK;
   MGS_REQUIRE(means && quats && scales && viewmat && K && radii && means2d && depths && conics,
               "projection_fwd: null pointer");
@@ -306,6 +306,8 @@ extern "C" int mgs_project_color_fwd(int n, const float* means, const float* qua
   const bool per_axis = (bin_flags & MGS_BIN_RADIUS_OPACITY_AWARE) != 0;
   MGS_REQUIRE((bin_flags & (MGS_BIN_CAMERA_ORTHO | MGS_BIN_CAMERA_FISHEYE)) != (MGS_BIN_CAMERA_ORTHO | MGS_BIN_CAMERA_FISHEYE),
               "project_color_fwd: bin_flags sets both MGS_BIN_CAMERA_ORTHO and MGS_BIN_CAMERA_FISHEYE");
+  MGS_REQUIRE(!several_camera_bits(bin_flags, MGS_BIN_CAMERA_ORTHO | MGS_BIN_CAMERA_FISHEYE | MGS_BIN_CAMERA_FISHEYE_KB),
+              "project_color_fwd: bin_flags sets more than one MGS_BIN_CAMERA_* bit");
   const int cam_model = bin_camera_model(bin_flags);
   const int params = bin_flags & (MGS_PARAMS_RAW | MGS_PARAMS_OPAC_PLAIN);
   MGS_REQUIRE(!(params & MGS_PARAMS_RAW) || opacities,

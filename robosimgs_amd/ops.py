@@ -17,6 +17,7 @@ from __future__ import annotations
 import ctypes
 from typing import Optional, Tuple
 
+import numpy as np
 import torch
 from torch import Tensor
 
@@ -59,19 +60,113 @@ PARAMS_RAW = 64          # the parameter form: bin_flags, the mgs_render_frames*
 PARAMS_OPAC_PLAIN = 128  # bin_flags, with PARAMS_RAW: opac_out keeps the plain activated opacity (not anti-aliased)
 CAMERA_BIN_FLAGS = {0: 0, 1: BIN_CAMERA_ORTHO, 2: BIN_CAMERA_FISHEYE}           # MGS_CAMERA_* -> bin_flags bits
 CAMERA_FRAME_FLAGS = {0: 0, 1: FRAMES_CAMERA_ORTHO, 2: FRAMES_CAMERA_FISHEYE}   # MGS_CAMERA_* -> mgs_render_frames* bits
+# The lens (include/mgs_lens.h): camera_model="fisheye" with distortion coefficients is a model of its own inside the library
+CAMERA_FISHEYE_KB = 3                                           # MGS_CAMERA_FISHEYE_KB
+BIN_CAMERA_FISHEYE_KB = FRAMES_CAMERA_FISHEYE_KB = 256          # its bin_flags / mgs_render_frames* bit
+LENS_ROW_FLOATS = 16       # floats per camera behind K / Ks under that model: K | k1..k4 | u_max | 0 0
+
+
+# (In the two lookups below the tables of the three named models come last, so an entry of theirs wins over the lens's:
+#  tests/test_gpu_camera_models.py puts a key 3 with two camera bits into them to reach the C ABI's both-bits error.)
+def camera_bin_flags(camera) -> int:
+    """MGS_CAMERA_* -> the bin_flags bits that select it."""
+    return {CAMERA_FISHEYE_KB: BIN_CAMERA_FISHEYE_KB, **CAMERA_BIN_FLAGS}[int(camera)]
+
+
+def camera_frame_flags(camera) -> int:
+    """MGS_CAMERA_* -> the mgs_render_frames* bits that select it."""
+    return {CAMERA_FISHEYE_KB: FRAMES_CAMERA_FISHEYE_KB, **CAMERA_FRAME_FLAGS}[int(camera)]
 
 
 def frames_flags(expected_last, latency, tight, per_axis, camera, raw=False) -> int:
     """The flags word of mgs_render_frames / _train / _backward."""
     return ((RASTER_EXPECTED_LAST if expected_last else 0) | (RASTER_LATENCY if latency else 0)
             | (0 if tight else FRAMES_CLASSIC_BOUNDS) | (FRAMES_RADIUS_OPACITY_AWARE if per_axis else 0)
-            | CAMERA_FRAME_FLAGS[int(camera)] | (PARAMS_RAW if raw else 0))
+            | camera_frame_flags(camera) | (PARAMS_RAW if raw else 0))
 
 
-def camera_model_id(camera_model) -> int:
+class LensRows:
+    """A lens that already sits on the device as camera rows: `rows` is a contiguous float32 [C,16] tensor in the layout
+    lens_rows() builds (K | k1..k4 | u_max | 0 0).  Given as distortion= by a caller that keeps the rows in a buffer of its
+    own and overwrites K in place (FrameRenderer's camera slots); the kernels then read K from the rows, not from Ks."""
+    __slots__ = ("rows",)
+
+    def __init__(self, rows: Tensor):
+        self.rows = rows
+
+
+def lens_coefficients(distortion, n_cams=None):
+    """distortion= as the calls take it -- None, or host data (sequence / ndarray) [4] or [C,4] of OpenCV fisheye k1..k4 --
+    -> None when there is no lens (None or all zero: the ideal-fisheye instantiation), else a float64 ndarray [C,4] or
+    [1,4] (one lens for every camera).  A LensRows is returned as it is."""
+    if distortion is None or isinstance(distortion, LensRows):
+        return distortion
+    if torch.is_tensor(distortion):
+        if distortion.is_cuda:
+            raise ValueError("distortion is host data (a sequence or ndarray [4] or [C,4]), not a device tensor")
+        distortion = distortion.numpy()
+    k = np.asarray(distortion, dtype=np.float64)
+    if k.ndim == 1:
+        k = k[None]
+    if k.ndim != 2 or k.shape[1] != 4 or (n_cams is not None and k.shape[0] not in (1, int(n_cams))):
+        raise ValueError(f"distortion must be [4] or [C,4] (k1..k4 per camera), got {tuple(np.shape(distortion))}")
+    if not np.isfinite(k).all():
+        raise ValueError("distortion coefficients must be finite")
+    return k if k.any() else None
+
+
+def camera_model_id(camera_model, distortion=None) -> int:
+    """MGS_CAMERA_* of camera_model; with distortion= (lens_coefficients: valid only with "fisheye") that are not all
+    zero, MGS_CAMERA_FISHEYE_KB."""
     if camera_model not in CAMERA_MODELS:
         raise ValueError(f"camera_model {camera_model!r} not in {tuple(CAMERA_MODELS)}")
+    if distortion is not None:
+        if camera_model != "fisheye":
+            raise ValueError(f"distortion= (fisheye lens coefficients k1..k4) needs camera_model='fisheye', got {camera_model!r}")
+        if lens_coefficients(distortion) is not None:
+            return CAMERA_FISHEYE_KB
     return CAMERA_MODELS[camera_model]
+
+
+# (coefficient bytes, cameras, device) -> [C,7] device tensor k1..k4 | u_max | 0 0.  An entry is NEVER dropped: a captured
+# graph (a Trainer step around rasterization(distortion=)) holds its address.  At _LENS_TAILS_MAX entries (28 bytes of
+# payload each) further lenses are uploaded per call and owned by that call's rows alone.
+_LENS_TAILS: dict = {}
+_LENS_TAILS_MAX = 4096
+
+
+def lens_rows(Ks: Tensor, distortion) -> Tensor:
+    """The [C,16] camera rows of MGS_CAMERA_FISHEYE_KB for Ks [C,3,3] on the device and a lens (lens_coefficients):
+    K row-major | k1..k4 | u_max | 0 0, u_max = theta_max^2 computed per camera on the host in fp64
+    (camera.lens_theta_max); a LensRows hands its own rows back.  The lens part is uploaded once per distinct lens and
+    device and kept for the life of the process, so a later call -- one under graph capture too -- only concatenates
+    device tensors.  A lens this process has not seen cannot be uploaded under graph capture: ValueError (render once with it
+    before capturing, as a warm-up does)."""
+    from .camera import lens_theta_max
+    C = Ks.shape[0]
+    k = lens_coefficients(distortion, C)
+    if k is None:
+        raise ValueError("lens_rows needs distortion coefficients that are not all zero")
+    if isinstance(k, LensRows):
+        rows = k.rows
+        require_device(rows)
+        if tuple(rows.shape) != (C, LENS_ROW_FLOATS) or rows.dtype != torch.float32 or not rows.is_contiguous() \
+                or rows.device != Ks.device:
+            raise ValueError(f"LensRows.rows must be a contiguous float32 tensor [{C},{LENS_ROW_FLOATS}] on {Ks.device}")
+        return rows
+    key = (k.tobytes(), k.shape[0], Ks.device)
+    tail = _LENS_TAILS.get(key)
+    if tail is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise ValueError("this lens has not been used in this process yet and its coefficients cannot be uploaded under "
+                             "graph capture: render once with distortion= before capturing")
+        host = np.zeros((k.shape[0], LENS_ROW_FLOATS - 9))
+        host[:, :4] = k
+        host[:, 4] = [lens_theta_max(row) ** 2 for row in k]
+        tail = torch.from_numpy(host.astype(np.float32)).to(Ks.device)
+        if len(_LENS_TAILS) < _LENS_TAILS_MAX:
+            _LENS_TAILS[key] = tail
+    return torch.cat([Ks.reshape(C, 9), tail.expand(C, -1)], dim=1).contiguous()
 
 
 def radii_x(radii):
@@ -88,7 +183,7 @@ def radii_meta(radii):
 def projection_fwd_raw(means, quats, scales, viewmat, K, width, height, eps2d, near_plane,
                        far_plane, radius_clip, calc_compensations, opacities=None, radius_rule=0, camera=0):
     """radius_rule 1 (MGS_RADIUS_OPACITY_AWARE): radii comes back planar [2,N] (x extents, y extents).
-    camera: MGS_CAMERA_* (camera_model_id)."""
+    camera: MGS_CAMERA_* (camera_model_id); under CAMERA_FISHEYE_KB `K` is the camera's 16-float row (lens_rows)."""
     n = means.shape[0]
     dev = means.device
     radii = torch.empty((2, n) if radius_rule else (n,), dtype=torch.int32, device=dev)
@@ -116,7 +211,8 @@ def project_color_fwd_raw(means, quats, scales, opacities, sh_degree, sh_coeffs,
     lean (needs want_splats and bin_seed): radii / means2d / conics / feats are not written and come back
     as None -- an inference frame, whose raster reads the records and whose binning reads the seed.
     per_axis: project with MGS_RADIUS_OPACITY_AWARE; radii is then planar [2,N] (radii_x / radii_meta).
-    camera: the camera model, MGS_CAMERA_* (camera_model_id).
+    camera: the camera model, MGS_CAMERA_* (camera_model_id); under CAMERA_FISHEYE_KB `K` (and `Ks` of the frames calls
+    below) holds 16-float camera rows (lens_rows).
     raw: scales are log-scales and opacities logits (MGS_PARAMS_RAW); every output is the activated form's.  Unless
     lean, the 5th item is then kept whether anti-aliased or not: the activated opacity (x compensation when
     anti-aliased), which the raster and project_color_bwd_raw need."""
@@ -144,7 +240,7 @@ def project_color_fwd_raw(means, quats, scales, opacities, sh_degree, sh_coeffs,
         ptr(sh_coeffs), ptr(viewmat), ptr(K), width, height, eps2d, near_plane, far_plane,
         radius_clip, ptr(radii_x(radii)), ptr(means2d), ptr(depths), ptr(conics), ptr(opac), stride,
         ptr(feats), ptr(splats),
-        (BIN_TIGHT if bin_seed == "tight" else 0) | (BIN_RADIUS_OPACITY_AWARE if per_axis else 0) | CAMERA_BIN_FLAGS[int(camera)]
+        (BIN_TIGHT if bin_seed == "tight" else 0) | (BIN_RADIUS_OPACITY_AWARE if per_axis else 0) | camera_bin_flags(camera)
         | (PARAMS_RAW if raw else 0) | (PARAMS_OPAC_PLAIN if keep_plain else 0),
         ptr(seed[0]) if seed else None,
         ptr(seed[1]) if seed else None, ptr(radii[1]) if (per_axis and radii is not None) else None, stream_handle()),
@@ -635,7 +731,7 @@ def fully_fused_projection(means: Tensor, covars: Optional[Tensor], quats: Tenso
                            far_plane: float = 1e10, radius_clip: float = 0.0,
                            packed: bool = False, sparse_grad: bool = False,
                            calc_compensations: bool = False, opacities: Optional[Tensor] = None,
-                           radius_rule: str = "classic", camera_model: str = "pinhole"
+                           radius_rule: str = "classic", camera_model: str = "pinhole", distortion=None
                            ) -> Tuple[Tensor, Tensor, Tensor, Tensor, Optional[Tensor]]:
     """World -> screen EWA projection of N Gaussians for C cameras.
     Returns radii [C,N] i32, means2d [C,N,2], depths [C,N], conics [C,N,3],
@@ -644,7 +740,9 @@ def fully_fused_projection(means: Tensor, covars: Optional[Tensor], quats: Tenso
     (gsplat >= 1.5, SURVEY.md A.4: per-axis extents min(3.33, sqrt(2 ln(255 opacity))) sqrt(Sigma_ii), radii [C,N,2];
     `opacities` [N] optional as in that operator, no gradient flows to it -- the extent is not differentiable).
     camera_model: "pinhole", "ortho" or "fisheye" (ideal equidistant, r = f theta), as gsplat's operator; include/mgs.h
-    MGS_CAMERA_* gives the maps.  Depths are camera z under every model."""
+    MGS_CAMERA_* gives the maps.  Depths are camera z under every model.
+    distortion (with "fisheye"): OpenCV fisheye coefficients k1..k4, host data [4] or [C,4] -- theta_d = theta (1 + k1 theta^2
+    + ... + k4 theta^8); Gaussians past the angle where that polynomial folds back are culled.  None / all zero: the ideal lens."""
     if covars is not None:
         raise NotImplementedError("precomputed covariances are not supported; pass quats+scales")
     if packed:
@@ -658,7 +756,9 @@ def fully_fused_projection(means: Tensor, covars: Optional[Tensor], quats: Tenso
     if viewmats.dim() != 3 or viewmats.shape[1:] != (4, 4) or Ks.shape != (viewmats.shape[0], 3, 3):
         raise ValueError("expected viewmats [C,4,4], Ks [C,3,3]")
     rule = radius_rule_id(radius_rule)
-    camera = camera_model_id(camera_model)
+    camera = camera_model_id(camera_model, distortion)
+    if camera == CAMERA_FISHEYE_KB:
+        Ks = lens_rows(Ks, distortion)
     if opacities is not None:
         require_device(opacities)
         opacities = _f32c(opacities.detach())

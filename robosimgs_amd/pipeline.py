@@ -24,7 +24,7 @@ from typing import Dict, List, Optional
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, ops
 from .rendering import rasterization
 
 # ---- streams for the in-flight slots: one hardware queue each, none of them the consumer's -------------------------
@@ -106,7 +106,7 @@ class FrameRenderer:
                  sizing_camera=None, group_ids: Optional[torch.Tensor] = None, n_groups: int = 0,
                  rotate_sh: bool = True, reorder: Optional[str] = "morton", dataset_output=None, dataset_K=None,
                  dataset_keep_float: bool = False, class_ids: Optional[torch.Tensor] = None, n_classes: Optional[int] = None,
-                 labels: bool = False, **raster_kw):
+                 labels: bool = False, distortion=None, **raster_kw):
         """tensors: dict(means, quats, scales, opacities, colors, sh_degree) on the GPU
         (Gaussians.to_torch()); `self.t` is the renderer's own (by default Morton-ordered) copy.  isect_capacity: slots reserved for tile intersections per
         frame; if None it is measured once with `sizing_camera` = (viewmat, K) (required then)
@@ -131,6 +131,11 @@ class FrameRenderer:
         labels=True with group_ids: class = group id + 1, the static Gaussians class 0, n_classes = n_groups + 1.  Every
         slot's graphs then hold the label launch, and fetch() / render() also return "labels" [H,W] uint8 (255: no part)
         and "label_weights" [H,W] float32, the slot's own buffers like the frame.
+
+        distortion=(k1, k2, k3, k4) with camera_model="fisheye": the renderer's lens (rasterization's distortion=), one per
+        renderer like dataset_K.  The coefficients and the end of the lens's range sit behind the camera in every slot's
+        buffer, written once at capture; a submit stays one 25-float copy.  Combines with group_ids and labels; refused
+        with dataset_output (pinhole-only).
 
         raw_params=True (forwarded to rasterization like every raster_kw): `tensors` hold log-scales and opacity logits
         (Gaussians.to_torch(raw=True)), so a loaded .ply renders without an activation pass on the host.  Static scenes
@@ -183,6 +188,10 @@ class FrameRenderer:
         self.dev = tensors["means"].device
         self.width, self.height, self.mode = int(width), int(height), render_mode
         self.kw = dict(raster_kw)
+        # the lens: None when there is none (no coefficients, or all zero: the ideal fisheye)
+        ops.camera_model_id(self.kw.get("camera_model", "pinhole"), distortion)      # fisheye only
+        k = ops.lens_coefficients(distortion, 1)
+        self.distortion = tuple(float(v) for v in k[0]) if k is not None else None
         self.dataset_dtype, self.dataset_K, self.dataset_keep_float = dataset_output, None, bool(dataset_keep_float)
         if dataset_output is not None:
             if self.kw.get("camera_model", "pinhole") != "pinhole":
@@ -222,9 +231,11 @@ class FrameRenderer:
         Kt = torch.as_tensor(np.asarray(K, dtype=np.float32)).reshape(1, 3, 3).to(self.dev)
         return vm, Kt
 
-    def _raster(self, vm, K, cap, t=None, dataset_out=None, schedule=None, labels=True):
+    def _raster(self, vm, K, cap, t=None, dataset_out=None, schedule=None, labels=True, rows=None):
         t = self.t if t is None else t
         kw = self.kw if schedule is None else dict(self.kw, raster_schedule=schedule)
+        if self.distortion is not None:     # a slot's camera buffer carries the lens behind K; any other K gets it here
+            kw = dict(kw, distortion=ops.LensRows(rows) if rows is not None else self.distortion)
         if labels and self.class_ids is not None:
             kw = dict(kw, class_ids=self.class_ids, n_classes=self.n_classes)
         return rasterization(t["means"], t["quats"], t["scales"], t["opacities"], t["colors"], vm,
@@ -239,6 +250,13 @@ class FrameRenderer:
         vm.copy_(torch.eye(4, device=self.dev).reshape(1, 4, 4))
         vm[0, 2, 3] = -1e3                                 # warm-up camera: everything is behind it, nothing to bin
         K.copy_(torch.tensor([[[1.0, 0, 0.5], [0, 1.0, 0.5], [0, 0, 1]]], device=self.dev))
+        rows = None
+        if self.distortion is not None:
+            # floats 16..31 are the camera's row under the lens (include/mgs.h): K | k1..k4 | u_max | 0 0 -- the lens part
+            # is written here once, submit() overwrites the first 25 floats only
+            from .camera import lens_theta_max
+            cam[25:30].copy_(torch.tensor([*self.distortion, lens_theta_max(self.distortion) ** 2], dtype=torch.float32))
+            rows = cam[16:32].view(1, 16)
         pose = None
         if self.group_ids is not None:       # dynamic scene: this slot's transforms and posed copy
             from .transform import pack_transforms
@@ -263,11 +281,11 @@ class FrameRenderer:
 
         def body(schedule):
             if pose is None:
-                return self._raster(vm, K, self.capacity, dataset_out=ds_out, schedule=schedule)
+                return self._raster(vm, K, self.capacity, dataset_out=ds_out, schedule=schedule, rows=rows)
             from .transform import transform_gaussians
             posed = transform_gaussians(self.t, group_ids=self.group_ids, rotate_sh=self.rotate_sh,
                                         out=pose["t"], packed=(pose["x"], pose["r"]))
-            return self._raster(vm, K, self.capacity, posed, dataset_out=ds_out, schedule=schedule)
+            return self._raster(vm, K, self.capacity, posed, dataset_out=ds_out, schedule=schedule, rows=rows)
         variants, pool = {}, None
         for schedule in (("throughput", "latency") if self._both else (self.kw["raster_schedule"],)):
             with torch.cuda.stream(stream):

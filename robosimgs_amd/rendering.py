@@ -294,6 +294,7 @@ def rasterization(means: Tensor, quats: Tensor, scales: Tensor, opacities: Tenso
                   radius_rule: str = "classic",
                   dataset_out=None,
                   camera_model: str = "pinhole",
+                  distortion=None,
                   raw_params: bool = False,
                   class_ids: Optional[Tensor] = None,
                   n_classes: Optional[int] = None) -> Tuple[Tensor, Tensor, Dict]:
@@ -329,6 +330,13 @@ def rasterization(means: Tensor, quats: Tensor, scales: Tensor, opacities: Tenso
     distortion coefficients), gsplat's names; include/mgs.h MGS_CAMERA_* gives the maps.  Every path honours it (a
     compile-time policy of the projection kernels, like the radius rule).  Depths stay camera z and the SH view
     direction mean - campos under every model.  dataset_out is pinhole-only (its ray distance is pinhole's).
+
+    distortion (camera_model="fisheye" only, else ValueError): the lens's OpenCV fisheye coefficients k1..k4 as host data,
+    a sequence or ndarray [4] (one lens) or [C,4] (one per camera) -- cv2.fisheye / nerfstudio OPENCV_FISHEYE:
+    theta_d = theta (1 + k1 theta^2 + k2 theta^4 + k3 theta^6 + k4 theta^8).  Projection, Jacobian and every gradient are
+    the lens's (include/mgs.h MGS_CAMERA_FISHEYE_KB, a fourth instantiation of the projection kernels); a Gaussian past
+    theta_max, where the polynomial stops growing (camera.lens_theta_max, computed here on the host), is culled like one
+    behind the near plane.  None or all zero: the ideal lens, bit for bit the call without the keyword.  meta is unchanged.
 
     backward_segment (SH path, when gradients are wanted): list entries per unit of work of the backward raster
     (a power of two >= 64; 0 = one unit per tile, the whole-list walk).  The training forward stores per-pixel
@@ -369,7 +377,7 @@ def rasterization(means: Tensor, quats: Tensor, scales: Tensor, opacities: Tenso
     if tile_bounds not in ("tight", "classic"):
         raise ValueError(f"tile_bounds {tile_bounds!r} not in ('tight', 'classic')")
     rule = ops.radius_rule_id(radius_rule)
-    camera = ops.camera_model_id(camera_model)
+    camera = ops.camera_model_id(camera_model, distortion)
     if dataset_out is not None and camera != 0:
         raise ValueError(f"dataset_out converts depth to ray distance through a pinhole K^-1: camera_model "
                          f"{camera_model!r} has no dataset output")
@@ -397,6 +405,7 @@ def rasterization(means: Tensor, quats: Tensor, scales: Tensor, opacities: Tenso
         raise ValueError("expected viewmats [C,4,4], Ks [C,3,3]")
     means, quats, scales, opacities = _f32c(means), _f32c(quats), _f32c(scales), _f32c(opacities)
     colors, viewmats, Ks, backgrounds = _f32c(colors), _f32c(viewmats), _f32c(Ks), _f32c(backgrounds)
+    lens_rows = ops.lens_rows(Ks, distortion) if camera == ops.CAMERA_FISHEYE_KB else None
     width, height = int(width), int(height)
     antialiased = rasterize_mode == "antialiased"
     want_rgb = render_mode.startswith("RGB")
@@ -429,7 +438,9 @@ def rasterization(means: Tensor, quats: Tensor, scales: Tensor, opacities: Tenso
             labels=labels)
         # the autograd function publishes per-camera intermediates (and, after backward, "means2d_grad" /
         # "means2d_absgrad" lists) into the meta dict
-        render, alphas = _RenderSH.apply(means, quats, scales, opacities, colors, viewmats, Ks, backgrounds, cfg, meta)
+        # (under the lens the kernels read the cameras' 16-float rows where they read K otherwise)
+        render, alphas = _RenderSH.apply(means, quats, scales, opacities, colors, viewmats,
+                                         Ks if lens_rows is None else lens_rows, backgrounds, cfg, meta)
         if depth_only_via_sh:
             render = render[..., 3:4]
         if "label_frames" in meta:
@@ -469,7 +480,7 @@ def rasterization(means: Tensor, quats: Tensor, scales: Tensor, opacities: Tenso
         radii, means2d, depths, conics, comps = ops.fully_fused_projection(
             means, None, quats, scales, viewmats, Ks, width, height, eps2d, near_plane, far_plane,
             radius_clip, calc_compensations=antialiased, opacities=opacities if rule else None,
-            radius_rule=radius_rule, camera_model=camera_model)
+            radius_rule=radius_rule, camera_model=camera_model, distortion=distortion)
         opac = opacities.unsqueeze(0).expand(C, N)
         if antialiased:
             opac = opac * comps
@@ -523,6 +534,8 @@ def render(gaussians, cameras: Sequence, sh_degree: Optional[int] = None,
     if any(c.model != cams[0].model for c in cams):
         raise ValueError("all cameras of one call must share a camera model")
     kw.setdefault("camera_model", cams[0].model)
+    if cams[0].model == "fisheye" and any(c.distortion is not None for c in cams):
+        kw.setdefault("distortion", np.array([c.distortion or (0.0,) * 4 for c in cams], dtype=np.float64))
     t = tensors if tensors is not None else gaussians.to_torch(device, sh_degree)
     viewmats = torch.from_numpy(np.stack([c.viewmat() for c in cams]).astype(np.float32)).to(device)
     Ks = torch.from_numpy(np.stack([c.K for c in cams]).astype(np.float32)).to(device)
