@@ -15,7 +15,8 @@ __version__ = "0.1.0"
 
 _DEVICE_API = {"rasterization", "render", "check_isect_status", "fully_fused_projection",
                "spherical_harmonics", "isect_tiles", "isect_offset_encode",
-               "rasterize_to_pixels", "rasterize_labels", "render_sharded", "gather_frames"}
+               "rasterize_to_pixels", "rasterize_labels", "rasterize_votes", "assign_classes", "lift_labels",
+               "render_sharded", "gather_frames"}
 
 
 def __getattr__(name):  # lazy: keeps `import robosimgs_amd` torch-free for host-only use
@@ -23,9 +24,13 @@ def __getattr__(name):  # lazy: keeps `import robosimgs_amd` torch-free for host
         from . import rendering
         return getattr(rendering, name)
     if name in ("fully_fused_projection", "spherical_harmonics", "isect_tiles",
-                "isect_offset_encode", "rasterize_to_pixels", "rasterize_labels"):
+                "isect_offset_encode", "rasterize_to_pixels", "rasterize_labels", "rasterize_votes",
+                "assign_classes"):
         from . import ops
         return getattr(ops, name)
+    if name in ("lift_labels", "LiftResult"):
+        from . import lifting
+        return getattr(lifting, name)
     if name in ("composite_over", "frame_to_u8"):
         from . import compositing
         return getattr(compositing, name)

@@ -105,11 +105,17 @@ _LABEL_SIGNATURES = {
     "mgs_render_frames_labeled": (_SIGNATURES["mgs_render_frames"][0][:-3] + [p, i, p, p]
                                   + _SIGNATURES["mgs_render_frames"][0][-3:], c_int),
 }
+# every function include/mgs_lift.h declares (the same libraries again): votes are uint64 Q32 behind a void pointer
+_LIFT_SIGNATURES = {
+    "mgs_raster_votes": ([i, p, p, p, p, p, i, i, i, i, i, p, p, p, i, i, p, p], c_int),
+    "mgs_lift_assign": ([i, i, p, f, p, p, p], c_int),
+}
 del p, i, f, u32, img
 EXPORTS = list(_SIGNATURES)
 OPTIM_EXPORTS = list(_OPTIM_SIGNATURES)
 REFINE_EXPORTS = list(_REFINE_SIGNATURES)
 LABEL_EXPORTS = list(_LABEL_SIGNATURES)
+LIFT_EXPORTS = list(_LIFT_SIGNATURES)
 LABEL_NONE, LABELS_MAX_CLASSES = 255, 32    # MGS_LABEL_NONE, MGS_LABELS_MAX_CLASSES
 
 
@@ -131,7 +137,7 @@ def _load(path: str = None, hooks: bool = False) -> ctypes.CDLL:
         raise MgsError(f"{LIB_PATH} reports ABI version {have}, this binding was written for {MGS_VERSION} "
                        "(include/mgs.h): rebuild the library (`python robosimgs_amd/csrc/build.py --force`)")
     for name, (argtypes, restype) in (*_SIGNATURES.items(), *_OPTIM_SIGNATURES.items(), *_REFINE_SIGNATURES.items(),
-                                      *_LABEL_SIGNATURES.items()):
+                                      *_LABEL_SIGNATURES.items(), *_LIFT_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here == header/library mismatch
         fn.argtypes = argtypes
         fn.restype = restype

@@ -7,6 +7,8 @@ Appendix A.1), each a thin torch wrapper over one C-ABI entry point of libmgs.so
     isect_offset_encode      -> mgs_isect_offset_encode
     rasterize_to_pixels      -> mgs_rasterize_fwd / mgs_rasterize_bwd
     rasterize_labels         -> mgs_raster_labels (include/mgs_labels.h; no gsplat counterpart, no backward)
+    rasterize_votes          -> mgs_raster_votes (include/mgs_lift.h: 2D masks -> per-Gaussian class votes)
+    assign_classes           -> mgs_lift_assign
 
 Inputs are post-activation fp32 CUDA(HIP) tensors (the render-path calls also take the raw form, log-scales and
 opacity logits, with raw=True: include/mgs.h MGS_PARAMS_RAW); ids are int32, keys int64.  All kernels
@@ -612,6 +614,88 @@ def raster_labels_raw(tl: "TileLists", class_ids, n_classes, width, height, mean
     return labels, weights
 
 
+VOTE_ONE = 1 << 32       # a vote of one pixel at full weight (include/mgs_lift.h: unsigned Q32 fixed point)
+
+
+def check_vote_buffers(mask, n_classes, votes, shape) -> None:
+    """The kernel gathers prod(shape) mask bytes and adds into votes[row * n_classes + class] through raw pointers: the
+    buffers must hold exactly that.  torch's int64 carries the unsigned Q32 value (it cannot wrap while views x pixels
+    covered per view stays below 2^31: include/mgs_lift.h)."""
+    check_n_classes(n_classes)
+    if mask.dtype != torch.uint8 or not mask.is_contiguous() or tuple(mask.shape) != tuple(shape):
+        raise ValueError(f"mask must be a contiguous uint8 tensor {tuple(shape)}")
+    if votes.dtype != torch.int64 or not votes.is_contiguous() or votes.dim() != 2 or votes.shape[1] != n_classes:
+        raise ValueError(f"votes must be a contiguous int64 tensor [rows, {n_classes}]")
+    require_device(mask, votes)
+
+
+def raster_votes_raw(tl: "TileLists", mask, n_classes, width, height, votes, means2d=None, conics=None, opacities=None,
+                     splats=None, row_offset=0, use_group_order=True, tile_offsets=None):
+    """mgs_raster_votes on one camera's lists: ADDS into votes int64 [rows, n_classes] (Q32 fixed point, votes_to_float)
+    the blend weight every listed Gaussian contributes to the pixels of each class of `mask`, uint8 [H,W] with values
+    outside 0..n_classes-1 (255, say) voting for nothing (include/mgs_lift.h).  The Gaussians are the rows of `splats` --
+    the packed records the frame's raster read -- or of means2d / conics / opacities; list id `id` votes into row
+    id - row_offset and nowhere if that is outside the buffer.  use_group_order / tile_offsets: as raster_labels_raw.
+    Returns votes."""
+    src = splats if splats is not None else means2d
+    if src is None or (splats is None and (conics is None or opacities is None)):
+        raise ValueError("raster_votes_raw needs splats, or means2d, conics and opacities")
+    n = src.shape[0]
+    check_vote_buffers(mask, n_classes, votes, (height, width))
+    # the Gaussian arrays and the lists reach the kernel as raw pointers too
+    arrays = ((splats, (n, 12), "splats"),) if splats is not None else (
+        (means2d, (n, 2), "means2d"), (conics, (n, 3), "conics"), (opacities, (n,), "opacities"))
+    for t, shape, name in arrays:
+        if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shape:
+            raise ValueError(f"{name} must be a contiguous float32 tensor {shape}")
+    tile_w, tile_h = -(-width // TILE_SIZE), -(-height // TILE_SIZE)
+    order = getattr(tl, "group_order", None) if use_group_order else None
+    offsets = tile_offsets if tile_offsets is not None else tl.tile_offsets
+    for t, name in ((tl.flatten_ids, "flatten_ids"), (offsets, "tile_offsets"), (order, "group_order")):
+        if t is not None and (t.dtype != torch.int32 or not t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous int32 tensor")
+    if offsets.numel() < tile_w * tile_h + 1:
+        raise ValueError(f"tile_offsets holds {offsets.numel()} entries, the frame has {tile_w * tile_h} tiles (+ 1)")
+    require_device(src, conics, opacities, tl.flatten_ids, offsets, order)
+    check(_lib.lib().mgs_raster_votes(n, ptr(means2d), ptr(conics), ptr(opacities), ptr(splats), ptr(mask), int(n_classes),
+                                      width, height, tile_w, tile_h,
+                                      ptr(offsets), ptr(tl.flatten_ids), ptr(order), int(row_offset), votes.shape[0],
+                                      ptr(votes),
+                                      stream_handle()),
+          "mgs_raster_votes")
+    return votes
+
+
+def assign_classes(votes: Tensor, min_vote: float = 0.0, out=None) -> Tuple[Tensor, Tensor]:
+    """votes int64 [N,K] (rasterize_votes) -> (class_ids int32 [N], confidence float32 [N]): the class with the most
+    votes, ties to the lowest class, if that vote exceeds min_vote (in pixels of full weight, >= 0), else -1; confidence is
+    that vote's share of the row's total, 0 where the class is -1.  A Gaussian no mask pixel saw has class -1.
+    out = (class_ids, confidence) to write into existing buffers.  No read-back: capturable in a graph."""
+    require_device(votes)
+    if votes.dtype != torch.int64 or not votes.is_contiguous() or votes.dim() != 2:
+        raise ValueError("votes must be a contiguous int64 tensor [N, K]")
+    n, k = votes.shape
+    check_n_classes(k)
+    if out is None:
+        class_ids = torch.empty(n, dtype=torch.int32, device=votes.device)
+        confidence = torch.empty(n, dtype=torch.float32, device=votes.device)
+    else:
+        class_ids, confidence = out
+        require_device(class_ids, confidence)
+        if class_ids.dtype != torch.int32 or not class_ids.is_contiguous() or tuple(class_ids.shape) != (n,):
+            raise ValueError(f"class_ids must be a contiguous int32 tensor ({n},)")
+        if confidence.dtype != torch.float32 or not confidence.is_contiguous() or tuple(confidence.shape) != (n,):
+            raise ValueError(f"confidence must be a contiguous float32 tensor ({n},)")
+    check(_lib.lib().mgs_lift_assign(n, k, ptr(votes), float(min_vote), ptr(class_ids), ptr(confidence), stream_handle()),
+          "mgs_lift_assign")
+    return class_ids, confidence
+
+
+def votes_to_float(votes: Tensor) -> Tensor:
+    """Q32 votes -> float64, in pixels of full weight."""
+    return votes.to(torch.float64) * (1.0 / VOTE_ONE)
+
+
 def rasterize_bwd_raw(means2d, conics, feats, opacities, background, width, height, tile_w,
                       tile_h, tile_offsets, flatten_ids, alphas, last_ids, v_render, v_alphas,
                       absgrad=False, accum=None):
@@ -989,3 +1073,45 @@ def rasterize_labels(means2d: Tensor, conics: Tensor, opacities: Tensor, class_i
                           opacities.view(C * N), out=(labels[c], weights[c] if return_weights else None), use_group_order=False,
                           tile_offsets=offsets_ext[c * n_tiles:])
     return (labels, weights) if return_weights else labels
+
+
+@torch.no_grad()
+def rasterize_votes(means2d: Tensor, conics: Tensor, opacities: Tensor, masks: Tensor, n_classes: int, image_width: int,
+                    image_height: int, tile_size: int, isect_offsets: Tensor, flatten_ids: Tensor,
+                    votes: Optional[Tensor] = None) -> Tensor:
+    """2D part masks lifted onto the Gaussians of the frames rasterize_to_pixels blends from the same arguments: means2d
+    [C,N,2], conics [C,N,3], opacities [C,N], masks [C,H,W] uint8 (a value outside 0..n_classes-1 votes for nothing),
+    isect_offsets [C,th,tw], flatten_ids [n_isects] -> votes int64 [N, n_classes]: votes[i,k] is the sum over all C
+    cameras and all pixels with mask == k of the weight the blend gives Gaussian i there, as unsigned Q32 fixed point
+    (votes_to_float).  Integers: the same bits in every run and under any split of the cameras over calls; votes=
+    continues an earlier call.  assign_classes turns them into class ids.  Not differentiable."""
+    if tile_size != TILE_SIZE:
+        raise NotImplementedError(f"tile_size must be {TILE_SIZE}")
+    require_device(means2d, conics, opacities, masks, isect_offsets, flatten_ids, votes)
+    C, N = means2d.shape[0], means2d.shape[1]
+    if conics.shape != (C, N, 3) or opacities.shape != (C, N) or means2d.shape != (C, N, 2):
+        raise ValueError("expected means2d [C,N,2], conics [C,N,3], opacities [C,N]")
+    n_classes = check_n_classes(n_classes)
+    width, height = int(image_width), int(image_height)
+    tile_w, tile_h = -(-width // TILE_SIZE), -(-height // TILE_SIZE)
+    if tuple(isect_offsets.shape) != (C, tile_h, tile_w):
+        raise ValueError(f"isect_offsets shape {tuple(isect_offsets.shape)} != {(C, tile_h, tile_w)}")
+    if tuple(masks.shape) != (C, height, width) or masks.dtype != torch.uint8:
+        raise ValueError(f"masks must be a uint8 tensor {(C, height, width)}")
+    masks = masks.contiguous()
+    n_tiles = tile_w * tile_h
+    dev = means2d.device
+    if votes is None:
+        votes = torch.zeros(N, n_classes, dtype=torch.int64, device=dev)
+    elif tuple(votes.shape) != (N, n_classes):
+        raise ValueError(f"votes shape {tuple(votes.shape)} != {(N, n_classes)}")
+    means2d, conics, opacities = _f32c(means2d.detach()), _f32c(conics.detach()), _f32c(opacities.detach())
+    tl = TileLists()
+    tl.flatten_ids = flatten_ids.to(torch.int32).contiguous()
+    end = torch.full((1,), tl.flatten_ids.numel(), dtype=torch.int32, device=dev)
+    offsets_ext = torch.cat([isect_offsets.reshape(-1).to(torch.int32), end])
+    for c in range(C):       # ids in flatten_ids are cam*N + gaussian: the flat [C*N,...] views, rows from c*N
+        raster_votes_raw(tl, masks[c], n_classes, width, height, votes, means2d.view(C * N, 2), conics.view(C * N, 3),
+                         opacities.view(C * N), row_offset=c * N, use_group_order=False,
+                         tile_offsets=offsets_ext[c * n_tiles:])
+    return votes
