@@ -16,7 +16,7 @@ __version__ = "0.1.0"
 _DEVICE_API = {"rasterization", "render", "check_isect_status", "fully_fused_projection",
                "spherical_harmonics", "isect_tiles", "isect_offset_encode",
                "rasterize_to_pixels", "rasterize_labels", "rasterize_votes", "assign_classes", "lift_labels",
-               "render_sharded", "gather_frames"}
+               "fit_hinge", "fit_hinge_points", "render_sharded", "gather_frames"}
 
 
 def __getattr__(name):  # lazy: keeps `import robosimgs_amd` torch-free for host-only use
@@ -31,6 +31,9 @@ def __getattr__(name):  # lazy: keeps `import robosimgs_amd` torch-free for host
     if name in ("lift_labels", "LiftResult"):
         from . import lifting
         return getattr(lifting, name)
+    if name in ("fit_hinge", "fit_hinge_points", "hinge_fit_raw", "Hinge"):
+        from . import articulation
+        return getattr(articulation, name)
     if name in ("composite_over", "frame_to_u8"):
         from . import compositing
         return getattr(compositing, name)

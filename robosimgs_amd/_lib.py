@@ -110,12 +110,19 @@ _LIFT_SIGNATURES = {
     "mgs_raster_votes": ([i, p, p, p, p, p, i, i, i, i, i, p, p, p, i, i, p, p], c_int),
     "mgs_lift_assign": ([i, i, p, f, p, p, p], c_int),
 }
+# every function include/mgs_hinge.h declares (the same libraries again): the workspace size is a query of its own, and
+# joint is 16 doubles behind a void pointer
+_HINGE_SIGNATURES = {
+    "mgs_hinge_workspace_bytes": ([i, i], c_size_t),
+    "mgs_hinge_fit": ([i, p, i, p, f, p, c_size_t, p, p, p, p], c_int),
+}
 del p, i, f, u32, img
 EXPORTS = list(_SIGNATURES)
 OPTIM_EXPORTS = list(_OPTIM_SIGNATURES)
 REFINE_EXPORTS = list(_REFINE_SIGNATURES)
 LABEL_EXPORTS = list(_LABEL_SIGNATURES)
 LIFT_EXPORTS = list(_LIFT_SIGNATURES)
+HINGE_EXPORTS = list(_HINGE_SIGNATURES)
 LABEL_NONE, LABELS_MAX_CLASSES = 255, 32    # MGS_LABEL_NONE, MGS_LABELS_MAX_CLASSES
 
 
@@ -137,7 +144,8 @@ def _load(path: str = None, hooks: bool = False) -> ctypes.CDLL:
         raise MgsError(f"{LIB_PATH} reports ABI version {have}, this binding was written for {MGS_VERSION} "
                        "(include/mgs.h): rebuild the library (`python robosimgs_amd/csrc/build.py --force`)")
     for name, (argtypes, restype) in (*_SIGNATURES.items(), *_OPTIM_SIGNATURES.items(), *_REFINE_SIGNATURES.items(),
-                                      *_LABEL_SIGNATURES.items(), *_LIFT_SIGNATURES.items()):
+                                      *_LABEL_SIGNATURES.items(), *_LIFT_SIGNATURES.items(),
+                                      *_HINGE_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here == header/library mismatch
         fn.argtypes = argtypes
         fn.restype = restype
