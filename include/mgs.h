@@ -502,6 +502,15 @@ int mgs_project_color_bwd(int n, const float *means, const float *quats, const f
  *   foreground in front (no splats, or fg_depth <= bg_depth): out = fg,  depth = fg_depth
  *   foreground behind the splats:        out = bg + (1 - alpha) fg,       depth = bg_depth
  *   no foreground:                       out = bg + (1 - alpha) backdrop, depth = bg_depth | +inf
+ * At the edges the rule is its C reading, comparison by comparison:
+ *   has_fg = fg_mask ? fg_mask != 0 : (fg_depth > 0 && fg_depth < inf)      (a NaN depth is no foreground)
+ *   front  = has_fg && (!(alpha > 0) || fg_depth <= bg_depth)
+ *   depth  = front ? fg_depth : (alpha > 0 ? bg_depth : +inf)
+ * so alpha == 0, -0.0 and NaN mean "no splats here" (the foreground is in front, whatever either depth holds), the
+ * smallest subnormal alpha is splats, equal depths put the foreground in front, and a NaN on either side of
+ * fg_depth <= bg_depth puts it behind.  A front pixel is SELECTED: out is the foreground's bits and nothing
+ * the splat layer holds behind it (NaN, inf) reaches the output.  A blended pixel is plain fp32 arithmetic and
+ * propagates non-finite values.
  * The reference names this step (README.md:53-56) but has not released it.
  * ----------------------------------------------------------------------------------- */
 int mgs_composite_over(int n_px, const float *bg_rgb, const float *bg_alpha,
@@ -512,7 +521,10 @@ int mgs_composite_over(int n_px, const float *bg_rgb, const float *bg_alpha,
 /* 8-bit frame for the dataset writer / the multi-GPU gather: out[P,3] = round(255 *
  * clamp(rgb + (1 - alpha) * background, 0, 1)) -- splatfacto's post-processing
  * and the quantisation of an image file.  rgb[P,rgb_stride] (first three channels are used, so
- * an RGB+ED render can be passed as is), alpha[P], background[3] nullable (black). */
+ * an RGB+ED render can be passed as is), alpha[P], background[3] nullable (black).
+ * The byte is rint(255 * fmin(fmax(v, 0), 1)) of v = rgb + (1 - alpha) * background in fp32: round half to
+ * even (127.5 -> 128, 126.5 -> 126), v < 0 and -inf -> 0, v > 1 and +inf -> 255, NaN -> 0 (fmax drops it),
+ * whichever of rgb, alpha or inf - inf made it. */
 int mgs_frame_to_u8(int n_px, const float *rgb, int rgb_stride, const float *alpha,
                     const float *background, uint8_t *out, mgs_stream_t stream);
 
@@ -543,7 +555,10 @@ int mgs_frame_to_dataset(int width, int height, const float *colors, int color_s
  *   cells_w = int(w / scale) (computed by the caller as the reference does); every point goes
  *   to cell (clip(round_half_even(u / scale)), clip(round_half_even(v / scale))), each cell
  *   keeps min(bg_depth, depths) and the index of the first point attaining it (torch_scatter
- *   scatter_min; N where no point is strictly below bg_depth).  depth_map[h,w] is the
+ *   scatter_min; N where no point is strictly below bg_depth).  -0.0 and +0.0 are one depth (neither is below
+ *   the other, or below a zero bg_depth; the map stores +0.0).  A rounded quotient that is NaN, infinite or outside
+ *   [-2^31, 2^31) goes to cell 0 on that axis, +inf and 3e9 included: the reference's int32 cast gives INT_MIN
+ *   there and its clip does the rest.  depth_map[h,w] is the
  *   nearest-neighbour upsample (cv2.INTER_NEAREST), index[cells_w*cells_h] (nullable) is in the
  *   reference's cell order u * cells_h + v.  uv_stride = floats per uv row (2 or 3).
  *   Workspace: two-phase size query (8 bytes per cell).

@@ -41,7 +41,12 @@ def get_depth_map(uv, depth, h, w, bg_depth=1e10, scale=2):
     """point_utils.py:44-73.  Returns (depth_map [h,w] float32, index [(w/scale)*(h/scale)] int64
     in the reference's column-major cell order u * _h + v; index == N where no point won)."""
     _h, _w = int(h / scale), int(w / scale)
-    uv = np.round(np.asarray(uv, dtype=np.float64) / scale).astype(np.int32)[..., :2]   # half to even
+    q = np.round(np.asarray(uv, dtype=np.float64)[..., :2] / scale)                     # half to even
+    # the reference's .astype(np.int32) (point_utils.py:60), stated instead of relied on: on the machines it runs on
+    # the conversion gives INT_MIN for a NaN, an infinity and every value outside [-2^31, 2^31), which the clip
+    # below sends to cell 0 -- also where the value was huge and POSITIVE
+    in_range = np.isfinite(q) & (q >= -2.0 ** 31) & (q < 2.0 ** 31)
+    uv = np.where(in_range, q, -2.0 ** 31).astype(np.int64)
     uv = uv.clip(0, np.array([_w, _h]) - 1)
     d = np.asarray(depth, dtype=np.float32).reshape(-1)
     cell = uv[:, 0].astype(np.int64) * _h + uv[:, 1]

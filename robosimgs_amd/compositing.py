@@ -27,7 +27,8 @@ def composite_over(bg_rgb: torch.Tensor, bg_alpha: torch.Tensor, bg_depth: torch
     flat = lambda t_: _f32c(t_).reshape(n_px)
     b_rgb, f_rgb = _f32c(bg_rgb).reshape(n_px, 3), _f32c(fg_rgb).reshape(n_px, 3)
     b_a, b_d, f_d = flat(bg_alpha), flat(bg_depth), flat(fg_depth)
-    mask = fg_mask.reshape(n_px).to(torch.uint8).contiguous() if fg_mask is not None else None
+    # present where the mask is non-zero, whatever its type (0.5 and 256.0 are present; a cast alone would drop both)
+    mask = (fg_mask.reshape(n_px) != 0).to(torch.uint8).contiguous() if fg_mask is not None else None
     bd = (torch.tensor(list(backdrop), dtype=torch.float32, device=bg_rgb.device)
           if backdrop is not None else None)
     out_rgb = torch.empty(n_px, 3, dtype=torch.float32, device=bg_rgb.device)
@@ -43,7 +44,9 @@ def frame_to_u8(colors: torch.Tensor, alphas: torch.Tensor,
                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """colors [...,D>=3] (the first three channels are RGB, so an "RGB+ED" render works as is),
     alphas [...,1] or [...] -> uint8 [...,3] = round(255 * clamp(rgb + (1 - alpha) * bg, 0, 1)):
-    the image a dataset writer stores, a quarter of the bytes to gather or download."""
+    the image a dataset writer stores, a quarter of the bytes to gather or download.  Round half to even;
+    NaN gives 0 (include/mgs.h).  out: a contiguous uint8 tensor of 3 bytes per pixel on the colours'
+    device receives the frame (any byte offset)."""
     require_device(colors, alphas)
     lead = colors.shape[:-1]
     n_px = int(torch.Size(lead).numel())
@@ -53,6 +56,9 @@ def frame_to_u8(colors: torch.Tensor, alphas: torch.Tensor,
           if background is not None else None)
     if out is None:
         out = torch.empty(n_px, 3, dtype=torch.uint8, device=colors.device)
+    elif (not torch.is_tensor(out) or out.dtype != torch.uint8 or out.device != c.device
+          or out.numel() != 3 * n_px or not out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous uint8 tensor of {3 * n_px} bytes on {c.device}")
     check(_lib.lib().mgs_frame_to_u8(n_px, ptr(c), c.shape[1], ptr(a), ptr(bg), ptr(out), stream_handle()),
           "mgs_frame_to_u8")
     return out.reshape(*lead, 3)

@@ -34,11 +34,11 @@ __global__ __launch_bounds__(256) void composite_kernel(
       f0 = fg_rgb[3 * (size_t)p]; f1 = fg_rgb[3 * (size_t)p + 1]; f2 = fg_rgb[3 * (size_t)p + 2];
     }
     const bool front = has_fg && (!(a > 0.f) || zf <= zb);
-    const float t = front ? 0.f : 1.f;          // weight of the splat layer
-    const float w = front ? 1.f : 1.f - a;      // weight of the foreground / backdrop
-    out_rgb[3 * (size_t)p] = t * b0 + w * f0;
-    out_rgb[3 * (size_t)p + 1] = t * b1 + w * f1;
-    out_rgb[3 * (size_t)p + 2] = t * b2 + w * f2;
+    // a front pixel is the foreground's very bits: whatever the splats hold behind it (NaN, inf) stays hidden
+    const float w = 1.f - a;                    // weight of the foreground / backdrop behind the splats
+    out_rgb[3 * (size_t)p] = front ? f0 : b0 + w * f0;
+    out_rgb[3 * (size_t)p + 1] = front ? f1 : b1 + w * f1;
+    out_rgb[3 * (size_t)p + 2] = front ? f2 : b2 + w * f2;
     out_depth[p] = front ? zf : (a > 0.f ? zb : (has_fg ? zf : INFINITY));
   }
 }

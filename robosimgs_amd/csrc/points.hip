@@ -11,9 +11,11 @@ namespace {
 
 constexpr int kBlock = 256;
 
-// float -> uint32 whose unsigned order is the float order (negative depths included)
+// float -> uint32 whose unsigned order is the float order (negative depths included).  -0.0 maps to +0.0's key:
+// the reference's '<' does not tell the two zeros apart, so neither may undercut the other (or a zero bg_depth)
 __device__ __forceinline__ uint32_t sortable_bits(float f) {
   uint32_t u = __float_as_uint(f);
+  if (u == 0x80000000u) u = 0u;
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 __device__ __forceinline__ float from_sortable(uint32_t s) {
@@ -52,10 +54,12 @@ __global__ __launch_bounds__(kBlock) void zbuffer_splat_kernel(
   if (i >= n) return;
   float d = depth[i];
   if (d != d) return;                                             // NaN never wins a '<'
-  // np.round(uv / scale) (half to even), cast to int32, clipped to the cell grid
+  // np.round(uv / scale) (half to even), cast to int32, clipped to the cell grid.  The reference's cast sends a
+  // rounded quotient that is NaN, infinite or outside int32 to INT_MIN, which the clip turns into cell 0
+  // (include/mgs.h states the rule); only [0, 2^31) can land anywhere else
   float fu = rintf(uv[(size_t)i * uv_stride] / scale), fv = rintf(uv[(size_t)i * uv_stride + 1] / scale);
-  int u = fu != fu ? 0 : (int)fminf(fmaxf(fu, 0.f), (float)(cw - 1));
-  int v = fv != fv ? 0 : (int)fminf(fmaxf(fv, 0.f), (float)(ch - 1));
+  int u = (fu >= 0.f && fu < 2147483648.f) ? (int)fminf(fu, (float)(cw - 1)) : 0;
+  int v = (fv >= 0.f && fv < 2147483648.f) ? (int)fminf(fv, (float)(ch - 1)) : 0;
   unsigned long long key = ((unsigned long long)sortable_bits(d) << 32) | (unsigned)i;
   atomicMin(&zbuf[(size_t)u * ch + v], key);                       // cell order u * _h + v (:62)
 }

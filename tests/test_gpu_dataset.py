@@ -40,6 +40,29 @@ def test_kernel_writes_the_arrays_the_reference_read(i, tmp_path):
         frame_to_dataset(colors[..., :3].contiguous(), alpha, G[f"K_{i}"])
 
 
+@pytest.mark.parametrize("stride,dt", [(4, torch.float32), (6, torch.float64), (6, torch.float16)])
+def test_second_trip_of_the_stride_loop_bit_for_bit(stride, dt):
+    """One 1024 x 1025 frame (the grid is capped at 4096 workgroups of 256: the last row is a second trip) with a
+    background against oracle/dataset_np.py, every byte; the distance reads the LAST channel of a row of 4 or 6."""
+    from oracle import dataset_np as D
+    from robosimgs_amd.dataset import frame_to_dataset
+    h, w = 1025, 1024
+    rng = np.random.default_rng(stride)
+    colors = rng.random((h, w, stride), dtype=np.float32) * np.float32(1.2) - np.float32(0.1)
+    colors[..., -1] = rng.random((h, w), dtype=np.float32) * np.float32(9.5) + np.float32(0.5)
+    alpha = rng.random((h, w), dtype=np.float32)
+    alpha[rng.random((h, w)) < 0.2] = 0
+    K = np.array([[900.0, 0, 511.5], [0, 905.0, 512.0], [0, 0, 1]])
+    bg = (0.2, 0.4, 0.9)
+    rgba, dist = frame_to_dataset(torch.from_numpy(colors).to(DEV), torch.from_numpy(alpha).to(DEV), K, background=bg,
+                                  distance_dtype=dt)
+    r_rgba, r_dist = D.frame_to_dataset(colors, alpha, K, background=bg, distance_f64=True)
+    assert h * w > 4096 * 256 and dist.dtype == dt and dist.shape == (h, w, 1)
+    assert np.array_equal(rgba.cpu().numpy(), r_rgba)
+    assert np.array_equal(dist.cpu().numpy(), r_dist.astype({torch.float32: np.float32, torch.float64: np.float64,
+                                                              torch.float16: np.float16}[dt]))
+
+
 def test_rendered_frame_through_the_writer_and_back(tmp_path):
     """Render -> mgs_frame_to_dataset -> files -> this repo's distance_to_depth (reference-pinned in
     test_camera_golden.py): the z-depth that comes back is the renderer's ED channel to the last bit, the

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+import frame_helper_ref as F
 from robosimgs_amd import camera_ring, synthetic_scene
 
 pytestmark = pytest.mark.gpu
@@ -139,3 +140,90 @@ def test_frame_renderer_poses_groups_per_frame():
     static = FrameRenderer(t0, 256, 160, frames_in_flight=1, isect_capacity=600_000)
     with pytest.raises(ValueError):
         static.submit(cams[0].viewmat(), cams[0].K, rotations=[np.eye(3)], translations=[[0, 0, 0]])
+
+
+# ---- against tests/frame_helper_ref.py::transform_ref: every SH write path, out-of-range ids, in place ----------------
+NAMES = ("means", "quats", "scales", "colors")
+
+
+def _bits(x):
+    return x.contiguous().view(torch.int32) if torch.is_tensor(x) else np.ascontiguousarray(x).view(np.int32)
+
+
+def _tensors(t, deg):
+    d = {k: _t(t[k]) for k in NAMES + ("opacities",)}
+    d["sh_degree"] = deg
+    return d
+
+
+def _against_ref(t, deg, in_place, what):
+    """transform_gaussians on the arrays of `t` (n_groups = 3) against transform_ref.  Rows that do not move are
+    compared bit for bit; in place they are filled with a signalling-NaN pattern first, which any write that went
+    through arithmetic would change.  Returns the worst ratio to each bound."""
+    from robosimgs_amd import transform_gaussians
+    K = t["colors"].shape[1]
+    kc = (deg + 1) ** 2
+    gid = t["gids"]
+    moving = np.isin(gid, (0, 1, 2))
+    src = {k: t[k].copy() for k in NAMES}
+    if in_place:
+        for k in NAMES:
+            src[k][~moving] = np.array([F.SENTINEL], np.uint32).view(np.float32)[0]
+    dev = _tensors({**src, "opacities": t["opacities"]}, deg)
+    before = {k: dev[k].clone() for k in NAMES}
+    got = transform_gaussians(dev, t["rotations"], t["translations"], t["group_scales"], group_ids=_t_i32(gid),
+                              out=dev if in_place else None)
+    for k in NAMES:
+        assert (got[k].data_ptr() == dev[k].data_ptr()) == in_place, k
+        if not in_place:
+            assert torch.equal(_bits(dev[k]), _bits(before[k])), f"{what}: input {k} changed"
+    g = {k: got[k].cpu().numpy() for k in NAMES}
+    for k in NAMES:                               # static and out-of-range rows, coefficients above the degree, DC
+        assert np.array_equal(_bits(g[k][~moving]), _bits(src[k][~moving])), f"{what}: {k} of a row that does not move"
+    assert np.array_equal(_bits(g["colors"][:, kc:]), _bits(src["colors"][:, kc:])), f"{what}: above the degree"
+    assert np.array_equal(_bits(g["colors"][:, 0]), _bits(src["colors"][:, 0])), f"{what}: DC"
+    ref = F.transform_ref(t["means"], t["quats"], t["scales"], t["colors"], deg, gid, 3, t["rotations"],
+                          t["translations"], t["group_scales"])
+    m = moving
+    ratios = {k: F.worst_ratio(g[k][m], ref[k][0][m], ref[k][1][m]) for k in ("means", "scales", "colors")}
+    q64 = g["quats"][m].astype(np.float64)
+    ratios["norm"] = F.worst_ratio(np.linalg.norm(q64, axis=1), ref["norm"][0][m], ref["norm"][1][m])
+    ratios["rot"] = F.worst_ratio(F.quat_to_rotmat(q64), ref["rot"][0][m], ref["rot"][1][m])
+    print(f"transform {what} K={K} degree {deg} in place {in_place}: " + ", ".join(f"{k} {v:.3f}" for k, v in ratios.items()))
+    assert max(ratios.values()) <= 1.0, (what, ratios)
+    return ratios
+
+
+def _t_i32(a):
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(DEV)
+
+
+@pytest.mark.parametrize("in_place", [False, True])
+@pytest.mark.parametrize("K,deg", F.TRANSFORM_CASES)
+def test_every_sh_write_path_against_fp64(K, deg, in_place):
+    """200 Gaussians, ids from {-1, 0, 1, 2, 3, 7} with three groups (3 and 7 are out of range and pass through bit
+    for bit): rows of 16 coefficients (staged through LDS) at degrees 1, 2, 3, shorter and longer-than-needed rows
+    (read and written per lane, the copy-through above the active degree included), each to a fresh buffer and in
+    place."""
+    t = F.transform_inputs(200, K)
+    assert set(t["gids"].tolist()) == set(F.TRANSFORM_GIDS)
+    _against_ref(t, deg, in_place, "n=200")
+
+
+@pytest.mark.parametrize("K,deg", [(16, 3), (9, 1)])
+def test_a_wave_of_static_gaussians_in_place_next_to_a_moving_one(K, deg):
+    """128 Gaussians in place: the first wave's 64 are all static (the kernel returns before touching SH rows), the
+    second wave's all move."""
+    t = dict(F.transform_inputs(128, K))
+    t["gids"] = np.concatenate([np.full(64, -1), np.resize(np.array([0, 1, 2]), 64)]).astype(np.int32)
+    _against_ref(t, deg, True, "static wave | moving wave")
+    t["gids"] = t["gids"][::-1].copy()
+    _against_ref(t, deg, True, "moving wave | static wave")
+
+
+@pytest.mark.parametrize("n", [1, 63, 64, 65])
+@pytest.mark.parametrize("K,deg", [(16, 3), (9, 2)])
+def test_counts_around_one_wave(n, K, deg):
+    t = F.transform_inputs(n, K, gids=(0, -1, 1, 2, 5))
+    for in_place in (False, True):
+        _against_ref(t, deg, in_place, f"n={n}")
