@@ -454,6 +454,23 @@ int mgs_rasterize_bwd(int n, const float *means2d, const float *conics, const fl
  *   restarts from the forward's exact T -- and stay bit-reproducible run to run.
  *   flags: MGS_RASTER_BWD_RECORDS_ONLY, MGS_RASTER_BWD_SPLAT_SLOTS (needs `splats`, annotated by mgs_isect_tiles).  4-channel frames (v_render, expected_render, render_out) must be 16-byte
  *   aligned (rows are read as one 16-byte piece).
+ *   Workspace layout (what a MGS_RASTER_BWD_RECORDS_ONLY consumer and the stage tests read; every field starts on a
+ *   multiple of 256 bytes, capacity = max(isect_capacity, 1)):
+ *     byte 0                      records[capacity][record_floats] float; record_floats = 6 + padded channels (+2 with
+ *                                 absgrad) rounded up to a multiple of 4, channels padded to themselves up to 4, then to
+ *                                 8, 16, 32.  Record = {s, s_x, s_y, s_xx, s_xy, s_yy, colour gradients, (absgrad x, y)}
+ *     next multiple of 256        flags[capacity] uint8: non-zero = the slot's record was written by this call; the
+ *                                 record of an unflagged slot is NOT written (it keeps whatever the buffer held)
+ *     + capacity rounded to 256   256-byte counter header (fill of the big-rectangle lists)
+ *     + 256                       order / unit-table field: n_tiles int32 of launch order, or with checkpoints
+ *                                 {counts uint32[64]: [0] whole segments, [1 + c] partial segments of length class c;
+ *                                 whole int4[(capacity >> log2 interval) + n_tiles + 1]; part int4[32][n_tiles]}, entries
+ *                                 {tile, segment, list start, end of the tile's walk = min(max last_id, list end - 1)}
+ *     then (<= 4 channels)        the big-rectangle lists
+ *   The reduce sums, per Gaussian, the records of the flagged slots of its rectangle that lie below the capacity, within
+ *   a row by column, then the rows in row order.  Overflowed lists (status MGS_STATUS_ISECT_OVERFLOW): a slot at or past
+ *   isect_capacity does not exist -- it is neither written nor read -- so a rectangle cut by the capacity contributes the
+ *   slots below it and a rectangle wholly past it gives exact zeros; every row is still written.
  */
 int mgs_rasterize_bwd_det(int n, const float *means2d, const float *conics, const float *feats,
                           const float *opacities, const float *splats, const float *background,

@@ -677,7 +677,10 @@ __device__ __forceinline__ void big_discover(int wg, int n, const int4* __restri
   uint32_t run[kDiscoverPerThread], wave_total = 0;
 #pragma unroll
   for (int j = 0; j < kDiscoverPerThread; ++j) {
-    mm[j] = ballot((info[j].w & 0xffff) * (int)((unsigned)info[j].w >> 16) >= kBigPairs);
+    // overflowed lists: a rectangle wholly past the capacity owns no slot that exists -- the rows kernel writes its zeros
+    // (it is not "big" there either).  The listed ones start below the capacity, kBigPairs slots and more apart: at most
+    // capacity / kBigPairs + 1 = room of them, so no list can run out of room and leave a Gaussian to neither path.
+    mm[j] = ballot((info[j].w & 0xffff) * (int)((unsigned)info[j].w >> 16) >= kBigPairs && (uint32_t)info[j].x < capacity);
     run[j] = wave_total;
     wave_total += (uint32_t)__popcll(mm[j]);
   }
@@ -1005,6 +1008,7 @@ __global__ __launch_bounds__(256) void reduce_records_rows_kernel(
     info = pair_info[g];
     h = (int)((unsigned)info.w >> 16);
     if ((info.w & 0xffff) == 0) h = 0;
+    if ((uint32_t)info.x >= capacity) h = 0;            // overflowed lists: none of its slots exists (big_discover skips it too)
     is_big = (info.w & 0xffff) * h >= kBigPairs;        // (a wave of the launch's first workgroups takes it)
     if (is_big) h = 0;
     if (h > 0) {

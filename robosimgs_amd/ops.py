@@ -730,25 +730,125 @@ def _splat_slots_valid(tl, splats) -> bool:
     return tag is True or getattr(splats, "_mgs_splat_slots", None) is tag
 
 
+def _record_floats(channels: int, absgrad: bool) -> int:
+    """Floats per record of mgs_rasterize_bwd_det (include/mgs.h): 6 moments + padded channels (+2 with absgrad), rounded
+    up to a multiple of 4.  Channels are padded to themselves up to 4, then to 8, 16, 32."""
+    ch = int(channels)
+    padded = ch if ch <= 4 else 8 if ch <= 8 else 16 if ch <= 16 else 32
+    return (6 + padded + (2 if absgrad else 0) + 3) // 4 * 4
+
+
+def rasterize_bwd_det_workspace_bytes(channels: int, absgrad: bool, capacity: int, tile_w: int, tile_h: int,
+                                      checkpoint_interval: int = 0) -> int:
+    """Bytes mgs_rasterize_bwd_det asks for (its own size query: host arithmetic, no GPU work)."""
+    nb = ctypes.c_size_t(0)
+    d = 256          # a non-null pointer the size query never dereferences
+    ck = d if checkpoint_interval else None
+    check(_lib.lib().mgs_rasterize_bwd_det(0, *[None] * 6, int(channels), tile_w * TILE_SIZE, tile_h * TILE_SIZE, tile_w, tile_h,
+                                           *[None] * 9, int(capacity), ck, ck, int(checkpoint_interval), 0, None,
+                                           d if absgrad else None, None, None, None, None, ctypes.byref(nb), None),
+          "mgs_rasterize_bwd_det(size query)")
+    return nb.value
+
+
+def rasterize_bwd_det_workspace_layout(channels: int, absgrad: bool, capacity: int, tile_w: int, tile_h: int,
+                                       checkpoint_interval: int = 0) -> dict:
+    """Byte offsets of the workspace fields, as include/mgs.h documents them for mgs_rasterize_bwd_det: records at 0, flags
+    at the next multiple of 256, the 256-byte counter header, the order / unit-table field, the big-rectangle lists (up to
+    4 channels).  `total` equals rasterize_bwd_det_workspace_bytes (tests/test_bwd_reduce_host.py pins that)."""
+    def up(x):
+        return (int(x) + 255) // 256 * 256
+    cap, n_tiles = max(int(capacity), 1), tile_w * tile_h
+    rf = _record_floats(channels, absgrad)
+    shift = 0
+    while (1 << shift) < checkpoint_interval:
+        shift += 1
+    units = (cap >> shift) + n_tiles + 1 if checkpoint_interval else 0
+    tables = 256 + (units + 32 * n_tiles) * 16 if checkpoint_interval else 0
+    out = {"capacity": cap, "record_floats": rf, "shift": shift, "units": units, "records": 0}
+    out["flags"] = up(cap * rf * 4)
+    out["counters"] = out["flags"] + up(cap)
+    out["order"] = out["counters"] + 256
+    out["big_items"] = out["order"] + up(max(n_tiles * 4, tables, 1))
+    out["total"] = out["big_items"] + (up(64 * (cap // 256 + 1) * 4) if channels <= 4 else 0)
+    return out
+
+
+def _aligned_workspace(workspace: Tensor, need: int) -> Tensor:
+    if workspace.dtype != torch.uint8 or workspace.dim() != 1 or not workspace.is_contiguous():
+        raise ValueError("workspace: a contiguous 1-D uint8 tensor")
+    pad = -workspace.data_ptr() % 256
+    if workspace.numel() < pad + need:
+        raise ValueError(f"workspace: {workspace.numel()} bytes, the call needs {need} + {pad} of alignment slack")
+    return workspace[pad:]
+
+
+def rasterize_bwd_det_workspace_views(workspace: Tensor, channels: int, absgrad: bool, capacity: int, tile_w: int,
+                                      tile_h: int, checkpoint_interval: int = 0) -> dict:
+    """Views (no copies) of a workspace rasterize_bwd_det_raw(workspace=...) used: `records` [capacity, record_floats]
+    float32 and `flags` [capacity] uint8 (non-zero: the slot's record was written); `counters` [64] uint32 (the big
+    lists' fill); for a checkpointed call also the unit tables: `unit_counts` [64] uint32 ([0] whole segments, [1 + c]
+    partial segments of class c), `unit_whole` [units, 4] and `unit_part` [32, n_tiles, 4] int32 rows
+    {tile, segment, list start, end of the tile's walk}."""
+    lay = rasterize_bwd_det_workspace_layout(channels, absgrad, capacity, tile_w, tile_h, checkpoint_interval)
+    w = _aligned_workspace(workspace, lay["total"])
+    cap, rf, n_tiles = lay["capacity"], lay["record_floats"], tile_w * tile_h
+    v = {"records": w[:cap * rf * 4].view(torch.float32).view(cap, rf),
+         "flags": w[lay["flags"]:lay["flags"] + cap],
+         "counters": w[lay["counters"]:lay["counters"] + 256].view(torch.int32)}
+    if checkpoint_interval and channels <= 4:
+        o, units = lay["order"], lay["units"]
+        v["unit_counts"] = w[o:o + 256].view(torch.int32)
+        v["unit_whole"] = w[o + 256:o + 256 + units * 16].view(torch.int32).view(units, 4)
+        p = o + 256 + units * 16
+        v["unit_part"] = w[p:p + 32 * n_tiles * 16].view(torch.int32).view(32, n_tiles, 4)
+    return v
+
+
+def _check_bwd_out(out, n: int, ch: int, absgrad: bool, dev):
+    if len(out) != 5:
+        raise ValueError("out: (v_means2d, v_conics, v_feats, v_opacities, v_means2d_abs|None)")
+    shapes = ((n, 2), (n, 3), (n, ch), (n,), (n, 2))
+    for t, shape, name in zip(out, shapes, ("v_means2d", "v_conics", "v_feats", "v_opacities", "v_means2d_abs")):
+        if name == "v_means2d_abs" and (t is None) != (not absgrad):
+            raise ValueError("out: v_means2d_abs is given exactly when absgrad is set")
+        if t is None and name == "v_means2d_abs":
+            continue
+        if not isinstance(t, Tensor) or t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"out: {name} must be a contiguous float32 tensor of shape {shape}")
+        if t.device != dev:
+            raise ValueError(f"out: {name} is on {t.device}, the inputs on {dev}")
+    return tuple(out)
+
+
 def rasterize_bwd_det_raw(means2d, conics, feats, opacities, background, width, height, tile_w,
                           tile_h, tl: "TileLists", alphas, last_ids, v_render, v_alphas,
                           absgrad=False, splats=None, canary_bytes=0, expected_render=None,
-                          render_out=None, checkpoints=None, checkpoint_interval=0, records_only=False):
+                          render_out=None, checkpoints=None, checkpoint_interval=0, records_only=False,
+                          out=None, workspace=None):
     """Atomic-free, bit-reproducible raster backward (needs tl.pair_info from the binning).
     Returns freshly written (v_means2d, v_conics, v_feats, v_opacities, v_means2d_abs|None).
     expected_render: the forward's frame when it ran with expected_last (the kernel undoes the divide).
     checkpoints + checkpoint_interval + render_out (the forward's frame): the segmented walk (include/mgs.h).
     records_only: stop after the raster kernel (MGS_RASTER_BWD_RECORDS_ONLY; the returned tensors are not written).
     canary_bytes (tests): that many 0xA5 bytes are kept behind the workspace the library asked for
-    and returned as a sixth value, so a test can see that nothing was written past the workspace."""
+    and returned as a sixth value, so a test can see that nothing was written past the workspace.
+    out = (v_means2d, v_conics, v_feats, v_opacities, v_means2d_abs|None): the caller's buffers are written (and
+    returned) instead of fresh ones -- pre-filled with a sentinel they show a row no path wrote.
+    workspace: the caller's uint8 tensor of at least rasterize_bwd_det_workspace_bytes(...) + the slack to the next
+    multiple of 256 of its address (+ canary_bytes); used as is and left alive, rasterize_bwd_det_workspace_views reads
+    the records and flags out of it."""
     n = means2d.shape[0]
     ch = feats.shape[-1]
     dev = means2d.device
-    v_means2d = torch.empty(n, 2, dtype=torch.float32, device=dev)
-    v_conics = torch.empty(n, 3, dtype=torch.float32, device=dev)
-    v_feats = torch.empty(n, ch, dtype=torch.float32, device=dev)
-    v_opac = torch.empty(n, dtype=torch.float32, device=dev)
-    v_abs = torch.empty(n, 2, dtype=torch.float32, device=dev) if absgrad else None
+    if out is not None:
+        v_means2d, v_conics, v_feats, v_opac, v_abs = _check_bwd_out(out, n, ch, absgrad, dev)
+    else:
+        v_means2d = torch.empty(n, 2, dtype=torch.float32, device=dev)
+        v_conics = torch.empty(n, 3, dtype=torch.float32, device=dev)
+        v_feats = torch.empty(n, ch, dtype=torch.float32, device=dev)
+        v_opac = torch.empty(n, dtype=torch.float32, device=dev)
+        v_abs = torch.empty(n, 2, dtype=torch.float32, device=dev) if absgrad else None
     args = [n, ptr(means2d), ptr(conics), ptr(feats), ptr(opacities), ptr(splats), ptr(background),
             ch, width, height, tile_w, tile_h, ptr(tl.tile_offsets), ptr(tl.flatten_ids), ptr(alphas),
             ptr(last_ids), ptr(v_render), ptr(v_alphas), ptr(expected_render), ptr(tl.pair_info),
@@ -756,7 +856,17 @@ def rasterize_bwd_det_raw(means2d, conics, feats, opacities, background, width, 
             ptr(render_out), ptr(checkpoints), int(checkpoint_interval),
             (RASTER_BWD_RECORDS_ONLY if records_only else 0) | (RASTER_BWD_SPLAT_SLOTS if _splat_slots_valid(tl, splats) else 0),
             ptr(v_means2d), ptr(v_abs), ptr(v_conics), ptr(v_feats), ptr(v_opac)]
-    canary = sized_call(_lib.lib().mgs_rasterize_bwd_det, args, dev, cached=False, canary_bytes=canary_bytes)
+    if workspace is not None:
+        fn, nbytes = _lib.lib().mgs_rasterize_bwd_det, ctypes.c_size_t(0)
+        check(fn(*args, None, ctypes.byref(nbytes), None), "mgs_rasterize_bwd_det(size query)")
+        size = nbytes.value
+        w = _aligned_workspace(workspace, size + int(canary_bytes))
+        if workspace.device != dev:
+            raise ValueError(f"workspace is on {workspace.device}, the inputs on {dev}")
+        canary = w[size:size + canary_bytes].fill_(0xA5) if canary_bytes else None
+        check(fn(*args, w.data_ptr(), ctypes.byref(nbytes), stream_handle()), "mgs_rasterize_bwd_det")
+    else:
+        canary = sized_call(_lib.lib().mgs_rasterize_bwd_det, args, dev, cached=False, canary_bytes=canary_bytes)
     if canary_bytes:
         return v_means2d, v_conics, v_feats, v_opac, v_abs, canary
     return v_means2d, v_conics, v_feats, v_opac, v_abs
