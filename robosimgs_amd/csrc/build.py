@@ -2,6 +2,7 @@
 sits next to the sources so it travels with the repo snapshot to the GPU box."""
 from __future__ import annotations
 
+import glob
 import hashlib
 import os
 import shutil
@@ -13,10 +14,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = ["api.hip", "projection.hip", "sort.hip", "binning.hip", "tile_sort.hip", "raster_fwd.hip",
            "raster_bwd.hip", "backward.hip", "composite.hip", "points.hip", "loss.hip", "transform.hip", "frame.hip",
            "optim.hip", "refine.hip", "labels.hip", "lift.hip", "hinge.hip"]
-HEADERS = ["mgs_common.h", "mgs_math.h", "raster_common.h", "sh_staging.h", "tile_rect.h", "tile_order.h",
-           "pair_weight.h", "../../include/mgs.h", "../../include/mgs_optim.h",
-           "../../include/mgs_refine.h", "../../include/mgs_labels.h", "../../include/mgs_lens.h",
-           "../../include/mgs_lift.h", "../../include/mgs_hinge.h"]
+# every header of the library and of its public interface: a new one is in the stamp without being listed
+HEADERS = sorted(glob.glob(os.path.join(HERE, "*.h"))) + sorted(glob.glob(os.path.join(HERE, "../../include/*.h")))
 LIB = os.path.join(HERE, "libmgs.so")
 # The same sources with -DMGS_DEBUG_HOOKS: the process-global test / measurement knobs (mgs_debug_set_*) exist in this
 # build only; tests and A/B scripts load it (robosimgs_amd._lib.use_debug_lib), the product never does.

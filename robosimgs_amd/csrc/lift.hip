@@ -1,10 +1,10 @@
 // lift.hip -- 2D part masks lifted onto Gaussians (include/mgs_lift.h), gfx950.
 //
-// raster_votes_kernel is the transpose of raster_labels_kernel (labels.hip): the same walk of one camera's tile lists
-// (raster_common.h: one wave per 16x16 tile, four pixels per lane, batches of kQueue entries culled with quadrant_reach and
-// queued in LDS, started in tile_group_order), the same pair_weight (pair_weight.h) -- so the T and w of every voting pixel
-// are the forward's bit for bit -- but where the label kernel sums w over the Gaussians of a class per PIXEL, this one
-// sums w over the pixels of a class per GAUSSIAN:  V[i,k] = sum over p with mask(p) == k of w_i(p).
+// raster_votes_kernel is the transpose of raster_labels_kernel (labels.hip): the one walk of a camera's tile lists both
+// call (weight_walk.h: weight_walk, started in tile_group_order) -- so the T and w of every voting pixel are the forward's
+// bit for bit -- but where the label kernel sums w over the Gaussians of a class per PIXEL, this one sums w over the
+// pixels of a class per GAUSSIAN:  V[i,k] = sum over p with mask(p) == k of w_i(p).  What is this kernel's own: which
+// pixels start open, the entry's payload (the votes row) and the reduction below.
 //
 // Mask.  A lane keeps the mask bytes of its four pixels in one register (byte k = quadrant k); a pixel outside the image
 // or with a mask value outside 0..K-1 holds 255 and starts finished, exactly as a pixel outside the image does in the
@@ -20,8 +20,7 @@
 // a bit.  A tile under one part pays one reduction per entry; an entry that reaches no voting pixel pays none.
 //
 // lift_assign_kernel: one thread per Gaussian scans its K votes in ascending class with a strict >.
-#include "raster_common.h"
-#include "pair_weight.h"
+#include "weight_walk.h"
 #include "tile_order.h"
 #include "../../include/mgs_lift.h"
 
@@ -32,33 +31,25 @@ namespace {
 
 constexpr float kVoteOne = 4294967296.f;             // 2^32: one pixel of full weight
 
-struct VoteEntry {
-  float4 geo0;                       // q0, q1, q2, A   (raster_common.h: poly_coefs; A, B, C: conic pre-scaled)
-  float4 geo1;                       // B, C, votes row (bits), unused
-  float4 geo3;                       // mean - tile centre (x, y): read only by batches that test sigma >= 0
-};
-
 __global__ __launch_bounds__(64) void raster_votes_kernel(
     const float* __restrict__ means2d, const float* __restrict__ conics, const float* __restrict__ opacities,
     const float4* __restrict__ splats, const uint8_t* __restrict__ mask, int n_classes, int width, int height, int tile_w,
     int n_tiles, const int32_t* __restrict__ tile_offsets, const int32_t* __restrict__ flatten_ids,
     const int32_t* __restrict__ group_order, int row_offset, int n_rows, unsigned long long* __restrict__ votes) {
-  __shared__ VoteEntry queue[kQueue + 1];
+  __shared__ WeightEntry queue[kQueue + 1];
   const int tile = tile_of_unit((int)blockIdx.x, n_tiles, group_order);      // tile_order.h
   if (tile < 0) return;
   const unsigned lane = threadIdx.x & 63u;
-  const int tx = tile % tile_w, ty = tile / tile_w;
-  const float tile_x = (float)(tx * 16), tile_y = (float)(ty * 16);
   const int start = tile_offsets[tile], end = tile_offsets[tile + 1];
   if (start >= end) return;                       // no list: nobody to vote for
-  const int ix = tx * 16 + (int)(lane & 7), iy = ty * 16 + (int)(lane >> 3);
+  const TileFrame fr = tile_frame(tile, tile_w, lane);
 
   // the mask bytes of the lane's four pixels; 255: casts no vote
   unsigned cls_of[4];
   unsigned have = 0u;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-    const int x = ix + 8 * (k & 1), y = iy + 8 * (k >> 1);
+    const int x = fr.ix + 8 * (k & 1), y = fr.iy + 8 * (k >> 1);
     unsigned m = 255u;
     if (x < width && y < height) m = mask[(size_t)y * width + x];
     if (m >= (unsigned)n_classes) m = 255u;
@@ -69,108 +60,32 @@ __global__ __launch_bounds__(64) void raster_votes_kernel(
   const unsigned present = wave_or(have);         // wave-uniform: the classes that can be voted for in this tile
   if (present == 0u) return;
 
-  const float xo = (float)(lane & 7) - 7.5f, yo = (float)(lane >> 3) - 7.5f;
-  PixelPoly pq[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) pq[k] = pixel_poly(xo + 8.f * (k & 1), yo + 8.f * (k >> 1));
-  const float ctr_x = tile_x + 8.f, ctr_y = tile_y + 8.f;
-
-  float T[4];
   unsigned long long alive[4];                    // the quadrant's open voting pixels
 #pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    T[k] = 1.f;
-    alive[k] = ballot(((mask4 >> (8 * k)) & 255u) != 255u);
-  }
+  for (int k = 0; k < 4; ++k) alive[k] = ballot(((mask4 >> (8 * k)) & 255u) != 255u);
 
-  for (int b = start; b < end; b += kQueue) {
-    unsigned live = 0;
+  weight_walk(queue, fr, lane, start, end, splats, means2d, conics, opacities, flatten_ids, alive,
+              [&](int g) { return g - row_offset; },
+              [&](int row, auto quad) {
+                float w[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int k = 0; k < 4; ++k)
-      if (alive[k] != 0ull) live |= 1u << k;
-    if (live == 0) break;
-
-    // this batch's entries: one list entry per lane
-    const int c_idx = b + (int)lane;
-    const bool c_ok = c_idx < end;
-    float2 c_xy = make_float2(0.f, 0.f);
-    float c_ca = 1.f, c_cb = 0.f, c_cc = 1.f, c_op = 0.f;
-    int c_row = -1;
-    if (c_ok) {
-      const int g = flatten_ids[c_idx];
-      c_row = g - row_offset;
-      if (splats) {                               // the packed 48-byte record: its first two quarters
-        const float4 p0 = splats[3 * (size_t)g], p1 = splats[3 * (size_t)g + 1];
-        c_xy = make_float2(p0.x, p0.y);
-        c_ca = p0.z; c_cb = p0.w; c_cc = p1.x; c_op = p1.y;
-      } else {
-        c_xy = reinterpret_cast<const float2*>(means2d)[g];
-        c_ca = conics[3 * (size_t)g + 0];
-        c_cb = conics[3 * (size_t)g + 1];
-        c_cc = conics[3 * (size_t)g + 2];
-        c_op = opacities[g];
-      }
-    }
-
-    unsigned long long reach[4];
-    quadrant_reach(c_xy.x, c_xy.y, c_ca, c_cb, c_cc, c_op, c_ok, tile_x, tile_y, live, reach);
-    const unsigned long long keep = reach[0] | reach[1] | reach[2] | reach[3];
-    const bool queued = __builtin_amdgcn_inverse_ballot_w64(keep);
-    const bool all_safe = ballot(queued && !entry_is_safe(c_ca, c_cb, c_cc, c_op)) == 0ull;
-    if (queued) {
-      VoteEntry& e = queue[mask_rank(keep)];
-      const float sA = -0.5f * kLog2e * c_ca, sB = -kLog2e * c_cb, sC = -0.5f * kLog2e * c_cc;
-      const float m_x = c_xy.x - ctr_x, m_y = c_xy.y - ctr_y;
-      const PolyCoef q = poly_coefs(m_x, m_y, sA, sB, sC, __log2f(c_op));
-      e.geo0 = make_float4(q.q0, q.q1, q.q2, sA);
-      e.geo1 = make_float4(sB, sC, __int_as_float(c_row), 0.f);
-      e.geo3 = make_float4(m_x, m_y, 0.f, 0.f);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-
-    auto walk = [&](auto safe_tag) {
-      constexpr bool SAFE = decltype(safe_tag)::value;
-      // entry j was queued by the lane of the j-th set bit of `keep`
-      unsigned long long rest = keep;
-      const VoteEntry* e = queue;
-      while (rest != 0ull) {
-        const int at = __builtin_ctzll(rest);
-        rest &= rest - 1ull;
-        const float4 g0 = e->geo0, g1 = e->geo1;
-        float4 g3 = make_float4(0.f, 0.f, 0.f, 0.f);
-        if constexpr (!SAFE) g3 = e->geo3;
-        ++e;
-        float w[4] = {0.f, 0.f, 0.f, 0.f};
+                for (int k = 0; k < 4; ++k) quad(k, w[k]);
+                // a row outside 0..n_rows-1 occludes only
+                if ((unsigned)row >= (unsigned)n_rows) return;
+                if (ballot((w[0] + w[1]) + (w[2] + w[3]) > 0.f) == 0ull) return;      // counted at no voting pixel
+                unsigned long long* dst = votes + (size_t)row * (size_t)n_classes;
+                unsigned todo = present;
+                while (todo != 0u) {
+                  const unsigned c = (unsigned)__builtin_ctz(todo);
+                  todo &= todo - 1u;
+                  float s[4];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          if ((reach[k] >> at) & 1ull) {
-            w[k] = pair_weight<SAFE>(T[k], alive[k], pq[k], g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g3.x, g3.y);
-            if (alive[k] == 0ull) reach[k] = 0ull;         // the quadrant's last pixel closed: the batch skips it
-          }
-        }
-        // the row is the same for all 64 lanes of the evaluation: a scalar; outside 0..n_rows-1 it occludes only
-        const int row = __builtin_amdgcn_readfirstlane(__float_as_int(g1.z));
-        if ((unsigned)row >= (unsigned)n_rows) continue;
-        if (ballot((w[0] + w[1]) + (w[2] + w[3]) > 0.f) == 0ull) continue;      // counted at no voting pixel
-        unsigned long long* dst = votes + (size_t)row * (size_t)n_classes;
-        unsigned todo = present;
-        while (todo != 0u) {
-          const unsigned c = (unsigned)__builtin_ctz(todo);
-          todo &= todo - 1u;
-          float s[4];
-#pragma unroll
-          for (int k = 0; k < 4; ++k) s[k] = ((mask4 >> (8 * k)) & 255u) == c ? w[k] : 0.f;
-          const float sum = wave_reduce_to_lane63((s[0] + s[1]) + (s[2] + s[3]));     // fixed order: lane 63 holds it
-          if (lane == 63u && sum > 0.f)
-            atomicAdd(dst + c, (unsigned long long)rintf(sum * kVoteOne));            // global_atomic_add_x2, no return
-        }
-      }
-    };
-    if (all_safe) walk(std::true_type{}); else walk(std::false_type{});
-    __builtin_amdgcn_wave_barrier();   // queue is rewritten by the next batch
-  }
+                  for (int k = 0; k < 4; ++k) s[k] = ((mask4 >> (8 * k)) & 255u) == c ? w[k] : 0.f;
+                  const float sum = wave_reduce_to_lane63((s[0] + s[1]) + (s[2] + s[3]));     // fixed order: lane 63 holds it
+                  if (lane == 63u && sum > 0.f)
+                    atomicAdd(dst + c, (unsigned long long)rintf(sum * kVoteOne));            // global_atomic_add_x2, no return
+                }
+              });
 }
 
 __global__ __launch_bounds__(256) void lift_assign_kernel(int n_rows, int n_classes,
@@ -213,8 +128,7 @@ extern "C" int mgs_raster_votes(int n, const float* means2d, const float* conics
   MGS_REQUIRE(tile_w == (width + 15) / 16 && tile_h == (height + 15) / 16,
               "raster_votes: tile grid %dx%d does not match %dx%d at tile size 16", tile_w, tile_h, width, height);
   MGS_REQUIRE(tile_offsets && flatten_ids, "raster_votes: null tile lists");
-  const int n_tiles = tile_w * tile_h;
-  const int n_units = tile_group_order ? (n_tiles + 3) / 4 * 4 : n_tiles;       // tile slots of the launch
+  const int n_tiles = tile_w * tile_h, n_units = tile_launch_units(n_tiles, tile_group_order);
   hipLaunchKernelGGL(raster_votes_kernel, dim3(n_units), dim3(64), 0, (hipStream_t)stream, means2d, conics, opacities,
                      reinterpret_cast<const float4*>(splats), mask, n_classes, width, height, tile_w, n_tiles, tile_offsets,
                      flatten_ids, tile_group_order, row_offset, n_rows, reinterpret_cast<unsigned long long*>(votes));

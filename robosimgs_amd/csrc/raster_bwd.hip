@@ -244,8 +244,7 @@ __device__ __forceinline__ void raster_bwd_unit(const int unit,
   }
   if (tile < 0) return;
   const unsigned lane = threadIdx.x & 63u;
-  const int tx = tile % tile_w, ty = tile / tile_w;
-  const float tile_x = (float)(tx * 16), tile_y = (float)(ty * 16);
+  const TileFrame fr = tile_frame(tile, tile_w, lane);     // raster_common.h: the lane's four pixels, the tile's centre
   const int start = SPLIT ? seg_start : tile_offsets[tile], end = SPLIT ? seg_hi + 1 : tile_offsets[tile + 1];
   if (end <= start) return;
   // SPLIT: this unit's segment [lo, nxt) of the list (the table entry carries the list's start and the end of the walk)
@@ -254,12 +253,7 @@ __device__ __forceinline__ void raster_bwd_unit(const int unit,
   // (also consumes `capacity` up here: a scalar load still outstanding at the head of the walk would turn every
   //  LDS wait inside it into a wait for everything -- scalar loads return out of order)
   if (RECORDS && capacity == 0u) return;
-  const int ix = tx * 16 + (int)(lane & 7), iy = ty * 16 + (int)(lane >> 3);
-  // this lane's pixels as offsets from the tile centre, with their products (raster_common.h: PixelPoly)
-  PixelPoly pq[NQ];
-#pragma unroll
-  for (int k = 0; k < NQ; ++k)
-    pq[k] = pixel_poly((float)(lane & 7) - 7.5f + 8.f * (k & 1), (float)(int)(lane >> 3) - 7.5f + 8.f * (k >> 1));
+  const int ix = fr.ix, iy = fr.iy, tx = fr.tx, ty = fr.ty;
 
   BwdPixel<CHT> st[NQ];
   int hi = -1;
@@ -411,24 +405,13 @@ __device__ __forceinline__ void raster_bwd_unit(const int unit,
     float2 xy = make_float2(0.f, 0.f);
     float ca = 1.f, cb = 0.f, cc = 1.f, op = 0.f;
     float pf[4] = {0.f, 0.f, 0.f, 0.f};
-    uint32_t slot_base = 0u, slot_rect = 0u;          // splat_slots: the pair's record slot out of the record itself
+    float2 slot_words = make_float2(0.f, 0.f);        // splat_slots: the pair's record slot out of the record itself
     const bool packed = CHT <= 4 && splats != nullptr;
     if (idx <= hi) {
       g = flatten_ids[idx];
-      if (packed) {
-        const float4 p0 = splats[3 * (size_t)g], p1 = splats[3 * (size_t)g + 1], p2 = splats[3 * (size_t)g + 2];
-        xy = make_float2(p0.x, p0.y);
-        ca = p0.z; cb = p0.w; cc = p1.x; op = p1.y;
-        pf[0] = p1.z; pf[1] = p1.w; pf[2] = p2.x; pf[3] = p2.y;
-        slot_base = __float_as_uint(p2.z); slot_rect = __float_as_uint(p2.w);
-      } else {
-        xy = reinterpret_cast<const float2*>(means2d)[g];
-        ca = conics[3 * (size_t)g + 0];
-        cb = conics[3 * (size_t)g + 1];
-        cc = conics[3 * (size_t)g + 2];
-        op = opacities[g];
-      }
-      qmask = quadrant_mask(xy.x, xy.y, ca, cb, cc, op, tile_x, tile_y, live);
+      load_geometry(g, packed ? splats : nullptr, means2d, conics, opacities, xy, ca, cb, cc, op);
+      if (packed) load_record_tail(g, splats, pf, &slot_words);
+      qmask = quadrant_mask(xy.x, xy.y, ca, cb, cc, op, fr.tile_x, fr.tile_y, live);
     }
     const unsigned long long keep = ballot(qmask != 0u);
     const int count = __popcll(keep);
@@ -439,30 +422,25 @@ __device__ __forceinline__ void raster_bwd_unit(const int unit,
     const bool all_safe = ballot(qmask != 0u && !entry_is_safe(ca, cb, cc, op)) == 0ull;
     if (qmask != 0u) {
       BwdEntry<CHT, WIDE>& e = queue[mask_rank(keep)];
-      constexpr float kLog2e = 1.4426950408889634f;
-      const float sA = -0.5f * kLog2e * ca, sB = -kLog2e * cb, sC = -0.5f * kLog2e * cc, L = __log2f(op);
-      const float m_x = xy.x - (tile_x + 8.f), m_y = xy.y - (tile_y + 8.f);
-      const PolyCoef pc = poly_coefs(m_x, m_y, sA, sB, sC, L);
-      e.geo0 = make_float4(pc.q0, pc.q1, pc.q2, sA);
-      e.geo1 = make_float4(sB, sC, __uint_as_float(qmask), __int_as_float(idx));
+      const QueueGeo qg = queue_geometry(xy, ca, cb, cc, op, fr.ctr_x, fr.ctr_y);
+      e.geo0 = qg.geo0;
+      e.geo1 = make_float4(qg.sB, qg.sC, __uint_as_float(qmask), __int_as_float(idx));
       int gid = g;
       if (RECORDS) {
         if (packed && splat_slots) {        // (uniform) mgs_isect_tiles left {slot base, x0 | y0 << 10 | w << 20} in the record
+          const uint32_t slot_base = __float_as_uint(slot_words.x), slot_rect = __float_as_uint(slot_words.y);
           gid = (int)slot_base + (ty - (int)((slot_rect >> 10) & 1023u)) * (int)(slot_rect >> 20) + (tx - (int)(slot_rect & 1023u));
         } else {
           const int4 info = pair_info[g];
           gid = info.x + (ty - info.z) * (info.w & 0xffff) + (tx - info.y);   // the pair's slot
         }
       }
-      e.geo2 = make_float4(__int_as_float(gid), m_x, m_y, L);
+      e.geo2 = make_float4(__int_as_float(gid), qg.m_x, qg.m_y, qg.L);
       if constexpr (WIDE) e.geo3[0] = make_float4(ca, cb, cc, 0.f);
-      float f[((CHT + 3) / 4) * 4];
+      float f[CHT];
 #pragma unroll
-      for (int c = 0; c < ((CHT + 3) / 4) * 4; ++c)
-        f[c] = (c < CHT && c < channels) ? (packed ? pf[c & 3] : feats[(size_t)g * channels + c]) : 0.f;
-#pragma unroll
-      for (int j = 0; j < (CHT + 3) / 4; ++j)
-        e.feat[j] = make_float4(f[4 * j], f[4 * j + 1], f[4 * j + 2], f[4 * j + 3]);
+      for (int c = 0; c < CHT; ++c) f[c] = c < channels ? (packed ? pf[c & 3] : feats[(size_t)g * channels + c]) : 0.f;
+      pack_features(f, e.feat);
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -476,14 +454,7 @@ __device__ __forceinline__ void raster_bwd_unit(const int unit,
       float4 g3 = make_float4(0.f, 0.f, 0.f, 0.f);
       if constexpr (WIDE) g3 = e.geo3[0];
       float feat[CHT];
-#pragma unroll
-      for (int f = 0; f < (CHT + 3) / 4; ++f) {
-        float4 v = e.feat[f];
-        feat[4 * f] = v.x;
-        if (4 * f + 1 < CHT) feat[4 * f + 1] = v.y;
-        if (4 * f + 2 < CHT) feat[4 * f + 2] = v.z;
-        if (4 * f + 3 < CHT) feat[4 * f + 3] = v.w;
-      }
+      unpack_features(e.feat, feat);
       const unsigned m = __builtin_amdgcn_readfirstlane(__float_as_uint(g1.z));
       const int gi = __float_as_int(g1.w);
       const int gid = __builtin_amdgcn_readfirstlane(__float_as_int(g2.x));
@@ -495,7 +466,7 @@ __device__ __forceinline__ void raster_bwd_unit(const int unit,
 #pragma unroll
       for (int k = 0; k < NQ; ++k) {
         if (m & (1u << k))
-          grad_pixel<CHT, ABSGRAD, SAFE>(st[k], gg, pq[k], g2.y, g2.z, g3.x, g3.y, g3.z, g0.w, g1.x, g1.y,
+          grad_pixel<CHT, ABSGRAD, SAFE>(st[k], gg, fr.pq[k], g2.y, g2.z, g3.x, g3.y, g3.z, g0.w, g1.x, g1.y,
                                          g0.x, g0.y, g0.z, feat, gi, any);
       }
       if (!any) continue;          // (uniform: no lane of any quadrant took the Gaussian -- nothing to reduce)
@@ -786,17 +757,9 @@ __global__ __launch_bounds__(256) void reduce_records_kernel(
   for (int i = 0; i < 6; ++i) acc[i] = 0.f;
 #pragma unroll
   for (int c = 0; c < CHT; ++c) af[c] = 0.f;
-  float mean_x = 0.f, mean_y = 0.f, ca = 1.f, cb = 0.f, cc = 1.f, op = 1.f;
-  if (cnt > 0) {
-    if (splats) {
-      const float4 p0 = splats[3 * (size_t)g], p1 = splats[3 * (size_t)g + 1];
-      mean_x = p0.x; mean_y = p0.y; ca = p0.z; cb = p0.w; cc = p1.x; op = p1.y;
-    } else {
-      mean_x = means2d[2 * (size_t)g]; mean_y = means2d[2 * (size_t)g + 1];
-      ca = conics[3 * (size_t)g]; cb = conics[3 * (size_t)g + 1]; cc = conics[3 * (size_t)g + 2];
-      op = opacities[g];
-    }
-  }
+  float2 mean = make_float2(0.f, 0.f);
+  float ca = 1.f, cb = 0.f, cc = 1.f, op = 1.f;
+  if (cnt > 0) load_geometry(g, splats, means2d, conics, opacities, mean, ca, cb, cc, op);
   // (loading the records unconditionally and selecting by the flag afterwards -- one round trip instead
   //  of two -- was measured: 618 -> 676 us for the whole backward; the extra 64 MB cost more)
   // four slots per trip with predicated loads: the flag and record loads of a trip are all in
@@ -827,7 +790,7 @@ __global__ __launch_bounds__(256) void reduce_records_kernel(
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       // m exactly as the raster kernel formed it: mean - (16 tile + 8)
-      const float mx = mean_x - ((float)((info.y + col) * 16) + 8.f), my = mean_y - ((float)((info.z + row) * 16) + 8.f);
+      const float mx = mean.x - ((float)((info.y + col) * 16) + 8.f), my = mean.y - ((float)((info.z + row) * 16) + 8.f);
       float P, Q, Vaa, Vab, Vbb;
       moments_to_mean(mx, my, r[i][0], r[i][1], r[i][2], r[i][3], r[i][4], r[i][5], P, Q, Vaa, Vab, Vbb);
       acc[0] += P; acc[1] += Q; acc[2] += Vaa; acc[3] += Vab; acc[4] += Vbb; acc[5] += r[i][0];
@@ -946,14 +909,7 @@ __global__ __launch_bounds__(256) void reduce_records_rows_kernel(
       const int h = (int)((unsigned)oi.w >> 16);
       float2 om;
       float ca, cb, cc, op;
-      if (splats) {
-        const float4 p0 = splats[3 * (size_t)g], p1 = splats[3 * (size_t)g + 1];
-        om = make_float2(p0.x, p0.y); ca = p0.z; cb = p0.w; cc = p1.x; op = p1.y;
-      } else {
-        om = make_float2(means2d[2 * (size_t)g], means2d[2 * (size_t)g + 1]);
-        ca = conics[3 * (size_t)g]; cb = conics[3 * (size_t)g + 1]; cc = conics[3 * (size_t)g + 2];
-        op = opacities[g];
-      }
+      load_geometry(g, splats, means2d, conics, opacities, om, ca, cb, cc, op);
       float acc = 0.f;                                              // lane i < NV: component i, the rows in row order
       for (int base = 0; base < h; base += 64) {
         float rs[NV];
@@ -1003,7 +959,8 @@ __global__ __launch_bounds__(256) void reduce_records_rows_kernel(
   int4 info = make_int4(0, 0, 0, 0);
   int h = 0;
   bool is_big = false;
-  float mean_x = 0.f, mean_y = 0.f, ca = 1.f, cb = 0.f, cc = 1.f, op = 1.f;
+  float2 mean = make_float2(0.f, 0.f);
+  float ca = 1.f, cb = 0.f, cc = 1.f, op = 1.f;
   if (g < n) {
     info = pair_info[g];
     h = (int)((unsigned)info.w >> 16);
@@ -1011,16 +968,7 @@ __global__ __launch_bounds__(256) void reduce_records_rows_kernel(
     if ((uint32_t)info.x >= capacity) h = 0;            // overflowed lists: none of its slots exists (big_discover skips it too)
     is_big = (info.w & 0xffff) * h >= kBigPairs;        // (a wave of the launch's first workgroups takes it)
     if (is_big) h = 0;
-    if (h > 0) {
-      if (splats) {
-        const float4 p0 = splats[3 * (size_t)g], p1 = splats[3 * (size_t)g + 1];
-        mean_x = p0.x; mean_y = p0.y; ca = p0.z; cb = p0.w; cc = p1.x; op = p1.y;
-      } else {
-        mean_x = means2d[2 * (size_t)g]; mean_y = means2d[2 * (size_t)g + 1];
-        ca = conics[3 * (size_t)g]; cb = conics[3 * (size_t)g + 1]; cc = conics[3 * (size_t)g + 2];
-        op = opacities[g];
-      }
-    }
+    if (h > 0) load_geometry(g, splats, means2d, conics, opacities, mean, ca, cb, cc, op);
   }
   int incl = h;
 #pragma unroll
@@ -1031,7 +979,7 @@ __global__ __launch_bounds__(256) void reduce_records_rows_kernel(
   const int row0 = incl - h, n_rows = __shfl(incl, 63);
   s_row0[wv][lane] = row0;
   s_info[wv][lane] = info;
-  s_mean[wv][lane] = make_float2(mean_x, mean_y);
+  s_mean[wv][lane] = mean;
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -1237,7 +1185,7 @@ extern "C" int mgs_rasterize_bwd_det(int n, const float* means2d, const float* c
     hipLaunchKernelGGL(big_discover_kernel, dim3(div_up(n, 256 * kDiscoverPerThread)), dim3(256), 0, s, n, info, (uint32_t)cap, big_counts, big_items);
   // (segmented: whole blocks of the XCD-aware unit numbering; units past the live count leave at once)
   const int n_units = split ? (int)((n_seg_units + 8 * kBwdXcdRun - 1) / (8 * kBwdXcdRun)) * 8 * kBwdXcdRun
-                            : order ? (n_tiles + 3) / 4 * 4 : n_tiles;
+                            : tile_launch_units(n_tiles, order);
   with_channels(channels, [&](auto cht) {
     with_bool(v_means2d_abs != nullptr, [&](auto absgrad) {
       constexpr int C = decltype(cht)::value;

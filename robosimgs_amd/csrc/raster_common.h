@@ -1,4 +1,5 @@
-// raster_common.h -- pieces shared by the forward and backward tile raster kernels.
+// raster_common.h -- pieces shared by the kernels that walk a camera's tile lists: the forward and backward raster
+// (raster_fwd.hip, raster_bwd.hip) and, through weight_walk.h, the label and vote kernels (labels.hip, lift.hip).
 //
 // Geometry (raster_fwd_kernel, raster_bwd_kernel; raster_fwd_q_kernel gives each of the four
 // quadrants its own wave, one pixel per lane).  One wave64 owns one 16x16 tile.  Lane l holds FOUR pixels, one in each 8x8
@@ -27,6 +28,7 @@ constexpr float kAlphaMin = 1.0f / 255.0f;
 constexpr float kAlphaMax = 0.999f;
 constexpr float kTStop = 1e-4f;
 constexpr int kQueue = 64;
+constexpr float kLog2e = 1.4426950408889634f;   // the one definition: every kernel scales the conic with these bits (pair_power)
 
 struct QuadRect { float x0, x1, y0, y1; };   // pixel-centre extents of an 8x8 quadrant
 
@@ -235,6 +237,89 @@ __device__ __forceinline__ void lds_read_3f4(const float4* pa, const float4* pb,
   a = make_float4(va.x, va.y, va.z, va.w);
   b = make_float4(vb.x, vb.y, vb.z, vb.w);
   c = make_float4(vc.x, vc.y, vc.z, vc.w);
+}
+
+// ---- what the kernels that walk a camera's tile lists share (raster_fwd.hip, raster_bwd.hip, weight_walk.h) ----------
+// The lane's tile: one wave owns one 16x16 tile, lane l holds the pixel (l & 7, l >> 3) of each 8x8 quadrant.
+struct TileFrame {
+  int tx, ty;                        // the tile's column and row
+  float tile_x, tile_y;              // its corner, in pixels
+  float ctr_x, ctr_y;                // its centre
+  int ix, iy;                        // pixel centres of quadrant 0; quadrant k adds (8*(k&1), 8*(k>>1))
+  PixelPoly pq[4];                   // offsets of the lane's four pixels from the tile centre, and their products
+};
+__device__ __forceinline__ TileFrame tile_frame(int tile, int tile_w, unsigned lane) {
+  TileFrame f;
+  f.tx = tile % tile_w; f.ty = tile / tile_w;
+  f.tile_x = (float)(f.tx * 16); f.tile_y = (float)(f.ty * 16);
+  f.ctr_x = f.tile_x + 8.f; f.ctr_y = f.tile_y + 8.f;
+  f.ix = f.tx * 16 + (int)(lane & 7); f.iy = f.ty * 16 + (int)(lane >> 3);
+  const float xo = (float)(lane & 7) - 7.5f, yo = (float)(lane >> 3) - 7.5f;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) f.pq[k] = pixel_poly(xo + 8.f * (k & 1), yo + 8.f * (k >> 1));
+  return f;
+}
+
+// Gaussian g's mean, conic and opacity: the first two quarters of the packed 48-byte record, or the separate arrays.
+__device__ __forceinline__ void load_geometry(int g, const float4* __restrict__ splats, const float* __restrict__ means2d,
+                                              const float* __restrict__ conics, const float* __restrict__ opacities,
+                                              float2& xy, float& a, float& b, float& c, float& op) {
+  if (splats) {
+    const float4 p0 = splats[3 * (size_t)g], p1 = splats[3 * (size_t)g + 1];
+    xy = make_float2(p0.x, p0.y);
+    a = p0.z; b = p0.w; c = p1.x; op = p1.y;
+  } else {
+    xy = reinterpret_cast<const float2*>(means2d)[g];
+    a = conics[3 * (size_t)g + 0];
+    b = conics[3 * (size_t)g + 1];
+    c = conics[3 * (size_t)g + 2];
+    op = opacities[g];
+  }
+}
+
+// The rest of the record: its four features and, for a caller that wants them, the two words mgs_isect_tiles leaves
+// behind them (the record slots).
+__device__ __forceinline__ void load_record_tail(int g, const float4* __restrict__ splats, float (&f)[4],
+                                                 float2* slot_words = nullptr) {
+  const float4 p1 = splats[3 * (size_t)g + 1], p2 = splats[3 * (size_t)g + 2];
+  f[0] = p1.z; f[1] = p1.w; f[2] = p2.x; f[3] = p2.y;
+  if (slot_words) *slot_words = make_float2(p2.z, p2.w);
+}
+
+// The geometry of a queue entry: the conic pre-scaled by -log2 e, the mean relative to the tile centre, L = log2(opacity)
+// and the exponent's polynomial about the centre (pair_power, poly_coefs).  Every walker queues exactly these expressions.
+struct QueueGeo {
+  float4 geo0;                       // q0, q1, q2, A
+  float sB, sC, m_x, m_y, L;
+};
+__device__ __forceinline__ QueueGeo queue_geometry(float2 xy, float a, float b, float c, float op, float ctr_x, float ctr_y) {
+  QueueGeo q;
+  const float sA = -0.5f * kLog2e * a;
+  q.sB = -kLog2e * b; q.sC = -0.5f * kLog2e * c; q.L = __log2f(op);
+  q.m_x = xy.x - ctr_x; q.m_y = xy.y - ctr_y;
+  const PolyCoef pc = poly_coefs(q.m_x, q.m_y, sA, q.sB, q.sC, q.L);
+  q.geo0 = make_float4(pc.q0, pc.q1, pc.q2, sA);
+  return q;
+}
+
+// A Gaussian's CHT features as the queue entry's float4[(CHT + 3) / 4] (padded with zeros), and back.
+template <int CHT>
+__device__ __forceinline__ void pack_features(const float (&f)[CHT], float4 (&out)[(CHT + 3) / 4]) {
+#pragma unroll
+  for (int j = 0; j < (CHT + 3) / 4; ++j)
+    out[j] = make_float4(f[4 * j], 4 * j + 1 < CHT ? f[4 * j + 1] : 0.f, 4 * j + 2 < CHT ? f[4 * j + 2] : 0.f,
+                         4 * j + 3 < CHT ? f[4 * j + 3] : 0.f);
+}
+template <int CHT>
+__device__ __forceinline__ void unpack_features(const float4* in, float (&f)[CHT]) {
+#pragma unroll
+  for (int j = 0; j < (CHT + 3) / 4; ++j) {
+    const float4 v = in[j];
+    f[4 * j] = v.x;
+    if (4 * j + 1 < CHT) f[4 * j + 1] = v.y;
+    if (4 * j + 2 < CHT) f[4 * j + 2] = v.z;
+    if (4 * j + 3 < CHT) f[4 * j + 3] = v.w;
+  }
 }
 
 // full-wave sum: result valid in lane 63

@@ -52,8 +52,6 @@ struct PixelState {
 #endif
 };
 
-constexpr float kLog2e = 1.4426950408889634f;
-
 #ifdef MGS_RASTER_STATS
 // Instrumented build only (python robosimgs_amd/csrc/build.py with MGS_EXTRA_FLAGS=-DMGS_RASTER_STATS):
 // counts the work the forward raster really does; read back with mgs_debug_read_raster_stats().
@@ -183,6 +181,42 @@ __device__ __forceinline__ void blend_pixel_safe_asm(PixelState<CHT>& px, unsign
 // the kernel instead of 20, and no conversion pass reads them back.  A separate instantiation: the float-frame kernels'
 // code is what it was.
 struct NoDataset {};
+// The epilogue of one pixel (x, y) inside the image, both schedules: background, "ED" division, the stores.
+template <int CHT, bool TRACK_LAST, bool DATASET>
+__device__ __forceinline__ void store_pixel(const PixelState<CHT>& st, int x, int y, int width, int channels,
+                                            const float* __restrict__ background, int expected_last,
+                                            float* __restrict__ render, float* __restrict__ alphas,
+                                            int32_t* __restrict__ last_ids,
+                                            const std::conditional_t<DATASET, DatasetOut, NoDataset>& ds) {
+  const size_t p = (size_t)y * width + x;
+  const float alpha = 1.0f - fabsf(st.T);
+  // "ED": the last channel (depth sum) leaves as the expected depth, A.2 step 9
+  const float inv_alpha = expected_last ? 1.0f / fmaxf(alpha, 1e-10f) : 1.0f;
+  if constexpr (DATASET) {
+    static_assert(CHT == 4 && !TRACK_LAST, "dataset epilogue: RGB + expected depth, inference");
+    float v[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) v[c] = st.C[c] + (background ? fabsf(st.T) * background[c] : 0.f);
+    v[3] *= inv_alpha;
+    dataset_store(ds, p, x, y, v[0], v[1], v[2], v[3], alpha);
+    if (render) {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) render[p * 4 + c] = v[c];
+      alphas[p] = alpha;
+    }
+  } else {
+#pragma unroll
+    for (int c = 0; c < CHT; ++c)
+      if (c < channels) {
+        float v = st.C[c] + (background ? fabsf(st.T) * background[c] : 0.f);
+        if (c == channels - 1) v *= inv_alpha;
+        render[p * channels + c] = v;
+      }
+    alphas[p] = alpha;
+    if (TRACK_LAST) last_ids[p] = st.last;
+  }
+}
+
 template <int CHT, bool TRACK_LAST, bool DATASET = false>
 __global__ __launch_bounds__(64 * (TRACK_LAST ? 1 : kFwdWgWaves), (CHT <= 4 ? kFwdMinWaves : 1)) void raster_fwd_kernel(
     const float* __restrict__ means2d, const float* __restrict__ conics,
@@ -199,8 +233,8 @@ __global__ __launch_bounds__(64 * (TRACK_LAST ? 1 : kFwdWgWaves), (CHT <= 4 ? kF
   const int tile = tile_of_unit(blockIdx.x * kWgWaves + (int)(threadIdx.x >> 6), n_tiles, group_order);   // tile_order.h
   if (tile < 0) return;
   const unsigned lane = threadIdx.x & 63u;
-  const int tx = tile % tile_w, ty = tile / tile_w;
-  const float tile_x = (float)(tx * 16), tile_y = (float)(ty * 16);
+  const TileFrame fr = tile_frame(tile, tile_w, lane);     // raster_common.h: the lane's four pixels, the tile's centre
+  const int ix = fr.ix, iy = fr.iy;
   const int start = tile_offsets[tile], end = tile_offsets[tile + 1];
   if (opts & 1) {
     // Issue priority by list length.  A tile is one wave's serial job; while every SIMD is full each of
@@ -212,15 +246,6 @@ __global__ __launch_bounds__(64 * (TRACK_LAST ? 1 : kFwdWgWaves), (CHT <= 4 ? kF
     else if (2 * len > 3 * avg) __builtin_amdgcn_s_setprio(2);
     else if (len > avg) __builtin_amdgcn_s_setprio(1);
   }
-
-  // pixel centres of quadrant 0; quadrant k adds (8*(k&1), 8*(k>>1))
-  const int ix = tx * 16 + (int)(lane & 7), iy = ty * 16 + (int)(lane >> 3);
-  // offsets of this lane's four pixels from the tile centre, and their products (raster_common.h: PixelPoly)
-  const float xo = (float)(lane & 7) - 7.5f, yo = (float)(lane >> 3) - 7.5f;
-  PixelPoly pq[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) pq[k] = pixel_poly(xo + 8.f * (k & 1), yo + 8.f * (k >> 1));
-  const float ctr_x = tile_x + 8.f, ctr_y = tile_y + 8.f;
 
 #ifdef MGS_RASTER_STATS
   unsigned long long stat[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -249,19 +274,14 @@ __global__ __launch_bounds__(64 * (TRACK_LAST ? 1 : kFwdWgWaves), (CHT <= 4 ? kF
   auto fetch = [&](int idx, bool ok) {
     if (ok && CHT <= 4 && splats) {   // one packed 48-byte record instead of four gathers
       int g = flatten_ids[idx];
-      const float4 p0 = splats[3 * (size_t)g], p1 = splats[3 * (size_t)g + 1], p2 = splats[3 * (size_t)g + 2];
-      r_xy = make_float2(p0.x, p0.y);
-      r_ca = p0.z; r_cb = p0.w; r_cc = p1.x; r_op = p1.y;
-      const float ff[4] = {p1.z, p1.w, p2.x, p2.y};
+      float ff[4];
+      load_geometry(g, splats, nullptr, nullptr, nullptr, r_xy, r_ca, r_cb, r_cc, r_op);
+      load_record_tail(g, splats, ff);
 #pragma unroll
       for (int c = 0; c < CHT; ++c) r_feat[c] = ff[c & 3];
     } else if (ok) {
       int g = flatten_ids[idx];
-      r_xy = reinterpret_cast<const float2*>(means2d)[g];
-      r_ca = conics[3 * (size_t)g + 0];
-      r_cb = conics[3 * (size_t)g + 1];
-      r_cc = conics[3 * (size_t)g + 2];
-      r_op = opacities[g];
+      load_geometry(g, nullptr, means2d, conics, opacities, r_xy, r_ca, r_cb, r_cc, r_op);
 #pragma unroll
       for (int c = 0; c < CHT; ++c) r_feat[c] = c < channels ? feats[(size_t)g * channels + c] : 0.f;
     }
@@ -303,7 +323,7 @@ __global__ __launch_bounds__(64 * (TRACK_LAST ? 1 : kFwdWgWaves), (CHT <= 4 ? kF
     // for the walk, which tests them at the entry's lane instead of reading the entry's mask back from LDS.
     unsigned long long reach[4];
     if (cull) {
-      quadrant_reach(c_xy.x, c_xy.y, c_ca, c_cb, c_cc, c_op, c_ok, tile_x, tile_y, live, reach);
+      quadrant_reach(c_xy.x, c_xy.y, c_ca, c_cb, c_cc, c_op, c_ok, fr.tile_x, fr.tile_y, live, reach);
     } else {
 #pragma unroll
       for (int k = 0; k < 4; ++k) reach[k] = ((live >> k) & 1u) ? ballot(c_ok) : 0ull;
@@ -322,21 +342,11 @@ __global__ __launch_bounds__(64 * (TRACK_LAST ? 1 : kFwdWgWaves), (CHT <= 4 ? kF
 #pragma unroll
       for (int k = 0; k < 4; ++k) qmask |= __builtin_amdgcn_inverse_ballot_w64(reach[k]) ? 1u << k : 0u;
       QueueEntry<CHT>& e = queue[mask_rank(keep)];
-      const float sA = -0.5f * kLog2e * c_ca, sB = -kLog2e * c_cb, sC = -0.5f * kLog2e * c_cc;
-      const float m_x = c_xy.x - ctr_x, m_y = c_xy.y - ctr_y;
-      const PolyCoef q = poly_coefs(m_x, m_y, sA, sB, sC, __log2f(c_op));
-      e.geo0 = make_float4(q.q0, q.q1, q.q2, sA);
-      e.geo1 = make_float4(sB, sC, __uint_as_float(qmask), __int_as_float(c_idx));
-      e.geo3 = make_float4(m_x, m_y, 0.f, 0.f);
-#pragma unroll
-      for (int f = 0; f < (CHT + 3) / 4; ++f) {
-        float4 v;
-        v.x = c_feat[4 * f];
-        v.y = 4 * f + 1 < CHT ? c_feat[4 * f + 1] : 0.f;
-        v.z = 4 * f + 2 < CHT ? c_feat[4 * f + 2] : 0.f;
-        v.w = 4 * f + 3 < CHT ? c_feat[4 * f + 3] : 0.f;
-        e.feat[f] = v;
-      }
+      const QueueGeo q = queue_geometry(c_xy, c_ca, c_cb, c_cc, c_op, fr.ctr_x, fr.ctr_y);
+      e.geo0 = q.geo0;
+      e.geo1 = make_float4(q.sB, q.sC, __uint_as_float(qmask), __int_as_float(c_idx));
+      e.geo3 = make_float4(q.m_x, q.m_y, 0.f, 0.f);
+      pack_features(c_feat, e.feat);
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -349,13 +359,7 @@ __global__ __launch_bounds__(64 * (TRACK_LAST ? 1 : kFwdWgWaves), (CHT <= 4 ? kF
                            const float4& g3) {
       constexpr bool SAFE = decltype(safe_tag)::value;
       float feat[CHT];
-#pragma unroll
-      for (int f = 0; f < (CHT + 3) / 4; ++f) {
-        feat[4 * f] = ef[f].x;
-        if (4 * f + 1 < CHT) feat[4 * f + 1] = ef[f].y;
-        if (4 * f + 2 < CHT) feat[4 * f + 2] = ef[f].z;
-        if (4 * f + 3 < CHT) feat[4 * f + 3] = ef[f].w;
-      }
+      unpack_features(ef, feat);
       const int idx = __float_as_int(g1.w);
       // (measured and rejected, profiles/r3/00_experiments.md: one straight-line body per quadrant SET behind a
       //  switch on the mask, 268-278 us against 197; the live quadrants re-derived every 8 / 16 / 32 entries, +2 %)
@@ -366,10 +370,10 @@ __global__ __launch_bounds__(64 * (TRACK_LAST ? 1 : kFwdWgWaves), (CHT <= 4 ? kF
         if constexpr (kMasks<CHT> && SAFE) {
           // (the body tests reach[k] at `at` itself, s_bitcmp1_b64 and a branch: the compiler's own test of a
           //  variable bit of a 64-bit mask is a shift, an AND and a compare on top of the branch)
-          blend_pixel_safe_asm<CHT, TRACK_LAST, true>(st[k], alive[k], reach[k], at, pq[k], g0.x, g0.y, g0.z, g0.w, g1.x,
+          blend_pixel_safe_asm<CHT, TRACK_LAST, true>(st[k], alive[k], reach[k], at, fr.pq[k], g0.x, g0.y, g0.z, g0.w, g1.x,
                                                       g1.y, feat, idx);
         } else if ((reach[k] >> at) & 1ull) {
-          blend_pixel<CHT, TRACK_LAST, SAFE, kMasks<CHT>>(st[k], alive[k], pq[k], g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g3.x,
+          blend_pixel<CHT, TRACK_LAST, SAFE, kMasks<CHT>>(st[k], alive[k], fr.pq[k], g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g3.x,
                                                            g3.y, feat, idx);
         }
       };
@@ -441,35 +445,8 @@ __global__ __launch_bounds__(64 * (TRACK_LAST ? 1 : kFwdWgWaves), (CHT <= 4 ? kF
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const int x = ix + 8 * (k & 1), y = iy + 8 * (k >> 1);
-    if (x < width && y < height) {
-      const size_t p = (size_t)y * width + x;
-      const float alpha = 1.0f - fabsf(st[k].T);
-      // "ED": the last channel (depth sum) leaves as the expected depth, A.2 step 9
-      const float inv_alpha = expected_last ? 1.0f / fmaxf(alpha, 1e-10f) : 1.0f;
-      if constexpr (DATASET) {
-        static_assert(CHT == 4 && !TRACK_LAST, "dataset epilogue: RGB + expected depth, inference");
-        float v[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) v[c] = st[k].C[c] + (background ? fabsf(st[k].T) * background[c] : 0.f);
-        v[3] *= inv_alpha;
-        dataset_store(ds, p, x, y, v[0], v[1], v[2], v[3], alpha);
-        if (render) {
-#pragma unroll
-          for (int c = 0; c < 4; ++c) render[p * 4 + c] = v[c];
-          alphas[p] = alpha;
-        }
-        continue;
-      }
-#pragma unroll
-      for (int c = 0; c < CHT; ++c)
-        if (c < channels) {
-          float v = st[k].C[c] + (background ? fabsf(st[k].T) * background[c] : 0.f);
-          if (c == channels - 1) v *= inv_alpha;
-          render[p * channels + c] = v;
-        }
-      alphas[p] = alpha;
-      if (TRACK_LAST) last_ids[p] = st[k].last;
-    }
+    if (x < width && y < height)
+      store_pixel<CHT, TRACK_LAST, DATASET>(st[k], x, y, width, channels, background, expected_last, render, alphas, last_ids, ds);
   }
 }
 
@@ -522,6 +499,11 @@ __global__ __launch_bounds__(256) void raster_fwd_q_kernel(    // (bounded to 64
   float r_feat[CHT];
 #pragma unroll
   for (int c = 0; c < CHT; ++c) r_feat[c] = 0.f;
+  // (Both branches keep their loads written out, not through load_geometry / load_record_tail as in the kernel above.
+  //  This kernel prefetches: what is loaded here is waited for a batch later.  Through load_geometry the array path's
+  //  three conic loads merge into one and the compiler's s_waitcnt vmcnt(3) / (4) in front of the cull become vmcnt(0);
+  //  through the two helpers on the record the 1-channel inference instantiation takes 55 VGPRs instead of 53.  Both
+  //  from the compiler's report and listing, profiles/raster_shared/README.md.)
   auto fetch = [&](int idx, bool ok) {
     if (ok && CHT <= 4 && splats) {
       int g = flatten_ids[idx];
@@ -591,21 +573,11 @@ __global__ __launch_bounds__(256) void raster_fwd_q_kernel(    // (bounded to 64
     const bool all_safe = ballot(keep_me && !entry_is_safe(c_ca, c_cb, c_cc, c_op)) == 0ull;
     if (keep_me) {
       QueueEntry<CHT>& e = queue[mask_rank(keep)];
-      const float sA = -0.5f * kLog2e * c_ca, sB = -kLog2e * c_cb, sC = -0.5f * kLog2e * c_cc;
-      const float m_x = c_xy.x - (tile_x + 8.f), m_y = c_xy.y - (tile_y + 8.f);
-      const PolyCoef q = poly_coefs(m_x, m_y, sA, sB, sC, __log2f(c_op));
-      e.geo0 = make_float4(q.q0, q.q1, q.q2, sA);
-      e.geo1 = make_float4(sB, sC, 0.f, __int_as_float(c_idx));
-      e.geo3 = make_float4(m_x, m_y, 0.f, 0.f);
-#pragma unroll
-      for (int f = 0; f < (CHT + 3) / 4; ++f) {
-        float4 v;
-        v.x = c_feat[4 * f];
-        v.y = 4 * f + 1 < CHT ? c_feat[4 * f + 1] : 0.f;
-        v.z = 4 * f + 2 < CHT ? c_feat[4 * f + 2] : 0.f;
-        v.w = 4 * f + 3 < CHT ? c_feat[4 * f + 3] : 0.f;
-        e.feat[f] = v;
-      }
+      const QueueGeo q = queue_geometry(c_xy, c_ca, c_cb, c_cc, c_op, tile_x + 8.f, tile_y + 8.f);
+      e.geo0 = q.geo0;
+      e.geo1 = make_float4(q.sB, q.sC, 0.f, __int_as_float(c_idx));
+      e.geo3 = make_float4(q.m_x, q.m_y, 0.f, 0.f);
+      pack_features(c_feat, e.feat);
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -621,18 +593,16 @@ __global__ __launch_bounds__(256) void raster_fwd_q_kernel(    // (bounded to 64
         const int j1 = min(j0 + kChunk, count);
       for (int j = j0; j < j1; ++j) {
         const QueueEntry<CHT>& e = queue[j];
-        float4 g0, g1, ef0;
-        if constexpr (CHT <= 4) lds_read_3f4(&e.geo0, &e.geo1, &e.feat[0], g0, g1, ef0);
-        else { g0 = e.geo0; g1 = e.geo1; ef0 = e.feat[0]; }
-        float feat[CHT];
+        float4 g0, g1, ef[(CHT + 3) / 4];
+        if constexpr (CHT <= 4) {
+          lds_read_3f4(&e.geo0, &e.geo1, &e.feat[0], g0, g1, ef[0]);
+        } else {
+          g0 = e.geo0; g1 = e.geo1;
 #pragma unroll
-        for (int f = 0; f < (CHT + 3) / 4; ++f) {
-          const float4 v = f == 0 ? ef0 : e.feat[f];
-          feat[4 * f] = v.x;
-          if (4 * f + 1 < CHT) feat[4 * f + 1] = v.y;
-          if (4 * f + 2 < CHT) feat[4 * f + 2] = v.z;
-          if (4 * f + 3 < CHT) feat[4 * f + 3] = v.w;
+          for (int f = 0; f < (CHT + 3) / 4; ++f) ef[f] = e.feat[f];
         }
+        float feat[CHT];
+        unpack_features(ef, feat);
         if constexpr (kMasks<CHT> && SAFE) {
           unsigned long long unused = 0;
           blend_pixel_safe_asm<CHT, TRACK_LAST>(st, alive, unused, 0, pp, g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, feat, __float_as_int(g1.w));
@@ -657,34 +627,8 @@ __global__ __launch_bounds__(256) void raster_fwd_q_kernel(    // (bounded to 64
       if (lane == 0) reinterpret_cast<int32_t*>(ckpt)[4 * tile + k] = h;
     }
   }
-  if (inside) {
-    const size_t p = (size_t)iy * width + ix;
-    const float alpha = 1.0f - fabsf(st.T);
-    const float inv_alpha = expected_last ? 1.0f / fmaxf(alpha, 1e-10f) : 1.0f;
-    if constexpr (DATASET) {
-      static_assert(CHT == 4 && !TRACK_LAST, "dataset epilogue: RGB + expected depth, inference");
-      float v[4];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) v[c] = st.C[c] + (background ? fabsf(st.T) * background[c] : 0.f);
-      v[3] *= inv_alpha;
-      dataset_store(ds, p, ix, iy, v[0], v[1], v[2], v[3], alpha);
-      if (render) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) render[p * 4 + c] = v[c];
-        alphas[p] = alpha;
-      }
-      return;
-    }
-#pragma unroll
-    for (int c = 0; c < CHT; ++c)
-      if (c < channels) {
-        float v = st.C[c] + (background ? fabsf(st.T) * background[c] : 0.f);
-        if (c == channels - 1) v *= inv_alpha;
-        render[p * channels + c] = v;
-      }
-    alphas[p] = alpha;
-    if (TRACK_LAST) last_ids[p] = st.last;
-  }
+  if (inside)
+    store_pixel<CHT, TRACK_LAST, DATASET>(st, ix, iy, width, channels, background, expected_last, render, alphas, last_ids, ds);
 }
 
 }  // namespace
@@ -776,7 +720,7 @@ extern "C" int mgs_rasterize_fwd(int n, const float* means2d, const float* conic
   const bool per_block = (g_raster_opts & 4) || ((g_raster_opts & 2) && (flags & MGS_RASTER_LATENCY));
   if (g_raster_opts & 8) tile_group_order = nullptr;
   if ((g_raster_opts & 16) && !per_block && !last_ids) tile_group_order = nullptr;
-  const int n_units = tile_group_order ? (n_tiles + 3) / 4 * 4 : n_tiles;       // tile slots of the launch
+  const int n_units = tile_launch_units(n_tiles, tile_group_order);
   const int expected_last = (flags & MGS_RASTER_EXPECTED_LAST) ? 1 : 0;
   const size_t opts_lds = (size_t)(g_raster_opts >> 8) * 1024;
   // ds_arg: NoDataset{}, or the DatasetOut of a dataset frame (4 channels, inference, "ED")

@@ -89,6 +89,9 @@ __device__ __forceinline__ int tile_of_unit(int unit, int n_tiles, const int32_t
   return tile < n_tiles ? tile : -1;
 }
 
+// Tile slots of a raster launch: whole groups of four under a group order (the padding slots leave at once).
+inline int tile_launch_units(int n_tiles, const int32_t* group_order) { return group_order ? (n_tiles + 3) / 4 * 4 : n_tiles; }
+
 // Standalone: the order from finished tile offsets (radix path, or a caller that only has the lists).
 int launch_tile_group_order(int n_tiles, const int32_t* tile_offsets, int32_t* order, hipStream_t stream);
 
