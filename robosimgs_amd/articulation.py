@@ -96,6 +96,7 @@ class Hinge:
                  threshold: float = 0.01):
         self.joint, self.contact_a, self.contact_b, self.threshold = joint, contact_a, contact_b, float(threshold)
         self._record = None
+        self._torch_consts = {}
 
     def _host(self) -> np.ndarray:
         if self._record is None:
@@ -129,6 +130,24 @@ class Hinge:
         c, s = np.cos(ang)[..., None, None], np.sin(ang)[..., None, None]
         R = c * np.eye(3) + s * K + (1.0 - c) * np.outer(k, k)            # Rodrigues
         return R, p - R @ p
+
+    def pose_torch(self, angle: Tensor):
+        """`pose` in torch, differentiable in `angle`: Rodrigues on the angle's device and in its dtype, t = position -
+        R position; the values are those of `pose`.  A scalar angle gives R [3,3] and t [3], K angles R [K,3,3] and t [K,3]
+        -- what pose_gaussians(rotations=, translations=) takes for the part's group (R[None], t[None] for one angle)."""
+        key = (angle.device, angle.dtype)
+        consts = self._torch_consts.get(key)
+        if consts is None:                       # [k]x, k k^T, I and the position, uploaded once per device and dtype
+            k, p = self.axis, self.position
+            k = k / np.linalg.norm(k)
+            kw = dict(dtype=angle.dtype, device=angle.device)
+            consts = self._torch_consts[key] = (
+                torch.tensor([[0.0, -k[2], k[1]], [k[2], 0.0, -k[0]], [-k[1], k[0], 0.0]], **kw),
+                torch.tensor(np.outer(k, k), **kw), torch.eye(3, **kw), torch.tensor(p, **kw))
+        K, kk, eye, pt = consts
+        c, s = torch.cos(angle)[..., None, None], torch.sin(angle)[..., None, None]
+        R = c * eye + s * K + (1.0 - c) * kk                              # Rodrigues
+        return R, pt - R @ pt
 
     def __repr__(self):
         return (f"Hinge(position={self.position.tolist()}, axis={self.axis.tolist()}, axis_confidence={self.axis_confidence:.4f}, "
