@@ -16,7 +16,8 @@ __version__ = "0.1.0"
 _DEVICE_API = {"rasterization", "render", "check_isect_status", "fully_fused_projection",
                "spherical_harmonics", "isect_tiles", "isect_offset_encode",
                "rasterize_to_pixels", "rasterize_labels", "rasterize_votes", "assign_classes", "lift_labels",
-               "fit_hinge", "fit_hinge_points", "pose_gaussians", "render_sharded", "gather_frames"}
+               "fit_hinge", "fit_hinge_points", "pose_gaussians", "bind_particles", "deform_gaussians",
+               "render_sharded", "gather_frames"}
 
 
 def __getattr__(name):  # lazy: keeps `import robosimgs_amd` torch-free for host-only use
@@ -46,6 +47,9 @@ def __getattr__(name):  # lazy: keeps `import robosimgs_amd` torch-free for host
     if name in ("pose_gaussians", "pack_transforms_torch", "pose_bwd_raw"):
         from . import pose
         return getattr(pose, name)
+    if name in ("bind_particles", "deform_gaussians", "ParticleBinding", "deform_bind_raw", "deform_apply_raw"):
+        from . import deform
+        return getattr(deform, name)
     if name in ("l1_loss", "l1_ssim_loss", "ssim", "unit_gradient"):
         from . import losses
         return getattr(losses, name)

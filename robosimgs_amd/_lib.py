@@ -122,6 +122,13 @@ _POSE_SIGNATURES = {
     "mgs_pose_bwd_workspace_bytes": ([i, i], c_size_t),
     "mgs_pose_bwd": ([i, p, p, p, i, i, p, p, i, p, p, p, p, p, p, p, p, p, p, p, p, c_size_t, p], c_int),
 }
+# every function include/mgs_deform.h declares (the same libraries again): bind's workspace size is a query of its own, as
+# the hinge's is; select and status are nullable
+_DEFORM_SIGNATURES = {
+    "mgs_deform_bind_workspace_bytes": ([i, i], c_size_t),
+    "mgs_deform_bind": ([i, p, p, i, p, f, p, c_size_t, p, p, p, p, p, p], c_int),
+    "mgs_deform_apply": ([i, p, p, p, p, p, p, p, p, i, i, p, p, p, p, p, p], c_int),
+}
 del p, i, f, u32, img
 EXPORTS = list(_SIGNATURES)
 OPTIM_EXPORTS = list(_OPTIM_SIGNATURES)
@@ -130,6 +137,8 @@ LABEL_EXPORTS = list(_LABEL_SIGNATURES)
 LIFT_EXPORTS = list(_LIFT_SIGNATURES)
 HINGE_EXPORTS = list(_HINGE_SIGNATURES)
 POSE_EXPORTS = list(_POSE_SIGNATURES)
+DEFORM_EXPORTS = list(_DEFORM_SIGNATURES)
+DEFORM_K = 8                                # MGS_DEFORM_K
 LABEL_NONE, LABELS_MAX_CLASSES = 255, 32    # MGS_LABEL_NONE, MGS_LABELS_MAX_CLASSES
 
 
@@ -152,7 +161,8 @@ def _load(path: str = None, hooks: bool = False) -> ctypes.CDLL:
                        "(include/mgs.h): rebuild the library (`python robosimgs_amd/csrc/build.py --force`)")
     for name, (argtypes, restype) in (*_SIGNATURES.items(), *_OPTIM_SIGNATURES.items(), *_REFINE_SIGNATURES.items(),
                                       *_LABEL_SIGNATURES.items(), *_LIFT_SIGNATURES.items(),
-                                      *_HINGE_SIGNATURES.items(), *_POSE_SIGNATURES.items()):
+                                      *_HINGE_SIGNATURES.items(), *_POSE_SIGNATURES.items(),
+                                      *_DEFORM_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here == header/library mismatch
         fn.argtypes = argtypes
         fn.restype = restype

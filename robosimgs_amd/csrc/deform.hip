@@ -1,0 +1,446 @@
+// deform.hip -- Gaussians that follow simulated particles (include/mgs_deform.h), gfx950: bind once, move per frame.
+//
+// deform_knn_kernel (the hot path of the bind).  hinge_nn_kernel's structure: a workgroup of kDeformGroup threads keeps one
+// Gaussian mean per thread in registers and streams the particle set through LDS in tiles of kDeformTile float4 entries;
+// every lane of a wave reads the same entry, so the ds_read_b128 is a broadcast.  Each thread keeps its 8 best (d2, j)
+// pairs sorted in two fully unrolled arrays (registers: every index is a compile-time constant).  The common case of a
+// pair is the distance (3 subtractions, 1 multiply, 2 fma) and ONE compare against the current 8th; the insertion -- the
+// new pair written over the 8th, then seven compare-and-exchange steps towards the front, each moving on a strict "less"
+// only, so that a tie stays behind the lower index that came first -- runs under that branch, which a thread takes about
+// 8 ln(m / 8) times in all.  A non-finite particle is staged as +inf and an ineligible Gaussian walks as NaN: neither is
+// ever below the 8th.  The particle set is NOT split across workgroups: one workgroup walks all of it, so the lists need
+// no merge pass (a scene of few Gaussians leaves compute units idle; the bind runs once per object).
+//
+// deform_bind_kernel.  One thread per Gaussian, fp64 on the fp32 inputs: weights, centroid, weighted offsets, the moment
+// matrix Q, its eigenvalues (jacobi3.h) and its inverse by cofactors; every stored value is rounded to fp32 once.
+//
+// deform_apply_kernel (every frame).  One thread per Gaussian.  The neighbour-major binding arrays make every streamed
+// load coalesced; the 8 gathers of current particle positions are the only random access.  c and P are fp32 fma chains
+// of differences to the anchor x_0; the rotation and the deformed covariance are solved in fp64 with the same Jacobi.
+#include "mgs_common.h"
+#include "jacobi3.h"
+#include "../../include/mgs_deform.h"
+
+#include <float.h>
+#include <math.h>
+
+namespace mgs {
+namespace {
+
+constexpr int kDeformGroup = 256;         // threads of a workgroup (all three kernels)
+constexpr int kDeformTile = 1024;         // T: particles per LDS tile (16 KiB)
+constexpr int kK = MGS_DEFORM_K;
+constexpr int kRestRows = 12;
+constexpr double kDegenerate = 1e-3;      // the flat / thin threshold on eigenvalue (bind) and singular-value (apply) ratios
+
+enum { kFlagUnbound = 1, kFlagFlat = 2, kFlagThin = 4 };
+enum { kStatusUnbound = 1, kStatusFallback = 2, kStatusThin = 4, kStatusNonFinite = 8 };
+
+__device__ __forceinline__ bool finite3(float x, float y, float z) {
+  return isfinite(x) && isfinite(y) && isfinite(z);
+}
+
+__global__ __launch_bounds__(kDeformGroup) void deform_knn_kernel(int n, const float* __restrict__ means,
+                                                                 const uint8_t* __restrict__ select, int m,
+                                                                 const float* __restrict__ parts,
+                                                                 int32_t* __restrict__ idx, float* __restrict__ d2) {
+  __shared__ float4 tile[kDeformTile];
+  const int t = (int)threadIdx.x;
+  const long long i = (long long)blockIdx.x * kDeformGroup + t;
+  const float inf = __builtin_inff(), nan = __builtin_nanf("");
+
+  float qx = nan, qy = nan, qz = nan;               // ineligible: every distance is a NaN, which is below nothing
+  if (i < n && (!select || select[i])) {
+    qx = means[3 * i + 0];
+    qy = means[3 * i + 1];
+    qz = means[3 * i + 2];
+    if (!finite3(qx, qy, qz)) qx = nan;
+  }
+  float bd[kK];
+  int bi[kK];
+#pragma unroll
+  for (int k = 0; k < kK; ++k) { bd[k] = inf; bi[k] = -1; }
+  // a workgroup without one eligible Gaussian (the unselected part of a spatially ordered scene) walks nothing
+  const int n_walk = __syncthreads_or(qx == qx) ? m : 0;
+
+  const int n_tiles = (int)(((long long)n_walk + kDeformTile - 1) / kDeformTile);
+  for (int tl = 0; tl < n_tiles; ++tl) {
+    const long long obase = (long long)tl * kDeformTile;
+    const int count = m - obase < kDeformTile ? (int)(m - obase) : kDeformTile;
+    __syncthreads();                                // the walk of the previous tile is over
+    for (int e = t; e < count; e += kDeformGroup) {
+      const long long j = obase + e;
+      float4 p = make_float4(parts[3 * j + 0], parts[3 * j + 1], parts[3 * j + 2], 0.f);
+      if (!finite3(p.x, p.y, p.z)) p = make_float4(inf, inf, inf, 0.f);      // nobody's neighbour
+      tile[e] = p;
+    }
+    __syncthreads();
+#pragma unroll 4
+    for (int j = 0; j < count; ++j) {
+      const float4 p = tile[j];                     // the same address in every lane: a broadcast
+      const float dx = qx - p.x, dy = qy - p.y, dz = qz - p.z;
+      const float d = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
+      if (d < bd[kK - 1]) {                         // rare: j ascends, so an equal d2 (a higher index) stays out
+        bd[kK - 1] = d;
+        bi[kK - 1] = (int)obase + j;
+#pragma unroll
+        for (int k = kK - 1; k >= 1; --k) {
+          const bool up = bd[k] < bd[k - 1];        // strict: behind every equal d2 of a lower index
+          const float dl = up ? bd[k] : bd[k - 1], dh = up ? bd[k - 1] : bd[k];
+          const int il = up ? bi[k] : bi[k - 1], ih = up ? bi[k - 1] : bi[k];
+          bd[k - 1] = dl; bd[k] = dh;
+          bi[k - 1] = il; bi[k] = ih;
+        }
+      }
+    }
+  }
+  if (i < n) {
+#pragma unroll
+    for (int k = 0; k < kK; ++k) {
+      idx[(size_t)k * n + i] = bi[k];
+      d2[(size_t)k * n + i] = bd[k];
+    }
+  }
+}
+
+__global__ __launch_bounds__(kDeformGroup) void deform_bind_kernel(int n, const float* __restrict__ means,
+                                                                  const uint8_t* __restrict__ select,
+                                                                  const float* __restrict__ parts, float max_distance,
+                                                                  const float* __restrict__ d2, int32_t* __restrict__ idx,
+                                                                  float* __restrict__ w, float* __restrict__ p,
+                                                                  float* __restrict__ rest, uint8_t* __restrict__ flags) {
+  const long long i = (long long)blockIdx.x * kDeformGroup + threadIdx.x;
+  if (i >= n) return;
+  const size_t N = (size_t)n;
+  int id[kK];
+  float dd[kK];
+#pragma unroll
+  for (int k = 0; k < kK; ++k) { id[k] = idx[k * N + i]; dd[k] = d2[k * N + i]; }
+  const float mx = means[3 * i + 0], my = means[3 * i + 1], mz = means[3 * i + 2];
+  const bool bound = (!select || select[i]) && finite3(mx, my, mz) && id[kK - 1] >= 0 && !(sqrtf(dd[0]) > max_distance);
+  if (!bound) {
+#pragma unroll
+    for (int k = 0; k < kK; ++k) {
+      idx[k * N + i] = -1;
+      w[k * N + i] = 0.f;
+      p[(3 * k + 0) * N + i] = 0.f; p[(3 * k + 1) * N + i] = 0.f; p[(3 * k + 2) * N + i] = 0.f;
+    }
+#pragma unroll
+    for (int r = 0; r < kRestRows; ++r) rest[r * N + i] = 0.f;
+    flags[i] = kFlagUnbound;
+    return;
+  }
+
+  const double h2 = (double)dd[kK - 1];
+  double wt[kK], X[kK][3], sum = 0.0;
+#pragma unroll
+  for (int k = 0; k < kK; ++k) {
+    wt[k] = h2 > 0.0 ? exp(-(double)dd[k] / h2) : 1.0;
+    sum += wt[k];
+    const size_t j = (size_t)id[k];
+    X[k][0] = (double)parts[3 * j + 0]; X[k][1] = (double)parts[3 * j + 1]; X[k][2] = (double)parts[3 * j + 2];
+  }
+  double cx = 0.0, cy = 0.0, cz = 0.0;
+#pragma unroll
+  for (int k = 0; k < kK; ++k) {
+    wt[k] /= sum;
+    cx += wt[k] * X[k][0]; cy += wt[k] * X[k][1]; cz += wt[k] * X[k][2];
+  }
+  double q00 = 0.0, q01 = 0.0, q02 = 0.0, q11 = 0.0, q12 = 0.0, q22 = 0.0;
+#pragma unroll
+  for (int k = 0; k < kK; ++k) {
+    const double rx = X[k][0] - cx, ry = X[k][1] - cy, rz = X[k][2] - cz, wk = wt[k];
+    w[k * N + i] = (float)wk;
+    p[(3 * k + 0) * N + i] = (float)(wk * rx);
+    p[(3 * k + 1) * N + i] = (float)(wk * ry);
+    p[(3 * k + 2) * N + i] = (float)(wk * rz);
+    q00 += wk * rx * rx; q01 += wk * rx * ry; q02 += wk * rx * rz;
+    q11 += wk * ry * ry; q12 += wk * ry * rz; q22 += wk * rz * rz;
+  }
+
+  double a00 = q00, a01 = q01, a02 = q02, a11 = q11, a12 = q12, a22 = q22;
+  double v00, v01, v02, v10, v11, v12, v20, v21, v22;
+  jacobi_solve3(a00, a01, a02, a11, a12, a22, v00, v01, v02, v10, v11, v12, v20, v21, v22);
+  double l0 = a00, l1 = a11, l2 = a22, tmp;          // ascending
+  if (l0 > l1) { tmp = l0; l0 = l1; l1 = tmp; }
+  if (l1 > l2) { tmp = l1; l1 = l2; l2 = tmp; }
+  if (l0 > l1) { tmp = l0; l0 = l1; l1 = tmp; }
+  const bool flat = l0 < kDegenerate * l2;
+  const bool thin = l1 < kDegenerate * l2 || !(l2 > 0.0);
+
+  double i00 = 0.0, i01 = 0.0, i02 = 0.0, i11 = 0.0, i12 = 0.0, i22 = 0.0;
+  if (!flat && l2 > 0.0) {                           // the inverse by cofactors (Q is symmetric, so is its inverse)
+    const double c00 = q11 * q22 - q12 * q12, c01 = q02 * q12 - q01 * q22, c02 = q01 * q12 - q02 * q11;
+    const double inv = 1.0 / (q00 * c00 + q01 * c01 + q02 * c02);
+    i00 = c00 * inv; i01 = c01 * inv; i02 = c02 * inv;
+    i11 = (q00 * q22 - q02 * q02) * inv;
+    i12 = (q01 * q02 - q00 * q12) * inv;
+    i22 = (q00 * q11 - q01 * q01) * inv;
+  }
+  rest[0 * N + i] = (float)((double)mx - cx);
+  rest[1 * N + i] = (float)((double)my - cy);
+  rest[2 * N + i] = (float)((double)mz - cz);
+  rest[3 * N + i] = (float)i00; rest[4 * N + i] = (float)i01; rest[5 * N + i] = (float)i02;
+  rest[6 * N + i] = (float)i11; rest[7 * N + i] = (float)i12; rest[8 * N + i] = (float)i22;
+  rest[9 * N + i] = dd[kK - 1];
+  rest[10 * N + i] = l2 > 0.0 ? (float)(l1 / l2) : 0.f;
+  rest[11 * N + i] = l2 > 0.0 ? (float)(l0 / l2) : 0.f;
+  flags[i] = (uint8_t)((flat ? kFlagFlat : 0) | (thin ? kFlagThin : 0));
+}
+
+// exchange the eigenpairs a and b (the eigenvalue and column of v): names, not indices, so everything stays in registers
+#define MGS_SWAP_PAIR(la, lb, va0, va1, va2, vb0, vb1, vb2)                                    \
+  do {                                                                                         \
+    double t_ = la; la = lb; lb = t_;                                                          \
+    t_ = va0; va0 = vb0; vb0 = t_; t_ = va1; va1 = vb1; vb1 = t_; t_ = va2; va2 = vb2; vb2 = t_; \
+  } while (0)
+
+// the unit quaternion (w, x, y, z) of a proper rotation matrix, by the largest of the four pivots
+__device__ __forceinline__ void rotmat_to_quat(double r00, double r01, double r02, double r10, double r11, double r12,
+                                               double r20, double r21, double r22, double& qw, double& qx, double& qy,
+                                               double& qz) {
+  const double tr = r00 + r11 + r22;
+  if (tr > 0.0) {
+    const double s = 2.0 * sqrt(tr + 1.0);
+    qw = 0.25 * s; qx = (r21 - r12) / s; qy = (r02 - r20) / s; qz = (r10 - r01) / s;
+  } else if (r00 > r11 && r00 > r22) {
+    const double s = 2.0 * sqrt(1.0 + r00 - r11 - r22);
+    qw = (r21 - r12) / s; qx = 0.25 * s; qy = (r01 + r10) / s; qz = (r02 + r20) / s;
+  } else if (r11 > r22) {
+    const double s = 2.0 * sqrt(1.0 + r11 - r00 - r22);
+    qw = (r02 - r20) / s; qx = (r01 + r10) / s; qy = 0.25 * s; qz = (r12 + r21) / s;
+  } else {
+    const double s = 2.0 * sqrt(1.0 + r22 - r00 - r11);
+    qw = (r10 - r01) / s; qx = (r02 + r20) / s; qy = (r12 + r21) / s; qz = 0.25 * s;
+  }
+}
+
+__global__ __launch_bounds__(kDeformGroup) void deform_apply_kernel(
+    int n, const float* __restrict__ means, const float* __restrict__ quats, const float* __restrict__ scales,
+    const int32_t* __restrict__ idx, const float* __restrict__ w, const float* __restrict__ p,
+    const float* __restrict__ rest, const uint8_t* __restrict__ flags, int mode, int m, const float* __restrict__ now,
+    float* __restrict__ out_means, float* __restrict__ out_quats, float* __restrict__ out_scales,
+    uint8_t* __restrict__ status) {
+  const long long i = (long long)blockIdx.x * kDeformGroup + threadIdx.x;
+  if (i >= n) return;
+  const size_t N = (size_t)n;
+  float mu0 = means[3 * i + 0], mu1 = means[3 * i + 1], mu2 = means[3 * i + 2];
+  float4 q = reinterpret_cast<const float4*>(quats)[i];           // (w, x, y, z)
+  float s0 = scales[3 * i + 0], s1 = scales[3 * i + 1], s2 = scales[3 * i + 2];
+  const unsigned fl = flags[i];
+  unsigned st = 0u;
+
+  if (fl & kFlagUnbound) {
+    st = kStatusUnbound;
+  } else {
+    // the 8 current positions: the only random access
+    float x[kK][3];
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < kK; ++k) {
+      const int j = idx[k * N + i];
+      const bool in = j >= 0 && j < m;
+      const size_t jj = in ? (size_t)j : 0;
+      x[k][0] = now[3 * jj + 0]; x[k][1] = now[3 * jj + 1]; x[k][2] = now[3 * jj + 2];
+      ok = ok && in && finite3(x[k][0], x[k][1], x[k][2]);
+    }
+    if (!ok) {
+      st = kStatusNonFinite;
+    } else {
+      // c = sum w_j e_j and P = sum e_j p_j^T over j = 1..7, e_j = x_j - x_0: fp32 fma chains in order of j
+      float c0 = 0.f, c1 = 0.f, c2 = 0.f;
+      float P00 = 0.f, P01 = 0.f, P02 = 0.f, P10 = 0.f, P11 = 0.f, P12 = 0.f, P20 = 0.f, P21 = 0.f, P22 = 0.f;
+#pragma unroll
+      for (int k = 1; k < kK; ++k) {
+        const float e0 = x[k][0] - x[0][0], e1 = x[k][1] - x[0][1], e2 = x[k][2] - x[0][2];
+        const float wk = w[k * N + i];
+        const float pk0 = p[(3 * k + 0) * N + i], pk1 = p[(3 * k + 1) * N + i], pk2 = p[(3 * k + 2) * N + i];
+        if (k == 1) {
+          c0 = wk * e0; c1 = wk * e1; c2 = wk * e2;
+          P00 = e0 * pk0; P01 = e0 * pk1; P02 = e0 * pk2;
+          P10 = e1 * pk0; P11 = e1 * pk1; P12 = e1 * pk2;
+          P20 = e2 * pk0; P21 = e2 * pk1; P22 = e2 * pk2;
+        } else {
+          c0 = __builtin_fmaf(wk, e0, c0); c1 = __builtin_fmaf(wk, e1, c1); c2 = __builtin_fmaf(wk, e2, c2);
+          P00 = __builtin_fmaf(e0, pk0, P00); P01 = __builtin_fmaf(e0, pk1, P01); P02 = __builtin_fmaf(e0, pk2, P02);
+          P10 = __builtin_fmaf(e1, pk0, P10); P11 = __builtin_fmaf(e1, pk1, P11); P12 = __builtin_fmaf(e1, pk2, P12);
+          P20 = __builtin_fmaf(e2, pk0, P20); P21 = __builtin_fmaf(e2, pk1, P21); P22 = __builtin_fmaf(e2, pk2, P22);
+        }
+      }
+      const float xb0 = x[0][0] + c0, xb1 = x[0][1] + c1, xb2 = x[0][2] + c2;
+      const float d00 = rest[0 * N + i], d01 = rest[1 * N + i], d02 = rest[2 * N + i];
+
+      // P^T P and its eigenpairs, descending
+      const double p00 = P00, p01 = P01, p02 = P02, p10 = P10, p11 = P11, p12 = P12, p20 = P20, p21 = P21, p22 = P22;
+      double a00 = p00 * p00 + p10 * p10 + p20 * p20, a01 = p00 * p01 + p10 * p11 + p20 * p21;
+      double a02 = p00 * p02 + p10 * p12 + p20 * p22, a11 = p01 * p01 + p11 * p11 + p21 * p21;
+      double a12 = p01 * p02 + p11 * p12 + p21 * p22, a22 = p02 * p02 + p12 * p12 + p22 * p22;
+      double v00, v01, v02, v10, v11, v12, v20, v21, v22;
+      jacobi_solve3(a00, a01, a02, a11, a12, a22, v00, v01, v02, v10, v11, v12, v20, v21, v22);
+      if (a00 < a11) MGS_SWAP_PAIR(a00, a11, v00, v10, v20, v01, v11, v21);
+      if (a11 < a22) MGS_SWAP_PAIR(a11, a22, v01, v11, v21, v02, v12, v22);
+      if (a00 < a11) MGS_SWAP_PAIR(a00, a11, v00, v10, v20, v01, v11, v21);
+      // sigma_mid < 1e-3 sigma_max  <=>  lambda_mid < 1e-6 lambda_max
+      const bool thin = (fl & kFlagThin) || !(a00 > 0.0) || a11 < kDegenerate * kDegenerate * a00;
+
+      bool rigid = mode == 0;
+      float A00 = 0.f, A01 = 0.f, A02 = 0.f, A10 = 0.f, A11 = 0.f, A12 = 0.f, A20 = 0.f, A21 = 0.f, A22 = 0.f;
+      if (thin) {
+        st = kStatusThin;
+        mu0 = xb0 + d00; mu1 = xb1 + d01; mu2 = xb2 + d02;
+      } else if (!rigid) {
+        if (fl & kFlagFlat) {
+          rigid = true;
+        } else {                                    // A = P Q^-1 in fp32
+          const float ixx = rest[3 * N + i], ixy = rest[4 * N + i], ixz = rest[5 * N + i];
+          const float iyy = rest[6 * N + i], iyz = rest[7 * N + i], izz = rest[8 * N + i];
+          A00 = __builtin_fmaf(P02, ixz, __builtin_fmaf(P01, ixy, P00 * ixx));
+          A01 = __builtin_fmaf(P02, iyz, __builtin_fmaf(P01, iyy, P00 * ixy));
+          A02 = __builtin_fmaf(P02, izz, __builtin_fmaf(P01, iyz, P00 * ixz));
+          A10 = __builtin_fmaf(P12, ixz, __builtin_fmaf(P11, ixy, P10 * ixx));
+          A11 = __builtin_fmaf(P12, iyz, __builtin_fmaf(P11, iyy, P10 * ixy));
+          A12 = __builtin_fmaf(P12, izz, __builtin_fmaf(P11, iyz, P10 * ixz));
+          A20 = __builtin_fmaf(P22, ixz, __builtin_fmaf(P21, ixy, P20 * ixx));
+          A21 = __builtin_fmaf(P22, iyz, __builtin_fmaf(P21, iyy, P20 * ixy));
+          A22 = __builtin_fmaf(P22, izz, __builtin_fmaf(P21, iyz, P20 * ixz));
+          const double det = (double)A00 * ((double)A11 * A22 - (double)A12 * A21)
+                             - (double)A01 * ((double)A10 * A22 - (double)A12 * A20)
+                             + (double)A02 * ((double)A10 * A21 - (double)A11 * A20);
+          if (!(det > 0.0)) rigid = true;
+        }
+        if (rigid) st = kStatusFallback;
+      }
+
+      if (!thin && rigid) {
+        // u1 = P v1 / sigma1, u2 = P v2 made orthonormal to u1, u3 = u1 x u2, v3 = v1 x v2, R = sum u_k v_k^T
+        const double is1 = 1.0 / sqrt(a00);
+        const double u10 = (p00 * v00 + p01 * v10 + p02 * v20) * is1, u11 = (p10 * v00 + p11 * v10 + p12 * v20) * is1;
+        const double u12 = (p20 * v00 + p21 * v10 + p22 * v20) * is1;
+        double u20 = p00 * v01 + p01 * v11 + p02 * v21, u21 = p10 * v01 + p11 * v11 + p12 * v21;
+        double u22 = p20 * v01 + p21 * v11 + p22 * v21;
+        const double dot = u10 * u20 + u11 * u21 + u12 * u22;
+        u20 -= dot * u10; u21 -= dot * u11; u22 -= dot * u12;
+        const double in2 = 1.0 / sqrt(u20 * u20 + u21 * u21 + u22 * u22);
+        u20 *= in2; u21 *= in2; u22 *= in2;
+        const double u30 = u11 * u22 - u12 * u21, u31 = u12 * u20 - u10 * u22, u32 = u10 * u21 - u11 * u20;
+        const double w0 = v10 * v21 - v20 * v11, w1 = v20 * v01 - v00 * v21, w2 = v00 * v11 - v10 * v01;   // v3 = v1 x v2
+        const double r00 = u10 * v00 + u20 * v01 + u30 * w0, r01 = u10 * v10 + u20 * v11 + u30 * w1;
+        const double r02 = u10 * v20 + u20 * v21 + u30 * w2, r10 = u11 * v00 + u21 * v01 + u31 * w0;
+        const double r11 = u11 * v10 + u21 * v11 + u31 * w1, r12 = u11 * v20 + u21 * v21 + u31 * w2;
+        const double r20 = u12 * v00 + u22 * v01 + u32 * w0, r21 = u12 * v10 + u22 * v11 + u32 * w1;
+        const double r22 = u12 * v20 + u22 * v21 + u32 * w2;
+        mu0 = (float)((double)xb0 + (r00 * d00 + r01 * d01 + r02 * d02));
+        mu1 = (float)((double)xb1 + (r10 * d00 + r11 * d01 + r12 * d02));
+        mu2 = (float)((double)xb2 + (r20 * d00 + r21 * d01 + r22 * d02));
+        double aw, ax, ay, az;
+        rotmat_to_quat(r00, r01, r02, r10, r11, r12, r20, r21, r22, aw, ax, ay, az);
+        const double bw = q.x, bx = q.y, by = q.z, bz = q.w;
+        const double ow = aw * bw - ax * bx - ay * by - az * bz, ox = aw * bx + ax * bw + ay * bz - az * by;
+        const double oy = aw * by - ax * bz + ay * bw + az * bx, oz = aw * bz + ax * by - ay * bx + az * bw;
+        const double inv = 1.0 / sqrt(ow * ow + ox * ox + oy * oy + oz * oz);
+        q = make_float4((float)(ow * inv), (float)(ox * inv), (float)(oy * inv), (float)(oz * inv));
+      } else if (!thin) {
+        mu0 = xb0 + __builtin_fmaf(A02, d02, __builtin_fmaf(A01, d01, A00 * d00));
+        mu1 = xb1 + __builtin_fmaf(A12, d02, __builtin_fmaf(A11, d01, A10 * d00));
+        mu2 = xb2 + __builtin_fmaf(A22, d02, __builtin_fmaf(A21, d01, A20 * d00));
+        // M = A R(q) diag(s), Sigma' = M M^T
+        double bw = q.x, bx = q.y, by = q.z, bz = q.w;
+        const double inv = 1.0 / sqrt(bw * bw + bx * bx + by * by + bz * bz);
+        bw *= inv; bx *= inv; by *= inv; bz *= inv;
+        const double g00 = 1.0 - 2.0 * (by * by + bz * bz), g01 = 2.0 * (bx * by - bw * bz), g02 = 2.0 * (bx * bz + bw * by);
+        const double g10 = 2.0 * (bx * by + bw * bz), g11 = 1.0 - 2.0 * (bx * bx + bz * bz), g12 = 2.0 * (by * bz - bw * bx);
+        const double g20 = 2.0 * (bx * bz - bw * by), g21 = 2.0 * (by * bz + bw * bx), g22 = 1.0 - 2.0 * (bx * bx + by * by);
+        const double t0 = s0, t1 = s1, t2 = s2;
+        const double m00 = ((double)A00 * g00 + (double)A01 * g10 + (double)A02 * g20) * t0;
+        const double m01 = ((double)A00 * g01 + (double)A01 * g11 + (double)A02 * g21) * t1;
+        const double m02 = ((double)A00 * g02 + (double)A01 * g12 + (double)A02 * g22) * t2;
+        const double m10 = ((double)A10 * g00 + (double)A11 * g10 + (double)A12 * g20) * t0;
+        const double m11 = ((double)A10 * g01 + (double)A11 * g11 + (double)A12 * g21) * t1;
+        const double m12 = ((double)A10 * g02 + (double)A11 * g12 + (double)A12 * g22) * t2;
+        const double m20 = ((double)A20 * g00 + (double)A21 * g10 + (double)A22 * g20) * t0;
+        const double m21 = ((double)A20 * g01 + (double)A21 * g11 + (double)A22 * g21) * t1;
+        const double m22 = ((double)A20 * g02 + (double)A21 * g12 + (double)A22 * g22) * t2;
+        double e00 = m00 * m00 + m01 * m01 + m02 * m02, e01 = m00 * m10 + m01 * m11 + m02 * m12;
+        double e02 = m00 * m20 + m01 * m21 + m02 * m22, e11 = m10 * m10 + m11 * m11 + m12 * m12;
+        double e12 = m10 * m20 + m11 * m21 + m12 * m22, e22 = m20 * m20 + m21 * m21 + m22 * m22;
+        double z00, z01, z02, z10, z11, z12, z20, z21, z22;
+        jacobi_solve3(e00, e01, e02, e11, e12, e22, z00, z01, z02, z10, z11, z12, z20, z21, z22);
+        if (e00 > e11) MGS_SWAP_PAIR(e00, e11, z00, z10, z20, z01, z11, z21);       // ascending
+        if (e11 > e22) MGS_SWAP_PAIR(e11, e22, z01, z11, z21, z02, z12, z22);
+        if (e00 > e11) MGS_SWAP_PAIR(e00, e11, z00, z10, z20, z01, z11, z21);
+        const double detz = z00 * (z11 * z22 - z12 * z21) - z01 * (z10 * z22 - z12 * z20) + z02 * (z10 * z21 - z11 * z20);
+        if (detz < 0.0) { z02 = -z02; z12 = -z12; z22 = -z22; }
+        double aw, ax, ay, az;
+        rotmat_to_quat(z00, z01, z02, z10, z11, z12, z20, z21, z22, aw, ax, ay, az);
+        const double qn = 1.0 / sqrt(aw * aw + ax * ax + ay * ay + az * az);
+        q = make_float4((float)(aw * qn), (float)(ax * qn), (float)(ay * qn), (float)(az * qn));
+        s0 = fmaxf((float)sqrt(fmax(e00, 0.0)), FLT_MIN);
+        s1 = fmaxf((float)sqrt(fmax(e11, 0.0)), FLT_MIN);
+        s2 = fmaxf((float)sqrt(fmax(e22, 0.0)), FLT_MIN);
+      }
+    }
+  }
+  out_means[3 * i + 0] = mu0; out_means[3 * i + 1] = mu1; out_means[3 * i + 2] = mu2;
+  reinterpret_cast<float4*>(out_quats)[i] = q;
+  out_scales[3 * i + 0] = s0; out_scales[3 * i + 1] = s1; out_scales[3 * i + 2] = s2;
+  if (status) status[i] = (uint8_t)st;
+}
+
+#undef MGS_SWAP_PAIR
+
+size_t bind_workspace_bytes(int n) {
+  Bump b(1);
+  b.take(sizeof(float) * (size_t)kK * (size_t)n);      // d2 [8][n]: the sorted squared distances between the two launches
+  return b.total;
+}
+
+}  // namespace
+}  // namespace mgs
+
+using namespace mgs;
+
+extern "C" size_t mgs_deform_bind_workspace_bytes(int n, int m) {
+  if (n <= 0 || m < kK) return 0;
+  return bind_workspace_bytes(n);
+}
+
+extern "C" int mgs_deform_bind(int n, const float* means, const uint8_t* select, int m, const float* particles_rest,
+                               float max_distance, void* workspace, size_t workspace_bytes, int32_t* idx, float* w, float* p,
+                               float* rest, uint8_t* flags, mgs_stream_t stream) {
+  MGS_REQUIRE(n >= 0, "deform_bind: n %d is negative", n);
+  MGS_REQUIRE(m >= kK, "deform_bind: m %d particles, at least %d needed", m, kK);
+  MGS_REQUIRE(max_distance > 0.f, "deform_bind: max_distance %g is not a positive number", (double)max_distance);
+  if (n == 0) return MGS_OK;
+  MGS_REQUIRE(means && particles_rest, "deform_bind: means or particles_rest is null");
+  MGS_REQUIRE(idx && w && p && rest && flags, "deform_bind: an output (idx, w, p, rest, flags) is null");
+  MGS_REQUIRE(workspace, "deform_bind: workspace is null");
+  const size_t need = bind_workspace_bytes(n);
+  MGS_REQUIRE(workspace_bytes >= need, "deform_bind: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+  hipStream_t s = (hipStream_t)stream;
+  float* d2 = static_cast<float*>(workspace);
+  const dim3 grid(div_up((unsigned)n, (unsigned)kDeformGroup)), block(kDeformGroup);
+  hipLaunchKernelGGL(deform_knn_kernel, grid, block, 0, s, n, means, select, m, particles_rest, idx, d2);
+  int rc = check_launch("deform_bind");
+  if (rc) return rc;
+  hipLaunchKernelGGL(deform_bind_kernel, grid, block, 0, s, n, means, select, particles_rest, max_distance,
+                     (const float*)d2, idx, w, p, rest, flags);
+  return check_launch("deform_bind");
+}
+
+extern "C" int mgs_deform_apply(int n, const float* means, const float* quats, const float* scales, const int32_t* idx,
+                                const float* w, const float* p, const float* rest, const uint8_t* flags, int mode, int m,
+                                const float* particles_now, float* out_means, float* out_quats, float* out_scales,
+                                uint8_t* status, mgs_stream_t stream) {
+  MGS_REQUIRE(n >= 0, "deform_apply: n %d is negative", n);
+  MGS_REQUIRE(m >= kK, "deform_apply: m %d particles, at least %d needed", m, kK);
+  MGS_REQUIRE(mode == 0 || mode == 1, "deform_apply: mode %d is neither 0 (rigid) nor 1 (affine)", mode);
+  if (n == 0) return MGS_OK;
+  MGS_REQUIRE(means && quats && scales, "deform_apply: means, quats or scales is null");
+  MGS_REQUIRE(idx && w && p && rest && flags, "deform_apply: a binding array (idx, w, p, rest, flags) is null");
+  MGS_REQUIRE(particles_now, "deform_apply: particles_now is null");
+  MGS_REQUIRE(out_means && out_quats && out_scales, "deform_apply: an output is null");
+  const dim3 grid(div_up((unsigned)n, (unsigned)kDeformGroup)), block(kDeformGroup);
+  hipLaunchKernelGGL(deform_apply_kernel, grid, block, 0, (hipStream_t)stream, n, means, quats, scales, idx, w, p, rest,
+                     flags, mode, m, particles_now, out_means, out_quats, out_scales, status);
+  return check_launch("deform_apply");
+}

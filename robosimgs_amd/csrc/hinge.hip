@@ -19,9 +19,10 @@
 // summed with a fixed butterfly and the four waves in wave order.  At most kHingePartBlocks workgroups per set.
 //
 // hinge_final_kernel (one workgroup).  The partial sums are added in index order, then one thread forms the two means,
-// the position, the covariance (n - 1), solves the symmetric 3x3 eigenproblem with cyclic Jacobi sweeps in fp64 (every
-// index a compile-time constant: no scratch), applies the sign rule and the fallback and writes the 16 doubles.
+// the position, the covariance (n - 1), solves the symmetric 3x3 eigenproblem with cyclic Jacobi sweeps in fp64 (jacobi3.h:
+// every index a compile-time constant, no scratch), applies the sign rule and the fallback and writes the 16 doubles.
 #include "mgs_common.h"
+#include "jacobi3.h"
 #include "../../include/mgs_hinge.h"
 
 #include <math.h>
@@ -202,24 +203,6 @@ __global__ __launch_bounds__(kHingeGroup) void hinge_moments_kernel(
   }
 }
 
-// one Jacobi rotation of a symmetric 3x3 matrix that zeroes its (p, q) entry; r is the third index, and v's columns p and q
-// follow.  Scalars throughout: every entry stays in a register.
-__device__ __forceinline__ void jacobi_rotate(double& app, double& aqq, double& apq, double& arp, double& arq, double& v0p,
-                                              double& v0q, double& v1p, double& v1q, double& v2p, double& v2q) {
-  if (apq == 0.0) return;
-  const double theta = (aqq - app) / (2.0 * apq);
-  const double tn = (theta < 0.0 ? -1.0 : 1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-  const double c = 1.0 / sqrt(tn * tn + 1.0), sn = tn * c;
-  app -= tn * apq;
-  aqq += tn * apq;
-  apq = 0.0;
-  double x = arp, y = arq;
-  arp = c * x - sn * y; arq = sn * x + c * y;
-  x = v0p; y = v0q; v0p = c * x - sn * y; v0q = sn * x + c * y;
-  x = v1p; y = v1q; v1p = c * x - sn * y; v1q = sn * x + c * y;
-  x = v2p; y = v2q; v2p = c * x - sn * y; v2q = sn * x + c * y;
-}
-
 __global__ __launch_bounds__(64) void hinge_final_kernel(int n_a, const float* __restrict__ pts_a,
                                                          const unsigned* __restrict__ header,
                                                          const double* __restrict__ partials, int blocks_a, int blocks_b,
@@ -255,15 +238,8 @@ __global__ __launch_bounds__(64) void hinge_final_kernel(int n_a, const float* _
   double a11 = ((sums[0][7] + sums[1][7]) - sy * sy * inv_n) * inv;
   double a12 = ((sums[0][8] + sums[1][8]) - sy * sz * inv_n) * inv;
   double a22 = ((sums[0][9] + sums[1][9]) - sz * sz * inv_n) * inv;
-  double v00 = 1.0, v01 = 0.0, v02 = 0.0, v10 = 0.0, v11 = 1.0, v12 = 0.0, v20 = 0.0, v21 = 0.0, v22 = 1.0;
-
-#pragma unroll 1
-  for (int sweep = 0; sweep < 16; ++sweep) {
-    if (a01 == 0.0 && a02 == 0.0 && a12 == 0.0) break;
-    jacobi_rotate(a00, a11, a01, a02, a12, v00, v01, v10, v11, v20, v21);        // (0, 1), r = 2
-    jacobi_rotate(a00, a22, a02, a01, a12, v00, v02, v10, v12, v20, v22);        // (0, 2), r = 1
-    jacobi_rotate(a11, a22, a12, a01, a02, v01, v02, v11, v12, v21, v22);        // (1, 2), r = 0
-  }
+  double v00, v01, v02, v10, v11, v12, v20, v21, v22;
+  jacobi_solve3(a00, a01, a02, a11, a12, a22, v00, v01, v02, v10, v11, v12, v20, v21, v22);       // jacobi3.h
 
   // the eigenvalues ascending; the columns 1 and 2 of v follow the first two exchanges, so that the largest
   // eigenvalue's vector ends in column 2 (pairwise exchanges: a three-way choice of column becomes an indexed read of a

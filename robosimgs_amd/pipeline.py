@@ -106,7 +106,7 @@ class FrameRenderer:
                  sizing_camera=None, group_ids: Optional[torch.Tensor] = None, n_groups: int = 0,
                  rotate_sh: bool = True, reorder: Optional[str] = "morton", dataset_output=None, dataset_K=None,
                  dataset_keep_float: bool = False, class_ids: Optional[torch.Tensor] = None, n_classes: Optional[int] = None,
-                 labels: bool = False, distortion=None, **raster_kw):
+                 labels: bool = False, distortion=None, deform=None, deform_mode: str = "rigid", **raster_kw):
         """tensors: dict(means, quats, scales, opacities, colors, sh_degree) on the GPU
         (Gaussians.to_torch()); `self.t` is the renderer's own (by default Morton-ordered) copy.  isect_capacity: slots reserved for tile intersections per
         frame; if None it is measured once with `sizing_camera` = (viewmat, K) (required then)
@@ -137,6 +137,13 @@ class FrameRenderer:
         buffer, written once at capture; a submit stays one 25-float copy.  Combines with group_ids and labels; refused
         with dataset_output (pinhole-only).
 
+        Soft objects: deform=bind_particles(tensors["means"], particles_rest, ...) -- a ParticleBinding in
+        the order of `tensors` (the renderer permutes it along with its Morton copy) -- and deform_mode "rigid" or "affine".
+        Every slot owns an [M,3] particle buffer (the rest positions at first) and its graph starts with
+        mgs_deform_apply(rest state -> the slot's posed copy); submit(..., particles=) overwrites the buffer for that frame,
+        and fetch() also returns "deform_status" (uint8 [N], the renderer's own index order).  With group_ids as well the
+        group transform then runs on that copy: the two must move disjoint Gaussians (every bound Gaussian has group id -1).
+
         raw_params=True (forwarded to rasterization like every raster_kw): `tensors` hold log-scales and opacity logits
         (Gaussians.to_torch(raw=True)), so a loaded .ply renders without an activation pass on the host.  Static scenes
         only: the group transform multiplies activated scales by the group's s."""
@@ -150,6 +157,21 @@ class FrameRenderer:
         # scene renders 4,400 instead of 3,880 frames/s at 1 M Gaussians: a tile's list entries gather from a narrow
         # index range, a binning workgroup's pairs fall into few tile groups, culled Gaussians are culled by the wave.
         # `self.order` maps the renderer's index to the caller's; reorder=None keeps the caller's order.
+        if deform is not None:
+            from .deform import FLAG_UNBOUND, MODES, ParticleBinding
+            if raster_kw.get("raw_params"):
+                raise ValueError("raw_params=True is not available with deform: mgs_deform_apply reads activated scales "
+                                 "(the affine mode returns the roots of a covariance's eigenvalues)")
+            if not isinstance(deform, ParticleBinding) or deform.n != tensors["means"].shape[0]:
+                raise ValueError(f"deform must be a ParticleBinding of the scene's {tensors['means'].shape[0]} Gaussians "
+                                 "(bind_particles)")
+            if deform_mode not in MODES:
+                raise ValueError(f"deform_mode {deform_mode!r} not in {tuple(MODES)}")
+            if deform.particles is None or tuple(deform.particles.shape) != (deform.m, 3):
+                raise ValueError(f"deform.particles must hold the rest positions [{deform.m},3] (bind_particles keeps them)")
+            if group_ids is not None and bool((((deform.flags & FLAG_UNBOUND) == 0) & (group_ids >= 0)).any().item()):
+                raise ValueError("a Gaussian is both bound to particles and in a group: deform and group_ids must move "
+                                 "disjoint Gaussians (give bound Gaussians group id -1, or bind with select=)")
         if reorder not in (None, "morton"):
             raise ValueError(f"reorder {reorder!r} not in (None, 'morton')")
         self.order = None
@@ -176,7 +198,10 @@ class FrameRenderer:
                 group_ids = group_ids.index_select(0, self.order)
             if class_ids is not None:
                 class_ids = class_ids.index_select(0, self.order)
+            if deform is not None:
+                deform = deform.reordered(self.order)
         self.t = tensors
+        self.deform, self.deform_mode = deform, deform_mode     # the binding in the renderer's own index order (None: rigid scene)
         # the classes in the renderer's own index order (None: no label frames)
         self.class_ids = class_ids.to(torch.int32).contiguous() if class_ids is not None else None
         self.n_classes = int(n_classes) if class_ids is not None else None
@@ -267,6 +292,13 @@ class FrameRenderer:
                     "t": {k: (v.clone() if torch.is_tensor(v) and k in ("means", "quats", "scales", "colors") else v)
                           for k, v in self.t.items()}}
 
+        dfm = None
+        if self.deform is not None:          # soft object: this slot's particles, status bytes and (shared with `pose`) posed copy
+            rest_x = self.deform.particles.to(device=self.dev, dtype=torch.float32)
+            dfm = {"x": rest_x.clone().contiguous(), "status": torch.zeros(self.deform.n, dtype=torch.uint8, device=self.dev),
+                   "t": pose["t"] if pose is not None else {k: self.t[k].to(torch.float32).clone().contiguous()
+                                                            for k in ("means", "quats", "scales")}}
+
         ds, ds_out = None, None
         if self.dataset_dtype is not None:          # the slot's dataset frame: [RGBA8 plane | distance plane] as bytes
             n_px = self.width * self.height
@@ -280,11 +312,17 @@ class FrameRenderer:
             ds_out = (ds["rgba"].unsqueeze(0), ds["distance"].unsqueeze(0), self.dataset_K, self.dataset_keep_float)
 
         def body(schedule):
-            if pose is None:
+            if pose is None and dfm is None:
                 return self._raster(vm, K, self.capacity, dataset_out=ds_out, schedule=schedule, rows=rows)
-            from .transform import transform_gaussians
-            posed = transform_gaussians(self.t, group_ids=self.group_ids, rotate_sh=self.rotate_sh,
-                                        out=pose["t"], packed=(pose["x"], pose["r"]))
+            posed = self.t
+            if dfm is not None:
+                from .deform import deform_gaussians
+                posed = deform_gaussians(self.t, self.deform, dfm["x"], mode=self.deform_mode, out=dfm["t"],
+                                         status=dfm["status"])
+            if pose is not None:         # (after a deformation: in place on the slot's copy, the two move disjoint Gaussians)
+                from .transform import transform_gaussians
+                posed = transform_gaussians(posed, group_ids=self.group_ids, rotate_sh=self.rotate_sh,
+                                            out=pose["t"], packed=(pose["x"], pose["r"]))
             return self._raster(vm, K, self.capacity, posed, dataset_out=ds_out, schedule=schedule, rows=rows)
         variants, pool = {}, None
         for schedule in (("throughput", "latency") if self._both else (self.kw["raster_schedule"],)):
@@ -301,7 +339,7 @@ class FrameRenderer:
             # (the overflow word among them) are whatever the graph pool's memory held
             variants[schedule] = {"graph": graph, "colors": colors, "alphas": alphas, "meta": meta, "replayed": False}
         first = variants[self.kw["raster_schedule"]]
-        return {"stream": stream, "vm": vm, "K": K, "cam": cam, "pose": pose, "variants": variants, "variant": self.kw["raster_schedule"],
+        return {"stream": stream, "vm": vm, "K": K, "cam": cam, "pose": pose, "deform": dfm, "variants": variants, "variant": self.kw["raster_schedule"],
                 "graph": first["graph"], "colors": first["colors"], "alphas": first["alphas"], "meta": first["meta"],
                 "done": torch.cuda.Event(), "released": torch.cuda.Event(), "state": "free", "ds": ds}
 
@@ -314,15 +352,25 @@ class FrameRenderer:
         out = torch.cat([v.reshape(16).float(), k.reshape(9).float()])
         return out.to(device) if device is not None else out
 
-    def submit(self, viewmat, K=None, rotations=None, translations=None, scales=None) -> int:
+    def submit(self, viewmat, K=None, rotations=None, translations=None, scales=None, particles=None) -> int:
         """Enqueue one frame (viewmat: OpenCV world-to-camera 4x4, K: 3x3; numpy or tensors; or
         viewmat = pack_camera(viewmat, K) and K = None).  Dynamic scenes: rotations [G,3,3],
         translations [G,3] (and uniform scales [G]) pose the groups for this frame; omitted, the
-        slot keeps the pose of its previous frame (the rest pose at first).
+        slot keeps the pose of its previous frame (the rest pose at first).  Soft objects (deform=): particles [M,3], a tensor
+        or array on the host or the device, are this frame's particle positions; omitted, the slot keeps its previous ones.
+        A device tensor is read after everything enqueued so far on the current stream (the simulator's step).
         Returns a ticket for fetch().  Slots are used round-robin: the slot's previous frame
         must have been fetched and released."""
         slot = self._next
         s = self._slots[slot]
+        if particles is not None:                       # checked before anything is copied or the slot is taken
+            if self.deform is None:
+                raise ValueError("this FrameRenderer was built without deform=: there are no particles to move")
+            if not torch.is_tensor(particles):
+                particles = torch.from_numpy(np.ascontiguousarray(np.asarray(particles, dtype=np.float32)))
+            if tuple(particles.shape) != (self.deform.m, 3):
+                raise ValueError(f"particles must be [{self.deform.m},3] (the particle set the binding was made for), got "
+                                 f"{tuple(particles.shape)}")
         if s["state"] != "free":
             raise RuntimeError(f"slot {slot} still holds a frame that was not released "
                                f"({self.n_slots} frames in flight at most)")
@@ -350,6 +398,7 @@ class FrameRenderer:
         elif not torch.is_tensor(viewmat) and not torch.is_tensor(K):
             packed = torch.from_numpy(np.concatenate([np.asarray(viewmat, dtype=np.float32).reshape(16),
                                                       np.asarray(K, dtype=np.float32).reshape(9)]))
+        caller = torch.cuda.current_stream(self.dev)
         with torch.cuda.stream(s["stream"]):
             s["stream"].wait_event(s["released"])      # the previous consumer's reads are done
             if packed is not None:
@@ -357,6 +406,11 @@ class FrameRenderer:
             else:
                 s["vm"].copy_(torch.as_tensor(viewmat).reshape(1, 4, 4), non_blocking=True)
                 s["K"].copy_(torch.as_tensor(K).reshape(1, 3, 3), non_blocking=True)
+            if particles is not None:
+                if particles.is_cuda:       # a simulator's output: produced on the caller's stream, read here on the slot's
+                    s["stream"].wait_stream(caller)
+                    particles.record_stream(s["stream"])
+                s["deform"]["x"].copy_(particles, non_blocking=True)
             if rotations is not None:
                 if s["pose"] is None:
                     raise ValueError("this FrameRenderer was built without group_ids: the scene is static")
@@ -394,6 +448,8 @@ class FrameRenderer:
         out = {"colors": s["colors"][0], "alphas": s["alphas"][0], "meta": s["meta"]}
         if self.class_ids is not None:
             out["labels"], out["label_weights"] = s["meta"]["labels"][0], s["meta"]["label_weights"][0]
+        if s["deform"] is not None:
+            out["deform_status"] = s["deform"]["status"]
         if s["ds"] is not None:
             out.update(s["ds"])
             if not self.dataset_keep_float:          # the float frame was never written
