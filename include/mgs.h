@@ -486,8 +486,10 @@ int mgs_rasterize_bwd_det(int n, const float *means2d, const float *conics, cons
 
 /* Fused-colour backward: chain rule of mgs_project_color_fwd.
  *   v_feats[N,feat_stride] (channel 3, if present, is d/d depth), v_means2d, v_conics,
- *   v_depths (nullable, extra d/d depth), v_opac_out (cotangent of opacities*compensation;
- *   needed iff antialiased) ->
+ *   v_depths[N] (nullable: a depth cotangent of its own; the kernel differentiates depth with
+ *   v_feats[:,3] + v_depths when feat_stride is 4 and with v_depths alone when it is 3, so a caller whose
+ *   depth gradient arrives outside the feature row needs no 4-wide copy), v_opac_out (cotangent of
+ *   opacities*compensation; needed iff antialiased) ->
  *   v_means[N,3], v_quats[N,4], v_scales[N,3], v_sh_coeffs[N,K,3], and, iff antialiased,
  *   v_opacities[N].  accumulate == 0: every output row is overwritten (zeros for culled
  *   Gaussians and for coefficients above the active degree); accumulate != 0: added to,

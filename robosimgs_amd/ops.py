@@ -257,16 +257,18 @@ def project_color_fwd_raw(means, quats, scales, opacities, sh_degree, sh_coeffs,
 
 def project_color_bwd_raw(means, quats, scales, opacities, sh_degree, sh_coeffs, viewmat, K, width, height, eps2d,
                           radii, conics, antialiased, feats, v_feats, v_means2d, v_conics, v_opac_aa, v_means, v_quats,
-                          v_scales, v_sh, v_opacities, v_viewmat=None, accumulate=False, camera=0, raw=False):
+                          v_scales, v_sh, v_opacities, v_viewmat=None, accumulate=False, camera=0, v_depths=None, raw=False):
     """The chain rule of project_color_fwd_raw for one camera.  radii, conics, feats: what the forward returned;
     v_opac_aa: the cotangent of its opac_aa (antialiased only).  v_means / v_quats / v_scales / v_sh and, antialiased,
     v_opacities are overwritten, or added to with `accumulate`; v_viewmat [4,4] (optional) is always added to.
     raw (the forward's): scales / opacities are log-scales / logits; v_opac_aa -- the blend's opacity gradient -- and
-    v_opacities are then needed anti-aliased or not, and v_scales / v_opacities are the gradients of the raw tensors."""
+    v_opacities are then needed anti-aliased or not, and v_scales / v_opacities are the gradients of the raw tensors.
+    v_depths [N] (optional): a depth cotangent of its own, added to channel 3 of v_feats when feats is 4 wide and the only
+    depth cotangent when it is 3 wide."""
     check(_lib.lib().mgs_project_color_bwd(
         means.shape[0], ptr(means), ptr(quats), ptr(scales), ptr(opacities), sh_degree, sh_coeffs.shape[1], ptr(sh_coeffs),
         ptr(viewmat), ptr(K), width, height, eps2d, ptr(radii_x(radii)), ptr(conics), int(antialiased), feats.shape[1],
-        ptr(feats), ptr(v_feats), ptr(v_means2d), ptr(v_conics), None, ptr(v_opac_aa), ptr(v_means), ptr(v_quats),
+        ptr(feats), ptr(v_feats), ptr(v_means2d), ptr(v_conics), ptr(v_depths), ptr(v_opac_aa), ptr(v_means), ptr(v_quats),
         ptr(v_scales), ptr(v_sh), ptr(v_opacities), ptr(v_viewmat), int(accumulate),
         int(camera) | (PARAMS_RAW if raw else 0), stream_handle()), "mgs_project_color_bwd")
 
