@@ -50,6 +50,9 @@ def __getattr__(name):  # lazy: keeps `import robosimgs_amd` torch-free for host
     if name in ("bind_particles", "deform_gaussians", "ParticleBinding", "deform_bind_raw", "deform_apply_raw"):
         from . import deform
         return getattr(deform, name)
+    if name == "Mesh":
+        from . import mesh
+        return mesh.Mesh
     if name in ("l1_loss", "l1_ssim_loss", "ssim", "unit_gradient"):
         from . import losses
         return getattr(losses, name)
