@@ -4,7 +4,11 @@ particles -- no simulator needed -- and FrameRenderer(deform=binding) deforms th
 a submit uploads one [M,3] tensor.  A rigid block beside the sheet stays unbound (max_distance).  Synthetic inputs, so
 it runs anywhere an MI355X is visible:
 
-    python examples/deform_cloth.py [n_frames] [rigid|affine]
+    python examples/deform_cloth.py [n_frames] [rigid|affine] [--rotate-sh]
+
+--rotate-sh: the sheet gets degree-3 SH (a view-dependent sheen) and FrameRenderer(deform_rotate_sh=True) turns every
+Gaussian's SH rows with it; a second renderer without the rotation renders the same frames, and the difference between the
+two images is printed: the sheen that stayed in the world frame where the cloth turned.
 """
 import math
 import sys
@@ -19,8 +23,10 @@ from robosimgs_amd.gaussians import Gaussians  # noqa: E402
 
 
 def main():
-    n_frames = int(sys.argv[1]) if len(sys.argv) > 1 else 48
-    mode = sys.argv[2] if len(sys.argv) > 2 else "rigid"
+    rotate_sh = "--rotate-sh" in sys.argv
+    argv = [a for a in sys.argv[1:] if a != "--rotate-sh"]
+    n_frames = int(argv[0]) if len(argv) > 0 else 48
+    mode = argv[1] if len(argv) > 1 else "rigid"
     W, H = 960, 540
     rng = np.random.default_rng(0)
     ns, ms = 160, 48                                           # 160 x 160 Gaussians over 48 x 48 particles, 1.6 x 1.6
@@ -32,8 +38,9 @@ def main():
     stripes = (np.floor(means[:, 0] * 5) + np.floor(means[:, 1] * 5)) % 2
     colour = np.where(stripes[:, None] > 0, [0.85, 0.2, 0.2], [0.95, 0.9, 0.8]) + rng.uniform(-0.03, 0.03, (n, 3))
     scene = Gaussians(means, np.tile(np.log([0.008, 0.008, 0.002]), (n, 1)), np.tile([1.0, 0, 0, 0], (n, 1)), np.full(n, 3.0),
-                      (colour - 0.5) / 0.28209479177387814, np.zeros((n, 0, 3)))
-    tensors = scene.to_torch("cuda", 0)
+                      (colour - 0.5) / 0.28209479177387814,
+                      rng.normal(0.0, 0.12, (n, 15, 3)) if rotate_sh else np.zeros((n, 0, 3)))
+    tensors = scene.to_torch("cuda", 3 if rotate_sh else 0)
 
     px, py = torch.meshgrid(torch.linspace(-0.85, 0.85, ms), torch.linspace(-0.85, 0.85, ms), indexing="ij")
     rest = torch.stack([px.reshape(-1), py.reshape(-1), torch.zeros(ms * ms)], 1).cuda()
@@ -42,7 +49,9 @@ def main():
 
     cams = camera_ring(n_frames, W, H, radius=2.4)
     r = FrameRenderer(tensors, W, H, render_mode="RGB", frames_in_flight=3, sizing_camera=(cams[0].viewmat(), cams[0].K),
-                      capacity_margin=2.5, deform=binding, deform_mode=mode)
+                      capacity_margin=2.5, deform=binding, deform_mode=mode, deform_rotate_sh=rotate_sh)
+    unturned = FrameRenderer(tensors, W, H, render_mode="RGB", frames_in_flight=1, sizing_camera=(cams[0].viewmat(), cams[0].K),
+                             capacity_margin=2.5, deform=binding, deform_mode=mode) if rotate_sh else None
 
     def particles_at(k):                                       # a travelling wave across the sheet, on the device
         phase = 2 * math.pi * k / n_frames
@@ -52,7 +61,7 @@ def main():
         return x
 
     counts = np.zeros(5, np.int64)                             # ok, unbound, fell back to rigid, thin, non-finite
-    covered, tickets, nxt = [], [], 0
+    covered, tickets, nxt, diffs = [], [], 0, []
     for _ in range(n_frames):
         while nxt < n_frames and len(tickets) < r.n_slots:
             tickets.append(r.submit(cams[nxt].viewmat(), cams[nxt].K, particles=particles_at(nxt)))
@@ -63,6 +72,12 @@ def main():
         counts += np.array([int((st == 0).sum()), int((st & STATUS_UNBOUND != 0).sum()), int((st & STATUS_FALLBACK != 0).sum()),
                             int((st & STATUS_THIN != 0).sum()), int((st & STATUS_NONFINITE != 0).sum())])
         covered.append(float((f["colors"].sum(-1) > 0.05).float().mean()))
+        if unturned is not None:                               # the same frame with the SH rows left in the world frame
+            k = len(covered) - 1
+            tk0 = unturned.submit(cams[k].viewmat(), cams[k].K, particles=particles_at(k))
+            d = (f["colors"] - unturned.fetch(tk0)["colors"]).abs()
+            diffs.append((float(d.mean()), float(d.max()), float((d.amax(-1) > 1.0 / 255).float().mean())))
+            unturned.release(tk0)
         r.release(tk)
     torch.cuda.synchronize()
     share = 100.0 * counts / (n * n_frames)
@@ -70,6 +85,10 @@ def main():
           f"{covered[0]:.3f} {covered[n_frames // 2]:.3f} {covered[-1]:.3f}")
     print(f"status per Gaussian and frame: deformed {share[0]:.2f} %, unbound {share[1]:.2f} %, affine fell back to rigid "
           f"{share[2]:.2f} %, thin (translated only) {share[3]:.2f} %, non-finite neighbour {share[4]:.2f} %")
+    if diffs:
+        d = np.array(diffs)
+        print(f"SH rows turned with the cloth against left in the world frame, per frame: mean |difference| {d[:, 0].mean():.4f} "
+              f"(worst frame {d[:, 0].max():.4f}), largest {d[:, 1].max():.3f}, pixels off by more than 1/255: {100 * d[:, 2].mean():.1f} %")
 
 
 if __name__ == "__main__":

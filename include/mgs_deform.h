@@ -9,7 +9,8 @@
  * ([m,3] fp32).  mgs_deform_bind, once per object, ties every Gaussian to its MGS_DEFORM_K = 8 nearest particles of the
  * rest state; mgs_deform_apply, once per frame, moves the Gaussians with the particles' current positions: a rotation by
  * shape matching (Mueller et al. 2005) or the affine map of the neighbourhood with Sigma' = A Sigma A^T (PhysGaussian).
- * Opacities and colours are not touched and SH rows are not rotated (what mgs_transform_gaussians does without SH rows).
+ * Opacities and colours are not touched and SH rows are not rotated (what mgs_transform_gaussians does without SH rows);
+ * mgs_deform_sh.h adds the call that also turns each Gaussian's SH rows.
  *
  * The binding arrays are neighbour-major, so that one thread per Gaussian reads coalesced (N = n):
  *     idx    int32 [8][N]      neighbour indices, row 0 the nearest (the anchor); -1 in every row of an unbound Gaussian

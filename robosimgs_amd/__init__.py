@@ -47,7 +47,8 @@ def __getattr__(name):  # lazy: keeps `import robosimgs_amd` torch-free for host
     if name in ("pose_gaussians", "pack_transforms_torch", "pose_bwd_raw"):
         from . import pose
         return getattr(pose, name)
-    if name in ("bind_particles", "deform_gaussians", "ParticleBinding", "deform_bind_raw", "deform_apply_raw"):
+    if name in ("bind_particles", "deform_gaussians", "ParticleBinding", "deform_bind_raw", "deform_apply_raw",
+                "deform_apply_sh_raw"):
         from . import deform
         return getattr(deform, name)
     if name == "Mesh":

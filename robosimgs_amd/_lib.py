@@ -129,6 +129,11 @@ _DEFORM_SIGNATURES = {
     "mgs_deform_bind": ([i, p, p, i, p, f, p, c_size_t, p, p, p, p, p, p], c_int),
     "mgs_deform_apply": ([i, p, p, p, p, p, p, p, p, i, i, p, p, p, p, p, p], c_int),
 }
+# every function include/mgs_deform_sh.h declares (the same libraries again): mgs_deform_apply's sixteen parameters, then
+# (sh_degree, coeff_stride, sh_coeffs, out_sh, copy_unbound) in front of the stream
+_DEFORM_SH_SIGNATURES = {
+    "mgs_deform_apply_sh": (_DEFORM_SIGNATURES["mgs_deform_apply"][0][:-1] + [i, i, p, p, i, p], c_int),
+}
 del p, i, f, u32, img
 EXPORTS = list(_SIGNATURES)
 OPTIM_EXPORTS = list(_OPTIM_SIGNATURES)
@@ -138,6 +143,7 @@ LIFT_EXPORTS = list(_LIFT_SIGNATURES)
 HINGE_EXPORTS = list(_HINGE_SIGNATURES)
 POSE_EXPORTS = list(_POSE_SIGNATURES)
 DEFORM_EXPORTS = list(_DEFORM_SIGNATURES)
+DEFORM_SH_EXPORTS = list(_DEFORM_SH_SIGNATURES)
 DEFORM_K = 8                                # MGS_DEFORM_K
 LABEL_NONE, LABELS_MAX_CLASSES = 255, 32    # MGS_LABEL_NONE, MGS_LABELS_MAX_CLASSES
 
@@ -162,7 +168,7 @@ def _load(path: str = None, hooks: bool = False) -> ctypes.CDLL:
     for name, (argtypes, restype) in (*_SIGNATURES.items(), *_OPTIM_SIGNATURES.items(), *_REFINE_SIGNATURES.items(),
                                       *_LABEL_SIGNATURES.items(), *_LIFT_SIGNATURES.items(),
                                       *_HINGE_SIGNATURES.items(), *_POSE_SIGNATURES.items(),
-                                      *_DEFORM_SIGNATURES.items()):
+                                      *_DEFORM_SIGNATURES.items(), *_DEFORM_SH_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here == header/library mismatch
         fn.argtypes = argtypes
         fn.restype = restype

@@ -17,9 +17,14 @@
 // deform_apply_kernel (every frame).  One thread per Gaussian.  The neighbour-major binding arrays make every streamed
 // load coalesced; the 8 gathers of current particle positions are the only random access.  c and P are fp32 fma chains
 // of differences to the anchor x_0; the rotation and the deformed covariance are solved in fp64 with the same Jacobi.
+// Its SH instantiation (include/mgs_deform_sh.h) then turns the lane's SH rows by the rotation it found, in fp32 registers
+// (sh_rotate.h), rows of 16 coefficients staged through LDS (sh_staging.h); the instantiation without SH is untouched by it.
 #include "mgs_common.h"
 #include "jacobi3.h"
+#include "sh_staging.h"
+#include "sh_rotate.h"
 #include "../../include/mgs_deform.h"
+#include "../../include/mgs_deform_sh.h"
 
 #include <float.h>
 #include <math.h>
@@ -29,6 +34,7 @@ namespace {
 
 constexpr int kDeformGroup = 256;         // threads of a workgroup (all three kernels)
 constexpr int kDeformTile = 1024;         // T: particles per LDS tile (16 KiB)
+constexpr int kDeformShGroup = 64;        // threads of a workgroup of the apply's SH instantiation: one wave
 constexpr int kK = MGS_DEFORM_K;
 constexpr int kRestRows = 12;
 constexpr double kDegenerate = 1e-3;      // the flat / thin threshold on eigenvalue (bind) and singular-value (apply) ratios
@@ -215,178 +221,271 @@ __device__ __forceinline__ void rotmat_to_quat(double r00, double r01, double r0
   }
 }
 
-__global__ __launch_bounds__(kDeformGroup) void deform_apply_kernel(
+// R = argmax over SO(3) of tr(R^T P) from the eigenpairs of P^T P, as doubles r00 .. r22 in the scope that uses it:
+// u1 = P v1 / sigma1, u2 = P v2 made orthonormal to u1, u3 = u1 x u2, v3 = v1 x v2, R = sum u_k v_k^T (v3 = v1 x v2 is w)
+#define MGS_SHAPE_ROTATION()                                                                                        \
+  const double is1 = 1.0 / sqrt(a00);                                                                               \
+  const double u10 = (p00 * v00 + p01 * v10 + p02 * v20) * is1, u11 = (p10 * v00 + p11 * v10 + p12 * v20) * is1;    \
+  const double u12 = (p20 * v00 + p21 * v10 + p22 * v20) * is1;                                                     \
+  double u20 = p00 * v01 + p01 * v11 + p02 * v21, u21 = p10 * v01 + p11 * v11 + p12 * v21;                          \
+  double u22 = p20 * v01 + p21 * v11 + p22 * v21;                                                                   \
+  const double dot = u10 * u20 + u11 * u21 + u12 * u22;                                                             \
+  u20 -= dot * u10; u21 -= dot * u11; u22 -= dot * u12;                                                             \
+  const double in2 = 1.0 / sqrt(u20 * u20 + u21 * u21 + u22 * u22);                                                 \
+  u20 *= in2; u21 *= in2; u22 *= in2;                                                                               \
+  const double u30 = u11 * u22 - u12 * u21, u31 = u12 * u20 - u10 * u22, u32 = u10 * u21 - u11 * u20;               \
+  const double w0 = v10 * v21 - v20 * v11, w1 = v20 * v01 - v00 * v21, w2 = v00 * v11 - v10 * v01;                  \
+  const double r00 = u10 * v00 + u20 * v01 + u30 * w0, r01 = u10 * v10 + u20 * v11 + u30 * w1;                      \
+  const double r02 = u10 * v20 + u20 * v21 + u30 * w2, r10 = u11 * v00 + u21 * v01 + u31 * w0;                      \
+  const double r11 = u11 * v10 + u21 * v11 + u31 * w1, r12 = u11 * v20 + u21 * v21 + u31 * w2;                      \
+  const double r20 = u12 * v00 + u22 * v01 + u32 * w0, r21 = u12 * v10 + u22 * v11 + u32 * w1;                      \
+  const double r22 = u12 * v20 + u22 * v21 + u32 * w2;
+
+// What the SH phase does with a lane's row: nothing (an unbound Gaussian, unless asked to copy), copy it through (bound
+// but not turning: thin, a non-finite neighbour) or rotate it.
+enum { kRowUnbound = 0, kRowCopy = 1, kRowRotate = 2 };
+
+// the SH phase's copy of R, rounded to fp32 once (row-major)
+#define MGS_STORE_ROTATION()                                                                                \
+  do {                                                                                                      \
+    Rf[0] = (float)r00; Rf[1] = (float)r01; Rf[2] = (float)r02; Rf[3] = (float)r10; Rf[4] = (float)r11;     \
+    Rf[5] = (float)r12; Rf[6] = (float)r20; Rf[7] = (float)r21; Rf[8] = (float)r22;                         \
+    row = kRowRotate;                                                                                       \
+  } while (0)
+
+// SH = false: the geometry alone, kDeformGroup threads, no LDS -- what mgs_deform_apply launches.
+// SH = true: one wave per workgroup (kDeformShGroup; the staging area of a wave is 13,312 B of LDS, so twelve resident
+// waves of a CU hold 159,744 of its 163,840 B however they are grouped, and a workgroup of one wave makes the two
+// barriers free).  After the geometry is written the wave turns the SH rows of its rotating lanes (sh_rotate.h).  Rows of
+// 16 coefficients go through LDS (sh_staging.h: the HBM side is lane-linear) and only rows some lane has to write are
+// fetched; shorter rows are read per lane.  Nobody leaves before the last barrier: a lane past n has nothing to write.
+template <bool SH, bool STAGED>
+__global__ __launch_bounds__(SH ? kDeformShGroup : kDeformGroup) void deform_apply_kernel(
     int n, const float* __restrict__ means, const float* __restrict__ quats, const float* __restrict__ scales,
     const int32_t* __restrict__ idx, const float* __restrict__ w, const float* __restrict__ p,
     const float* __restrict__ rest, const uint8_t* __restrict__ flags, int mode, int m, const float* __restrict__ now,
     float* __restrict__ out_means, float* __restrict__ out_quats, float* __restrict__ out_scales,
-    uint8_t* __restrict__ status) {
-  const long long i = (long long)blockIdx.x * kDeformGroup + threadIdx.x;
-  if (i >= n) return;
-  const size_t N = (size_t)n;
-  float mu0 = means[3 * i + 0], mu1 = means[3 * i + 1], mu2 = means[3 * i + 2];
-  float4 q = reinterpret_cast<const float4*>(quats)[i];           // (w, x, y, z)
-  float s0 = scales[3 * i + 0], s1 = scales[3 * i + 1], s2 = scales[3 * i + 2];
-  const unsigned fl = flags[i];
-  unsigned st = 0u;
+    uint8_t* __restrict__ status, int sh_degree, int stride_f, const float* __restrict__ sh_in,
+    float* __restrict__ sh_out, int copy_unbound) {
+  constexpr int kGroup = SH ? kDeformShGroup : kDeformGroup;
+  const long long i = (long long)blockIdx.x * kGroup + threadIdx.x;
+  const bool live = i < n;
+  if constexpr (!SH) {
+    if (!live) return;
+  }
+  int row = kRowUnbound;                  // what the SH phase does with this lane's row
+  float Rf[9];                            // R rounded to fp32, row-major, where row == kRowRotate
+  if (SH ? live : true) {
+    row = kRowCopy;
+    const size_t N = (size_t)n;
+    float mu0 = means[3 * i + 0], mu1 = means[3 * i + 1], mu2 = means[3 * i + 2];
+    float4 q = reinterpret_cast<const float4*>(quats)[i];           // (w, x, y, z)
+    float s0 = scales[3 * i + 0], s1 = scales[3 * i + 1], s2 = scales[3 * i + 2];
+    const unsigned fl = flags[i];
+    unsigned st = 0u;
 
-  if (fl & kFlagUnbound) {
-    st = kStatusUnbound;
-  } else {
-    // the 8 current positions: the only random access
-    float x[kK][3];
-    bool ok = true;
-#pragma unroll
-    for (int k = 0; k < kK; ++k) {
-      const int j = idx[k * N + i];
-      const bool in = j >= 0 && j < m;
-      const size_t jj = in ? (size_t)j : 0;
-      x[k][0] = now[3 * jj + 0]; x[k][1] = now[3 * jj + 1]; x[k][2] = now[3 * jj + 2];
-      ok = ok && in && finite3(x[k][0], x[k][1], x[k][2]);
-    }
-    if (!ok) {
-      st = kStatusNonFinite;
+    if (fl & kFlagUnbound) {
+      st = kStatusUnbound;
+      row = kRowUnbound;
     } else {
-      // c = sum w_j e_j and P = sum e_j p_j^T over j = 1..7, e_j = x_j - x_0: fp32 fma chains in order of j
-      float c0 = 0.f, c1 = 0.f, c2 = 0.f;
-      float P00 = 0.f, P01 = 0.f, P02 = 0.f, P10 = 0.f, P11 = 0.f, P12 = 0.f, P20 = 0.f, P21 = 0.f, P22 = 0.f;
+      // the 8 current positions: the only random access
+      float x[kK][3];
+      bool ok = true;
 #pragma unroll
-      for (int k = 1; k < kK; ++k) {
-        const float e0 = x[k][0] - x[0][0], e1 = x[k][1] - x[0][1], e2 = x[k][2] - x[0][2];
-        const float wk = w[k * N + i];
-        const float pk0 = p[(3 * k + 0) * N + i], pk1 = p[(3 * k + 1) * N + i], pk2 = p[(3 * k + 2) * N + i];
-        if (k == 1) {
-          c0 = wk * e0; c1 = wk * e1; c2 = wk * e2;
-          P00 = e0 * pk0; P01 = e0 * pk1; P02 = e0 * pk2;
-          P10 = e1 * pk0; P11 = e1 * pk1; P12 = e1 * pk2;
-          P20 = e2 * pk0; P21 = e2 * pk1; P22 = e2 * pk2;
-        } else {
-          c0 = __builtin_fmaf(wk, e0, c0); c1 = __builtin_fmaf(wk, e1, c1); c2 = __builtin_fmaf(wk, e2, c2);
-          P00 = __builtin_fmaf(e0, pk0, P00); P01 = __builtin_fmaf(e0, pk1, P01); P02 = __builtin_fmaf(e0, pk2, P02);
-          P10 = __builtin_fmaf(e1, pk0, P10); P11 = __builtin_fmaf(e1, pk1, P11); P12 = __builtin_fmaf(e1, pk2, P12);
-          P20 = __builtin_fmaf(e2, pk0, P20); P21 = __builtin_fmaf(e2, pk1, P21); P22 = __builtin_fmaf(e2, pk2, P22);
+      for (int k = 0; k < kK; ++k) {
+        const int j = idx[k * N + i];
+        const bool in = j >= 0 && j < m;
+        const size_t jj = in ? (size_t)j : 0;
+        x[k][0] = now[3 * jj + 0]; x[k][1] = now[3 * jj + 1]; x[k][2] = now[3 * jj + 2];
+        ok = ok && in && finite3(x[k][0], x[k][1], x[k][2]);
+      }
+      if (!ok) {
+        st = kStatusNonFinite;
+      } else {
+        // c = sum w_j e_j and P = sum e_j p_j^T over j = 1..7, e_j = x_j - x_0: fp32 fma chains in order of j
+        float c0 = 0.f, c1 = 0.f, c2 = 0.f;
+        float P00 = 0.f, P01 = 0.f, P02 = 0.f, P10 = 0.f, P11 = 0.f, P12 = 0.f, P20 = 0.f, P21 = 0.f, P22 = 0.f;
+#pragma unroll
+        for (int k = 1; k < kK; ++k) {
+          const float e0 = x[k][0] - x[0][0], e1 = x[k][1] - x[0][1], e2 = x[k][2] - x[0][2];
+          const float wk = w[k * N + i];
+          const float pk0 = p[(3 * k + 0) * N + i], pk1 = p[(3 * k + 1) * N + i], pk2 = p[(3 * k + 2) * N + i];
+          if (k == 1) {
+            c0 = wk * e0; c1 = wk * e1; c2 = wk * e2;
+            P00 = e0 * pk0; P01 = e0 * pk1; P02 = e0 * pk2;
+            P10 = e1 * pk0; P11 = e1 * pk1; P12 = e1 * pk2;
+            P20 = e2 * pk0; P21 = e2 * pk1; P22 = e2 * pk2;
+          } else {
+            c0 = __builtin_fmaf(wk, e0, c0); c1 = __builtin_fmaf(wk, e1, c1); c2 = __builtin_fmaf(wk, e2, c2);
+            P00 = __builtin_fmaf(e0, pk0, P00); P01 = __builtin_fmaf(e0, pk1, P01); P02 = __builtin_fmaf(e0, pk2, P02);
+            P10 = __builtin_fmaf(e1, pk0, P10); P11 = __builtin_fmaf(e1, pk1, P11); P12 = __builtin_fmaf(e1, pk2, P12);
+            P20 = __builtin_fmaf(e2, pk0, P20); P21 = __builtin_fmaf(e2, pk1, P21); P22 = __builtin_fmaf(e2, pk2, P22);
+          }
+        }
+        const float xb0 = x[0][0] + c0, xb1 = x[0][1] + c1, xb2 = x[0][2] + c2;
+        const float d00 = rest[0 * N + i], d01 = rest[1 * N + i], d02 = rest[2 * N + i];
+
+        // P^T P and its eigenpairs, descending
+        const double p00 = P00, p01 = P01, p02 = P02, p10 = P10, p11 = P11, p12 = P12, p20 = P20, p21 = P21, p22 = P22;
+        double a00 = p00 * p00 + p10 * p10 + p20 * p20, a01 = p00 * p01 + p10 * p11 + p20 * p21;
+        double a02 = p00 * p02 + p10 * p12 + p20 * p22, a11 = p01 * p01 + p11 * p11 + p21 * p21;
+        double a12 = p01 * p02 + p11 * p12 + p21 * p22, a22 = p02 * p02 + p12 * p12 + p22 * p22;
+        double v00, v01, v02, v10, v11, v12, v20, v21, v22;
+        jacobi_solve3(a00, a01, a02, a11, a12, a22, v00, v01, v02, v10, v11, v12, v20, v21, v22);
+        if (a00 < a11) MGS_SWAP_PAIR(a00, a11, v00, v10, v20, v01, v11, v21);
+        if (a11 < a22) MGS_SWAP_PAIR(a11, a22, v01, v11, v21, v02, v12, v22);
+        if (a00 < a11) MGS_SWAP_PAIR(a00, a11, v00, v10, v20, v01, v11, v21);
+        // sigma_mid < 1e-3 sigma_max  <=>  lambda_mid < 1e-6 lambda_max
+        const bool thin = (fl & kFlagThin) || !(a00 > 0.0) || a11 < kDegenerate * kDegenerate * a00;
+
+        bool rigid = mode == 0;
+        float A00 = 0.f, A01 = 0.f, A02 = 0.f, A10 = 0.f, A11 = 0.f, A12 = 0.f, A20 = 0.f, A21 = 0.f, A22 = 0.f;
+        if (thin) {
+          st = kStatusThin;
+          mu0 = xb0 + d00; mu1 = xb1 + d01; mu2 = xb2 + d02;
+        } else if (!rigid) {
+          if (fl & kFlagFlat) {
+            rigid = true;
+          } else {                                    // A = P Q^-1 in fp32
+            const float ixx = rest[3 * N + i], ixy = rest[4 * N + i], ixz = rest[5 * N + i];
+            const float iyy = rest[6 * N + i], iyz = rest[7 * N + i], izz = rest[8 * N + i];
+            A00 = __builtin_fmaf(P02, ixz, __builtin_fmaf(P01, ixy, P00 * ixx));
+            A01 = __builtin_fmaf(P02, iyz, __builtin_fmaf(P01, iyy, P00 * ixy));
+            A02 = __builtin_fmaf(P02, izz, __builtin_fmaf(P01, iyz, P00 * ixz));
+            A10 = __builtin_fmaf(P12, ixz, __builtin_fmaf(P11, ixy, P10 * ixx));
+            A11 = __builtin_fmaf(P12, iyz, __builtin_fmaf(P11, iyy, P10 * ixy));
+            A12 = __builtin_fmaf(P12, izz, __builtin_fmaf(P11, iyz, P10 * ixz));
+            A20 = __builtin_fmaf(P22, ixz, __builtin_fmaf(P21, ixy, P20 * ixx));
+            A21 = __builtin_fmaf(P22, iyz, __builtin_fmaf(P21, iyy, P20 * ixy));
+            A22 = __builtin_fmaf(P22, izz, __builtin_fmaf(P21, iyz, P20 * ixz));
+            const double det = (double)A00 * ((double)A11 * A22 - (double)A12 * A21)
+                               - (double)A01 * ((double)A10 * A22 - (double)A12 * A20)
+                               + (double)A02 * ((double)A10 * A21 - (double)A11 * A20);
+            if (!(det > 0.0)) rigid = true;
+          }
+          if (rigid) st = kStatusFallback;
+        }
+
+        if (!thin && rigid) {
+          MGS_SHAPE_ROTATION();
+          if constexpr (SH) MGS_STORE_ROTATION();
+          mu0 = (float)((double)xb0 + (r00 * d00 + r01 * d01 + r02 * d02));
+          mu1 = (float)((double)xb1 + (r10 * d00 + r11 * d01 + r12 * d02));
+          mu2 = (float)((double)xb2 + (r20 * d00 + r21 * d01 + r22 * d02));
+          double aw, ax, ay, az;
+          rotmat_to_quat(r00, r01, r02, r10, r11, r12, r20, r21, r22, aw, ax, ay, az);
+          const double bw = q.x, bx = q.y, by = q.z, bz = q.w;
+          const double ow = aw * bw - ax * bx - ay * by - az * bz, ox = aw * bx + ax * bw + ay * bz - az * by;
+          const double oy = aw * by - ax * bz + ay * bw + az * bx, oz = aw * bz + ax * by - ay * bx + az * bw;
+          const double inv = 1.0 / sqrt(ow * ow + ox * ox + oy * oy + oz * oz);
+          q = make_float4((float)(ow * inv), (float)(ox * inv), (float)(oy * inv), (float)(oz * inv));
+        } else if (!thin) {
+          if constexpr (SH) {                         // the colour field turns with the neighbourhood's rotation, it does not shear
+            MGS_SHAPE_ROTATION();
+            MGS_STORE_ROTATION();
+          }
+          mu0 = xb0 + __builtin_fmaf(A02, d02, __builtin_fmaf(A01, d01, A00 * d00));
+          mu1 = xb1 + __builtin_fmaf(A12, d02, __builtin_fmaf(A11, d01, A10 * d00));
+          mu2 = xb2 + __builtin_fmaf(A22, d02, __builtin_fmaf(A21, d01, A20 * d00));
+          // M = A R(q) diag(s), Sigma' = M M^T
+          double bw = q.x, bx = q.y, by = q.z, bz = q.w;
+          const double inv = 1.0 / sqrt(bw * bw + bx * bx + by * by + bz * bz);
+          bw *= inv; bx *= inv; by *= inv; bz *= inv;
+          const double g00 = 1.0 - 2.0 * (by * by + bz * bz), g01 = 2.0 * (bx * by - bw * bz), g02 = 2.0 * (bx * bz + bw * by);
+          const double g10 = 2.0 * (bx * by + bw * bz), g11 = 1.0 - 2.0 * (bx * bx + bz * bz), g12 = 2.0 * (by * bz - bw * bx);
+          const double g20 = 2.0 * (bx * bz - bw * by), g21 = 2.0 * (by * bz + bw * bx), g22 = 1.0 - 2.0 * (bx * bx + by * by);
+          const double t0 = s0, t1 = s1, t2 = s2;
+          const double m00 = ((double)A00 * g00 + (double)A01 * g10 + (double)A02 * g20) * t0;
+          const double m01 = ((double)A00 * g01 + (double)A01 * g11 + (double)A02 * g21) * t1;
+          const double m02 = ((double)A00 * g02 + (double)A01 * g12 + (double)A02 * g22) * t2;
+          const double m10 = ((double)A10 * g00 + (double)A11 * g10 + (double)A12 * g20) * t0;
+          const double m11 = ((double)A10 * g01 + (double)A11 * g11 + (double)A12 * g21) * t1;
+          const double m12 = ((double)A10 * g02 + (double)A11 * g12 + (double)A12 * g22) * t2;
+          const double m20 = ((double)A20 * g00 + (double)A21 * g10 + (double)A22 * g20) * t0;
+          const double m21 = ((double)A20 * g01 + (double)A21 * g11 + (double)A22 * g21) * t1;
+          const double m22 = ((double)A20 * g02 + (double)A21 * g12 + (double)A22 * g22) * t2;
+          double e00 = m00 * m00 + m01 * m01 + m02 * m02, e01 = m00 * m10 + m01 * m11 + m02 * m12;
+          double e02 = m00 * m20 + m01 * m21 + m02 * m22, e11 = m10 * m10 + m11 * m11 + m12 * m12;
+          double e12 = m10 * m20 + m11 * m21 + m12 * m22, e22 = m20 * m20 + m21 * m21 + m22 * m22;
+          double z00, z01, z02, z10, z11, z12, z20, z21, z22;
+          jacobi_solve3(e00, e01, e02, e11, e12, e22, z00, z01, z02, z10, z11, z12, z20, z21, z22);
+          if (e00 > e11) MGS_SWAP_PAIR(e00, e11, z00, z10, z20, z01, z11, z21);       // ascending
+          if (e11 > e22) MGS_SWAP_PAIR(e11, e22, z01, z11, z21, z02, z12, z22);
+          if (e00 > e11) MGS_SWAP_PAIR(e00, e11, z00, z10, z20, z01, z11, z21);
+          const double detz = z00 * (z11 * z22 - z12 * z21) - z01 * (z10 * z22 - z12 * z20) + z02 * (z10 * z21 - z11 * z20);
+          if (detz < 0.0) { z02 = -z02; z12 = -z12; z22 = -z22; }
+          double aw, ax, ay, az;
+          rotmat_to_quat(z00, z01, z02, z10, z11, z12, z20, z21, z22, aw, ax, ay, az);
+          const double qn = 1.0 / sqrt(aw * aw + ax * ax + ay * ay + az * az);
+          q = make_float4((float)(aw * qn), (float)(ax * qn), (float)(ay * qn), (float)(az * qn));
+          s0 = fmaxf((float)sqrt(fmax(e00, 0.0)), FLT_MIN);
+          s1 = fmaxf((float)sqrt(fmax(e11, 0.0)), FLT_MIN);
+          s2 = fmaxf((float)sqrt(fmax(e22, 0.0)), FLT_MIN);
         }
       }
-      const float xb0 = x[0][0] + c0, xb1 = x[0][1] + c1, xb2 = x[0][2] + c2;
-      const float d00 = rest[0 * N + i], d01 = rest[1 * N + i], d02 = rest[2 * N + i];
-
-      // P^T P and its eigenpairs, descending
-      const double p00 = P00, p01 = P01, p02 = P02, p10 = P10, p11 = P11, p12 = P12, p20 = P20, p21 = P21, p22 = P22;
-      double a00 = p00 * p00 + p10 * p10 + p20 * p20, a01 = p00 * p01 + p10 * p11 + p20 * p21;
-      double a02 = p00 * p02 + p10 * p12 + p20 * p22, a11 = p01 * p01 + p11 * p11 + p21 * p21;
-      double a12 = p01 * p02 + p11 * p12 + p21 * p22, a22 = p02 * p02 + p12 * p12 + p22 * p22;
-      double v00, v01, v02, v10, v11, v12, v20, v21, v22;
-      jacobi_solve3(a00, a01, a02, a11, a12, a22, v00, v01, v02, v10, v11, v12, v20, v21, v22);
-      if (a00 < a11) MGS_SWAP_PAIR(a00, a11, v00, v10, v20, v01, v11, v21);
-      if (a11 < a22) MGS_SWAP_PAIR(a11, a22, v01, v11, v21, v02, v12, v22);
-      if (a00 < a11) MGS_SWAP_PAIR(a00, a11, v00, v10, v20, v01, v11, v21);
-      // sigma_mid < 1e-3 sigma_max  <=>  lambda_mid < 1e-6 lambda_max
-      const bool thin = (fl & kFlagThin) || !(a00 > 0.0) || a11 < kDegenerate * kDegenerate * a00;
-
-      bool rigid = mode == 0;
-      float A00 = 0.f, A01 = 0.f, A02 = 0.f, A10 = 0.f, A11 = 0.f, A12 = 0.f, A20 = 0.f, A21 = 0.f, A22 = 0.f;
-      if (thin) {
-        st = kStatusThin;
-        mu0 = xb0 + d00; mu1 = xb1 + d01; mu2 = xb2 + d02;
-      } else if (!rigid) {
-        if (fl & kFlagFlat) {
-          rigid = true;
-        } else {                                    // A = P Q^-1 in fp32
-          const float ixx = rest[3 * N + i], ixy = rest[4 * N + i], ixz = rest[5 * N + i];
-          const float iyy = rest[6 * N + i], iyz = rest[7 * N + i], izz = rest[8 * N + i];
-          A00 = __builtin_fmaf(P02, ixz, __builtin_fmaf(P01, ixy, P00 * ixx));
-          A01 = __builtin_fmaf(P02, iyz, __builtin_fmaf(P01, iyy, P00 * ixy));
-          A02 = __builtin_fmaf(P02, izz, __builtin_fmaf(P01, iyz, P00 * ixz));
-          A10 = __builtin_fmaf(P12, ixz, __builtin_fmaf(P11, ixy, P10 * ixx));
-          A11 = __builtin_fmaf(P12, iyz, __builtin_fmaf(P11, iyy, P10 * ixy));
-          A12 = __builtin_fmaf(P12, izz, __builtin_fmaf(P11, iyz, P10 * ixz));
-          A20 = __builtin_fmaf(P22, ixz, __builtin_fmaf(P21, ixy, P20 * ixx));
-          A21 = __builtin_fmaf(P22, iyz, __builtin_fmaf(P21, iyy, P20 * ixy));
-          A22 = __builtin_fmaf(P22, izz, __builtin_fmaf(P21, iyz, P20 * ixz));
-          const double det = (double)A00 * ((double)A11 * A22 - (double)A12 * A21)
-                             - (double)A01 * ((double)A10 * A22 - (double)A12 * A20)
-                             + (double)A02 * ((double)A10 * A21 - (double)A11 * A20);
-          if (!(det > 0.0)) rigid = true;
-        }
-        if (rigid) st = kStatusFallback;
+    }
+    out_means[3 * i + 0] = mu0; out_means[3 * i + 1] = mu1; out_means[3 * i + 2] = mu2;
+    reinterpret_cast<float4*>(out_quats)[i] = q;
+    out_scales[3 * i + 0] = s0; out_scales[3 * i + 1] = s1; out_scales[3 * i + 2] = s2;
+    if (status) status[i] = (uint8_t)st;
+  }
+  if constexpr (SH) {
+    __shared__ float4 lds[STAGED ? kShWaveSlots : 1];
+    const bool turn = row == kRowRotate && sh_degree >= 1;
+    // rows of bound Gaussians are always written, rotated or copied; rows of unbound ones only on request
+    const bool wr = live && (row != kRowUnbound || copy_unbound);
+    const unsigned long long need = ballot(wr);
+    if (need == 0ull) return;                                    // the whole workgroup: it is one wave
+    const int g0 = (int)((long long)blockIdx.x * kGroup);
+    const int kc = (sh_degree + 1) * (sh_degree + 1) - 1;        // coefficients above the DC term
+    float* rowp;                                                 // this lane's 16 x rgb (or shorter) row
+    if constexpr (STAGED) {
+      sh_rows_to_lds(sh_in, g0, n, need, lds);
+      __syncthreads();
+      rowp = reinterpret_cast<float*>(lds + threadIdx.x * kShPitchF4);
+    } else {
+      rowp = const_cast<float*>(sh_in) + (size_t)(live ? i : 0) * stride_f;
+    }
+    float c[15 * 3], o[15 * 3];
+#pragma unroll
+    for (int k = 0; k < 45; ++k) c[k] = (wr && k < kc * 3) ? rowp[3 + k] : 0.f;
+#pragma unroll
+    for (int k = 0; k < 45; ++k) o[k] = c[k];
+    if (turn) {
+      // degree 1: coefficients 1..3 (c[0..8]), degree 2: 4..8 (c[9..23]), degree 3: 9..15 (c[24..44])
+      sh_rotate_band1(Rf, c, o);
+      if (sh_degree >= 2) sh_rotate_band<2>(Rf, c + 9, o + 9);
+      if (sh_degree >= 3) sh_rotate_band<3>(Rf, c + 24, o + 24);
+    }
+    if constexpr (STAGED) {
+      if (turn) {
+#pragma unroll
+        for (int k = 0; k < 45; ++k)
+          if (k < kc * 3) rowp[3 + k] = o[k];
       }
-
-      if (!thin && rigid) {
-        // u1 = P v1 / sigma1, u2 = P v2 made orthonormal to u1, u3 = u1 x u2, v3 = v1 x v2, R = sum u_k v_k^T
-        const double is1 = 1.0 / sqrt(a00);
-        const double u10 = (p00 * v00 + p01 * v10 + p02 * v20) * is1, u11 = (p10 * v00 + p11 * v10 + p12 * v20) * is1;
-        const double u12 = (p20 * v00 + p21 * v10 + p22 * v20) * is1;
-        double u20 = p00 * v01 + p01 * v11 + p02 * v21, u21 = p10 * v01 + p11 * v11 + p12 * v21;
-        double u22 = p20 * v01 + p21 * v11 + p22 * v21;
-        const double dot = u10 * u20 + u11 * u21 + u12 * u22;
-        u20 -= dot * u10; u21 -= dot * u11; u22 -= dot * u12;
-        const double in2 = 1.0 / sqrt(u20 * u20 + u21 * u21 + u22 * u22);
-        u20 *= in2; u21 *= in2; u22 *= in2;
-        const double u30 = u11 * u22 - u12 * u21, u31 = u12 * u20 - u10 * u22, u32 = u10 * u21 - u11 * u20;
-        const double w0 = v10 * v21 - v20 * v11, w1 = v20 * v01 - v00 * v21, w2 = v00 * v11 - v10 * v01;   // v3 = v1 x v2
-        const double r00 = u10 * v00 + u20 * v01 + u30 * w0, r01 = u10 * v10 + u20 * v11 + u30 * w1;
-        const double r02 = u10 * v20 + u20 * v21 + u30 * w2, r10 = u11 * v00 + u21 * v01 + u31 * w0;
-        const double r11 = u11 * v10 + u21 * v11 + u31 * w1, r12 = u11 * v20 + u21 * v21 + u31 * w2;
-        const double r20 = u12 * v00 + u22 * v01 + u32 * w0, r21 = u12 * v10 + u22 * v11 + u32 * w1;
-        const double r22 = u12 * v20 + u22 * v21 + u32 * w2;
-        mu0 = (float)((double)xb0 + (r00 * d00 + r01 * d01 + r02 * d02));
-        mu1 = (float)((double)xb1 + (r10 * d00 + r11 * d01 + r12 * d02));
-        mu2 = (float)((double)xb2 + (r20 * d00 + r21 * d01 + r22 * d02));
-        double aw, ax, ay, az;
-        rotmat_to_quat(r00, r01, r02, r10, r11, r12, r20, r21, r22, aw, ax, ay, az);
-        const double bw = q.x, bx = q.y, by = q.z, bz = q.w;
-        const double ow = aw * bw - ax * bx - ay * by - az * bz, ox = aw * bx + ax * bw + ay * bz - az * by;
-        const double oy = aw * by - ax * bz + ay * bw + az * bx, oz = aw * bz + ax * by - ay * bx + az * bw;
-        const double inv = 1.0 / sqrt(ow * ow + ox * ox + oy * oy + oz * oz);
-        q = make_float4((float)(ow * inv), (float)(ox * inv), (float)(oy * inv), (float)(oz * inv));
-      } else if (!thin) {
-        mu0 = xb0 + __builtin_fmaf(A02, d02, __builtin_fmaf(A01, d01, A00 * d00));
-        mu1 = xb1 + __builtin_fmaf(A12, d02, __builtin_fmaf(A11, d01, A10 * d00));
-        mu2 = xb2 + __builtin_fmaf(A22, d02, __builtin_fmaf(A21, d01, A20 * d00));
-        // M = A R(q) diag(s), Sigma' = M M^T
-        double bw = q.x, bx = q.y, by = q.z, bz = q.w;
-        const double inv = 1.0 / sqrt(bw * bw + bx * bx + by * by + bz * bz);
-        bw *= inv; bx *= inv; by *= inv; bz *= inv;
-        const double g00 = 1.0 - 2.0 * (by * by + bz * bz), g01 = 2.0 * (bx * by - bw * bz), g02 = 2.0 * (bx * bz + bw * by);
-        const double g10 = 2.0 * (bx * by + bw * bz), g11 = 1.0 - 2.0 * (bx * bx + bz * bz), g12 = 2.0 * (by * bz - bw * bx);
-        const double g20 = 2.0 * (bx * bz - bw * by), g21 = 2.0 * (by * bz + bw * bx), g22 = 1.0 - 2.0 * (bx * bx + by * by);
-        const double t0 = s0, t1 = s1, t2 = s2;
-        const double m00 = ((double)A00 * g00 + (double)A01 * g10 + (double)A02 * g20) * t0;
-        const double m01 = ((double)A00 * g01 + (double)A01 * g11 + (double)A02 * g21) * t1;
-        const double m02 = ((double)A00 * g02 + (double)A01 * g12 + (double)A02 * g22) * t2;
-        const double m10 = ((double)A10 * g00 + (double)A11 * g10 + (double)A12 * g20) * t0;
-        const double m11 = ((double)A10 * g01 + (double)A11 * g11 + (double)A12 * g21) * t1;
-        const double m12 = ((double)A10 * g02 + (double)A11 * g12 + (double)A12 * g22) * t2;
-        const double m20 = ((double)A20 * g00 + (double)A21 * g10 + (double)A22 * g20) * t0;
-        const double m21 = ((double)A20 * g01 + (double)A21 * g11 + (double)A22 * g21) * t1;
-        const double m22 = ((double)A20 * g02 + (double)A21 * g12 + (double)A22 * g22) * t2;
-        double e00 = m00 * m00 + m01 * m01 + m02 * m02, e01 = m00 * m10 + m01 * m11 + m02 * m12;
-        double e02 = m00 * m20 + m01 * m21 + m02 * m22, e11 = m10 * m10 + m11 * m11 + m12 * m12;
-        double e12 = m10 * m20 + m11 * m21 + m12 * m22, e22 = m20 * m20 + m21 * m21 + m22 * m22;
-        double z00, z01, z02, z10, z11, z12, z20, z21, z22;
-        jacobi_solve3(e00, e01, e02, e11, e12, e22, z00, z01, z02, z10, z11, z12, z20, z21, z22);
-        if (e00 > e11) MGS_SWAP_PAIR(e00, e11, z00, z10, z20, z01, z11, z21);       // ascending
-        if (e11 > e22) MGS_SWAP_PAIR(e11, e22, z01, z11, z21, z02, z12, z22);
-        if (e00 > e11) MGS_SWAP_PAIR(e00, e11, z00, z10, z20, z01, z11, z21);
-        const double detz = z00 * (z11 * z22 - z12 * z21) - z01 * (z10 * z22 - z12 * z20) + z02 * (z10 * z21 - z11 * z20);
-        if (detz < 0.0) { z02 = -z02; z12 = -z12; z22 = -z22; }
-        double aw, ax, ay, az;
-        rotmat_to_quat(z00, z01, z02, z10, z11, z12, z20, z21, z22, aw, ax, ay, az);
-        const double qn = 1.0 / sqrt(aw * aw + ax * ax + ay * ay + az * az);
-        q = make_float4((float)(aw * qn), (float)(ax * qn), (float)(ay * qn), (float)(az * qn));
-        s0 = fmaxf((float)sqrt(fmax(e00, 0.0)), FLT_MIN);
-        s1 = fmaxf((float)sqrt(fmax(e11, 0.0)), FLT_MIN);
-        s2 = fmaxf((float)sqrt(fmax(e22, 0.0)), FLT_MIN);
+      __syncthreads();
+      // lane-linear write-back of the rows that were fetched
+      float4* dst = reinterpret_cast<float4*>(sh_out + (size_t)g0 * 48);
+#pragma unroll
+      for (int r = 0; r < kShRowF4; ++r) {
+        const unsigned f = r * kShWave + threadIdx.x, owner = f / kShRowF4;
+        if (((need >> owner) & 1ull) && g0 + (int)owner < n) dst[f] = lds[owner * kShPitchF4 + (f - owner * kShRowF4)];
       }
+    } else if (wr) {
+      float* dst = sh_out + (size_t)i * stride_f;
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) dst[ch] = rowp[ch];         // the DC term
+#pragma unroll
+      for (int k = 0; k < 45; ++k)
+        if (k < kc * 3) dst[3 + k] = o[k];
+      for (int k = 3 + kc * 3; k < stride_f; ++k) dst[k] = rowp[k];   // coefficients above the active degree
     }
   }
-  out_means[3 * i + 0] = mu0; out_means[3 * i + 1] = mu1; out_means[3 * i + 2] = mu2;
-  reinterpret_cast<float4*>(out_quats)[i] = q;
-  out_scales[3 * i + 0] = s0; out_scales[3 * i + 1] = s1; out_scales[3 * i + 2] = s2;
-  if (status) status[i] = (uint8_t)st;
 }
 
 #undef MGS_SWAP_PAIR
+#undef MGS_STORE_ROTATION
+#undef MGS_SHAPE_ROTATION
 
 size_t bind_workspace_bytes(int n) {
   Bump b(1);
@@ -440,7 +539,37 @@ extern "C" int mgs_deform_apply(int n, const float* means, const float* quats, c
   MGS_REQUIRE(particles_now, "deform_apply: particles_now is null");
   MGS_REQUIRE(out_means && out_quats && out_scales, "deform_apply: an output is null");
   const dim3 grid(div_up((unsigned)n, (unsigned)kDeformGroup)), block(kDeformGroup);
-  hipLaunchKernelGGL(deform_apply_kernel, grid, block, 0, (hipStream_t)stream, n, means, quats, scales, idx, w, p, rest,
-                     flags, mode, m, particles_now, out_means, out_quats, out_scales, status);
+  hipLaunchKernelGGL((deform_apply_kernel<false, false>), grid, block, 0, (hipStream_t)stream, n, means, quats, scales, idx,
+                     w, p, rest, flags, mode, m, particles_now, out_means, out_quats, out_scales, status, 0, 0,
+                     (const float*)nullptr, (float*)nullptr, 0);
   return check_launch("deform_apply");
+}
+
+extern "C" int mgs_deform_apply_sh(int n, const float* means, const float* quats, const float* scales, const int32_t* idx,
+                                   const float* w, const float* p, const float* rest, const uint8_t* flags, int mode, int m,
+                                   const float* particles_now, float* out_means, float* out_quats, float* out_scales,
+                                   uint8_t* status, int sh_degree, int coeff_stride, const float* sh_coeffs, float* out_sh,
+                                   int copy_unbound, mgs_stream_t stream) {
+  MGS_REQUIRE(n >= 0, "deform_apply_sh: n %d is negative", n);
+  MGS_REQUIRE(m >= kK, "deform_apply_sh: m %d particles, at least %d needed", m, kK);
+  MGS_REQUIRE(mode == 0 || mode == 1, "deform_apply_sh: mode %d is neither 0 (rigid) nor 1 (affine)", mode);
+  MGS_REQUIRE(sh_degree >= 0 && sh_degree <= 3, "deform_apply_sh: sh_degree %d is outside 0..3", sh_degree);
+  MGS_REQUIRE(coeff_stride >= (sh_degree + 1) * (sh_degree + 1),
+              "deform_apply_sh: rows of %d coefficients cannot hold the %d of degree %d", coeff_stride,
+              (sh_degree + 1) * (sh_degree + 1), sh_degree);
+  if (n == 0) return MGS_OK;
+  MGS_REQUIRE(means && quats && scales, "deform_apply_sh: means, quats or scales is null");
+  MGS_REQUIRE(idx && w && p && rest && flags, "deform_apply_sh: a binding array (idx, w, p, rest, flags) is null");
+  MGS_REQUIRE(particles_now, "deform_apply_sh: particles_now is null");
+  MGS_REQUIRE(out_means && out_quats && out_scales, "deform_apply_sh: an output is null");
+  MGS_REQUIRE(sh_coeffs && out_sh, "deform_apply_sh: sh_coeffs or out_sh is null");
+  MGS_REQUIRE(out_sh != sh_coeffs, "deform_apply_sh: out_sh is sh_coeffs (the rest rows must survive: every frame turns them anew)");
+  const dim3 grid(div_up((unsigned)n, (unsigned)kDeformShGroup)), block(kDeformShGroup);
+  const int stride_f = coeff_stride * 3;
+  with_bool(coeff_stride == 16, [&](auto staged) {
+    hipLaunchKernelGGL((deform_apply_kernel<true, decltype(staged)::value>), grid, block, 0, (hipStream_t)stream, n, means,
+                       quats, scales, idx, w, p, rest, flags, mode, m, particles_now, out_means, out_quats, out_scales,
+                       status, sh_degree, stride_f, sh_coeffs, out_sh, copy_unbound != 0);
+  });
+  return check_launch("deform_apply_sh");
 }

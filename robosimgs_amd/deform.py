@@ -11,7 +11,13 @@ to the lower index) and stores weights, weighted rest offsets and the neighbourh
 matching (Mueller et al. 2005), mode "affine" also stretches it, Sigma' = A Sigma A^T (PhysGaussian).  Stateless,
 capturable, nothing is read back, no floating-point atomics: the same inputs give the same bytes.  Opacities and colours
 are shared with the input and SH rows are not rotated: what transform_gaussians(rotate_sh=False) gives.
-`FrameRenderer(deform=binding)` runs it inside every slot's graph (pipeline.py).
+
+    posed = deform_gaussians(tensors, binding, particles_now, rotate_sh=True, out=posed)     # colours turn too
+
+rotate_sh=True (include/mgs_deform_sh.h) turns every Gaussian's SH rows by the rotation its rigid branch applies -- in both
+modes, so an affine frame has the colours of a rigid one -- in the same launch; the result then owns a `colors` tensor
+(192 bytes per Gaussian at degree 3).  Rows of thin, unbound and non-finite Gaussians are the rest rows bit for bit.
+`FrameRenderer(deform=binding[, deform_rotate_sh=True])` runs it inside every slot's graph (pipeline.py).
 """
 from __future__ import annotations
 
@@ -116,6 +122,25 @@ def deform_apply_raw(means: Tensor, quats: Tensor, scales: Tensor, binding: Part
                                       stream_handle()), "mgs_deform_apply")
 
 
+def deform_apply_sh_raw(means: Tensor, quats: Tensor, scales: Tensor, binding: ParticleBinding, mode: int, particles: Tensor,
+                        out_means: Tensor, out_quats: Tensor, out_scales: Tensor, sh_degree: int, colors: Tensor,
+                        out_colors: Tensor, copy_unbound: bool = True, status: Optional[Tensor] = None) -> None:
+    """mgs_deform_apply_sh on torch's current stream: deform_apply_raw that also turns the SH rows, one launch, no
+    workspace, capturable.  colors and out_colors: float32 [n,K,3], contiguous, different buffers, K >= (sh_degree + 1)^2.
+    copy_unbound=False leaves the rows of unbound Gaussians in out_colors as they are."""
+    require_device(means, quats, scales, particles, out_means, out_quats, out_scales, status, binding.idx, colors, out_colors)
+    for t, what in ((colors, "colors"), (out_colors, "out_colors")):
+        if t.dim() != 3 or t.shape[0] != binding.n or t.shape[2] != 3 or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"{what} must be a contiguous float32 tensor [{binding.n},K,3], got {t.dtype} {list(t.shape)}")
+    if out_colors.shape != colors.shape:
+        raise ValueError(f"out_colors {list(out_colors.shape)} is not the shape of colors {list(colors.shape)}")
+    check(_lib.lib().mgs_deform_apply_sh(binding.n, ptr(means), ptr(quats), ptr(scales), ptr(binding.idx), ptr(binding.w),
+                                         ptr(binding.p), ptr(binding.rest), ptr(binding.flags), int(mode), binding.m,
+                                         ptr(particles), ptr(out_means), ptr(out_quats), ptr(out_scales), ptr(status),
+                                         int(sh_degree), int(colors.shape[1]), ptr(colors), ptr(out_colors),
+                                         int(bool(copy_unbound)), stream_handle()), "mgs_deform_apply_sh")
+
+
 @torch.no_grad()
 def bind_particles(means: Tensor, particles: Tensor, select: Optional[Tensor] = None,
                    max_distance: float = math.inf) -> ParticleBinding:
@@ -145,12 +170,18 @@ def bind_particles(means: Tensor, particles: Tensor, select: Optional[Tensor] = 
 
 @torch.no_grad()
 def deform_gaussians(tensors: Dict, binding: ParticleBinding, particles: Tensor, mode: str = "rigid",
-                     out: Optional[Dict] = None, status: Optional[Tensor] = None) -> Dict:
+                     out: Optional[Dict] = None, status: Optional[Tensor] = None, rotate_sh: bool = False,
+                     copy_unbound: bool = True) -> Dict:
     """Move the Gaussians of `tensors` (the REST state: dict(means, quats, scales, opacities, colors, sh_degree) on the GPU,
     scales activated) with the particles' current positions [M,3].  The dictionary contract of transform_gaussians: returns
     a new dict that shares `opacities` and `colors`; pass out=<previous result> to reuse its buffers every frame.
     out=tensors is refused: the rest state must survive, every frame deforms it anew.  status: uint8 [N], receives per
-    Gaussian 0 or the STATUS_* bits (unbound, affine fell back to rigid, thin: translated only, a neighbour was non-finite)."""
+    Gaussian 0 or the STATUS_* bits (unbound, affine fell back to rigid, thin: translated only, a neighbour was non-finite).
+    rotate_sh=True, with colors [N,K,3], K >= (sh_degree + 1)^2 and sh_degree >= 1: every Gaussian's SH rows turn with it
+    (mgs_deform_apply_sh, the same single launch) and the result has a `colors` tensor of its own: out["colors"] where it
+    has the right shape and is not the rest state's buffer (a previous rotate_sh=False result shares the rest's colours),
+    a new tensor otherwise.  copy_unbound=False then leaves the rows of unbound Gaussians in that tensor as they are (a
+    caller that filled them once); bound rows are always rewritten.  Otherwise the call is the one without SH."""
     if mode not in MODES:
         raise ValueError(f"mode {mode!r} not in {tuple(MODES)}")
     if out is tensors and out is not None:
@@ -163,7 +194,11 @@ def deform_gaussians(tensors: Dict, binding: ParticleBinding, particles: Tensor,
     _particles(particles, binding.m, "particles")
     if status is not None and (status.dtype != torch.uint8 or tuple(status.shape) != (n,) or not status.is_contiguous()):
         raise ValueError(f"status must be a contiguous uint8 tensor [{n}]")
-    require_device(means, particles, status)
+    colors, deg = tensors["colors"], int(tensors.get("sh_degree") or 0)
+    do_sh = bool(rotate_sh) and torch.is_tensor(colors) and colors.dim() == 3 and colors.shape[1] >= (deg + 1) ** 2 and deg >= 1
+    if do_sh and (colors.shape[0] != n or colors.shape[2] != 3 or not colors.dtype.is_floating_point):
+        raise ValueError(f"colors must be [{n},K,3], got {colors.dtype} {list(colors.shape)}")
+    require_device(means, particles, status, colors if do_sh else None)
     means, quats, scales, x = _f32c(means), _f32c(quats), _f32c(scales), _f32c(particles)
     res = out if out is not None else {}
     outs = []
@@ -176,11 +211,21 @@ def deform_gaussians(tensors: Dict, binding: ParticleBinding, particles: Tensor,
         elif o.data_ptr() == src.data_ptr():
             raise ValueError(f"out[{key!r}] is the rest state's own buffer: the rest state must survive")
         outs.append(o)
-    deform_apply_raw(means, quats, scales, binding, MODES[mode], x, *outs, status=status)
+    if do_sh:
+        sh_in = _f32c(colors)
+        o = res.get("colors")
+        if (not torch.is_tensor(o) or o.dtype != torch.float32 or o.shape != sh_in.shape or not o.is_contiguous()
+                or not o.is_cuda or o.data_ptr() == sh_in.data_ptr() or o.data_ptr() == colors.data_ptr()):
+            o = torch.empty_like(sh_in)
+            copy_unbound = True                      # nobody has filled a fresh tensor's unbound rows
+        deform_apply_sh_raw(means, quats, scales, binding, MODES[mode], x, *outs, deg, sh_in, o, copy_unbound, status=status)
+        colors = o
+    else:
+        deform_apply_raw(means, quats, scales, binding, MODES[mode], x, *outs, status=status)
     return {"means": outs[0], "quats": outs[1], "scales": outs[2], "opacities": tensors["opacities"],
-            "colors": tensors["colors"], "sh_degree": tensors.get("sh_degree")}
+            "colors": colors, "sh_degree": tensors.get("sh_degree")}
 
 
-__all__ = ["ParticleBinding", "bind_particles", "deform_gaussians", "deform_bind_raw", "deform_apply_raw",
+__all__ = ["ParticleBinding", "bind_particles", "deform_gaussians", "deform_bind_raw", "deform_apply_raw", "deform_apply_sh_raw",
            "bind_workspace_bytes", "MODES", "REST_ROWS", "FLAG_UNBOUND", "FLAG_FLAT", "FLAG_THIN", "STATUS_UNBOUND",
            "STATUS_FALLBACK", "STATUS_THIN", "STATUS_NONFINITE"]

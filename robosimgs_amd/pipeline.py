@@ -106,7 +106,8 @@ class FrameRenderer:
                  sizing_camera=None, group_ids: Optional[torch.Tensor] = None, n_groups: int = 0,
                  rotate_sh: bool = True, reorder: Optional[str] = "morton", dataset_output=None, dataset_K=None,
                  dataset_keep_float: bool = False, class_ids: Optional[torch.Tensor] = None, n_classes: Optional[int] = None,
-                 labels: bool = False, distortion=None, deform=None, deform_mode: str = "rigid", **raster_kw):
+                 labels: bool = False, distortion=None, deform=None, deform_mode: str = "rigid",
+                 deform_rotate_sh: bool = False, **raster_kw):
         """tensors: dict(means, quats, scales, opacities, colors, sh_degree) on the GPU
         (Gaussians.to_torch()); `self.t` is the renderer's own (by default Morton-ordered) copy.  isect_capacity: slots reserved for tile intersections per
         frame; if None it is measured once with `sizing_camera` = (viewmat, K) (required then)
@@ -143,6 +144,12 @@ class FrameRenderer:
         mgs_deform_apply(rest state -> the slot's posed copy); submit(..., particles=) overwrites the buffer for that frame,
         and fetch() also returns "deform_status" (uint8 [N], the renderer's own index order).  With group_ids as well the
         group transform then runs on that copy: the two must move disjoint Gaussians (every bound Gaussian has group id -1).
+        deform_rotate_sh=True (scenes of SH degree >= 1): the slot's graph starts with mgs_deform_apply_sh instead, which
+        also turns every bound Gaussian's SH rows with it (deform_gaussians(rotate_sh=True)).  Every slot then owns a copy
+        of the colours, cloned from the rest rows at construction: 192 MB per slot at 1 M Gaussians of degree 3, the same
+        as with group_ids.  Without group_ids the rows of unbound Gaussians in that copy are never rewritten; with
+        group_ids they are copied from the rest rows every frame, because the group transform then turns its rows in
+        place on that copy and must not find last frame's result there.
 
         raw_params=True (forwarded to rasterization like every raster_kw): `tensors` hold log-scales and opacity logits
         (Gaussians.to_torch(raw=True)), so a loaded .ply renders without an activation pass on the host.  Static scenes
@@ -202,6 +209,9 @@ class FrameRenderer:
                 deform = deform.reordered(self.order)
         self.t = tensors
         self.deform, self.deform_mode = deform, deform_mode     # the binding in the renderer's own index order (None: rigid scene)
+        colors = tensors["colors"]
+        self.deform_rotate_sh = (bool(deform_rotate_sh) and deform is not None and int(tensors.get("sh_degree") or 0) >= 1
+                                 and colors.dim() == 3 and colors.shape[1] >= (int(tensors["sh_degree"]) + 1) ** 2)
         # the classes in the renderer's own index order (None: no label frames)
         self.class_ids = class_ids.to(torch.int32).contiguous() if class_ids is not None else None
         self.n_classes = int(n_classes) if class_ids is not None else None
@@ -298,6 +308,8 @@ class FrameRenderer:
             dfm = {"x": rest_x.clone().contiguous(), "status": torch.zeros(self.deform.n, dtype=torch.uint8, device=self.dev),
                    "t": pose["t"] if pose is not None else {k: self.t[k].to(torch.float32).clone().contiguous()
                                                             for k in ("means", "quats", "scales")}}
+            if self.deform_rotate_sh and pose is None:       # (with groups the posed copy already owns its colours)
+                dfm["t"]["colors"] = self.t["colors"].to(torch.float32).clone().contiguous()
 
         ds, ds_out = None, None
         if self.dataset_dtype is not None:          # the slot's dataset frame: [RGBA8 plane | distance plane] as bytes
@@ -317,8 +329,11 @@ class FrameRenderer:
             posed = self.t
             if dfm is not None:
                 from .deform import deform_gaussians
+                # copy_unbound: the group transform below turns its rows in place on the slot's copy, so it must find
+                # the rest rows there every frame; without groups the unbound rows of the copy never change
                 posed = deform_gaussians(self.t, self.deform, dfm["x"], mode=self.deform_mode, out=dfm["t"],
-                                         status=dfm["status"])
+                                         status=dfm["status"], rotate_sh=self.deform_rotate_sh,
+                                         copy_unbound=pose is not None)
             if pose is not None:         # (after a deformation: in place on the slot's copy, the two move disjoint Gaussians)
                 from .transform import transform_gaussians
                 posed = transform_gaussians(posed, group_ids=self.group_ids, rotate_sh=self.rotate_sh,

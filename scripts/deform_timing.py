@@ -6,15 +6,20 @@ Gaussians of which 200 k (the soft object, `select`) are bound to 50 k particles
            instruction per 2 cycles on each of 256 x 4 SIMDs at 2.4 GHz)
   apply    mgs_deform_apply, rigid and affine, over the whole scene (unbound Gaussians pass through); "needed" = the bytes
            the algorithm moves, from the shapes, and their share of the MI355X's 8 TB/s
+  + SH     mgs_deform_apply_sh (include/mgs_deform_sh.h), degree 3, copy_unbound = 0: 384 B more per bound Gaussian (its
+           192-byte row read and written).  --parent-lib <libmgs.so of the parent commit>: that build's mgs_deform_apply
+           alternates with this one's in the same loop (the path without SH must not have slowed).  For scale,
+           mgs_transform_gaussians (host-made matrices) on the same 200 k rows as one group, with and without SH
   torch    the only baseline there is -- the parent commit has no such path: cdist + topk in chunks, then batched moments
            and torch.linalg.svd
   frames   FrameRenderer frames per second at 1 M Gaussians, 1920 x 1080, three frames in flight, with and without deform=
 
 Device events, a warm-up, the variants alternating call by call in one process.  Needs a GPU: there is no fallback.
 
-    python scripts/deform_timing.py [--rounds 10] [--frames 120] [--out table.md] [--resources]
+    python scripts/deform_timing.py [--rounds 10] [--frames 120] [--out table.md] [--resources] [--parent-lib PATH]
 """
 import argparse
+import ctypes
 import math
 import os
 import platform
@@ -92,6 +97,7 @@ def main():
     ap.add_argument("--frames", type=int, default=120, help="frames per timed block of the FrameRenderer comparison")
     ap.add_argument("--out", default=None)
     ap.add_argument("--resources", action="store_true", help="only print the compiler's resource report (needs no GPU)")
+    ap.add_argument("--parent-lib", default=None, help="a libmgs.so built from the parent commit: its mgs_deform_apply is timed too")
     a = ap.parse_args()
     out = []
 
@@ -108,7 +114,12 @@ def main():
         return
     import numpy as np
     import torch
-    from robosimgs_amd import FrameRenderer, camera_ring, deform as D, synthetic_scene
+    from robosimgs_amd import FrameRenderer, _lib, camera_ring, deform as D, synthetic_scene, transform_gaussians
+    from robosimgs_amd.transform import pack_transforms
+    parent = None
+    if a.parent_lib:                       # (not _lib._load: the parent has no mgs_deform_apply_sh to bind)
+        parent = ctypes.CDLL(a.parent_lib)
+        parent.mgs_deform_apply.argtypes, parent.mgs_deform_apply.restype = _lib._DEFORM_SIGNATURES["mgs_deform_apply"]
 
     dev = torch.device("cuda")
     say(f"{torch.cuda.get_device_name(0)} on {platform.node()}, torch {torch.__version__}")
@@ -159,12 +170,38 @@ def main():
         st = torch.zeros(N, dtype=torch.uint8, device=dev)
         bound_t = torch_bind(soft_means, rest)
         soft_q = tensors["quats"][soft].contiguous()
+        outs_sh = dict({k: torch.empty_like(v) for k, v in outs.items()}, colors=tensors["colors"].clone())
+        gid = torch.where(soft, 0, -1).to(torch.int32)
+        ang = 0.3
+        xr = pack_transforms([[[math.cos(ang), -math.sin(ang), 0], [math.sin(ang), math.cos(ang), 0], [0, 0, 1]]], [[0.01, 0, 0]], None, 3)
+        packed = (torch.from_numpy(xr[0]).to(dev), torch.from_numpy(xr[1]).to(dev))
+        outs_t = dict(tensors, colors=tensors["colors"].clone(), **{k: torch.empty_like(v) for k, v in outs.items()})
+
+        def raw_apply(L, mode):              # mgs_deform_apply as the C ABI has it: the same call path for both builds
+            rc = L.mgs_deform_apply(N, tensors["means"].data_ptr(), tensors["quats"].data_ptr(), tensors["scales"].data_ptr(),
+                                         idx.data_ptr(), w.data_ptr(), p.data_ptr(), rs.data_ptr(), fl.data_ptr(), mode, M,
+                                         now.data_ptr(), outs["means"].data_ptr(), outs["quats"].data_ptr(),
+                                         outs["scales"].data_ptr(), st.data_ptr(), torch.cuda.current_stream().cuda_stream)
+            assert rc == 0, rc
         calls = {
             "rigid": lambda: D.deform_gaussians(tensors, binding, now, mode="rigid", out=outs, status=st),
             "affine": lambda: D.deform_gaussians(tensors, binding, now, mode="affine", out=outs, status=st),
+            "rigid + SH": lambda: D.deform_gaussians(tensors, binding, now, mode="rigid", out=outs_sh, status=st, rotate_sh=True,
+                                                     copy_unbound=False),
+            "affine + SH": lambda: D.deform_gaussians(tensors, binding, now, mode="affine", out=outs_sh, status=st, rotate_sh=True,
+                                                      copy_unbound=False),
+            "transform": lambda: transform_gaussians(tensors, group_ids=gid, rotate_sh=False, out=outs_t, packed=packed),
+            "transform + SH": lambda: transform_gaussians(outs_t, group_ids=gid, rotate_sh=True, out=outs_t, packed=packed),
             "torch rigid": lambda: torch_apply(bound_t, now, soft_q, False),
             "torch affine": lambda: torch_apply(bound_t, now, soft_q, True),
         }
+        if parent is not None:
+            # (rigid: this build follows the parent's; affine: the parent's follows this build's -- whoever runs second finds
+            # the binding arrays in the caches)
+            calls["parent rigid"] = lambda: raw_apply(parent, 0)
+            calls["this rigid"] = lambda: raw_apply(_lib.lib(), 0)
+            calls["this affine"] = lambda: raw_apply(_lib.lib(), 1)
+            calls["parent affine"] = lambda: raw_apply(parent, 1)
         for k, fn in calls.items():
             for _ in range(1 if k.startswith("torch") else 3):
                 fn()
@@ -183,6 +220,8 @@ def main():
         # reads idx 32, w 28 (rows 1..7), p 84, d0 12 (affine: + Q^-1 24) and gathers 8 positions of 12 B
         base = N * (1 + 40 + 40 + 1)
         need = {"rigid": base + n_soft * (32 + 28 + 84 + 12 + 96), "affine": base + n_soft * (32 + 28 + 84 + 36 + 96)}
+        for k in ("rigid", "affine"):                                          # a bound Gaussian's 192-byte row, read and written
+            need[k + " + SH"] = need[k] + n_soft * 384
         say()
         say(f"{label}:")
         say("| apply | us (min .. max) | needed | share of 8 TB/s | composed from torch ops, us | status: deformed / unbound / fell back / thin |")
@@ -192,6 +231,23 @@ def main():
             s = status[k]
             say(f"| {k} | {med:.1f} ({min(t[k]):.1f} .. {max(t[k]):.1f}) | {need[k] / 1e6:.0f} MB | {need[k] / (med * 1e-6) / HBM:.1%} | "
                 f"{statistics.median(t['torch ' + k]):.0f} | {s[0]} / {s[1]} / {s[2]} / {s[4]} |")
+        for k in ("rigid + SH", "affine + SH"):
+            med = statistics.median(t[k])
+            say(f"| {k} | {med:.1f} ({min(t[k]):.1f} .. {max(t[k]):.1f}) | {need[k] / 1e6:.0f} MB | {need[k] / (med * 1e-6) / HBM:.1%} | | |")
+        for k in ("parent rigid", "parent affine"):
+            if k in t:
+                own = t["this " + k.split()[1]]
+                say(f"| {k} (mgs_deform_apply of the parent commit's build, called through ctypes) | {statistics.median(t[k]):.1f} "
+                    f"({min(t[k]):.1f} .. {max(t[k]):.1f}) | | | | this build's, called the same way: {statistics.median(own):.1f} "
+                    f"({min(own):.1f} .. {max(own):.1f}), median "
+                    f"{'ABOVE' if statistics.median(own) > max(t[k]) else 'below' if statistics.median(own) < min(t[k]) else 'inside'} "
+                    f"the parent's spread |")
+        md = {k: statistics.median(t[k]) for k in t}
+        say(f"| mgs_transform_gaussians, the same {n_soft} rows as one group | {md['transform']:.1f} ({min(t['transform']):.1f} .. "
+            f"{max(t['transform']):.1f}) | | | | + SH (in place, host-made matrices): {md['transform + SH']:.1f} "
+            f"({min(t['transform + SH']):.1f} .. {max(t['transform + SH']):.1f}) |")
+        say(f"SH - no SH: deform rigid {md['rigid + SH'] - md['rigid']:+.1f} us, deform affine {md['affine + SH'] - md['affine']:+.1f} us, "
+            f"transform {md['transform + SH'] - md['transform']:+.1f} us")
 
         return binding
 
@@ -208,7 +264,8 @@ def main():
     cams = camera_ring(a.frames, W, H)
     packed = [FrameRenderer.pack_camera(c.viewmat(), c.K) for c in cams]
     kw = dict(render_mode="RGB", frames_in_flight=3, sizing_camera=(cams[0].viewmat(), cams[0].K), capacity_margin=2.0)
-    renderers = {"static": FrameRenderer(tensors, W, H, **kw), "deform": FrameRenderer(tensors, W, H, deform=binding, **kw)}
+    renderers = {"static": FrameRenderer(tensors, W, H, **kw), "deform": FrameRenderer(tensors, W, H, deform=binding, **kw),
+                 "deform + SH": FrameRenderer(tensors, W, H, deform=binding, deform_rotate_sh=True, **kw)}
     feeds = [(rest + 0.01 * torch.sin(7.0 * rest.roll(1, 1) + 0.1 * k)).contiguous() for k in range(8)]
 
     def block(name):
@@ -218,7 +275,7 @@ def main():
         t0 = time.perf_counter()
         for _ in range(a.frames):
             while nxt < a.frames and len(tickets) < r.n_slots:
-                extra = dict(particles=feeds[nxt % len(feeds)]) if name == "deform" else {}
+                extra = dict(particles=feeds[nxt % len(feeds)]) if name.startswith("deform") else {}
                 tickets.append(r.submit(packed[nxt], None, **extra))
                 nxt += 1
             tk = tickets.pop(0)
