@@ -17,6 +17,7 @@ _DEVICE_API = {"rasterization", "render", "check_isect_status", "fully_fused_pro
                "spherical_harmonics", "isect_tiles", "isect_offset_encode",
                "rasterize_to_pixels", "rasterize_labels", "rasterize_votes", "assign_classes", "lift_labels",
                "fit_hinge", "fit_hinge_points", "pose_gaussians", "bind_particles", "deform_gaussians",
+               "rasterize_mesh", "mesh_vertices", "mesh_raster", "mesh_resolve",
                "render_sharded", "gather_frames"}
 
 
@@ -54,6 +55,9 @@ def __getattr__(name):  # lazy: keeps `import robosimgs_amd` torch-free for host
     if name == "Mesh":
         from . import mesh
         return mesh.Mesh
+    if name in ("rasterize_mesh", "MeshRenderer", "mesh_vertices", "mesh_raster", "mesh_resolve", "mesh_workspace_bytes"):
+        from . import mesh_render
+        return getattr(mesh_render, name)
     if name in ("l1_loss", "l1_ssim_loss", "ssim", "unit_gradient"):
         from . import losses
         return getattr(losses, name)

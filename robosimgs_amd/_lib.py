@@ -134,6 +134,15 @@ _DEFORM_SIGNATURES = {
 _DEFORM_SH_SIGNATURES = {
     "mgs_deform_apply_sh": (_DEFORM_SIGNATURES["mgs_deform_apply"][0][:-1] + [i, i, p, p, i, p], c_int),
 }
+# every function include/mgs_mesh.h declares (the same libraries again): the workspace size is a query of its own; link_ids,
+# scales, the colours and normals are nullable
+_MESH_SIGNATURES = {
+    "mgs_mesh_workspace_bytes": ([i, i, i, i, i, POINTER(c_size_t)], c_int),
+    "mgs_mesh_vertices": ([i, i, p, p, i, p, p, p, p, p, p], c_int),
+    "mgs_mesh_raster": ([i, i, p, i, p, p, i, i, f, f, i, p, c_size_t, p], c_int),
+    "mgs_mesh_resolve": ([i, i, p, i, p, p, p, p, i, i, i, f, p, c_size_t, p, p, p, p, p], c_int),
+    "mgs_rasterize_mesh": ([i, i, p, p, i, p, p, p, p, p, i, p, p, p, i, i, f, f, i, i, f, p, c_size_t, p, p, p, p, p, p], c_int),
+}
 del p, i, f, u32, img
 EXPORTS = list(_SIGNATURES)
 OPTIM_EXPORTS = list(_OPTIM_SIGNATURES)
@@ -144,6 +153,8 @@ HINGE_EXPORTS = list(_HINGE_SIGNATURES)
 POSE_EXPORTS = list(_POSE_SIGNATURES)
 DEFORM_EXPORTS = list(_DEFORM_SIGNATURES)
 DEFORM_SH_EXPORTS = list(_DEFORM_SH_SIGNATURES)
+MESH_EXPORTS = list(_MESH_SIGNATURES)
+MESH_MAX_SIDE, MESH_LARGE_BLOCKS = 16368, 15   # MGS_MESH_MAX_SIDE, MGS_MESH_LARGE_BLOCKS
 DEFORM_K = 8                                # MGS_DEFORM_K
 LABEL_NONE, LABELS_MAX_CLASSES = 255, 32    # MGS_LABEL_NONE, MGS_LABELS_MAX_CLASSES
 
@@ -168,7 +179,8 @@ def _load(path: str = None, hooks: bool = False) -> ctypes.CDLL:
     for name, (argtypes, restype) in (*_SIGNATURES.items(), *_OPTIM_SIGNATURES.items(), *_REFINE_SIGNATURES.items(),
                                       *_LABEL_SIGNATURES.items(), *_LIFT_SIGNATURES.items(),
                                       *_HINGE_SIGNATURES.items(), *_POSE_SIGNATURES.items(),
-                                      *_DEFORM_SIGNATURES.items(), *_DEFORM_SH_SIGNATURES.items()):
+                                      *_DEFORM_SIGNATURES.items(), *_DEFORM_SH_SIGNATURES.items(),
+                                      *_MESH_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here == header/library mismatch
         fn.argtypes = argtypes
         fn.restype = restype

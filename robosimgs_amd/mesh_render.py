@@ -1,0 +1,310 @@
+"""Triangle meshes rendered on the GPU (include/mgs_mesh.h, csrc/mesh.hip): the opaque foreground of a hybrid frame, as an
+operator of its own that the caller composites over a Gaussian render.
+
+    box = Mesh.merge([Mesh.from_glb("lid.glb"), Mesh.from_glb("body.glb")], link_ids=[0, -1]).to("cuda")
+    rgb, depth, meta = rasterize_mesh(box, viewmats, Ks, 1280, 720, rotations=R[None], translations=t[None])
+    out_rgb, out_depth = composite_over(bg_rgb, bg_alpha, bg_depth, rgb[0], depth[0])
+
+    r = MeshRenderer(box, 1280, 720, headlight=True)           # workspace and outputs allocated once
+    rgb, depth, meta = r.render(viewmats, Ks, rotations=R_dev, translations=t_dev)       # launches only
+
+Four stages on torch's current stream, over C cameras: a kernel clears the visibility buffer; the vertex stage poses and
+views the vertices (x' = s R x + t for a vertex whose link id is in 0 .. L-1 with L = len(rotations); every other vertex is
+static -- a link id >= L is not an error, because finding one would take a read-back); the face stage rasterises with a
+64-bit atomic minimum on (depth bits, face index); the resolve stage writes rgb, depth, face ids and optionally normals.
+Semantics and fp32 evaluation order: tests/mesh_ref.py.  Nothing synchronises, allocates (in MeshRenderer.render), reads back
+or copies from the host; no floating-point atomic: the same inputs give the same bytes in every run.  `depth` is 0 where no
+face covers the pixel, which is what composite_over(fg_depth=) takes as absent.
+
+Argument errors are ValueErrors raised before any launch.  There is no fallback: a missing library is an error.
+"""
+from __future__ import annotations
+
+import ctypes
+from typing import Dict, Optional, Tuple
+
+import torch
+from torch import Tensor
+
+from . import _lib
+from ._lib import MESH_MAX_SIDE, check, ptr, stream_handle
+from .mesh import Mesh
+
+
+def _check_sizes(n_cams: int, V: int, F: int, width: int, height: int) -> None:
+    if n_cams < 1:
+        raise ValueError(f"n_cams {n_cams}: at least one camera is needed")
+    if V < 1 or F < 1:
+        raise ValueError(f"a mesh of {V} vertices and {F} faces cannot be rasterised: at least one of each is needed")
+    if not (1 <= width <= MESH_MAX_SIDE and 1 <= height <= MESH_MAX_SIDE):
+        raise ValueError(f"image {width} x {height}: each side must be in 1 .. {MESH_MAX_SIDE}")
+
+
+def _check_planes(near_plane: float, far_plane: float) -> None:
+    if not (near_plane > 0):
+        raise ValueError(f"near_plane {near_plane} is not a positive number")
+    if not (far_plane >= near_plane):
+        raise ValueError(f"far_plane {far_plane} is not a number at or above near_plane {near_plane}")
+
+
+def _check_ambient(ambient: float) -> None:
+    if not (0.0 <= ambient <= 1.0):
+        raise ValueError(f"ambient {ambient} is outside 0 .. 1")
+
+
+def _dev(t, shape: Tuple, dtype, what: str, device=None, nullable: bool = False) -> Optional[Tensor]:
+    """A launch-ready tensor or a ValueError: a contiguous `dtype` CUDA tensor of `shape` (-1: any) on `device`."""
+    if t is None:
+        if nullable:
+            return None
+        raise ValueError(f"{what} is missing")
+    if not torch.is_tensor(t):
+        raise ValueError(f"{what} must be a tensor, got {type(t).__name__}")
+    if t.dim() != len(shape) or any(s != -1 and s != d for s, d in zip(shape, t.shape)):
+        raise ValueError(f"{what} must be {list(shape)} (-1: any), got {list(t.shape)}")
+    if t.dtype != dtype:
+        raise ValueError(f"{what} must be {dtype}, got {t.dtype}")
+    if not t.is_cuda:
+        raise ValueError(f"{what} is a CPU tensor: the mesh rasteriser runs on the GPU only")
+    if device is not None and t.device != device:
+        raise ValueError(f"{what} is on {t.device}, the mesh is on {device}")
+    if not t.is_contiguous():
+        raise ValueError(f"{what} must be contiguous")
+    return t
+
+
+def _links(rotations, translations, scales, device):
+    """(L, rotations [L,3,3], translations [L,3], scales [L] | None), launch-ready."""
+    if rotations is None and translations is None:
+        if scales is not None:
+            raise ValueError("scales given without rotations and translations")
+        return 0, None, None, None
+    if rotations is None or translations is None:
+        raise ValueError("rotations and translations go together: one of them is missing")
+    rotations = _dev(rotations, (-1, 3, 3), torch.float32, "rotations", device)
+    L = int(rotations.shape[0])
+    translations = _dev(translations, (L, 3), torch.float32, "translations", device)
+    scales = _dev(scales, (L,), torch.float32, "scales", device, nullable=True)
+    return L, rotations, translations, scales
+
+
+def _workspace(workspace: Optional[Tensor], need: int, device) -> Tuple[Tensor, int]:
+    """(the uint8 tensor, the offset of its first 256-byte aligned byte); allocated where none is given."""
+    if workspace is None:
+        workspace = torch.empty(need + 256, dtype=torch.uint8, device=device)
+    else:
+        _dev(workspace, (-1,), torch.uint8, "workspace", device)
+    pad = -workspace.data_ptr() % 256
+    if workspace.numel() - pad < need:
+        raise ValueError(f"workspace of {workspace.numel()} bytes, {need + 256} needed (mesh_workspace_bytes + 256)")
+    return workspace, pad
+
+
+def mesh_workspace_bytes(n_cams: int, n_vertices: int, n_faces: int, width: int, height: int) -> int:
+    """mgs_mesh_workspace_bytes: visibility uint64 [C,H,W], a counter per camera, 64 bytes per (camera, face)."""
+    _check_sizes(n_cams, n_vertices, n_faces, width, height)
+    n = ctypes.c_size_t(0)
+    check(_lib.lib().mgs_mesh_workspace_bytes(int(n_cams), int(n_vertices), int(n_faces), int(width), int(height), ctypes.byref(n)),
+          "mgs_mesh_workspace_bytes")
+    return int(n.value)
+
+
+def _visibility(workspace: Tensor, pad: int, n_cams: int, width: int, height: int) -> Tensor:
+    return workspace[pad:pad + 8 * n_cams * height * width].view(torch.int64).view(n_cams, height, width)
+
+
+# ---- stage operators (each mirrors one entry point; no synchronisation) ---------------------------------------------------
+@torch.no_grad()
+def mesh_vertices(vertices: Tensor, viewmats: Tensor, link_ids: Optional[Tensor] = None, rotations: Optional[Tensor] = None,
+                  translations: Optional[Tensor] = None, scales: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+    """mgs_mesh_vertices: verts_cam float32 [C,V,3].  vertices float32 [V,3], viewmats float32 [C,4,4], link_ids int32 [V] or
+    None (all static), rotations float32 [L,3,3], translations [L,3], scales [L] or None; a link id outside 0 .. L-1 is static."""
+    vertices = _dev(vertices, (-1, 3), torch.float32, "vertices")
+    dev, V = vertices.device, int(vertices.shape[0])
+    viewmats = _dev(viewmats, (-1, 4, 4), torch.float32, "viewmats", dev)
+    C = int(viewmats.shape[0])
+    _check_sizes(C, V, 1, 1, 1)
+    link_ids = _dev(link_ids, (V,), torch.int32, "link_ids", dev, nullable=True)
+    L, rotations, translations, scales = _links(rotations, translations, scales, dev)
+    if out is None:
+        out = torch.empty((C, V, 3), dtype=torch.float32, device=dev)
+    else:
+        _dev(out, (C, V, 3), torch.float32, "out", dev)
+    check(_lib.lib().mgs_mesh_vertices(C, V, ptr(vertices), ptr(link_ids), L, ptr(rotations), ptr(translations), ptr(scales),
+                                       ptr(viewmats), ptr(out), stream_handle()), "mgs_mesh_vertices")
+    return out
+
+
+@torch.no_grad()
+def mesh_raster(verts_cam: Tensor, faces: Tensor, Ks: Tensor, width: int, height: int, near_plane: float = 0.01,
+                far_plane: float = 1e10, cull_backfaces: bool = False, workspace: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """mgs_mesh_raster (clear + faces): (visibility, workspace).  visibility is an int64 view [C,H,W] of the workspace's first
+    field: the bits of (float_bits(z) << 32) | face per pixel, -1 (all ones) where uncovered.  workspace: a uint8 tensor of
+    mesh_workspace_bytes(...) + 256 bytes, allocated where None; hand it to mesh_resolve."""
+    verts_cam = _dev(verts_cam, (-1, -1, 3), torch.float32, "verts_cam")
+    dev, C, V = verts_cam.device, int(verts_cam.shape[0]), int(verts_cam.shape[1])
+    faces = _dev(faces, (-1, 3), torch.int32, "faces", dev)
+    F, width, height = int(faces.shape[0]), int(width), int(height)
+    _check_sizes(C, V, F, width, height)
+    _check_planes(near_plane, far_plane)
+    Ks = _dev(Ks, (C, 3, 3), torch.float32, "Ks", dev)
+    need = mesh_workspace_bytes(C, V, F, width, height)
+    workspace, pad = _workspace(workspace, need, dev)
+    check(_lib.lib().mgs_mesh_raster(C, V, ptr(verts_cam), F, ptr(faces), ptr(Ks), width, height, float(near_plane),
+                                     float(far_plane), int(bool(cull_backfaces)), workspace.data_ptr() + pad,
+                                     workspace.numel() - pad, stream_handle()), "mgs_mesh_raster")
+    return _visibility(workspace, pad, C, width, height), workspace
+
+
+def _outputs(out: Optional[Dict], C: int, height: int, width: int, normals: bool, dev) -> Dict:
+    res = dict(out) if out is not None else {}
+    want = {"rgb": ((C, height, width, 3), torch.float32), "depth": ((C, height, width), torch.float32),
+            "face_ids": ((C, height, width), torch.int32)}
+    if normals:
+        want["normals"] = ((C, height, width, 3), torch.float32)
+    for name, (shape, dtype) in want.items():
+        if res.get(name) is None:
+            res[name] = torch.empty(shape, dtype=dtype, device=dev)
+        else:
+            _dev(res[name], shape, dtype, f"out[{name!r}]", dev)
+    return res
+
+
+@torch.no_grad()
+def mesh_resolve(verts_cam: Tensor, faces: Tensor, Ks: Tensor, width: int, height: int, workspace: Tensor,
+                 vertex_colors: Optional[Tensor] = None, face_colors: Optional[Tensor] = None, headlight: bool = False,
+                 ambient: float = 0.3, return_normals: bool = False, out: Optional[Dict] = None) -> Dict:
+    """mgs_mesh_resolve on the workspace mesh_raster left: dict(rgb float32 [C,H,W,3], depth float32 [C,H,W], face_ids int32
+    [C,H,W] and, with return_normals, normals float32 [C,H,W,3]).  Uncovered pixels are (0, 0, 0), 0 and -1."""
+    verts_cam = _dev(verts_cam, (-1, -1, 3), torch.float32, "verts_cam")
+    dev, C, V = verts_cam.device, int(verts_cam.shape[0]), int(verts_cam.shape[1])
+    faces = _dev(faces, (-1, 3), torch.int32, "faces", dev)
+    F, width, height = int(faces.shape[0]), int(width), int(height)
+    _check_sizes(C, V, F, width, height)
+    _check_ambient(ambient)
+    Ks = _dev(Ks, (C, 3, 3), torch.float32, "Ks", dev)
+    vertex_colors = _dev(vertex_colors, (V, 3), torch.float32, "vertex_colors", dev, nullable=True)
+    face_colors = _dev(face_colors, (F, 3), torch.float32, "face_colors", dev, nullable=True)
+    workspace, pad = _workspace(_dev(workspace, (-1,), torch.uint8, "workspace", dev), mesh_workspace_bytes(C, V, F, width, height), dev)
+    res = _outputs(out, C, height, width, return_normals, dev)
+    check(_lib.lib().mgs_mesh_resolve(C, V, ptr(verts_cam), F, ptr(faces), ptr(vertex_colors), ptr(face_colors), ptr(Ks), width,
+                                      height, int(bool(headlight)), float(ambient), workspace.data_ptr() + pad,
+                                      workspace.numel() - pad, ptr(res["rgb"]), ptr(res["depth"]), ptr(res["face_ids"]),
+                                      ptr(res.get("normals")), stream_handle()), "mgs_mesh_resolve")
+    return res
+
+
+# ---- the renderer -------------------------------------------------------------------------------------------------------------
+class MeshRenderer:
+    """A mesh, an image size and a camera count with everything allocated once: the workspace, verts_cam [C,V,3] and the
+    outputs.  render() checks its arguments and launches (mgs_rasterize_mesh: five launches on torch's current stream): no
+    allocation, no copy, no synchronisation, so it can be captured in a graph of its own and replayed with viewmats, Ks
+    and the link transforms overwritten in place.  Every call writes the same output tensors.
+
+    options: near_plane=0.01, far_plane=1e10, cull_backfaces=False, headlight=False, ambient=0.3, return_normals=False;
+    out: dict of preallocated outputs (rgb, depth, face_ids, normals), workspace: a uint8 tensor of
+    mesh_workspace_bytes(...) + 256 bytes."""
+
+    def __init__(self, mesh: Mesh, width: int, height: int, n_cams: int = 1, *, near_plane: float = 0.01,
+                 far_plane: float = 1e10, cull_backfaces: bool = False, headlight: bool = False, ambient: float = 0.3,
+                 return_normals: bool = False, out: Optional[Dict] = None, workspace: Optional[Tensor] = None):
+        if not isinstance(mesh, Mesh):
+            raise ValueError(f"mesh must be a Mesh, got {type(mesh).__name__}")
+        self.width, self.height, self.n_cams = int(width), int(height), int(n_cams)
+        _check_sizes(self.n_cams, mesh.n_vertices, mesh.n_faces, self.width, self.height)
+        _check_planes(near_plane, far_plane)
+        _check_ambient(ambient)
+        if mesh.device.type != "cuda":
+            raise ValueError(f"the mesh is on {mesh.device} (CPU tensors): the mesh rasteriser runs on the GPU only, use mesh.to('cuda')")
+        self.mesh, self.device = mesh, mesh.device
+        self.near_plane, self.far_plane, self.ambient = float(near_plane), float(far_plane), float(ambient)
+        self.cull_backfaces, self.headlight, self.return_normals = bool(cull_backfaces), bool(headlight), bool(return_normals)
+        V, F, C = mesh.n_vertices, mesh.n_faces, self.n_cams
+        self._vertices = _dev(mesh.vertices, (V, 3), torch.float32, "mesh.vertices")
+        self._faces = _dev(mesh.faces, (F, 3), torch.int32, "mesh.faces", self.device)
+        self._vcol = _dev(mesh.vertex_colors, (V, 3), torch.float32, "mesh.vertex_colors", self.device, nullable=True)
+        self._fcol = _dev(mesh.face_colors, (F, 3), torch.float32, "mesh.face_colors", self.device, nullable=True)
+        self._link = _dev(mesh.link_ids, (V,), torch.int32, "mesh.link_ids", self.device, nullable=True)
+        self.workspace_bytes = mesh_workspace_bytes(C, V, F, self.width, self.height)
+        self.workspace, self._pad = _workspace(workspace, self.workspace_bytes, self.device)
+        self.verts_cam = torch.empty((C, V, 3), dtype=torch.float32, device=self.device)
+        self.out = _outputs(out, C, self.height, self.width, self.return_normals, self.device)
+
+    @torch.no_grad()
+    def render(self, viewmats: Tensor, Ks: Tensor, rotations: Optional[Tensor] = None, translations: Optional[Tensor] = None,
+               scales: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Dict]:
+        """viewmats float32 [C,4,4] (world to camera), Ks float32 [C,3,3], rotations float32 [L,3,3], translations [L,3],
+        scales [L] or None: contiguous tensors on the mesh's device.  Link l of the mesh takes transform l; a link id >= L
+        (or < 0) is static.  Returns (rgb [C,H,W,3], depth [C,H,W], meta) with meta = dict(face_ids int32 [C,H,W], verts_cam
+        [C,V,3][, normals [C,H,W,3]]): the renderer's own tensors, overwritten by the next call."""
+        C, m = self.n_cams, self.mesh
+        viewmats = _dev(viewmats, (C, 4, 4), torch.float32, "viewmats", self.device)
+        Ks = _dev(Ks, (C, 3, 3), torch.float32, "Ks", self.device)
+        L, rotations, translations, scales = _links(rotations, translations, scales, self.device)
+        o = self.out
+        check(_lib.lib().mgs_rasterize_mesh(
+            C, m.n_vertices, ptr(self._vertices), ptr(self._link), L, ptr(rotations), ptr(translations), ptr(scales),
+            ptr(viewmats), ptr(Ks), m.n_faces, ptr(self._faces), ptr(self._vcol), ptr(self._fcol), self.width, self.height,
+            self.near_plane, self.far_plane, int(self.cull_backfaces), int(self.headlight), self.ambient,
+            self.workspace.data_ptr() + self._pad, self.workspace.numel() - self._pad, ptr(self.verts_cam), ptr(o["rgb"]),
+            ptr(o["depth"]), ptr(o["face_ids"]), ptr(o.get("normals")), stream_handle()), "mgs_rasterize_mesh")
+        meta = {"face_ids": o["face_ids"], "verts_cam": self.verts_cam}
+        if self.return_normals:
+            meta["normals"] = o["normals"]
+        return o["rgb"], o["depth"], meta
+
+def _to_device(x, dtype, device):
+    """A host array, list or tensor of any float dtype as a contiguous `dtype` tensor on `device` (None stays None)."""
+    if x is None:
+        return None
+    if not torch.is_tensor(x):
+        x = torch.as_tensor(x)
+    return x.to(device=device, dtype=dtype).contiguous()
+
+
+def rasterize_mesh(mesh: Mesh, viewmats, Ks, width: int, height: int, *, rotations=None, translations=None, scales=None,
+                   near_plane: float = 0.01, far_plane: float = 1e10, cull_backfaces: bool = False, headlight: bool = False,
+                   ambient: float = 0.3, return_normals: bool = False, out: Optional[Dict] = None,
+                   workspace: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Dict]:
+    """Render `mesh` (on the GPU) from C cameras: (rgb float32 [C,H,W,3], depth float32 [C,H,W], meta) with meta =
+    dict(face_ids int32 [C,H,W] (-1 where uncovered), verts_cam float32 [C,V,3][, normals float32 [C,H,W,3]]).
+
+    viewmats [C,4,4] (or [4,4]) and Ks [C,3,3] (or [3,3]): tensors or arrays of any float type; an OpenCV pinhole camera.
+    rotations [L,3,3], translations [L,3], scales [L]: the convention of transform_gaussians (x' = s R x + t for the
+    vertices of link l), so Hinge.pose(angle) feeds them directly (R [3,3] and t [3] are one link).  Link ids >= L are
+    static: len(rotations) < mesh.n_links() is not an error, because finding it would take a read-back.
+    depth is the z-depth of the nearest face, 0 where there is none: what composite_over(fg_depth=) takes as it stands.
+    rgb: vertex colours interpolated, else face colours, else 0.7 grey; headlight=True multiplies by ambient +
+    (1 - ambient) |cos| between the face normal and the pixel's ray.  out / workspace: buffers of an earlier call to reuse
+    (see MeshRenderer, which also keeps the checks and conversions out of a per-frame loop)."""
+    if not isinstance(mesh, Mesh):
+        raise ValueError(f"mesh must be a Mesh, got {type(mesh).__name__}")
+    for what, x in (("viewmats", viewmats), ("Ks", Ks)):
+        if x is None:
+            raise ValueError(f"{what} is missing")
+    vm, K = torch.as_tensor(viewmats), torch.as_tensor(Ks)
+    vm = vm[None] if vm.dim() == 2 else vm
+    K = K[None] if K.dim() == 2 else K
+    if vm.dim() != 3 or tuple(vm.shape[1:]) != (4, 4):
+        raise ValueError(f"viewmats must be [C,4,4], got {list(vm.shape)}")
+    if tuple(K.shape) != (vm.shape[0], 3, 3):
+        raise ValueError(f"Ks must be [{vm.shape[0]},3,3], got {list(K.shape)}")
+    if not vm.dtype.is_floating_point or not K.dtype.is_floating_point:
+        raise ValueError(f"viewmats and Ks must be floating-point, got {vm.dtype} and {K.dtype}")
+    if rotations is not None and translations is not None:
+        rotations, translations = torch.as_tensor(rotations), torch.as_tensor(translations)
+        if rotations.dim() == 2 and translations.dim() == 1:
+            rotations, translations = rotations[None], translations[None]
+        if rotations.dim() != 3 or tuple(rotations.shape[1:]) != (3, 3) or tuple(translations.shape) != (rotations.shape[0], 3):
+            raise ValueError(f"rotations must be [L,3,3] and translations [L,3], got {list(rotations.shape)} and "
+                             f"{list(translations.shape)}")
+        if scales is not None and tuple(torch.as_tensor(scales).shape) != (rotations.shape[0],):
+            raise ValueError(f"scales must be [{rotations.shape[0]}], got {list(torch.as_tensor(scales).shape)}")
+    r = MeshRenderer(mesh, width, height, int(vm.shape[0]), near_plane=near_plane, far_plane=far_plane,
+                     cull_backfaces=cull_backfaces, headlight=headlight, ambient=ambient, return_normals=return_normals,
+                     out=out, workspace=workspace)
+    f32 = lambda x: _to_device(x, torch.float32, r.device)
+    return r.render(f32(vm), f32(K), rotations=f32(rotations), translations=f32(translations), scales=f32(scales))
+
+
+__all__ = ["MeshRenderer", "rasterize_mesh", "mesh_vertices", "mesh_raster", "mesh_resolve", "mesh_workspace_bytes"]
