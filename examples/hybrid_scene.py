@@ -3,11 +3,15 @@ FrameRenderer, and in front of it a triangle mesh -- the reference's open box, i
 MeshRenderer and composited by depth.  The loop of examples/articulated_scene.py with the stand-in disc replaced by a
 mesh render.  Synthetic background, so it runs anywhere an MI355X is visible:
 
-    python examples/hybrid_scene.py [n_frames]
+    python examples/hybrid_scene.py [n_frames] [--exact]
 
 The mesh render and the composite run eagerly on the consumer stream, once per fetched frame: there is no graph around
 them (composite_over builds its backdrop tensor from a host list and allocates its outputs on every call, so it is not
 capture-safe; and DESIGN.md 4.16 says why mesh kernels stay out of FrameRenderer's graphs).
+
+--exact renders the background eagerly through rasterization(foreground=...) instead and writes its hybrid_rgb: every
+pixel's own front-to-back blend stopped at the mesh's depth, where composite_over compares the mesh with
+the frame's expected depth once.  No FrameRenderer and no graph on that path.
 """
 import math
 import os
@@ -20,7 +24,7 @@ import torch
 ROOT = __file__.rsplit("/", 2)[0]
 sys.path.insert(0, ROOT)
 from robosimgs_amd import (FrameRenderer, Mesh, MeshRenderer, camera_ring, composite_over, frame_to_u8,  # noqa: E402
-                           synthetic_scene)
+                           rasterization, synthetic_scene)
 from robosimgs_amd.articulation import Hinge  # noqa: E402
 
 
@@ -37,11 +41,13 @@ def open_box():
 
 
 def main():
-    n_frames = int(sys.argv[1]) if len(sys.argv) > 1 else 60
+    argv = [a for a in sys.argv[1:] if a != "--exact"]
+    exact = "--exact" in sys.argv[1:]
+    n_frames = int(argv[0]) if argv else 60
     W, H = 1280, 720
     scene = synthetic_scene(300_000, math.log(0.02), 3, seed=0)
     cams = camera_ring(n_frames, W, H, radius=7.0)
-    r = FrameRenderer(scene.to_torch("cuda", 3), W, H, render_mode="RGB+ED", frames_in_flight=3,
+    r = None if exact else FrameRenderer(scene.to_torch("cuda", 3), W, H, render_mode="RGB+ED", frames_in_flight=3,
                       sizing_camera=(cams[0].viewmat(), cams[0].K), capacity_margin=2.0)
     box, hinge = open_box()
     mesh = MeshRenderer(box.to("cuda"), W, H, headlight=True)           # workspace and outputs allocated once
@@ -62,10 +68,21 @@ def main():
         frames.append(frame_to_u8(rgb, torch.ones(H, W, device="cuda")).cpu())     # already composited: alpha 1
         box_pixels.append((meta["face_ids"] >= 0).sum())
 
+    def consume_exact(i, t):
+        fg_rgb, fg_depth, meta = mesh.render(vm_dev[i], K_dev[i], rotations=R_dev[i], translations=t_dev[i])
+        _, _, m = rasterization(t["means"], t["quats"], t["scales"], t["opacities"], t["colors"], vm_dev[i], K_dev[i], W, H,
+                                sh_degree=t["sh_degree"], render_mode="RGB+ED", foreground=(fg_rgb, fg_depth),
+                                backdrop=(0.05, 0.05, 0.08))
+        frames.append(frame_to_u8(m["hybrid_rgb"][0], torch.ones(H, W, device="cuda")).cpu())
+        box_pixels.append((meta["face_ids"] >= 0).sum())
+
     tickets, nxt = [], 0
+    scene_t = scene.to_torch("cuda", 3) if exact else None
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for i in range(n_frames):
+    for i in range(n_frames if exact else 0):
+        consume_exact(i, scene_t)
+    for i in range(0 if exact else n_frames):
         while nxt < n_frames and len(tickets) < r.n_slots:
             tickets.append(r.submit(cams[nxt].viewmat(), cams[nxt].K))
             nxt += 1
@@ -75,7 +92,8 @@ def main():
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     print(f"{n_frames} frames of {W}x{H}, {box.n_faces} mesh faces in front of {len(scene)} Gaussians: "
-          f"{n_frames / dt:.0f} frames/s including the mesh render, compositing, 8-bit conversion and download")
+          f"{n_frames / dt:.0f} frames/s including the mesh render, "
+          f"{'the exact composite (eager)' if exact else 'compositing'}, 8-bit conversion and download")
     print("mean pixel value of the first / last frame:", float(frames[0].float().mean()), float(frames[-1].float().mean()))
     print("pixels of the box in the first / middle frame:", int(box_pixels[0]), int(box_pixels[n_frames // 2]))
 

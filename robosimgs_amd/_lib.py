@@ -143,6 +143,11 @@ _MESH_SIGNATURES = {
     "mgs_mesh_resolve": ([i, i, p, i, p, p, p, p, i, i, i, f, p, c_size_t, p, p, p, p, p], c_int),
     "mgs_rasterize_mesh": ([i, i, p, p, i, p, p, p, p, p, i, p, p, p, i, i, f, f, i, i, f, p, c_size_t, p, p, p, p, p, p], c_int),
 }
+# every function include/mgs_hybrid.h declares (the same libraries again): backdrop, tile_group_order and fg_visibility
+# are nullable
+_HYBRID_SIGNATURES = {
+    "mgs_raster_over_opaque": ([i, p, p, p, p, i, p, p, p, p, p, p, i, i, i, i, p, p, p, p, p, p, p], c_int),
+}
 del p, i, f, u32, img
 EXPORTS = list(_SIGNATURES)
 OPTIM_EXPORTS = list(_OPTIM_SIGNATURES)
@@ -154,6 +159,7 @@ POSE_EXPORTS = list(_POSE_SIGNATURES)
 DEFORM_EXPORTS = list(_DEFORM_SIGNATURES)
 DEFORM_SH_EXPORTS = list(_DEFORM_SH_SIGNATURES)
 MESH_EXPORTS = list(_MESH_SIGNATURES)
+HYBRID_EXPORTS = list(_HYBRID_SIGNATURES)
 MESH_MAX_SIDE, MESH_LARGE_BLOCKS = 16368, 15   # MGS_MESH_MAX_SIDE, MGS_MESH_LARGE_BLOCKS
 DEFORM_K = 8                                # MGS_DEFORM_K
 LABEL_NONE, LABELS_MAX_CLASSES = 255, 32    # MGS_LABEL_NONE, MGS_LABELS_MAX_CLASSES
@@ -180,7 +186,7 @@ def _load(path: str = None, hooks: bool = False) -> ctypes.CDLL:
                                       *_LABEL_SIGNATURES.items(), *_LIFT_SIGNATURES.items(),
                                       *_HINGE_SIGNATURES.items(), *_POSE_SIGNATURES.items(),
                                       *_DEFORM_SIGNATURES.items(), *_DEFORM_SH_SIGNATURES.items(),
-                                      *_MESH_SIGNATURES.items()):
+                                      *_MESH_SIGNATURES.items(), *_HYBRID_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError here == header/library mismatch
         fn.argtypes = argtypes
         fn.restype = restype

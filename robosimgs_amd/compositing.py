@@ -20,7 +20,9 @@ def composite_over(bg_rgb: torch.Tensor, bg_alpha: torch.Tensor, bg_depth: torch
     """bg_rgb [...,3] (premultiplied accumulation as returned by `rasterization`), bg_alpha [...,1]
     or [...], bg_depth [...,1] or [...] (z-depth, the "ED" channel); fg_rgb [...,3], fg_depth [...]
     (z-depth of the opaque foreground; <= 0 or inf where absent unless fg_mask is given).
-    Returns (rgb [...,3], depth [...])."""
+    Returns (rgb [...,3], depth [...]).  One depth comparison per pixel against the frame's expected depth: where the
+    splats at a pixel lie on both sides of the foreground, rasterization(foreground=...) / ops.rasterize_over_opaque give
+    the exact composite (include/mgs_hybrid.h)."""
     require_device(bg_rgb, bg_alpha, bg_depth, fg_rgb, fg_depth, fg_mask)
     lead = bg_rgb.shape[:-1]
     n_px = int(torch.Size(lead).numel())

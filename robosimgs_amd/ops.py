@@ -9,6 +9,7 @@ Appendix A.1), each a thin torch wrapper over one C-ABI entry point of libmgs.so
     rasterize_labels         -> mgs_raster_labels (include/mgs_labels.h; no gsplat counterpart, no backward)
     rasterize_votes          -> mgs_raster_votes (include/mgs_lift.h: 2D masks -> per-Gaussian class votes)
     assign_classes           -> mgs_lift_assign
+    rasterize_over_opaque    -> mgs_raster_over_opaque (include/mgs_hybrid.h: the frame's blend stopped at an opaque foreground)
 
 Inputs are post-activation fp32 CUDA(HIP) tensors (the render-path calls also take the raw form, log-scales and
 opacity logits, with raw=True: include/mgs.h MGS_PARAMS_RAW); ids are int32, keys int64.  All kernels
@@ -616,6 +617,60 @@ def raster_labels_raw(tl: "TileLists", class_ids, n_classes, width, height, mean
     return labels, weights
 
 
+def _check_hybrid_buffer(name, t, shape, dev) -> None:
+    if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != tuple(shape) or t.device != dev:
+        raise ValueError(f"{name} must be a contiguous float32 tensor {tuple(shape)} on {dev}, got {t.dtype} "
+                         f"{tuple(t.shape)} on {t.device}")
+
+
+def backdrop_f32(backdrop, dev) -> Optional[Tensor]:
+    """backdrop as the kernels read it: None, or three floats on the device."""
+    if backdrop is None:
+        return None
+    b = torch.as_tensor(backdrop, dtype=torch.float32, device=dev).contiguous()
+    if tuple(b.shape) != (3,):
+        raise ValueError(f"backdrop shape {tuple(b.shape)} != (3,)")
+    return b
+
+
+def raster_over_opaque_raw(tl: "TileLists", means2d, conics, opacities, feats, depths, fg_rgb, fg_depth, render, alphas,
+                           width, height, backdrop=None, out=None, return_visibility=True, use_group_order=True,
+                           tile_offsets=None):
+    """mgs_raster_over_opaque on one camera's lists (include/mgs_hybrid.h): the frame's own blend stopped per pixel at
+    the foreground's depth.  means2d [n,2], conics [n,3], opacities [n] (what the raster saw), feats [n,D] with rgb in the
+    first three columns (D >= 3), depths [n]; fg_rgb [H,W,3], fg_depth [H,W]; render [H,W,4] ("RGB+ED"), alphas [H,W];
+    backdrop None or a float32 tensor [3] on the device.  Returns (rgb [H,W,3], depth [H,W], fg_visibility [H,W] | None);
+    out = the same triple to write into existing buffers.  use_group_order / tile_offsets: as raster_labels_raw."""
+    n, dev = means2d.shape[0], means2d.device
+    if feats.dim() != 2 or feats.shape[1] < 3:
+        raise ValueError(f"feats shape {tuple(feats.shape)}: rgb in the first three of at least three columns")
+    for name, t, shape in (("means2d", means2d, (n, 2)), ("conics", conics, (n, 3)), ("opacities", opacities, (n,)),
+                           ("feats", feats, (n, feats.shape[1])), ("depths", depths, (n,)),
+                           ("fg_rgb", fg_rgb, (height, width, 3)), ("fg_depth", fg_depth, (height, width)),
+                           ("render", render, (height, width, 4)), ("alphas", alphas, (height, width))):
+        _check_hybrid_buffer(name, t, shape, dev)
+    if backdrop is not None:
+        _check_hybrid_buffer("backdrop", backdrop, (3,), dev)
+    if out is None:
+        rgb = torch.empty(height, width, 3, dtype=torch.float32, device=dev)
+        depth = torch.empty(height, width, dtype=torch.float32, device=dev)
+        vis = torch.empty(height, width, dtype=torch.float32, device=dev) if return_visibility else None
+    else:
+        rgb, depth, vis = out
+    _check_hybrid_buffer("out rgb", rgb, (height, width, 3), dev)
+    _check_hybrid_buffer("out depth", depth, (height, width), dev)
+    if vis is not None:
+        _check_hybrid_buffer("fg_visibility", vis, (height, width), dev)
+    tile_w, tile_h = -(-width // TILE_SIZE), -(-height // TILE_SIZE)
+    order = getattr(tl, "group_order", None) if use_group_order else None
+    check(_lib.lib().mgs_raster_over_opaque(
+        n, ptr(means2d), ptr(conics), ptr(opacities), ptr(feats), int(feats.shape[1]), ptr(depths), ptr(fg_rgb),
+        ptr(fg_depth), ptr(render), ptr(alphas), ptr(backdrop), width, height, tile_w, tile_h,
+        ptr(tile_offsets if tile_offsets is not None else tl.tile_offsets), ptr(tl.flatten_ids), ptr(order), ptr(rgb),
+        ptr(depth), ptr(vis), stream_handle()), "mgs_raster_over_opaque")
+    return rgb, depth, vis
+
+
 VOTE_ONE = 1 << 32       # a vote of one pixel at full weight (include/mgs_lift.h: unsigned Q32 fixed point)
 
 
@@ -1185,6 +1240,64 @@ def rasterize_labels(means2d: Tensor, conics: Tensor, opacities: Tensor, class_i
                           opacities.view(C * N), out=(labels[c], weights[c] if return_weights else None), use_group_order=False,
                           tile_offsets=offsets_ext[c * n_tiles:])
     return (labels, weights) if return_weights else labels
+
+
+@torch.no_grad()
+def rasterize_over_opaque(means2d: Tensor, conics: Tensor, colors: Tensor, depths: Tensor, opacities: Tensor,
+                          fg_rgb: Tensor, fg_depth: Tensor, render_colors: Tensor, render_alphas: Tensor,
+                          image_width: int, image_height: int, tile_size: int, isect_offsets: Tensor, flatten_ids: Tensor,
+                          backdrop=None, return_visibility: bool = False):
+    """The exact composite of the frames rasterize_to_pixels blends from the same arguments with an opaque foreground
+    (include/mgs_hybrid.h): each pixel's own front-to-back blend, stopped at the foreground's depth, the foreground
+    entering at the transmittance reached there.  means2d [C,N,2], conics [C,N,3], colors [C,N,D] (rgb in the first three
+    columns, D >= 3), depths [C,N], opacities [C,N]; fg_rgb [C,H,W,3], fg_depth [C,H,W] (z-depth, 0 where no face is:
+    rasterize_mesh's outputs as they are); render_colors [C,H,W,4] in "RGB+ED" mode and render_alphas [C,H,W] or
+    [C,H,W,1]: the plain frame, copied where there is no foreground (+ (1 - alpha) backdrop, depth +inf where alpha is 0);
+    isect_offsets [C,th,tw], flatten_ids [n_isects]; backdrop None or three floats.
+    Returns (rgb [C,H,W,3], depth [C,H,W]) and with return_visibility also fg_visibility [C,H,W], the share of the
+    foreground that reaches the eye (0 where there is none).  Not differentiable."""
+    if tile_size != TILE_SIZE:
+        raise NotImplementedError(f"tile_size must be {TILE_SIZE}")
+    require_device(means2d, conics, colors, depths, opacities, fg_rgb, fg_depth, render_colors, render_alphas, isect_offsets,
+                   flatten_ids)
+    C, N = means2d.shape[0], means2d.shape[1]
+    if conics.shape != (C, N, 3) or opacities.shape != (C, N) or means2d.shape != (C, N, 2) or depths.shape != (C, N):
+        raise ValueError("expected means2d [C,N,2], conics [C,N,3], depths [C,N], opacities [C,N]")
+    if colors.dim() != 3 or colors.shape[:2] != (C, N) or colors.shape[2] < 3:
+        raise ValueError("expected colors [C,N,D] with rgb in the first three of D >= 3 columns")
+    width, height = int(image_width), int(image_height)
+    tile_w, tile_h = -(-width // TILE_SIZE), -(-height // TILE_SIZE)
+    if tuple(isect_offsets.shape) != (C, tile_h, tile_w):
+        raise ValueError(f"isect_offsets shape {tuple(isect_offsets.shape)} != {(C, tile_h, tile_w)}")
+    if tuple(fg_rgb.shape) != (C, height, width, 3) or tuple(fg_depth.shape) != (C, height, width):
+        raise ValueError(f"expected fg_rgb {(C, height, width, 3)} and fg_depth {(C, height, width)}")
+    if tuple(render_colors.shape) != (C, height, width, 4):
+        raise ValueError(f"render_colors shape {tuple(render_colors.shape)} != {(C, height, width, 4)}: an 'RGB+ED' frame")
+    if render_alphas.numel() != C * height * width or render_alphas.shape[:3] != (C, height, width):
+        raise ValueError(f"render_alphas shape {tuple(render_alphas.shape)} is neither {(C, height, width)} nor "
+                         f"{(C, height, width, 1)}")
+    n_tiles = tile_w * tile_h
+    dev = means2d.device
+    D = colors.shape[2]
+    means2d, conics, opacities = _f32c(means2d.detach()), _f32c(conics.detach()), _f32c(opacities.detach())
+    colors, depths = _f32c(colors.detach()), _f32c(depths.detach())
+    fg_rgb, fg_depth = _f32c(fg_rgb.detach()), _f32c(fg_depth.detach())
+    render = _f32c(render_colors.detach())
+    alphas = _f32c(render_alphas.detach()).reshape(C, height, width)
+    bd = backdrop_f32(backdrop, dev)
+    tl = TileLists()
+    tl.flatten_ids = flatten_ids.to(torch.int32).contiguous()
+    end = torch.full((1,), tl.flatten_ids.numel(), dtype=torch.int32, device=dev)
+    offsets_ext = torch.cat([isect_offsets.reshape(-1).to(torch.int32), end])
+    rgb = torch.empty(C, height, width, 3, dtype=torch.float32, device=dev)
+    depth = torch.empty(C, height, width, dtype=torch.float32, device=dev)
+    vis = torch.empty(C, height, width, dtype=torch.float32, device=dev) if return_visibility else None
+    for c in range(C):       # ids in flatten_ids are cam*N + gaussian: the kernel gets the flat [C*N,...] views
+        raster_over_opaque_raw(tl, means2d.view(C * N, 2), conics.view(C * N, 3), opacities.view(C * N),
+                               colors.view(C * N, D), depths.view(C * N), fg_rgb[c], fg_depth[c], render[c], alphas[c],
+                               width, height, backdrop=bd, out=(rgb[c], depth[c], vis[c] if return_visibility else None),
+                               use_group_order=False, tile_offsets=offsets_ext[c * n_tiles:])
+    return (rgb, depth, vis) if return_visibility else (rgb, depth)
 
 
 @torch.no_grad()

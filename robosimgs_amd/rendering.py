@@ -77,6 +77,7 @@ class _RenderConfig:
     dataset: Optional[tuple]    # dataset_out
     raw: bool = False           # raw_params: scales are log-scales, opacities logits (MGS_PARAMS_RAW)
     labels: Optional[tuple] = None   # (class_ids int32 [N], n_classes): a label frame per camera (include/mgs_labels.h)
+    hybrid: Optional[tuple] = None   # (fg_rgb [C,H,W,3], fg_depth [C,H,W], backdrop [3] | None): include/mgs_hybrid.h
 
     @property
     def channels(self) -> int:
@@ -101,6 +102,23 @@ def _stk(xs):
     return xs[0].unsqueeze(0) if len(xs) == 1 else torch.stack(xs)
 
 
+def _hybrid_buffers(C, height, width, dev):
+    """The three frames rasterization(foreground=) publishes, as the meta entries that hold them."""
+    return dict(hybrid_rgb=torch.empty(C, height, width, 3, dtype=torch.float32, device=dev),
+                hybrid_depth=torch.empty(C, height, width, dtype=torch.float32, device=dev),
+                fg_visibility=torch.empty(C, height, width, dtype=torch.float32, device=dev))
+
+
+def _hybrid_camera(cfg: "_RenderConfig", cam: "_Camera", opacities, render, alphas, c: int, out: dict) -> None:
+    """mgs_raster_over_opaque on the arrays and lists camera c's raster has just read (its opacity: anti-aliased or
+    activated where the frame's is), into frame c of `out`."""
+    fg_rgb, fg_depth, backdrop = cfg.hybrid
+    opac = cam.opac_aa if (cfg.antialiased or cfg.raw) else opacities.detach()
+    ops.raster_over_opaque_raw(cam.lists, cam.means2d, cam.conics, opac, cam.feats, cam.depths, fg_rgb[c], fg_depth[c],
+                               render[c], alphas[c], cfg.width, cfg.height, backdrop=backdrop,
+                               out=(out["hybrid_rgb"][c], out["hybrid_depth"][c], out["fg_visibility"][c]))
+
+
 class _RenderSH(torch.autograd.Function):
     """SH-coloured frames for C cameras: fused projection+colour, binning, raster."""
 
@@ -122,6 +140,9 @@ class _RenderSH(torch.autograd.Function):
             lab = torch.empty(C, height, width, dtype=torch.uint8, device=dev)
             lab_w = torch.empty(C, height, width, dtype=torch.float32, device=dev)
             meta_out["label_frames"] = dict(labels=lab, label_weights=lab_w)
+        hyb = None
+        if cfg.hybrid is not None:          # the exact composite with an opaque foreground: no gradient either
+            hyb = meta_out["hybrid_frames"] = _hybrid_buffers(C, height, width, dev)
         ctx.set_materialize_grads(False)       # an unused output's cotangent arrives as None, not as a zero frame
         # lean: an inference frame with a fixed list capacity keeps only what its own kernels read -- the packed
         # records, the binning seed and the depths; radii / means2d / conics / feats / tiles_per_gauss are neither
@@ -157,6 +178,8 @@ class _RenderSH(torch.autograd.Function):
                                        st.tile_lists(c, v), v["splats"], None))
                 if lab is not None:         # on the camera's own records and lists, kept in the state
                     ops.raster_labels_raw(per_cam[c].lists, *cfg.labels, width, height, splats=v["splats"], out=(lab[c], lab_w[c]))
+                if hyb is not None:
+                    _hybrid_camera(cfg, per_cam[c], opacities, render, alphas, c, hyb)
             ctx.train_state = st
             ctx.save_for_backward(means, quats, scales, opacities, sh_coeffs, viewmats, Ks, backgrounds, alphas, None, render)
             meta_out["per_cam"] = per_cam
@@ -194,6 +217,8 @@ class _RenderSH(torch.autograd.Function):
             if lab is not None:             # the records the raster has just read: its opacity, its lists, its launch order
                 ops.raster_labels_raw(tl, *cfg.labels, width, height, splats=splats, out=(lab[c], lab_w[c]))
             per_cam.append(_Camera(radii, means2d, depths, conics, opac_aa, feats, tl, splats, ckpt))
+            if hyb is not None:             # the frame just written, blended again up to the foreground's depth
+                _hybrid_camera(cfg, per_cam[c], opacities, render, alphas, c, hyb)
         ctx.per_cam = per_cam
         # "RGB+ED": the kernel's epilogue divided the depth channel by max(alpha, 1e-10); the
         # backward undoes that with the saved frame (an OUTPUT: it must go through
@@ -297,8 +322,23 @@ def rasterization(means: Tensor, quats: Tensor, scales: Tensor, opacities: Tenso
                   distortion=None,
                   raw_params: bool = False,
                   class_ids: Optional[Tensor] = None,
-                  n_classes: Optional[int] = None) -> Tuple[Tensor, Tensor, Dict]:
+                  n_classes: Optional[int] = None,
+                  foreground: Optional[Tuple[Tensor, Tensor]] = None,
+                  backdrop=None) -> Tuple[Tensor, Tensor, Dict]:
     """Render N Gaussians from C cameras.
+
+    foreground = (fg_rgb [C,H,W,3], fg_depth [C,H,W]), an opaque layer as rasterize_mesh returns it (z-depth, 0 where no
+    face is), with render_mode="RGB+ED": every frame also gets its exact composite with that layer (include/mgs_hybrid.h,
+    DESIGN.md 4.17) -- meta["hybrid_rgb"] [C,H,W,3] and meta["hybrid_depth"] [C,H,W], the pixel's own front-to-back blend
+    stopped at the foreground's depth with the foreground entering at the transmittance reached there, and
+    meta["fg_visibility"] [C,H,W], that transmittance (0 where there is no foreground; there the frame itself is copied,
+    + (1 - alpha) backdrop, backdrop = three floats or None).  Where the splats at a pixel straddle the foreground --
+    a table edge, foliage, a semi-transparent layer in front of the arm -- this is what composite_over's single depth
+    comparison cannot give.  Colours, alphas and every other meta entry are what they are without the keyword.  On the
+    per-Gaussian feature path ([N,3] / [C,N,3] colours) and on the SH path with per-camera intermediates; refused with
+    lean_meta=True or dataset_out (the one-C-call frames keep nothing per Gaussian) and not part of FrameRenderer's
+    captured graphs.  Under rasterize_mode="antialiased" or raw_params it blends with the opacity the raster saw.  No
+    gradient.
 
     class_ids (any integer tensor [N] on the device) with n_classes = K <= 32: every frame also gets a part-label frame,
     meta["labels"] [C,H,W] uint8 -- the class whose Gaussians hold the largest share of the pixel's blend weights, ties to
@@ -398,6 +438,21 @@ def rasterization(means: Tensor, quats: Tensor, scales: Tensor, opacities: Tenso
         labels = (cls, ops.check_n_classes(n_classes))
     elif n_classes is not None:
         raise ValueError("n_classes given without class_ids")
+    hybrid = None
+    if foreground is not None:
+        if render_mode != "RGB+ED":
+            raise ValueError(f"foreground= composites colour and expected depth: it needs render_mode='RGB+ED', not {render_mode!r}")
+        if lean_meta or dataset_out is not None:
+            raise ValueError("foreground= blends each camera's own arrays and lists again, which lean_meta=True / dataset_out "
+                             "frames do not keep: render without them (FrameRenderer's graphs do not carry this operator)")
+        fg_rgb, fg_depth = foreground
+        require_device(fg_rgb, fg_depth)
+        if tuple(fg_rgb.shape) != (C, int(height), int(width), 3) or tuple(fg_depth.shape) != (C, int(height), int(width)):
+            raise ValueError(f"foreground must be (fg_rgb {(C, int(height), int(width), 3)}, fg_depth {(C, int(height), int(width))}), "
+                             f"got {tuple(fg_rgb.shape)} and {tuple(fg_depth.shape)}")
+        hybrid = (_f32c(fg_rgb.detach()), _f32c(fg_depth.detach()), ops.backdrop_f32(backdrop, means.device))
+    elif backdrop is not None:
+        raise ValueError("backdrop given without foreground")
     if means.shape != (N, 3) or quats.shape != (N, 4) or scales.shape != (N, 3) \
             or opacities.shape != (N,):
         raise ValueError("expected means [N,3], quats [N,4], scales [N,3], opacities [N]")
@@ -435,7 +490,7 @@ def rasterization(means: Tensor, quats: Tensor, scales: Tensor, opacities: Tenso
             antialiased, want_depth, isect_capacity, bool(absgrad), tight=tile_bounds == "tight", per_axis=bool(rule),
             camera=camera, expected_depth=render_mode in ("RGB+ED", "ED"), latency=raster_schedule == "latency",
             lean=bool(lean_meta), segment=int(backward_segment), dataset=dataset_out, raw=bool(raw_params),
-            labels=labels)
+            labels=labels, hybrid=hybrid)
         # the autograd function publishes per-camera intermediates (and, after backward, "means2d_grad" /
         # "means2d_absgrad" lists) into the meta dict
         # (under the lens the kernels read the cameras' 16-float rows where they read K otherwise)
@@ -445,6 +500,8 @@ def rasterization(means: Tensor, quats: Tensor, scales: Tensor, opacities: Tenso
             render = render[..., 3:4]
         if "label_frames" in meta:
             meta.update(meta.pop("label_frames"))
+        if "hybrid_frames" in meta:
+            meta.update(meta.pop("hybrid_frames"))
         if "lean" in meta:              # inference frames through mgs_render_frames: counts and status only
             meta.update(meta.pop("lean"))
             return render, alphas, meta
@@ -509,6 +566,12 @@ def rasterization(means: Tensor, quats: Tensor, scales: Tensor, opacities: Tenso
         if render_mode in ("ED", "RGB+ED"):      # operator path (explicit features): divide here
             render = torch.cat([render[..., :-1],
                                 render[..., -1:] / alphas.clamp(min=1e-10)], dim=-1)
+        if hybrid is not None:                   # on the divided frame: where there is no foreground it is copied
+            if feats.shape[-1] != 4:
+                raise ValueError("foreground= needs three colour channels: colors [N,3] or [C,N,3]")
+            meta["hybrid_rgb"], meta["hybrid_depth"], meta["fg_visibility"] = ops.rasterize_over_opaque(
+                means2d, conics, feats, depths, opac, hybrid[0], hybrid[1], render, alphas, width, height, TILE_SIZE, offsets,
+                flatten_ids, backdrop=hybrid[2], return_visibility=True)
     return render, alphas, meta
 
 
