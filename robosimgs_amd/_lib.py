@@ -149,6 +149,10 @@ _HYBRID_SIGNATURES = {
     "mgs_raster_over_opaque": ([i, p, p, p, p, i, p, p, p, p, p, p, i, i, i, i, p, p, p, p, p, p, p], c_int),
 }
 del p, i, f, u32, img
+# what _load binds: a new header adds its table here
+_SIGNATURE_TABLES = (_SIGNATURES, _OPTIM_SIGNATURES, _REFINE_SIGNATURES, _LABEL_SIGNATURES, _LIFT_SIGNATURES,
+                     _HINGE_SIGNATURES, _POSE_SIGNATURES, _DEFORM_SIGNATURES, _DEFORM_SH_SIGNATURES, _MESH_SIGNATURES,
+                     _HYBRID_SIGNATURES)
 EXPORTS = list(_SIGNATURES)
 OPTIM_EXPORTS = list(_OPTIM_SIGNATURES)
 REFINE_EXPORTS = list(_REFINE_SIGNATURES)
@@ -182,14 +186,11 @@ def _load(path: str = None, hooks: bool = False) -> ctypes.CDLL:
     if have != MGS_VERSION:      # shifted parameter lists would end in a GPU fault, not in an error
         raise MgsError(f"{LIB_PATH} reports ABI version {have}, this binding was written for {MGS_VERSION} "
                        "(include/mgs.h): rebuild the library (`python robosimgs_amd/csrc/build.py --force`)")
-    for name, (argtypes, restype) in (*_SIGNATURES.items(), *_OPTIM_SIGNATURES.items(), *_REFINE_SIGNATURES.items(),
-                                      *_LABEL_SIGNATURES.items(), *_LIFT_SIGNATURES.items(),
-                                      *_HINGE_SIGNATURES.items(), *_POSE_SIGNATURES.items(),
-                                      *_DEFORM_SIGNATURES.items(), *_DEFORM_SH_SIGNATURES.items(),
-                                      *_MESH_SIGNATURES.items(), *_HYBRID_SIGNATURES.items()):
-        fn = getattr(lib, name)          # AttributeError here == header/library mismatch
-        fn.argtypes = argtypes
-        fn.restype = restype
+    for table in _SIGNATURE_TABLES:
+        for name, (argtypes, restype) in table.items():
+            fn = getattr(lib, name)          # AttributeError here == header/library mismatch
+            fn.argtypes = argtypes
+            fn.restype = restype
     if hooks:
         for name in DEBUG_HOOKS:
             fn = getattr(lib, name)
@@ -289,3 +290,30 @@ def require_device(*tensors) -> None:
         if t is not None and not t.is_cuda:
             raise MgsError("the render path runs on the GPU only: got a CPU tensor "
                            "(there is no CPU fallback; see oracle/ for the test-only checker)")
+
+
+def check_tensor(name: str, t, dtype, shape, device=None) -> None:
+    """The kernels read and write their arguments through raw pointers: `t` must be a contiguous tensor of `dtype` and
+    `shape` (-1: any extent), on `device` where one is given, or the call ends here in a ValueError.  Attribute reads
+    only: nothing is synchronised, allocated or launched."""
+    if (isinstance(t, torch.Tensor) and t.dtype == dtype and t.dim() == len(shape) and t.is_contiguous()
+            and all(s == -1 or s == d for s, d in zip(shape, t.shape)) and (device is None or t.device == device)):
+        return
+    want = (f"a contiguous {str(dtype)[6:]} tensor {list(shape)}" + (" (-1: any extent)" if -1 in shape else "")
+            + ("" if device is None else f" on {device}"))
+    got = type(t).__name__ if not isinstance(t, torch.Tensor) else (
+        f"{'a' if t.is_contiguous() else 'a strided'} {str(t.dtype)[6:]} tensor {list(t.shape)} on {t.device}")
+    raise ValueError(f"{name} must be {want}, got {got}")
+
+
+def aligned_workspace(workspace, need: int, device):
+    """A caller's workspace as the library takes it: (the uint8 tensor, the offset of its first 256-byte aligned byte);
+    need + 256 bytes are allocated on `device` where none is given.  A given one is any contiguous uint8 tensor: whether it
+    is large enough, 1-D or on that device is the call site's, or the library's, to say."""
+    if workspace is None:
+        workspace = torch.empty(need + 256, dtype=torch.uint8, device=device)
+    elif not (isinstance(workspace, torch.Tensor) and workspace.dtype == torch.uint8 and workspace.is_contiguous()):
+        raise ValueError("workspace must be a contiguous uint8 tensor, got "
+                         + (f"{workspace.dtype} with strides {workspace.stride()}" if isinstance(workspace, torch.Tensor)
+                            else type(workspace).__name__))
+    return workspace, -workspace.data_ptr() % 256

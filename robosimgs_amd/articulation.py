@@ -19,7 +19,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from ._lib import check, ptr, require_device, sized_call, stream_handle
+from ._lib import aligned_workspace, check, check_tensor, ptr, require_device, sized_call, stream_handle
 from .ops import _f32c
 
 JOINT_DOUBLES = 16       # include/mgs_hinge.h: position 0..2, axis 3..5, confidence, min_distance, counts, eigenvalues, flags
@@ -67,20 +67,18 @@ def hinge_fit_raw(points_a: Tensor, points_b: Tensor, threshold: float = 0.01, c
     a, b = _points(points_a, "points_a"), _points(points_b, "points_b")
     n_a, n_b, dev = a.shape[0], b.shape[0], a.device
     for c, n, what in ((contact_a, n_a, "contact_a"), (contact_b, n_b, "contact_b")):
-        if c is not None and (c.dtype != torch.uint8 or tuple(c.shape) != (n,) or not c.is_contiguous()):
-            raise ValueError(f"{what} must be a contiguous uint8 tensor [{n}]")
+        if c is not None:
+            check_tensor(what, c, torch.uint8, (n,))
     if joint is None:
         joint = torch.empty(JOINT_DOUBLES, dtype=torch.float64, device=dev)
-    elif joint.dtype != torch.float64 or tuple(joint.shape) != (JOINT_DOUBLES,) or not joint.is_contiguous():
-        raise ValueError(f"joint must be a contiguous float64 tensor [{JOINT_DOUBLES}]")
+    else:
+        check_tensor("joint", joint, torch.float64, (JOINT_DOUBLES,))
     L = _lib.lib()
     args = [n_a, ptr(a), n_b, ptr(b), float(threshold)]
     if workspace is None:
         sized_call(_sized_entry(L), args, dev, cached=True, trailing=(ptr(contact_a), ptr(contact_b), ptr(joint)))
     else:
-        if workspace.dtype != torch.uint8 or not workspace.is_contiguous():
-            raise ValueError("workspace must be a contiguous uint8 tensor (hinge_workspace)")
-        pad = -workspace.data_ptr() % 256
+        workspace, pad = aligned_workspace(workspace, 0, dev)
         check(L.mgs_hinge_fit(*args, workspace.data_ptr() + pad, max(0, workspace.numel() - pad), ptr(contact_a),
                               ptr(contact_b), ptr(joint), stream_handle()), "mgs_hinge_fit")
     return joint

@@ -28,7 +28,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from ._lib import DEFORM_K, check, ptr, require_device, stream_handle
+from ._lib import DEFORM_K, aligned_workspace, check, check_tensor, ptr, require_device, stream_handle
 from .ops import _f32c
 
 REST_ROWS = 12           # include/mgs_deform.h: d0 (3), Q^-1 (6), h^2, lambda_mid / lambda_max, lambda_min / lambda_max
@@ -72,10 +72,7 @@ class ParticleBinding:
                 "p": ((DEFORM_K, 3, self.n), torch.float32), "rest": ((REST_ROWS, self.n), torch.float32),
                 "flags": ((self.n,), torch.uint8)}
         for name, (shape, dtype) in want.items():
-            t = getattr(self, name)
-            if tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous():
-                raise ValueError(f"binding.{name} must be a contiguous {dtype} tensor {list(shape)}, got {t.dtype} "
-                                 f"{list(t.shape)}")
+            check_tensor(f"binding.{name}", getattr(self, name), dtype, shape)
 
     def reordered(self, order: Tensor) -> "ParticleBinding":
         """The binding of the Gaussians taken in `order` (int64 [N']: new position -> old index; FrameRenderer's Morton
@@ -101,11 +98,8 @@ def deform_bind_raw(means: Tensor, particles: Tensor, select: Optional[Tensor], 
     otherwise one is allocated for the call."""
     require_device(means, particles, select, idx, w, p, rest, flags, workspace)
     n, m, L = int(means.shape[0]), int(particles.shape[0]), _lib.lib()
-    if workspace is None:
-        workspace = torch.empty(int(L.mgs_deform_bind_workspace_bytes(n, m)) + 256, dtype=torch.uint8, device=means.device)
-    elif workspace.dtype != torch.uint8 or not workspace.is_contiguous():
-        raise ValueError("workspace must be a contiguous uint8 tensor")
-    pad = -workspace.data_ptr() % 256
+    need = 0 if workspace is not None else int(L.mgs_deform_bind_workspace_bytes(n, m))
+    workspace, pad = aligned_workspace(workspace, need, means.device)
     check(L.mgs_deform_bind(n, ptr(means), ptr(select), m, ptr(particles), float(max_distance),
                             workspace.data_ptr() + pad, max(0, workspace.numel() - pad), ptr(idx), ptr(w), ptr(p), ptr(rest),
                             ptr(flags), stream_handle()), "mgs_deform_bind")
@@ -130,8 +124,7 @@ def deform_apply_sh_raw(means: Tensor, quats: Tensor, scales: Tensor, binding: P
     copy_unbound=False leaves the rows of unbound Gaussians in out_colors as they are."""
     require_device(means, quats, scales, particles, out_means, out_quats, out_scales, status, binding.idx, colors, out_colors)
     for t, what in ((colors, "colors"), (out_colors, "out_colors")):
-        if t.dim() != 3 or t.shape[0] != binding.n or t.shape[2] != 3 or t.dtype != torch.float32 or not t.is_contiguous():
-            raise ValueError(f"{what} must be a contiguous float32 tensor [{binding.n},K,3], got {t.dtype} {list(t.shape)}")
+        check_tensor(what, t, torch.float32, (binding.n, -1, 3))
     if out_colors.shape != colors.shape:
         raise ValueError(f"out_colors {list(out_colors.shape)} is not the shape of colors {list(colors.shape)}")
     check(_lib.lib().mgs_deform_apply_sh(binding.n, ptr(means), ptr(quats), ptr(scales), ptr(binding.idx), ptr(binding.w),
@@ -192,8 +185,8 @@ def deform_gaussians(tensors: Dict, binding: ParticleBinding, particles: Tensor,
         if t.shape[0] != n:
             raise ValueError(f"{what} has {t.shape[0]} rows, the binding was made for {n} Gaussians")
     _particles(particles, binding.m, "particles")
-    if status is not None and (status.dtype != torch.uint8 or tuple(status.shape) != (n,) or not status.is_contiguous()):
-        raise ValueError(f"status must be a contiguous uint8 tensor [{n}]")
+    if status is not None:
+        check_tensor("status", status, torch.uint8, (n,))
     colors, deg = tensors["colors"], int(tensors.get("sh_degree") or 0)
     do_sh = bool(rotate_sh) and torch.is_tensor(colors) and colors.dim() == 3 and colors.shape[1] >= (deg + 1) ** 2 and deg >= 1
     if do_sh and (colors.shape[0] != n or colors.shape[2] != 3 or not colors.dtype.is_floating_point):
@@ -206,10 +199,10 @@ def deform_gaussians(tensors: Dict, binding: ParticleBinding, particles: Tensor,
         o = res.get(key)
         if o is None:
             o = torch.empty_like(src)
-        elif o.dtype != torch.float32 or o.shape != src.shape or not o.is_contiguous():
-            raise ValueError(f"out[{key!r}] must be a contiguous float32 tensor {list(src.shape)}")
-        elif o.data_ptr() == src.data_ptr():
-            raise ValueError(f"out[{key!r}] is the rest state's own buffer: the rest state must survive")
+        else:
+            check_tensor(f"out[{key!r}]", o, torch.float32, src.shape)
+            if o.data_ptr() == src.data_ptr():
+                raise ValueError(f"out[{key!r}] is the rest state's own buffer: the rest state must survive")
         outs.append(o)
     if do_sh:
         sh_in = _f32c(colors)

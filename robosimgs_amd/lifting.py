@@ -17,8 +17,8 @@ import torch
 from torch import Tensor
 
 from . import ops
-from ._lib import MgsError
-from .ops import TILE_SIZE, _f32c, require_device
+from ._lib import MgsError, check_tensor, require_device
+from .ops import _f32c
 
 
 class LiftResult(NamedTuple):
@@ -60,9 +60,9 @@ def lift_labels(means: Tensor, quats: Tensor, scales: Tensor, opacities: Tensor,
     cam_rows = ops.lens_rows(Ks, distortion) if camera == ops.CAMERA_FISHEYE_KB else Ks
     if votes is None:
         votes = torch.zeros(N, n_classes, dtype=torch.int64, device=dev)
-    elif votes.dtype != torch.int64 or tuple(votes.shape) != (N, n_classes) or not votes.is_contiguous():
-        raise ValueError(f"votes must be a contiguous int64 tensor {(N, n_classes)}")
-    tile_w, tile_h = -(-width // TILE_SIZE), -(-height // TILE_SIZE)
+    else:
+        check_tensor("votes", votes, torch.int64, (N, n_classes))
+    tile_w, tile_h = ops.tile_grid(width, height)
     for c in range(C):
         radii, means2d, depths, conics, comp = ops.projection_fwd_raw(
             means, quats, scales, viewmats[c], cam_rows[c], width, height, float(eps2d), float(near_plane), float(far_plane),

@@ -27,7 +27,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from ._lib import MESH_MAX_SIDE, check, ptr, stream_handle
+from ._lib import MESH_MAX_SIDE, aligned_workspace, check, ptr, stream_handle
 from .mesh import Mesh
 
 
@@ -90,11 +90,9 @@ def _links(rotations, translations, scales, device):
 
 def _workspace(workspace: Optional[Tensor], need: int, device) -> Tuple[Tensor, int]:
     """(the uint8 tensor, the offset of its first 256-byte aligned byte); allocated where none is given."""
-    if workspace is None:
-        workspace = torch.empty(need + 256, dtype=torch.uint8, device=device)
-    else:
+    if workspace is not None:
         _dev(workspace, (-1,), torch.uint8, "workspace", device)
-    pad = -workspace.data_ptr() % 256
+    workspace, pad = aligned_workspace(workspace, need, device)
     if workspace.numel() - pad < need:
         raise ValueError(f"workspace of {workspace.numel()} bytes, {need + 256} needed (mesh_workspace_bytes + 256)")
     return workspace, pad

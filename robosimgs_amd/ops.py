@@ -14,10 +14,15 @@ Appendix A.1), each a thin torch wrapper over one C-ABI entry point of libmgs.so
 Inputs are post-activation fp32 CUDA(HIP) tensors (the render-path calls also take the raw form, log-scales and
 opacity logits, with raw=True: include/mgs.h MGS_PARAMS_RAW); ids are int32, keys int64.  All kernels
 are enqueued on torch's current stream.  Nothing here computes on the CPU.
+
+The three operators that walk a camera's tile lists (labels, votes, over_opaque) share their host side: _walk_source and
+_walk_lists check what the kernel reads through raw pointers (_lib.check_tensor), _gsplat_lists and _flat_arrays turn
+gsplat's flat [C,...] arguments into per-camera raw calls.  A further walk-based operator is a wrapper around those.
 """
 from __future__ import annotations
 
 import ctypes
+import math
 from typing import Optional, Tuple
 
 import numpy as np
@@ -25,9 +30,14 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from ._lib import check, ptr, require_device, sized_call, stream_handle
+from ._lib import aligned_workspace, check, check_tensor, ptr, require_device, sized_call, stream_handle
 
 TILE_SIZE = 16
+
+
+def tile_grid(width: int, height: int) -> Tuple[int, int]:
+    """(tile_w, tile_h): the 16x16 tiles that cover a width x height frame."""
+    return -(-width // TILE_SIZE), -(-height // TILE_SIZE)
 
 
 def _f32c(t: Optional[Tensor]) -> Optional[Tensor]:
@@ -153,9 +163,7 @@ def lens_rows(Ks: Tensor, distortion) -> Tensor:
     if isinstance(k, LensRows):
         rows = k.rows
         require_device(rows)
-        if tuple(rows.shape) != (C, LENS_ROW_FLOATS) or rows.dtype != torch.float32 or not rows.is_contiguous() \
-                or rows.device != Ks.device:
-            raise ValueError(f"LensRows.rows must be a contiguous float32 tensor [{C},{LENS_ROW_FLOATS}] on {Ks.device}")
+        check_tensor("LensRows.rows", rows, torch.float32, (C, LENS_ROW_FLOATS), Ks.device)
         return rows
     key = (k.tobytes(), k.shape[0], Ks.device)
     tail = _LENS_TAILS.get(key)
@@ -411,7 +419,7 @@ class TrainState:
         self.capacity, self.antialiased, self.interval, self.flags = int(capacity), bool(antialiased), int(interval), flags
         self.buf = torch.empty(self.per_camera * n_cams + 256, dtype=torch.uint8, device=device)
         self.pad = (-self.buf.data_ptr()) % 256
-        self.n_tiles = (-(-width // TILE_SIZE)) * (-(-height // TILE_SIZE))
+        self.n_tiles = math.prod(tile_grid(width, height))
 
     def ptr(self) -> int:
         return self.buf.data_ptr() + self.pad
@@ -579,14 +587,45 @@ def check_label_buffers(class_ids, n, n_classes, labels, weights, shape) -> None
     """The kernels write prod(shape) label bytes (and as many floats) through raw pointers and gather class_ids at every
     listed Gaussian: the buffers must hold exactly that."""
     check_n_classes(n_classes)
-    if class_ids.dtype != torch.int32 or not class_ids.is_contiguous() or class_ids.numel() != n:
-        raise ValueError(f"class_ids must be a contiguous int32 tensor of {n} entries (class_ids_i32)")
-    if labels.dtype != torch.uint8 or not labels.is_contiguous() or tuple(labels.shape) != tuple(shape):
-        raise ValueError(f"labels must be a contiguous uint8 tensor {tuple(shape)}")
-    if weights is not None and (weights.dtype != torch.float32 or not weights.is_contiguous()
-                                or tuple(weights.shape) != tuple(shape)):
-        raise ValueError(f"label_weights must be a contiguous float32 tensor {tuple(shape)}")
+    check_tensor("class_ids", class_ids, torch.int32, (n,))
+    check_tensor("labels", labels, torch.uint8, shape)
+    if weights is not None:
+        check_tensor("label_weights", weights, torch.float32, shape)
     require_device(class_ids, labels, weights)
+
+
+def _walk_source(what: str, means2d, conics, opacities, splats):
+    """The Gaussians a walk kernel gathers, through raw pointers: the packed records `splats` [n,12], or means2d [n,2],
+    conics [n,3] and opacities [n].  Returns (n, device)."""
+    src = splats if splats is not None else means2d
+    if src is None or (splats is None and (conics is None or opacities is None)):
+        raise ValueError(f"{what} needs splats, or means2d, conics and opacities")
+    n = src.shape[0]
+    if splats is not None:
+        check_tensor("splats", splats, torch.float32, (n, 12))
+    else:
+        check_tensor("means2d", means2d, torch.float32, (n, 2))
+        check_tensor("conics", conics, torch.float32, (n, 3))
+        check_tensor("opacities", opacities, torch.float32, (n,))
+    require_device(src, conics, opacities)
+    return n, src.device
+
+
+def _walk_lists(tl: "TileLists", width, height, use_group_order, tile_offsets):
+    """The lists a walk kernel reads, through raw pointers, for a width x height frame: ((tile_w, tile_h), the offset table
+    -- tile_offsets, or tl.tile_offsets where that is None --, tl.flatten_ids, tl.group_order or None).  Int32, contiguous
+    and on the device, an offset per tile and the end of the last list, or a ValueError."""
+    tile_w, tile_h = tile_grid(width, height)
+    offsets = tile_offsets if tile_offsets is not None else tl.tile_offsets
+    order = getattr(tl, "group_order", None) if use_group_order else None
+    check_tensor("flatten_ids", tl.flatten_ids, torch.int32, (-1,))
+    check_tensor("tile_offsets", offsets, torch.int32, (-1,))
+    if order is not None:
+        check_tensor("group_order", order, torch.int32, (-1,))
+    if offsets.numel() < tile_w * tile_h + 1:
+        raise ValueError(f"tile_offsets holds {offsets.numel()} entries, the frame has {tile_w * tile_h} tiles (+ 1)")
+    require_device(tl.flatten_ids, offsets, order)
+    return (tile_w, tile_h), offsets, tl.flatten_ids, order
 
 
 def raster_labels_raw(tl: "TileLists", class_ids, n_classes, width, height, means2d=None, conics=None, opacities=None,
@@ -597,30 +636,18 @@ def raster_labels_raw(tl: "TileLists", class_ids, n_classes, width, height, mean
     opacities.  out = (labels, label_weights|None) to write into existing buffers.  use_group_order: start the tiles in
     tl.group_order where the lists have one (a schedule, never a result); tile_offsets: another offset table than
     tl.tile_offsets (a camera's slice of a concatenated one)."""
-    src = splats if splats is not None else means2d
-    if src is None or (splats is None and (conics is None or opacities is None)):
-        raise ValueError("raster_labels_raw needs splats, or means2d, conics and opacities")
-    n, dev = src.shape[0], src.device
+    n, dev = _walk_source("raster_labels_raw", means2d, conics, opacities, splats)
     if out is None:
         labels = torch.empty(height, width, dtype=torch.uint8, device=dev)
         weights = torch.empty(height, width, dtype=torch.float32, device=dev) if return_weights else None
     else:
         labels, weights = out
     check_label_buffers(class_ids, n, n_classes, labels, weights, (height, width))
-    tile_w, tile_h = -(-width // TILE_SIZE), -(-height // TILE_SIZE)
-    order = getattr(tl, "group_order", None) if use_group_order else None
+    (tile_w, tile_h), offsets, flatten_ids, order = _walk_lists(tl, width, height, use_group_order, tile_offsets)
     check(_lib.lib().mgs_raster_labels(n, ptr(means2d), ptr(conics), ptr(opacities), ptr(splats), ptr(class_ids),
-                                       int(n_classes), width, height, tile_w, tile_h,
-                                       ptr(tile_offsets if tile_offsets is not None else tl.tile_offsets),
-                                       ptr(tl.flatten_ids), ptr(order), ptr(labels), ptr(weights), stream_handle()),
-          "mgs_raster_labels")
+                                       int(n_classes), width, height, tile_w, tile_h, ptr(offsets), ptr(flatten_ids),
+                                       ptr(order), ptr(labels), ptr(weights), stream_handle()), "mgs_raster_labels")
     return labels, weights
-
-
-def _check_hybrid_buffer(name, t, shape, dev) -> None:
-    if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != tuple(shape) or t.device != dev:
-        raise ValueError(f"{name} must be a contiguous float32 tensor {tuple(shape)} on {dev}, got {t.dtype} "
-                         f"{tuple(t.shape)} on {t.device}")
 
 
 def backdrop_f32(backdrop, dev) -> Optional[Tensor]:
@@ -644,46 +671,33 @@ def raster_over_opaque_raw(tl: "TileLists", means2d, conics, opacities, feats, d
     n, dev = means2d.shape[0], means2d.device
     if feats.dim() != 2 or feats.shape[1] < 3:
         raise ValueError(f"feats shape {tuple(feats.shape)}: rgb in the first three of at least three columns")
+    require_device(means2d)
     for name, t, shape in (("means2d", means2d, (n, 2)), ("conics", conics, (n, 3)), ("opacities", opacities, (n,)),
-                           ("feats", feats, (n, feats.shape[1])), ("depths", depths, (n,)),
+                           ("feats", feats, (n, -1)), ("depths", depths, (n,)),
                            ("fg_rgb", fg_rgb, (height, width, 3)), ("fg_depth", fg_depth, (height, width)),
                            ("render", render, (height, width, 4)), ("alphas", alphas, (height, width))):
-        _check_hybrid_buffer(name, t, shape, dev)
+        check_tensor(name, t, torch.float32, shape, dev)
     if backdrop is not None:
-        _check_hybrid_buffer("backdrop", backdrop, (3,), dev)
+        check_tensor("backdrop", backdrop, torch.float32, (3,), dev)
     if out is None:
         rgb = torch.empty(height, width, 3, dtype=torch.float32, device=dev)
         depth = torch.empty(height, width, dtype=torch.float32, device=dev)
         vis = torch.empty(height, width, dtype=torch.float32, device=dev) if return_visibility else None
     else:
         rgb, depth, vis = out
-    _check_hybrid_buffer("out rgb", rgb, (height, width, 3), dev)
-    _check_hybrid_buffer("out depth", depth, (height, width), dev)
-    if vis is not None:
-        _check_hybrid_buffer("fg_visibility", vis, (height, width), dev)
-    tile_w, tile_h = -(-width // TILE_SIZE), -(-height // TILE_SIZE)
-    order = getattr(tl, "group_order", None) if use_group_order else None
+        check_tensor("out rgb", rgb, torch.float32, (height, width, 3), dev)
+        check_tensor("out depth", depth, torch.float32, (height, width), dev)
+        if vis is not None:
+            check_tensor("fg_visibility", vis, torch.float32, (height, width), dev)
+    (tile_w, tile_h), offsets, flatten_ids, order = _walk_lists(tl, width, height, use_group_order, tile_offsets)
     check(_lib.lib().mgs_raster_over_opaque(
         n, ptr(means2d), ptr(conics), ptr(opacities), ptr(feats), int(feats.shape[1]), ptr(depths), ptr(fg_rgb),
-        ptr(fg_depth), ptr(render), ptr(alphas), ptr(backdrop), width, height, tile_w, tile_h,
-        ptr(tile_offsets if tile_offsets is not None else tl.tile_offsets), ptr(tl.flatten_ids), ptr(order), ptr(rgb),
-        ptr(depth), ptr(vis), stream_handle()), "mgs_raster_over_opaque")
+        ptr(fg_depth), ptr(render), ptr(alphas), ptr(backdrop), width, height, tile_w, tile_h, ptr(offsets),
+        ptr(flatten_ids), ptr(order), ptr(rgb), ptr(depth), ptr(vis), stream_handle()), "mgs_raster_over_opaque")
     return rgb, depth, vis
 
 
 VOTE_ONE = 1 << 32       # a vote of one pixel at full weight (include/mgs_lift.h: unsigned Q32 fixed point)
-
-
-def check_vote_buffers(mask, n_classes, votes, shape) -> None:
-    """The kernel gathers prod(shape) mask bytes and adds into votes[row * n_classes + class] through raw pointers: the
-    buffers must hold exactly that.  torch's int64 carries the unsigned Q32 value (it cannot wrap while views x pixels
-    covered per view stays below 2^31: include/mgs_lift.h)."""
-    check_n_classes(n_classes)
-    if mask.dtype != torch.uint8 or not mask.is_contiguous() or tuple(mask.shape) != tuple(shape):
-        raise ValueError(f"mask must be a contiguous uint8 tensor {tuple(shape)}")
-    if votes.dtype != torch.int64 or not votes.is_contiguous() or votes.dim() != 2 or votes.shape[1] != n_classes:
-        raise ValueError(f"votes must be a contiguous int64 tensor [rows, {n_classes}]")
-    require_device(mask, votes)
 
 
 def raster_votes_raw(tl: "TileLists", mask, n_classes, width, height, votes, means2d=None, conics=None, opacities=None,
@@ -694,32 +708,17 @@ def raster_votes_raw(tl: "TileLists", mask, n_classes, width, height, votes, mea
     the packed records the frame's raster read -- or of means2d / conics / opacities; list id `id` votes into row
     id - row_offset and nowhere if that is outside the buffer.  use_group_order / tile_offsets: as raster_labels_raw.
     Returns votes."""
-    src = splats if splats is not None else means2d
-    if src is None or (splats is None and (conics is None or opacities is None)):
-        raise ValueError("raster_votes_raw needs splats, or means2d, conics and opacities")
-    n = src.shape[0]
-    check_vote_buffers(mask, n_classes, votes, (height, width))
-    # the Gaussian arrays and the lists reach the kernel as raw pointers too
-    arrays = ((splats, (n, 12), "splats"),) if splats is not None else (
-        (means2d, (n, 2), "means2d"), (conics, (n, 3), "conics"), (opacities, (n,), "opacities"))
-    for t, shape, name in arrays:
-        if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shape:
-            raise ValueError(f"{name} must be a contiguous float32 tensor {shape}")
-    tile_w, tile_h = -(-width // TILE_SIZE), -(-height // TILE_SIZE)
-    order = getattr(tl, "group_order", None) if use_group_order else None
-    offsets = tile_offsets if tile_offsets is not None else tl.tile_offsets
-    for t, name in ((tl.flatten_ids, "flatten_ids"), (offsets, "tile_offsets"), (order, "group_order")):
-        if t is not None and (t.dtype != torch.int32 or not t.is_contiguous()):
-            raise ValueError(f"{name} must be a contiguous int32 tensor")
-    if offsets.numel() < tile_w * tile_h + 1:
-        raise ValueError(f"tile_offsets holds {offsets.numel()} entries, the frame has {tile_w * tile_h} tiles (+ 1)")
-    require_device(src, conics, opacities, tl.flatten_ids, offsets, order)
+    n, _ = _walk_source("raster_votes_raw", means2d, conics, opacities, splats)
+    # the kernel gathers width * height mask bytes and adds into votes[row * n_classes + class]; torch's int64 carries the
+    # unsigned Q32 value (it cannot wrap while views x pixels covered per view stays below 2^31: include/mgs_lift.h)
+    n_classes = check_n_classes(n_classes)
+    check_tensor("mask", mask, torch.uint8, (height, width))
+    check_tensor("votes", votes, torch.int64, (-1, n_classes))
+    require_device(mask, votes)
+    (tile_w, tile_h), offsets, flatten_ids, order = _walk_lists(tl, width, height, use_group_order, tile_offsets)
     check(_lib.lib().mgs_raster_votes(n, ptr(means2d), ptr(conics), ptr(opacities), ptr(splats), ptr(mask), int(n_classes),
-                                      width, height, tile_w, tile_h,
-                                      ptr(offsets), ptr(tl.flatten_ids), ptr(order), int(row_offset), votes.shape[0],
-                                      ptr(votes),
-                                      stream_handle()),
-          "mgs_raster_votes")
+                                      width, height, tile_w, tile_h, ptr(offsets), ptr(flatten_ids), ptr(order),
+                                      int(row_offset), votes.shape[0], ptr(votes), stream_handle()), "mgs_raster_votes")
     return votes
 
 
@@ -729,8 +728,7 @@ def assign_classes(votes: Tensor, min_vote: float = 0.0, out=None) -> Tuple[Tens
     that vote's share of the row's total, 0 where the class is -1.  A Gaussian no mask pixel saw has class -1.
     out = (class_ids, confidence) to write into existing buffers.  No read-back: capturable in a graph."""
     require_device(votes)
-    if votes.dtype != torch.int64 or not votes.is_contiguous() or votes.dim() != 2:
-        raise ValueError("votes must be a contiguous int64 tensor [N, K]")
+    check_tensor("votes", votes, torch.int64, (-1, -1))
     n, k = votes.shape
     check_n_classes(k)
     if out is None:
@@ -739,10 +737,8 @@ def assign_classes(votes: Tensor, min_vote: float = 0.0, out=None) -> Tuple[Tens
     else:
         class_ids, confidence = out
         require_device(class_ids, confidence)
-        if class_ids.dtype != torch.int32 or not class_ids.is_contiguous() or tuple(class_ids.shape) != (n,):
-            raise ValueError(f"class_ids must be a contiguous int32 tensor ({n},)")
-        if confidence.dtype != torch.float32 or not confidence.is_contiguous() or tuple(confidence.shape) != (n,):
-            raise ValueError(f"confidence must be a contiguous float32 tensor ({n},)")
+        check_tensor("class_ids", class_ids, torch.int32, (n,))
+        check_tensor("confidence", confidence, torch.float32, (n,))
     check(_lib.lib().mgs_lift_assign(n, k, ptr(votes), float(min_vote), ptr(class_ids), ptr(confidence), stream_handle()),
           "mgs_lift_assign")
     return class_ids, confidence
@@ -831,10 +827,10 @@ def rasterize_bwd_det_workspace_layout(channels: int, absgrad: bool, capacity: i
     return out
 
 
-def _aligned_workspace(workspace: Tensor, need: int) -> Tensor:
-    if workspace.dtype != torch.uint8 or workspace.dim() != 1 or not workspace.is_contiguous():
-        raise ValueError("workspace: a contiguous 1-D uint8 tensor")
-    pad = -workspace.data_ptr() % 256
+def _aligned_workspace(workspace: Tensor, need: int, device) -> Tensor:
+    """The caller's workspace from its first 256-byte aligned byte on: at least `need` bytes, or a ValueError."""
+    check_tensor("workspace", workspace, torch.uint8, (-1,), device)
+    workspace, pad = aligned_workspace(workspace, need, device)
     if workspace.numel() < pad + need:
         raise ValueError(f"workspace: {workspace.numel()} bytes, the call needs {need} + {pad} of alignment slack")
     return workspace[pad:]
@@ -848,7 +844,7 @@ def rasterize_bwd_det_workspace_views(workspace: Tensor, channels: int, absgrad:
     partial segments of class c), `unit_whole` [units, 4] and `unit_part` [32, n_tiles, 4] int32 rows
     {tile, segment, list start, end of the tile's walk}."""
     lay = rasterize_bwd_det_workspace_layout(channels, absgrad, capacity, tile_w, tile_h, checkpoint_interval)
-    w = _aligned_workspace(workspace, lay["total"])
+    w = _aligned_workspace(workspace, lay["total"], workspace.device)
     cap, rf, n_tiles = lay["capacity"], lay["record_floats"], tile_w * tile_h
     v = {"records": w[:cap * rf * 4].view(torch.float32).view(cap, rf),
          "flags": w[lay["flags"]:lay["flags"] + cap],
@@ -865,16 +861,12 @@ def rasterize_bwd_det_workspace_views(workspace: Tensor, channels: int, absgrad:
 def _check_bwd_out(out, n: int, ch: int, absgrad: bool, dev):
     if len(out) != 5:
         raise ValueError("out: (v_means2d, v_conics, v_feats, v_opacities, v_means2d_abs|None)")
+    if (out[4] is None) != (not absgrad):
+        raise ValueError("out: v_means2d_abs is given exactly when absgrad is set")
     shapes = ((n, 2), (n, 3), (n, ch), (n,), (n, 2))
-    for t, shape, name in zip(out, shapes, ("v_means2d", "v_conics", "v_feats", "v_opacities", "v_means2d_abs")):
-        if name == "v_means2d_abs" and (t is None) != (not absgrad):
-            raise ValueError("out: v_means2d_abs is given exactly when absgrad is set")
-        if t is None and name == "v_means2d_abs":
-            continue
-        if not isinstance(t, Tensor) or t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous():
-            raise ValueError(f"out: {name} must be a contiguous float32 tensor of shape {shape}")
-        if t.device != dev:
-            raise ValueError(f"out: {name} is on {t.device}, the inputs on {dev}")
+    names = ("v_means2d", "v_conics", "v_feats", "v_opacities", "v_means2d_abs")
+    for t, shape, name in zip(out[:5 if absgrad else 4], shapes, names):
+        check_tensor(f"out {name}", t, torch.float32, shape, dev)
     return tuple(out)
 
 
@@ -917,9 +909,7 @@ def rasterize_bwd_det_raw(means2d, conics, feats, opacities, background, width, 
         fn, nbytes = _lib.lib().mgs_rasterize_bwd_det, ctypes.c_size_t(0)
         check(fn(*args, None, ctypes.byref(nbytes), None), "mgs_rasterize_bwd_det(size query)")
         size = nbytes.value
-        w = _aligned_workspace(workspace, size + int(canary_bytes))
-        if workspace.device != dev:
-            raise ValueError(f"workspace is on {workspace.device}, the inputs on {dev}")
+        w = _aligned_workspace(workspace, size + int(canary_bytes), dev)
         canary = w[size:size + canary_bytes].fill_(0xA5) if canary_bytes else None
         check(fn(*args, w.data_ptr(), ctypes.byref(nbytes), stream_handle()), "mgs_rasterize_bwd_det")
     else:
@@ -1122,12 +1112,40 @@ def isect_offset_encode(isect_ids: Tensor, n_cameras: int, tile_width: int,
     return out
 
 
+def _gsplat_lists(isect_offsets: Tensor, flatten_ids: Tensor, C: int, width: int, height: int, tile_size: int, *arrays):
+    """gsplat's lists -- isect_offsets [C,th,tw], flatten_ids [n_isects] with ids cam*N + gaussian -- as the raw calls
+    read them: (tl, n_tiles) with tl.flatten_ids int32 and tl.tile_offsets the int32 table of all C cameras with the end
+    of the last list appended; camera c walks tl with tile_offsets=tl.tile_offsets[c * n_tiles:] over the flat [C*N,...]
+    arrays.  One conversion, one full and one cat per operator call.  The refusals come in the operators' order: the tile
+    size, then a CPU tensor among the lists and `arrays` (the operator's other tensors), then the grid."""
+    if tile_size != TILE_SIZE:
+        raise NotImplementedError(f"tile_size must be {TILE_SIZE}")
+    require_device(isect_offsets, flatten_ids, *arrays)
+    tile_w, tile_h = tile_grid(width, height)
+    if tuple(isect_offsets.shape) != (C, tile_h, tile_w):
+        raise ValueError(f"isect_offsets shape {tuple(isect_offsets.shape)} != {(C, tile_h, tile_w)}")
+    tl = TileLists()
+    tl.flatten_ids = flatten_ids.to(torch.int32).contiguous()
+    end = torch.full((1,), tl.flatten_ids.numel(), dtype=torch.int32, device=flatten_ids.device)
+    tl.tile_offsets = torch.cat([isect_offsets.reshape(-1).to(torch.int32), end])
+    return tl, tile_w * tile_h
+
+
+def _flat_arrays(means2d: Tensor, conics: Tensor, opacities: Tensor):
+    """The [C,N,...] arrays of a non-differentiable operator: (C, N, their detached float32 flat [C*N,...] views)."""
+    C, N = means2d.shape[0], means2d.shape[1]
+    if conics.shape != (C, N, 3) or opacities.shape != (C, N) or means2d.shape != (C, N, 2):
+        raise ValueError("expected means2d [C,N,2], conics [C,N,3], opacities [C,N]")
+    return C, N, (_f32c(means2d.detach()).view(C * N, 2), _f32c(conics.detach()).view(C * N, 3),
+                  _f32c(opacities.detach()).view(C * N))
+
+
 class _RasterizeToPixels(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means2d, conics, colors, opacities, backgrounds, width, height,
                 offsets_ext, flatten_ids, absgrad):
         C, N, ch = colors.shape
-        tile_w, tile_h = -(-width // TILE_SIZE), -(-height // TILE_SIZE)
+        tile_w, tile_h = tile_grid(width, height)
         n_tiles = tile_w * tile_h
         dev = means2d.device
         render = torch.empty(C, height, width, ch, dtype=torch.float32, device=dev)
@@ -1185,22 +1203,14 @@ def rasterize_to_pixels(means2d: Tensor, conics: Tensor, colors: Tensor, opaciti
         raise NotImplementedError("packed=True is not supported")
     if masks is not None:
         raise NotImplementedError("tile masks are not supported")
-    if tile_size != TILE_SIZE:
-        raise NotImplementedError(f"tile_size must be {TILE_SIZE}")
-    require_device(means2d, conics, colors, opacities, isect_offsets, flatten_ids, backgrounds)
-    C, N = means2d.shape[0], means2d.shape[1]
+    tl, _ = _gsplat_lists(isect_offsets, flatten_ids, means2d.shape[0], image_width, image_height, tile_size,
+                          means2d, conics, colors, opacities, backgrounds)
     ch = colors.shape[-1]
     if not 1 <= ch <= 32:
         raise ValueError(f"{ch} colour channels: supported range is 1..32")
-    tile_w, tile_h = -(-image_width // TILE_SIZE), -(-image_height // TILE_SIZE)
-    if tuple(isect_offsets.shape) != (C, tile_h, tile_w):
-        raise ValueError(f"isect_offsets shape {tuple(isect_offsets.shape)} != {(C, tile_h, tile_w)}")
-    flatten_ids = flatten_ids.to(torch.int32).contiguous()
-    end = torch.full((1,), flatten_ids.numel(), dtype=torch.int32, device=means2d.device)
-    offsets_ext = torch.cat([isect_offsets.reshape(-1).to(torch.int32), end])
     return _RasterizeToPixels.apply(_f32c(means2d), _f32c(conics), _f32c(colors),
                                     _f32c(opacities), _f32c(backgrounds), int(image_width),
-                                    int(image_height), offsets_ext, flatten_ids, bool(absgrad))
+                                    int(image_height), tl.tile_offsets, tl.flatten_ids, bool(absgrad))
 
 
 @torch.no_grad()
@@ -1213,32 +1223,18 @@ def rasterize_labels(means2d: Tensor, conics: Tensor, opacities: Tensor, class_i
     pixel, ties to the lowest k, 255 where no counted Gaussian has such a class; with return_weights also that sum,
     [C,H,W] float32.  A Gaussian whose class is outside 0..n_classes-1 occludes and is never reported.  The weights are
     the blend's own bit for bit.  Not differentiable."""
-    if tile_size != TILE_SIZE:
-        raise NotImplementedError(f"tile_size must be {TILE_SIZE}")
-    require_device(means2d, conics, opacities, isect_offsets, flatten_ids)
-    C, N = means2d.shape[0], means2d.shape[1]
-    if conics.shape != (C, N, 3) or opacities.shape != (C, N) or means2d.shape != (C, N, 2):
-        raise ValueError("expected means2d [C,N,2], conics [C,N,3], opacities [C,N]")
-    n_classes = check_n_classes(n_classes)
     width, height = int(image_width), int(image_height)
-    tile_w, tile_h = -(-width // TILE_SIZE), -(-height // TILE_SIZE)
-    if tuple(isect_offsets.shape) != (C, tile_h, tile_w):
-        raise ValueError(f"isect_offsets shape {tuple(isect_offsets.shape)} != {(C, tile_h, tile_w)}")
-    n_tiles = tile_w * tile_h
+    tl, n_tiles = _gsplat_lists(isect_offsets, flatten_ids, means2d.shape[0], width, height, tile_size,
+                                means2d, conics, opacities)
+    C, N, flat = _flat_arrays(means2d, conics, opacities)
+    n_classes = check_n_classes(n_classes)
     dev = means2d.device
-    # ids in flatten_ids are cam*N + gaussian: the kernel gets the flat [C*N,...] views and the classes once per camera
-    cls = class_ids_i32(class_ids, N).repeat(C)
-    means2d, conics, opacities = _f32c(means2d.detach()), _f32c(conics.detach()), _f32c(opacities.detach())
-    tl = TileLists()
-    tl.flatten_ids = flatten_ids.to(torch.int32).contiguous()
-    end = torch.full((1,), tl.flatten_ids.numel(), dtype=torch.int32, device=dev)
-    offsets_ext = torch.cat([isect_offsets.reshape(-1).to(torch.int32), end])
+    cls = class_ids_i32(class_ids, N).repeat(C)          # ids in flatten_ids are cam*N + gaussian: the classes once per camera
     labels = torch.empty(C, height, width, dtype=torch.uint8, device=dev)
     weights = torch.empty(C, height, width, dtype=torch.float32, device=dev) if return_weights else None
     for c in range(C):
-        raster_labels_raw(tl, cls, n_classes, width, height, means2d.view(C * N, 2), conics.view(C * N, 3),
-                          opacities.view(C * N), out=(labels[c], weights[c] if return_weights else None), use_group_order=False,
-                          tile_offsets=offsets_ext[c * n_tiles:])
+        raster_labels_raw(tl, cls, n_classes, width, height, *flat, out=(labels[c], weights[c] if return_weights else None),
+                          use_group_order=False, tile_offsets=tl.tile_offsets[c * n_tiles:])
     return (labels, weights) if return_weights else labels
 
 
@@ -1256,19 +1252,12 @@ def rasterize_over_opaque(means2d: Tensor, conics: Tensor, colors: Tensor, depth
     isect_offsets [C,th,tw], flatten_ids [n_isects]; backdrop None or three floats.
     Returns (rgb [C,H,W,3], depth [C,H,W]) and with return_visibility also fg_visibility [C,H,W], the share of the
     foreground that reaches the eye (0 where there is none).  Not differentiable."""
-    if tile_size != TILE_SIZE:
-        raise NotImplementedError(f"tile_size must be {TILE_SIZE}")
-    require_device(means2d, conics, colors, depths, opacities, fg_rgb, fg_depth, render_colors, render_alphas, isect_offsets,
-                   flatten_ids)
-    C, N = means2d.shape[0], means2d.shape[1]
-    if conics.shape != (C, N, 3) or opacities.shape != (C, N) or means2d.shape != (C, N, 2) or depths.shape != (C, N):
-        raise ValueError("expected means2d [C,N,2], conics [C,N,3], depths [C,N], opacities [C,N]")
-    if colors.dim() != 3 or colors.shape[:2] != (C, N) or colors.shape[2] < 3:
-        raise ValueError("expected colors [C,N,D] with rgb in the first three of D >= 3 columns")
     width, height = int(image_width), int(image_height)
-    tile_w, tile_h = -(-width // TILE_SIZE), -(-height // TILE_SIZE)
-    if tuple(isect_offsets.shape) != (C, tile_h, tile_w):
-        raise ValueError(f"isect_offsets shape {tuple(isect_offsets.shape)} != {(C, tile_h, tile_w)}")
+    tl, n_tiles = _gsplat_lists(isect_offsets, flatten_ids, means2d.shape[0], width, height, tile_size,
+                                means2d, conics, colors, depths, opacities, fg_rgb, fg_depth, render_colors, render_alphas)
+    C, N, flat = _flat_arrays(means2d, conics, opacities)
+    if colors.dim() != 3 or colors.shape[:2] != (C, N) or colors.shape[2] < 3 or depths.shape != (C, N):
+        raise ValueError("expected colors [C,N,D] with rgb in the first three of D >= 3 columns, and depths [C,N]")
     if tuple(fg_rgb.shape) != (C, height, width, 3) or tuple(fg_depth.shape) != (C, height, width):
         raise ValueError(f"expected fg_rgb {(C, height, width, 3)} and fg_depth {(C, height, width)}")
     if tuple(render_colors.shape) != (C, height, width, 4):
@@ -1276,27 +1265,19 @@ def rasterize_over_opaque(means2d: Tensor, conics: Tensor, colors: Tensor, depth
     if render_alphas.numel() != C * height * width or render_alphas.shape[:3] != (C, height, width):
         raise ValueError(f"render_alphas shape {tuple(render_alphas.shape)} is neither {(C, height, width)} nor "
                          f"{(C, height, width, 1)}")
-    n_tiles = tile_w * tile_h
     dev = means2d.device
-    D = colors.shape[2]
-    means2d, conics, opacities = _f32c(means2d.detach()), _f32c(conics.detach()), _f32c(opacities.detach())
-    colors, depths = _f32c(colors.detach()), _f32c(depths.detach())
+    colors, depths = _f32c(colors.detach()).view(C * N, colors.shape[2]), _f32c(depths.detach()).view(C * N)
     fg_rgb, fg_depth = _f32c(fg_rgb.detach()), _f32c(fg_depth.detach())
     render = _f32c(render_colors.detach())
     alphas = _f32c(render_alphas.detach()).reshape(C, height, width)
     bd = backdrop_f32(backdrop, dev)
-    tl = TileLists()
-    tl.flatten_ids = flatten_ids.to(torch.int32).contiguous()
-    end = torch.full((1,), tl.flatten_ids.numel(), dtype=torch.int32, device=dev)
-    offsets_ext = torch.cat([isect_offsets.reshape(-1).to(torch.int32), end])
     rgb = torch.empty(C, height, width, 3, dtype=torch.float32, device=dev)
     depth = torch.empty(C, height, width, dtype=torch.float32, device=dev)
     vis = torch.empty(C, height, width, dtype=torch.float32, device=dev) if return_visibility else None
-    for c in range(C):       # ids in flatten_ids are cam*N + gaussian: the kernel gets the flat [C*N,...] views
-        raster_over_opaque_raw(tl, means2d.view(C * N, 2), conics.view(C * N, 3), opacities.view(C * N),
-                               colors.view(C * N, D), depths.view(C * N), fg_rgb[c], fg_depth[c], render[c], alphas[c],
-                               width, height, backdrop=bd, out=(rgb[c], depth[c], vis[c] if return_visibility else None),
-                               use_group_order=False, tile_offsets=offsets_ext[c * n_tiles:])
+    for c in range(C):
+        raster_over_opaque_raw(tl, *flat, colors, depths, fg_rgb[c], fg_depth[c], render[c], alphas[c], width, height,
+                               backdrop=bd, out=(rgb[c], depth[c], vis[c] if return_visibility else None),
+                               use_group_order=False, tile_offsets=tl.tile_offsets[c * n_tiles:])
     return (rgb, depth, vis) if return_visibility else (rgb, depth)
 
 
@@ -1310,33 +1291,19 @@ def rasterize_votes(means2d: Tensor, conics: Tensor, opacities: Tensor, masks: T
     cameras and all pixels with mask == k of the weight the blend gives Gaussian i there, as unsigned Q32 fixed point
     (votes_to_float).  Integers: the same bits in every run and under any split of the cameras over calls; votes=
     continues an earlier call.  assign_classes turns them into class ids.  Not differentiable."""
-    if tile_size != TILE_SIZE:
-        raise NotImplementedError(f"tile_size must be {TILE_SIZE}")
-    require_device(means2d, conics, opacities, masks, isect_offsets, flatten_ids, votes)
-    C, N = means2d.shape[0], means2d.shape[1]
-    if conics.shape != (C, N, 3) or opacities.shape != (C, N) or means2d.shape != (C, N, 2):
-        raise ValueError("expected means2d [C,N,2], conics [C,N,3], opacities [C,N]")
-    n_classes = check_n_classes(n_classes)
     width, height = int(image_width), int(image_height)
-    tile_w, tile_h = -(-width // TILE_SIZE), -(-height // TILE_SIZE)
-    if tuple(isect_offsets.shape) != (C, tile_h, tile_w):
-        raise ValueError(f"isect_offsets shape {tuple(isect_offsets.shape)} != {(C, tile_h, tile_w)}")
+    tl, n_tiles = _gsplat_lists(isect_offsets, flatten_ids, means2d.shape[0], width, height, tile_size,
+                                means2d, conics, opacities, masks, votes)
+    C, N, flat = _flat_arrays(means2d, conics, opacities)
+    n_classes = check_n_classes(n_classes)
     if tuple(masks.shape) != (C, height, width) or masks.dtype != torch.uint8:
         raise ValueError(f"masks must be a uint8 tensor {(C, height, width)}")
     masks = masks.contiguous()
-    n_tiles = tile_w * tile_h
-    dev = means2d.device
     if votes is None:
-        votes = torch.zeros(N, n_classes, dtype=torch.int64, device=dev)
+        votes = torch.zeros(N, n_classes, dtype=torch.int64, device=means2d.device)
     elif tuple(votes.shape) != (N, n_classes):
         raise ValueError(f"votes shape {tuple(votes.shape)} != {(N, n_classes)}")
-    means2d, conics, opacities = _f32c(means2d.detach()), _f32c(conics.detach()), _f32c(opacities.detach())
-    tl = TileLists()
-    tl.flatten_ids = flatten_ids.to(torch.int32).contiguous()
-    end = torch.full((1,), tl.flatten_ids.numel(), dtype=torch.int32, device=dev)
-    offsets_ext = torch.cat([isect_offsets.reshape(-1).to(torch.int32), end])
-    for c in range(C):       # ids in flatten_ids are cam*N + gaussian: the flat [C*N,...] views, rows from c*N
-        raster_votes_raw(tl, masks[c], n_classes, width, height, votes, means2d.view(C * N, 2), conics.view(C * N, 3),
-                         opacities.view(C * N), row_offset=c * N, use_group_order=False,
-                         tile_offsets=offsets_ext[c * n_tiles:])
+    for c in range(C):       # ids in flatten_ids are cam*N + gaussian: camera c's votes go to rows id - c*N
+        raster_votes_raw(tl, masks[c], n_classes, width, height, votes, *flat, row_offset=c * N, use_group_order=False,
+                         tile_offsets=tl.tile_offsets[c * n_tiles:])
     return votes

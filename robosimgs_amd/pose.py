@@ -32,7 +32,7 @@ from torch import Tensor
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from ._lib import check, ptr, require_device, stream_handle
+from ._lib import aligned_workspace, check, ptr, require_device, stream_handle
 from .gaussians import _sh_fit_basis
 from .ops import _f32c
 
@@ -181,12 +181,7 @@ def pose_bwd_raw(means: Tensor, quats: Tensor, scales: Tensor, sh: Optional[Tens
         for name, like in (("v_means", means), ("v_quats", quats), ("v_scales", scales), ("v_sh", sh)):
             if like is not None and res.get(name) is None:
                 res[name] = torch.empty_like(like)
-    need = workspace_bytes(n, G)
-    if workspace is None:
-        workspace = torch.empty(need + 256, dtype=torch.uint8, device=dev)
-    elif workspace.dtype != torch.uint8 or not workspace.is_contiguous():
-        raise ValueError("workspace must be a contiguous uint8 tensor")
-    pad = -workspace.data_ptr() % 256
+    workspace, pad = aligned_workspace(workspace, workspace_bytes(n, G), dev)
     check(_lib.lib().mgs_pose_bwd(
         n, ptr(means), ptr(quats), ptr(scales), int(sh_degree), int(sh.shape[1]) if sh is not None else 1, ptr(sh),
         ptr(group_ids), G, ptr(xforms), ptr(sh_rot) if sh is not None else None,

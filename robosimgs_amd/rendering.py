@@ -127,7 +127,7 @@ class _RenderSH(torch.autograd.Function):
         C = viewmats.shape[0]
         dev = means.device
         width, height, ch, cap = cfg.width, cfg.height, cfg.channels, cfg.capacity
-        tile_w, tile_h = -(-width // TILE_SIZE), -(-height // TILE_SIZE)
+        tile_w, tile_h = ops.tile_grid(width, height)
         render = torch.empty(C, height, width, ch, dtype=torch.float32, device=dev)
         alphas = torch.empty(C, height, width, dtype=torch.float32, device=dev)
         # last_ids (and the backward's slot map) only when some input wants a gradient
@@ -247,7 +247,7 @@ class _RenderSH(torch.autograd.Function):
                 ctx.train_state, render_out, alphas, v_render, v_alphas, absgrad=cfg.absgrad,
                 want_viewmats=ctx.needs_input_grad[5], raw=cfg.raw)
         else:
-            tile_w, tile_h = -(-cfg.width // TILE_SIZE), -(-cfg.height // TILE_SIZE)
+            tile_w, tile_h = ops.tile_grid(cfg.width, cfg.height)
             # "RGB+ED": the raster backward's prologue undoes the divide by max(alpha, 1e-10) itself
             # (expected_render=...); only a background gradient needs the converted cotangent
             # the first camera overwrites the outputs, later ones accumulate: no zero-fill pass
@@ -465,7 +465,7 @@ def rasterization(means: Tensor, quats: Tensor, scales: Tensor, opacities: Tenso
     antialiased = rasterize_mode == "antialiased"
     want_rgb = render_mode.startswith("RGB")
     want_depth = render_mode != "RGB"
-    tile_w, tile_h = -(-width // TILE_SIZE), -(-height // TILE_SIZE)
+    tile_w, tile_h = ops.tile_grid(width, height)
     meta: Dict = _Meta({"width": width, "height": height, "tile_size": TILE_SIZE,
                         "tile_width": tile_w, "tile_height": tile_h, "n_cameras": C,
                         "camera_ids": None, "gaussian_ids": None})

@@ -264,6 +264,18 @@ def test_deform_gaussians_contract(D):
         assert torch.equal(c[k], b[k].index_select(0, order)), k
 
 
+def test_an_empty_scene_deforms_to_an_empty_scene(D):
+    """No Gaussian: every zero-element tensor has the same (null) address, which is no aliasing of the rest state."""
+    _, _, _, X, tensors = scene(8, 40, 5)
+    empty = {k: (v[:0].contiguous() if torch.is_tensor(v) else v) for k, v in tensors.items()}
+    binding = D.bind_particles(empty["means"], _t(X))
+    assert binding.n == 0 and binding.m == 40
+    for mode in ("rigid", "affine"):
+        out = D.deform_gaussians(empty, binding, _t(DR.move(X, "bend")), mode=mode)
+        assert [tuple(out[k].shape) for k in ("means", "quats", "scales")] == [(0, 3), (0, 4), (0, 3)]
+        assert out["colors"] is empty["colors"] and out["opacities"] is empty["opacities"]
+
+
 # ---- 5. graph capture ------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("mode", ["rigid", "affine"])
 def test_apply_replays_in_a_graph(D, mode):

@@ -189,6 +189,37 @@ def test_slanted_plane_through_the_scene(ops, stage, kind):
         assert float(np.abs(nxt.t_f[moved] - ref.t_f[moved]).max()) > 0.01
 
 
+def test_raster_over_opaque_raw_refuses_lists_the_kernel_cannot_read(ops, stage):
+    """The lists reach the kernel as raw pointers: a short, an int64 or a strided one is a ValueError that names it, raised
+    before anything is launched; the same call with good lists afterwards gives the bytes it gave before."""
+    assert stage.tw * stage.th >= 2
+    fg = tuple(_t(x) for x in stage.fg("main"))
+    tl = stage.tl
+
+    def call(lists, **kw):
+        return ops.raster_over_opaque_raw(lists, stage.m2d, stage.con, stage.opac, stage.feats, stage.z, *fg, stage.render,
+                                          stage.alphas, stage.w, stage.h, **kw)
+
+    def lists(**changed):
+        out = ops.TileLists()
+        for name in ("flatten_ids", "tile_offsets", "group_order"):
+            setattr(out, name, changed.get(name, getattr(tl, name)))
+        return out
+
+    before = call(tl)
+    doubled = torch.stack([tl.tile_offsets, tl.tile_offsets], dim=1)
+    for bad_tl, kw, word in ((tl, dict(tile_offsets=tl.tile_offsets[1:]), "tile_offsets"),
+                             (lists(tile_offsets=tl.tile_offsets[1:]), {}, "tile_offsets"),
+                             (lists(flatten_ids=tl.flatten_ids.long()), {}, "flatten_ids"),
+                             (tl, dict(tile_offsets=doubled[:, 0]), "tile_offsets"),
+                             (lists(tile_offsets=tl.tile_offsets.long()), {}, "tile_offsets"),
+                             (lists(group_order=tl.group_order.long()), {}, "group_order")):
+        with pytest.raises(ValueError, match="^" + word):
+            call(bad_tl, **kw)
+    for a, b in zip(call(tl), before):
+        assert _same(a, b)
+
+
 def test_real_producer_rasterize_mesh(ops, stage):
     """The open box, scaled to three units at the world origin, rendered by rasterize_mesh from the stage's camera: its
     outputs go straight in."""

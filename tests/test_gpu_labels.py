@@ -134,6 +134,37 @@ def test_stage_matches_fp64_class_weights(ops, stages, kind, k, frame):
     assert lab[lab != LG.NONE].max() < k and bool((first[1][first[0] == LG.NONE] == 0).all())
 
 
+def test_raster_labels_raw_refuses_lists_the_kernel_cannot_read(ops, stages):
+    """The lists reach the kernel as raw pointers: a short, an int64 or a strided one is a ValueError that names it, raised
+    before anything is launched; the same call with good lists afterwards gives the bytes it gave before."""
+    st = stages("ragged")
+    assert st.tw * st.th >= 2
+    cls = _ids(LG.class_ids("random", 7, st.base("random")))
+    before = st.run(ops, cls, 7, records=True, order=True)
+
+    def lists(**changed):
+        tl = ops.TileLists()
+        for name in ("flatten_ids", "tile_offsets", "group_order"):
+            setattr(tl, name, changed.get(name, getattr(st.tl, name)))
+        return tl
+
+    doubled = torch.stack([st.tl.tile_offsets, st.tl.tile_offsets], dim=1)
+    for bad_tl, kw, word in ((st.tl, dict(tile_offsets=st.tl.tile_offsets[1:]), "tile_offsets"),
+                             (lists(tile_offsets=st.tl.tile_offsets[1:]), {}, "tile_offsets"),
+                             (lists(flatten_ids=st.tl.flatten_ids.long()), {}, "flatten_ids"),
+                             (st.tl, dict(tile_offsets=doubled[:, 0]), "tile_offsets"),
+                             (lists(tile_offsets=st.tl.tile_offsets.long()), {}, "tile_offsets"),
+                             (lists(group_order=st.tl.group_order.long()), {}, "group_order")):
+        with pytest.raises(ValueError, match="^" + word):
+            ops.raster_labels_raw(bad_tl, cls, 7, st.w, st.h, splats=st.splats, **kw)
+    with pytest.raises(ValueError, match="^means2d must be a contiguous float32 tensor"):      # the votes call's array checks
+        ops.raster_labels_raw(st.tl, cls, 7, st.w, st.h, means2d=st.m2d[:, :1], conics=st.con, opacities=st.opac)
+    with pytest.raises(ValueError, match="^splats"):
+        ops.raster_labels_raw(st.tl, cls, 7, st.w, st.h, splats=st.splats[:, :8])
+    after = st.run(ops, cls, 7, records=True, order=True)
+    assert torch.equal(after[0], before[0]) and torch.equal(after[1].view(torch.int32), before[1].view(torch.int32))
+
+
 # ---- 2. against the feature operator --------------------------------------------------------------------------------------
 @pytest.mark.parametrize("frame", list(FRAMES))
 @pytest.mark.parametrize("k", (7, 32))
