@@ -31,9 +31,9 @@ constexpr int kFwdWgWaves = 4;
 template <int CHT>
 struct QueueEntry {
   float4 geo0;                       // q0, q1, q2, A   (raster_common.h: poly_coefs; A,B,C: conic pre-scaled)
-  float4 geo1;                       // B, C, quadrant mask (bits), list index (bits)
+  float4 geo1;                       // B, C, unused (0), list index (bits)
   float4 feat[(CHT + 3) / 4];
-  float4 geo3;                       // mean - tile centre (x, y): read only by batches that test sigma >= 0
+  float4 geo3;                       // mean - tile centre (x, y): written and read only by batches that test sigma >= 0
 };
 
 // Per-pixel state.  Two ways to remember that a pixel is finished (A.2 step 9's "done" flag):
@@ -112,68 +112,108 @@ constexpr bool kMasks = CHT == 3 || CHT == 4;
 // code: the same arithmetic in the same order as blend_pixel<CHT, ., true> -- bit-identical pixels -- under an EXEC that
 // is narrowed three times instead of selects: to the quadrant's open pixels (s_mov from `alive`), by the alpha >= 1/255
 // test (v_cmpx; a Gaussian that does not count leaves the pixel untouched) and by the T (1 - alpha) > 1e-4 test
-// (v_cmpx again: what is left accumulates; the lanes the second test dropped are the pixels this Gaussian closes and
-// leave `alive`).  15 vector instructions per 64 pairs -- 12 FMA-class, two compares, one v_exp: 45 cycles by
+// (v_cmpx again: what is left accumulates; the lanes the second test dropped -- vcc & ~exec -- are the pixels this
+// Gaussian closes and leave `alive`).  On gfx9 a VOP3 v_cmpx writes a scalar destination as well as EXEC: the second
+// one names EXEC itself, so no SGPR pair is spent on the accumulating lanes.
+// 15 vector instructions per 64 pairs -- 12 FMA-class, two compares, one v_exp: 45 cycles by
 // scripts/ubench/valu_issue.hip; the round-3 form with the sign of T as the flag had two selects more (16, 51 cycles).
-// gfx940+ needs one wait state after a transcendental before its result is read.
-// WALK (one wave per tile): `quad` holds the lanes of the batch whose Gaussian reaches this quadrant and `at` the lane
-// that queued this entry.  The body runs only if bit `at` of `quad` is set (s_bitcmp1_b64 and a branch over it), and
-// `quad` is emptied the moment the quadrant's last pixel closes, so that the rest of the batch skips the quadrant:
-// scalar instructions only (re-deriving the live quadrants with ballots every 8 / 16 / 32 entries was a loss in round 3).
-template <int CHT, bool TRACK_LAST, bool WALK = false>
-__device__ __forceinline__ void blend_pixel_safe_asm(PixelState<CHT>& px, unsigned long long& alive,
-                                                     unsigned long long& quad, int at, const PixelPoly& pp,
+// gfx940+ needs one wait state after a transcendental before its result is read (s_nop 0).
+// Scalar issue slots per body: s_mov exec | s_nop | s_andn2 vcc | s_andn2 alive, and, per statement, s_mov exec, -1.
+// MGS_SAFE_BODY(k) is that body on the operands of quadrant k; it leaves EXEC narrowed and SCC = "some pixel of the
+// quadrant is still open".
+#define MGS_SAFE_BODY(k)                                                                                   \
+  "s_mov_b64 exec, %[alive" #k "]\n"                                                                       \
+  "v_fma_f32 %[t1], %[q1], %[x" #k "], %[q0]\n"           /* pair_power_poly, same order */                \
+  "v_fmac_f32 %[t1], %[q2], %[y" #k "]\n"                                                                  \
+  "v_fmac_f32 %[t1], %[A], %[xx" #k "]\n"                                                                  \
+  "v_fmac_f32 %[t1], %[B], %[xy" #k "]\n"                                                                  \
+  "v_fmac_f32 %[t1], %[C], %[yy" #k "]\n"                                                                  \
+  "v_exp_f32 %[t1], %[t1]\n"                                                                               \
+  "s_nop 0\n"                                                                                              \
+  "v_cmpx_le_f32 vcc, %[amin], %[t1]\n"                   /* EXEC = VCC = open pixels the Gaussian counts for */ \
+  "v_fma_f32 %[t0], -%[t1], %[T" #k "], %[T" #k "]\n"                                                      \
+  "v_mul_f32 %[dx], %[t1], %[T" #k "]\n"                                                                   \
+  "v_cmpx_lt_f32_e64 exec, %[tstop], %[t0]\n"             /* EXEC = those of them that accumulate */       \
+  "v_mov_b32 %[T" #k "], %[t0]\n"                                                                          \
+  "v_fmac_f32 %[c0" #k "], %[dx], %[f0]\n"                                                                 \
+  "v_fmac_f32 %[c1" #k "], %[dx], %[f1]\n"                                                                 \
+  "v_fmac_f32 %[c2" #k "], %[dx], %[f2]\n"                                                                 \
+  ".if %[four]\n"                                                                                          \
+  "v_fmac_f32 %[c3" #k "], %[dx], %[f3]\n"                                                                 \
+  ".endif\n"                                                                                               \
+  ".if %[track]\n"                                                                                         \
+  "v_mov_b32 %[last" #k "], %[idx]\n"                                                                      \
+  ".endif\n"                                                                                               \
+  "s_andn2_b64 vcc, vcc, exec\n"                          /* counted but not accumulated: the pixels this Gaussian closes */ \
+  "s_andn2_b64 %[alive" #k "], %[alive" #k "], vcc\n"     /* (SCC = some pixel of the quadrant is still open) */
+// One wave per tile: `quad` holds the lanes of the batch whose Gaussian reaches quadrant k and `at` the lane that queued
+// this entry.  The body runs only if bit `at` of `quad` is set (s_bitcmp1_b64 and a branch over it), and `quad` is
+// emptied the moment the quadrant's last pixel closes (one s_cselect_b64 on the SCC above), so that the rest of the batch
+// skips the quadrant: scalar instructions only (re-deriving the live quadrants with ballots every 8 / 16 / 32 entries
+// was a loss in round 3).
+#define MGS_SAFE_WALK_BODY(k)                                                                              \
+  "s_bitcmp1_b64 %[quad" #k "], %[at]\n"                                                                   \
+  "s_cbranch_scc0 .Lmgs_next_quadrant" #k "_%=\n"                                                          \
+  MGS_SAFE_BODY(k)                                                                                         \
+  "s_cselect_b64 %[quad" #k "], %[quad" #k "], 0\n"                                                        \
+  ".Lmgs_next_quadrant" #k "_%=:\n"
+#define MGS_SAFE_STATE(k, px, alive_k, c3_k)                                                                            \
+  [alive##k] "+s"(alive_k), [T##k] "+v"((px).T), [c0##k] "+v"((px).C[0]), [c1##k] "+v"((px).C[1]), [c2##k] "+v"((px).C[2]), \
+  [c3##k] "+v"(c3_k), [last##k] "+v"((px).last)
+#define MGS_SAFE_PIXEL(k, pp) [x##k] "v"((pp).x), [y##k] "v"((pp).y), [xx##k] "v"((pp).xx), [xy##k] "v"((pp).xy), [yy##k] "v"((pp).yy)
+// dx: the weight w, t0: T (1 - alpha), t1: exponent, then alpha
+#define MGS_SAFE_TEMPS [dx] "=&v"(dx), [t0] "=&v"(t0), [t1] "=&v"(t1)
+#define MGS_SAFE_ENTRY                                                                                                     \
+  [q0] "v"(q0), [q1] "v"(q1), [q2] "v"(q2), [A] "v"(A), [B] "v"(B), [C] "v"(C), [f0] "v"(feat[0]), [f1] "v"(feat[1]),       \
+  [f2] "v"(feat[2]), [f3] "v"(f3), [amin] "s"(amin), [tstop] "s"(tstop), [four] "n"(CHT == 4 ? 1 : 0),                      \
+  [track] "n"(TRACK_LAST ? 1 : 0), [idx] "v"(idx)
+
+// One wave per 8x8 block: one body per queue entry.
+template <int CHT, bool TRACK_LAST>
+__device__ __forceinline__ void blend_pixel_safe_asm(PixelState<CHT>& px, unsigned long long& alive, const PixelPoly& pp,
                                                      float q0, float q1, float q2, float A, float B, float C,
                                                      const float* feat, int idx) {
   static_assert(CHT == 3 || CHT == 4, "hand-written blend: 3 or 4 channels");
-  float dx, t0, t1;               // dx: the weight w, t0: T (1 - alpha), t1: exponent, then alpha
-  unsigned long long acc;         // lanes that accumulate
+  float dx, t0, t1;
   const float amin = kAlphaMin, tstop = kTStop;
   float c3 = CHT == 4 ? px.C[CHT - 1] : 0.f;
   const float f3 = CHT == 4 ? feat[CHT - 1] : 0.f;
-  asm volatile(
-      ".if %[walk]\n"
-      "s_bitcmp1_b64 %[quad], %[at]\n"
-      "s_cbranch_scc0 .Lmgs_next_quadrant_%=\n"
-      ".endif\n"
-      "s_mov_b64 exec, %[alive]\n"
-      "v_fma_f32 %[t1], %[q1], %[x], %[q0]\n"          // pair_power_poly, same order
-      "v_fmac_f32 %[t1], %[q2], %[y]\n"
-      "v_fmac_f32 %[t1], %[A], %[xx]\n"
-      "v_fmac_f32 %[t1], %[B], %[xy]\n"
-      "v_fmac_f32 %[t1], %[C], %[yy]\n"
-      "v_exp_f32 %[t1], %[t1]\n"
-      "s_nop 0\n"
-      "v_cmpx_le_f32 vcc, %[amin], %[t1]\n"            // EXEC = VCC = open pixels the Gaussian counts for
-      "v_fma_f32 %[t0], -%[t1], %[T], %[T]\n"
-      "v_mul_f32 %[dx], %[t1], %[T]\n"
-      "v_cmpx_lt_f32_e64 %[acc], %[tstop], %[t0]\n"    // EXEC = acc = those of them that accumulate
-      "v_mov_b32 %[T], %[t0]\n"
-      "v_fmac_f32 %[c0], %[dx], %[f0]\n"
-      "v_fmac_f32 %[c1], %[dx], %[f1]\n"
-      "v_fmac_f32 %[c2], %[dx], %[f2]\n"
-      ".if %[four]\n"
-      "v_fmac_f32 %[c3], %[dx], %[f3]\n"
-      ".endif\n"
-      ".if %[track]\n"
-      "v_mov_b32 %[last], %[idx]\n"
-      ".endif\n"
-      "s_xor_b64 vcc, vcc, %[acc]\n"                   // counted but not accumulated: the pixels this Gaussian closes
-      "s_andn2_b64 %[alive], %[alive], vcc\n"          // (SCC = some pixel of the quadrant is still open)
-      ".if %[walk]\n"
-      "s_cselect_b64 vcc, -1, 0\n"
-      "s_and_b64 %[quad], %[quad], vcc\n"
-      ".endif\n"
-      "s_mov_b64 exec, -1\n"
-      ".Lmgs_next_quadrant_%=:\n"
-      : [dx] "=&v"(dx), [t0] "=&v"(t0), [t1] "=&v"(t1), [acc] "=&s"(acc), [alive] "+s"(alive), [quad] "+s"(quad),
-        [T] "+v"(px.T), [c0] "+v"(px.C[0]), [c1] "+v"(px.C[1]), [c2] "+v"(px.C[2]), [c3] "+v"(c3), [last] "+v"(px.last)
-      : [q0] "v"(q0), [q1] "v"(q1), [q2] "v"(q2), [x] "v"(pp.x), [y] "v"(pp.y), [xx] "v"(pp.xx), [xy] "v"(pp.xy),
-        [yy] "v"(pp.yy), [A] "v"(A), [B] "v"(B), [C] "v"(C),
-        [f0] "v"(feat[0]), [f1] "v"(feat[1]), [f2] "v"(feat[2]), [f3] "v"(f3), [amin] "s"(amin), [tstop] "s"(tstop),
-        [four] "n"(CHT == 4 ? 1 : 0), [track] "n"(TRACK_LAST ? 1 : 0), [idx] "v"(idx), [walk] "n"(WALK ? 1 : 0), [at] "s"(at)
-      : "vcc", "scc");            // (s_xor / s_andn2 write SCC: the loop counter's compare must not straddle the body)
+  asm volatile(MGS_SAFE_BODY(0)
+               "s_mov_b64 exec, -1\n"
+               : MGS_SAFE_TEMPS, MGS_SAFE_STATE(0, px, alive, c3)
+               : MGS_SAFE_ENTRY, MGS_SAFE_PIXEL(0, pp)
+               : "vcc", "scc");            // (the s_andn2 write SCC: the loop counter's compare must not straddle the body)
   if (CHT == 4) px.C[CHT - 1] = c3;
+}
+
+// One wave per tile: the bodies of an entry's four quadrants as ONE statement.  EXEC is restored once, at its end (a
+// skipped body leaves the EXEC of the one before it, and every body starts by setting its own), and the compiler's
+// wait state between two asm statements that share a register -- an s_nop 0 in front of each, taken or skipped -- is
+// paid once per entry instead of four times.  Measured against the one-statement-per-quadrant forms in
+// scripts/ubench/blend_body_scalar.hip (profiles/raster_scalar/README.md).
+template <int CHT, bool TRACK_LAST>
+__device__ __forceinline__ void blend_entry_safe_asm(PixelState<CHT>* st, unsigned long long* alive, unsigned long long* quad,
+                                                     int at, const PixelPoly* pq, float q0, float q1, float q2, float A,
+                                                     float B, float C, const float* feat, int idx) {
+  static_assert(CHT == 3 || CHT == 4, "hand-written blend: 3 or 4 channels");
+  float dx, t0, t1;
+  const float amin = kAlphaMin, tstop = kTStop;
+  float c3[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) c3[k] = CHT == 4 ? st[k].C[CHT - 1] : 0.f;
+  const float f3 = CHT == 4 ? feat[CHT - 1] : 0.f;
+  asm volatile(MGS_SAFE_WALK_BODY(0) MGS_SAFE_WALK_BODY(1) MGS_SAFE_WALK_BODY(2) MGS_SAFE_WALK_BODY(3)
+               "s_mov_b64 exec, -1\n"
+               : MGS_SAFE_TEMPS, MGS_SAFE_STATE(0, st[0], alive[0], c3[0]), MGS_SAFE_STATE(1, st[1], alive[1], c3[1]),
+                 MGS_SAFE_STATE(2, st[2], alive[2], c3[2]), MGS_SAFE_STATE(3, st[3], alive[3], c3[3]),
+                 [quad0] "+s"(quad[0]), [quad1] "+s"(quad[1]), [quad2] "+s"(quad[2]), [quad3] "+s"(quad[3])
+               : MGS_SAFE_ENTRY, [at] "s"(at), MGS_SAFE_PIXEL(0, pq[0]), MGS_SAFE_PIXEL(1, pq[1]), MGS_SAFE_PIXEL(2, pq[2]),
+                 MGS_SAFE_PIXEL(3, pq[3])
+               : "vcc", "scc");
+  if (CHT == 4) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) st[k].C[CHT - 1] = c3[k];
+  }
 }
 
 // DATASET (4 channels, inference, "ED"): the epilogue writes the dataset frame the reference reads -- RGBA8 + ray distance,
@@ -338,14 +378,11 @@ __global__ __launch_bounds__(64 * (TRACK_LAST ? 1 : kFwdWgWaves), (CHT <= 4 ? kF
     MGS_STAT(1, __popcll(keep));
     MGS_STAT(5, 1);
     if (queued) {
-      unsigned qmask = 0;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) qmask |= __builtin_amdgcn_inverse_ballot_w64(reach[k]) ? 1u << k : 0u;
       QueueEntry<CHT>& e = queue[mask_rank(keep)];
       const QueueGeo q = queue_geometry(c_xy, c_ca, c_cb, c_cc, c_op, fr.ctr_x, fr.ctr_y);
       e.geo0 = q.geo0;
-      e.geo1 = make_float4(q.sB, q.sC, __uint_as_float(qmask), __int_as_float(c_idx));
-      e.geo3 = make_float4(q.m_x, q.m_y, 0.f, 0.f);
+      e.geo1 = make_float4(q.sB, q.sC, 0.f, __int_as_float(c_idx));
+      if (!all_safe) e.geo3 = make_float4(q.m_x, q.m_y, 0.f, 0.f);
       pack_features(c_feat, e.feat);
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -363,24 +400,25 @@ __global__ __launch_bounds__(64 * (TRACK_LAST ? 1 : kFwdWgWaves), (CHT <= 4 ? kF
       const int idx = __float_as_int(g1.w);
       // (measured and rejected, profiles/r3/00_experiments.md: one straight-line body per quadrant SET behind a
       //  switch on the mask, 268-278 us against 197; the live quadrants re-derived every 8 / 16 / 32 entries, +2 %)
-      auto quad = [&](auto kc) {
-        constexpr int k = decltype(kc)::value;
-        // (kMasks: reach[k] is emptied the moment the quadrant's last pixel closes, blend_pixel_safe_asm)
-        MGS_STAT(2, (unsigned)((reach[k] >> at) & 1ull));
-        if constexpr (kMasks<CHT> && SAFE) {
-          // (the body tests reach[k] at `at` itself, s_bitcmp1_b64 and a branch: the compiler's own test of a
-          //  variable bit of a 64-bit mask is a shift, an AND and a compare on top of the branch)
-          blend_pixel_safe_asm<CHT, TRACK_LAST, true>(st[k], alive[k], reach[k], at, fr.pq[k], g0.x, g0.y, g0.z, g0.w, g1.x,
-                                                      g1.y, feat, idx);
-        } else if ((reach[k] >> at) & 1ull) {
-          blend_pixel<CHT, TRACK_LAST, SAFE, kMasks<CHT>>(st[k], alive[k], fr.pq[k], g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g3.x,
-                                                           g3.y, feat, idx);
-        }
-      };
-      quad(std::integral_constant<int, 0>{});
-      quad(std::integral_constant<int, 1>{});
-      quad(std::integral_constant<int, 2>{});
-      quad(std::integral_constant<int, 3>{});
+      // (kMasks: reach[k] is emptied the moment the quadrant's last pixel closes, blend_entry_safe_asm)
+#pragma unroll
+      for (int k = 0; k < 4; ++k) MGS_STAT(2, (unsigned)((reach[k] >> at) & 1ull));
+      if constexpr (kMasks<CHT> && SAFE) {
+        // (the bodies test reach[k] at `at` themselves, s_bitcmp1_b64 and a branch: the compiler's own test of a
+        //  variable bit of a 64-bit mask is a shift, an AND and a compare on top of the branch)
+        blend_entry_safe_asm<CHT, TRACK_LAST>(st, alive, reach, at, fr.pq, g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, feat, idx);
+      } else {
+        auto quad = [&](auto kc) {
+          constexpr int k = decltype(kc)::value;
+          if ((reach[k] >> at) & 1ull)
+            blend_pixel<CHT, TRACK_LAST, SAFE, kMasks<CHT>>(st[k], alive[k], fr.pq[k], g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g3.x,
+                                                             g3.y, feat, idx);
+        };
+        quad(std::integral_constant<int, 0>{});
+        quad(std::integral_constant<int, 1>{});
+        quad(std::integral_constant<int, 2>{});
+        quad(std::integral_constant<int, 3>{});
+      }
     };
     auto walk = [&](auto safe_tag) {
       constexpr bool SAFE = decltype(safe_tag)::value;
@@ -576,7 +614,8 @@ __global__ __launch_bounds__(256) void raster_fwd_q_kernel(    // (bounded to 64
       const QueueGeo q = queue_geometry(c_xy, c_ca, c_cb, c_cc, c_op, tile_x + 8.f, tile_y + 8.f);
       e.geo0 = q.geo0;
       e.geo1 = make_float4(q.sB, q.sC, 0.f, __int_as_float(c_idx));
-      e.geo3 = make_float4(q.m_x, q.m_y, 0.f, 0.f);
+      // (the instantiations that are launched, <= 4 channels: behind the branch <8, true> takes 74 VGPRs instead of 72)
+      if (CHT > 4 || !all_safe) e.geo3 = make_float4(q.m_x, q.m_y, 0.f, 0.f);
       pack_features(c_feat, e.feat);
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -604,8 +643,7 @@ __global__ __launch_bounds__(256) void raster_fwd_q_kernel(    // (bounded to 64
         float feat[CHT];
         unpack_features(ef, feat);
         if constexpr (kMasks<CHT> && SAFE) {
-          unsigned long long unused = 0;
-          blend_pixel_safe_asm<CHT, TRACK_LAST>(st, alive, unused, 0, pp, g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, feat, __float_as_int(g1.w));
+          blend_pixel_safe_asm<CHT, TRACK_LAST>(st, alive, pp, g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, feat, __float_as_int(g1.w));
         } else {
           float4 g3 = make_float4(0.f, 0.f, 0.f, 0.f);
           if constexpr (!SAFE) g3 = e.geo3;

@@ -101,3 +101,7 @@ for name, st in state.items():
     tt = {k: float(np.median(v[1:])) for k, v in st["t"].items()}
     print(f"{name}: projection {tt['proj']:.1f} us, binning {tt['proj+binning'] - tt['proj']:.1f} us, raster per tile {tt['tile']:.1f} us, per block "
           f"{tt['block']:.1f} us, 3 frames in flight {tt['fps']:.0f} frames/s  (medians of {len(st['t']['tile']) - 1} interleaved rounds)")
+    # every turn, the dropped first one included: a gain counts when the two builds' turns 2.. do not overlap
+    for k, unit in (("fps", "frames/s"), ("tile", "us"), ("block", "us")):
+        v = st["t"][k]
+        print(f"  {k} by turn ({unit}): " + " ".join(f"{x:.1f}" for x in v) + f"   turns 2..: min {min(v[1:]):.1f} max {max(v[1:]):.1f}")
