@@ -3,7 +3,7 @@ FrameRenderer, and in front of it a triangle mesh -- the reference's open box, i
 MeshRenderer and composited by depth.  The loop of examples/articulated_scene.py with the stand-in disc replaced by a
 mesh render.  Synthetic background, so it runs anywhere an MI355X is visible:
 
-    python examples/hybrid_scene.py [n_frames] [--exact]
+    python examples/hybrid_scene.py [n_frames] [--exact] [--textured]
 
 The mesh render and the composite run eagerly on the consumer stream, once per fetched frame: there is no graph around
 them (composite_over builds its backdrop tensor from a host list and allocates its outputs on every call, so it is not
@@ -12,6 +12,10 @@ capture-safe; and DESIGN.md 4.16 says why mesh kernels stay out of FrameRenderer
 --exact renders the background eagerly through rasterization(foreground=...) instead and writes its hybrid_rgb: every
 pixel's own front-to-back blend stopped at the mesh's depth, where composite_over compares the mesh with
 the frame's expected depth once.  No FrameRenderer and no graph on that path.
+
+--textured gives the box a procedural base-colour texture generated here (planks and a coarse checker, 512 x 512, no asset
+file) with planar uvs per face; MeshRenderer packs it and builds its mipmaps once, and render() filters it trilinearly
+(DESIGN.md 4.18).
 """
 import math
 import os
@@ -23,8 +27,8 @@ import torch
 
 ROOT = __file__.rsplit("/", 2)[0]
 sys.path.insert(0, ROOT)
-from robosimgs_amd import (FrameRenderer, Mesh, MeshRenderer, camera_ring, composite_over, frame_to_u8,  # noqa: E402
-                           rasterization, synthetic_scene)
+from robosimgs_amd import (FrameRenderer, Mesh, MeshRenderer, Texture, camera_ring, composite_over,  # noqa: E402
+                           frame_to_u8, rasterization, synthetic_scene)
 from robosimgs_amd.articulation import Hinge  # noqa: E402
 
 
@@ -40,8 +44,29 @@ def open_box():
     return Mesh.merge([lid, body], link_ids=[0, -1]), Hinge(torch.from_numpy(joint))
 
 
+def procedural_texture(side=512):
+    """uint8 [side,side,3]: wooden planks (a slow sine grain per plank) under a coarse checker."""
+    y, x = np.mgrid[0:side, 0:side] / side
+    plank = np.floor(x * 8)
+    grain = 0.5 + 0.5 * np.sin(2 * np.pi * (y * 3 + 0.37 * plank) + 6 * np.sin(2 * np.pi * x * 8))
+    base = np.stack([0.55 + 0.25 * grain, 0.36 + 0.18 * grain, 0.2 + 0.1 * grain], -1)
+    check = ((np.floor(x * 4) + np.floor(y * 4)) % 2)[..., None]
+    return np.clip(np.round(255 * base * (0.8 + 0.2 * check)), 0, 255).astype(np.uint8)
+
+
+def textured(box):
+    """`box` with planar uvs (the two longer axes of its bounding box, two repeats across) and one texture on every face."""
+    v = box.vertices.numpy()
+    axes = np.argsort(np.ptp(v, axis=0))[1:]
+    uv = (2.0 * (v[:, axes] - v[:, axes].min(0)) / np.ptp(v[:, axes], axis=0)).astype(np.float32)
+    faces = box.faces.numpy()
+    return Mesh(box.vertices, box.faces, box.vertex_colors, box.face_colors, box.link_ids, uv[faces],
+                np.zeros(len(faces), np.int32), [Texture(procedural_texture(), "repeat", "mirror")])
+
+
 def main():
-    argv = [a for a in sys.argv[1:] if a != "--exact"]
+    flags = ("--exact", "--textured")
+    argv = [a for a in sys.argv[1:] if a not in flags]
     exact = "--exact" in sys.argv[1:]
     n_frames = int(argv[0]) if argv else 60
     W, H = 1280, 720
@@ -50,6 +75,8 @@ def main():
     r = None if exact else FrameRenderer(scene.to_torch("cuda", 3), W, H, render_mode="RGB+ED", frames_in_flight=3,
                       sizing_camera=(cams[0].viewmat(), cams[0].K), capacity_margin=2.0)
     box, hinge = open_box()
+    if "--textured" in sys.argv[1:]:
+        box = textured(box)                                              # the vertex colours stay on as the tint
     mesh = MeshRenderer(box.to("cuda"), W, H, headlight=True)           # workspace and outputs allocated once
     # per frame: the camera and the lid's pose, uploaded before the loop so that the loop itself copies nothing
     angles = 0.6 * (1.0 - np.cos(2 * np.pi * np.arange(n_frames) / n_frames)) / 2

@@ -40,7 +40,10 @@
  * Limits, refused with MGS_ERR_INVALID_ARGUMENT and a message before any launch: n_cams < 1; V < 1; F < 1 (F is an int:
  * below 2^31); width or height outside 1 .. 16368; near_plane <= 0 or NaN; far_plane < near_plane or NaN; ambient outside
  * 0 .. 1; a null pointer that is not marked nullable; L < 0, or L > 0 without rotations and translations; a workspace that
- * is too small.  Every product of C H W or C V is formed in 64 bits. */
+ * is too small.  Every product of C H W or C V is formed in 64 bits.
+ *
+ * Textured meshes (per-corner uvs, base-colour textures, wrap modes, mipmaps) are mgs_mesh_texture.h's: entry points of
+ * their own beside these, which they leave as they are. */
 #ifndef MGS_MESH_H_
 #define MGS_MESH_H_
 

@@ -52,10 +52,11 @@ def __getattr__(name):  # lazy: keeps `import robosimgs_amd` torch-free for host
                 "deform_apply_sh_raw"):
         from . import deform
         return getattr(deform, name)
-    if name == "Mesh":
+    if name in ("Mesh", "Texture"):
         from . import mesh
-        return mesh.Mesh
-    if name in ("rasterize_mesh", "MeshRenderer", "mesh_vertices", "mesh_raster", "mesh_resolve", "mesh_workspace_bytes"):
+        return getattr(mesh, name)
+    if name in ("rasterize_mesh", "MeshRenderer", "mesh_vertices", "mesh_raster", "mesh_resolve", "mesh_workspace_bytes",
+                "TextureSet", "build_texture_set"):
         from . import mesh_render
         return getattr(mesh_render, name)
     if name in ("l1_loss", "l1_ssim_loss", "ssim", "unit_gradient"):

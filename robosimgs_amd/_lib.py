@@ -143,6 +143,14 @@ _MESH_SIGNATURES = {
     "mgs_mesh_resolve": ([i, i, p, i, p, p, p, p, i, i, i, f, p, c_size_t, p, p, p, p, p], c_int),
     "mgs_rasterize_mesh": ([i, i, p, p, i, p, p, p, p, p, i, p, p, p, i, i, f, f, i, i, f, p, c_size_t, p, p, p, p, p, p], c_int),
 }
+# every function include/mgs_mesh_texture.h declares (the same libraries again): the layout is a host-only query; wraps and
+# descriptors of the layout call, the colours and normals are nullable
+_MESH_TEXTURE_SIGNATURES = {
+    "mgs_mesh_texture_layout": ([i, p, p, p, POINTER(c_size_t)], c_int),
+    "mgs_mesh_build_mips": ([i, p, p, c_size_t, p], c_int),
+    "mgs_mesh_resolve_textured": (_MESH_SIGNATURES["mgs_mesh_resolve"][0][:-1] + [p, p, i, p, p, c_size_t, i, p], c_int),
+    "mgs_rasterize_mesh_textured": (_MESH_SIGNATURES["mgs_rasterize_mesh"][0][:-1] + [p, p, i, p, p, c_size_t, i, p], c_int),
+}
 # every function include/mgs_hybrid.h declares (the same libraries again): backdrop, tile_group_order and fg_visibility
 # are nullable
 _HYBRID_SIGNATURES = {
@@ -152,7 +160,7 @@ del p, i, f, u32, img
 # what _load binds: a new header adds its table here
 _SIGNATURE_TABLES = (_SIGNATURES, _OPTIM_SIGNATURES, _REFINE_SIGNATURES, _LABEL_SIGNATURES, _LIFT_SIGNATURES,
                      _HINGE_SIGNATURES, _POSE_SIGNATURES, _DEFORM_SIGNATURES, _DEFORM_SH_SIGNATURES, _MESH_SIGNATURES,
-                     _HYBRID_SIGNATURES)
+                     _MESH_TEXTURE_SIGNATURES, _HYBRID_SIGNATURES)
 EXPORTS = list(_SIGNATURES)
 OPTIM_EXPORTS = list(_OPTIM_SIGNATURES)
 REFINE_EXPORTS = list(_REFINE_SIGNATURES)
@@ -164,7 +172,12 @@ DEFORM_EXPORTS = list(_DEFORM_SIGNATURES)
 DEFORM_SH_EXPORTS = list(_DEFORM_SH_SIGNATURES)
 MESH_EXPORTS = list(_MESH_SIGNATURES)
 HYBRID_EXPORTS = list(_HYBRID_SIGNATURES)
+MESH_TEXTURE_EXPORTS = list(_MESH_TEXTURE_SIGNATURES)
 MESH_MAX_SIDE, MESH_LARGE_BLOCKS = 16368, 15   # MGS_MESH_MAX_SIDE, MGS_MESH_LARGE_BLOCKS
+# MGS_MESH_TEXTURE_MAX_SIDE, MGS_MESH_MAX_TEXTURES, MGS_MESH_TEXTURE_DESC_WORDS, MGS_MESH_WRAP_*, MGS_MESH_FILTER_*
+MESH_TEXTURE_MAX_SIDE, MESH_MAX_TEXTURES, MESH_TEXTURE_DESC_WORDS = 16384, 4096, 20
+MESH_WRAP = {"repeat": 0, "clamp": 1, "mirror": 2}
+MESH_FILTER = {"bilinear": 0, "trilinear": 1}
 DEFORM_K = 8                                # MGS_DEFORM_K
 LABEL_NONE, LABELS_MAX_CLASSES = 255, 32    # MGS_LABEL_NONE, MGS_LABELS_MAX_CLASSES
 

@@ -16,6 +16,11 @@ Semantics and fp32 evaluation order: tests/mesh_ref.py.  Nothing synchronises, a
 or copies from the host; no floating-point atomic: the same inputs give the same bytes in every run.  `depth` is 0 where no
 face covers the pixel, which is what composite_over(fg_depth=) takes as absent.
 
+A mesh with textures (Mesh.face_uvs, face_textures, textures) takes the textured resolve (include/mgs_mesh_texture.h,
+csrc/mesh_texture.hip; semantics: tests/texture_ref.py): MeshRenderer packs the textures and builds their mipmaps on the GPU
+once (build_texture_set), render() keeps its signature, texture_filter= chooses "trilinear" or "bilinear".  A mesh without
+textures goes down the untextured entry points, which are unchanged.
+
 Argument errors are ValueErrors raised before any launch.  There is no fallback: a missing library is an error.
 """
 from __future__ import annotations
@@ -27,8 +32,9 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from ._lib import MESH_MAX_SIDE, aligned_workspace, check, ptr, stream_handle
-from .mesh import Mesh
+from ._lib import (MESH_FILTER, MESH_MAX_SIDE, MESH_MAX_TEXTURES, MESH_TEXTURE_DESC_WORDS, MESH_TEXTURE_MAX_SIDE, MESH_WRAP,
+                   aligned_workspace, check, ptr, stream_handle)
+from .mesh import Mesh, Texture
 
 
 def _check_sizes(n_cams: int, V: int, F: int, width: int, height: int) -> None:
@@ -111,6 +117,83 @@ def _visibility(workspace: Tensor, pad: int, n_cams: int, width: int, height: in
     return workspace[pad:pad + 8 * n_cams * height * width].view(torch.int64).view(n_cams, height, width)
 
 
+# ---- textures (include/mgs_mesh_texture.h) -----------------------------------------------------------------------------------
+def _filter(texture_filter: str) -> int:
+    if texture_filter not in MESH_FILTER:
+        raise ValueError(f"texture_filter must be 'trilinear' or 'bilinear', got {texture_filter!r}")
+    return MESH_FILTER[texture_filter]
+
+
+class TextureSet:
+    """The textures of a mesh on the device, built once: descriptors int32 [T,20] (host copy: descriptors_host) and texels
+    int32 [texel_count], one word per texel, every level of every texture (include/mgs_mesh_texture.h has the layout).
+    level(t, l) is a uint8 view [h_l, w_l, 4] of one level."""
+
+    def __init__(self, descriptors_host: Tensor, descriptors: Tensor, texels: Tensor, mipmaps: bool):
+        self.descriptors_host, self.descriptors, self.texels, self.mipmaps = descriptors_host, descriptors, texels, mipmaps
+        self.n_textures, self.texel_count, self.device = int(descriptors.shape[0]), int(texels.numel()), texels.device
+
+    def level(self, t: int, l: int) -> Tensor:
+        w, h, levels = (int(v) for v in self.descriptors_host[t, :3])
+        if not 0 <= l < levels:
+            raise ValueError(f"texture {t} has {levels} levels, level {l} was asked for")
+        at, wl, hl = int(self.descriptors_host[t, 4 + l]) & 0xFFFFFFFF, max(1, w >> l), max(1, h >> l)
+        return self.texels[at:at + wl * hl].view(torch.uint8).view(hl, wl, 4)
+
+
+@torch.no_grad()
+def build_texture_set(textures, device, mipmaps: bool = True) -> TextureSet:
+    """Pack `textures` (a list of Texture) for the textured resolve: the descriptors and level 0 of every texture are copied to
+    `device` here, once; with mipmaps the other levels are built there (mgs_mesh_build_mips, one launch per level and texture),
+    without them every texture is described as its level 0 alone, so trilinear filtering degrades to bilinear."""
+    textures = list(textures)
+    if not textures or not all(isinstance(t, Texture) for t in textures):
+        raise ValueError("textures must be a non-empty list of Texture")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise ValueError(f"a texture set lives on the GPU, got device {device}")
+    T = len(textures)
+    if T > MESH_MAX_TEXTURES:
+        raise ValueError(f"{T} textures, at most {MESH_MAX_TEXTURES} in a set")
+    for k, t in enumerate(textures):
+        if not (1 <= t.width <= MESH_TEXTURE_MAX_SIDE and 1 <= t.height <= MESH_TEXTURE_MAX_SIDE):
+            raise ValueError(f"texture {k} is {t.width} x {t.height}: each side must be in 1 .. {MESH_TEXTURE_MAX_SIDE}")
+    sizes = torch.tensor([[t.width, t.height] for t in textures], dtype=torch.int32)
+    wraps = torch.tensor([[MESH_WRAP[t.wrap_s], MESH_WRAP[t.wrap_t]] for t in textures], dtype=torch.int32)
+    desc = torch.zeros((T, MESH_TEXTURE_DESC_WORDS), dtype=torch.int32)
+    n = ctypes.c_size_t(0)
+    L = _lib.lib()
+    check(L.mgs_mesh_texture_layout(T, sizes.data_ptr(), wraps.data_ptr(), desc.data_ptr(), ctypes.byref(n)), "mgs_mesh_texture_layout")
+    if not mipmaps:
+        # level 0 of every texture alone, packed: the same call on 1 x 1 "levels" does not exist, so lay them out here
+        at = 0
+        for k, t in enumerate(textures):
+            desc[k, 2], desc[k, 4], desc[k, 5:] = 1, at, 0
+            at += t.width * t.height
+        if at >= 2 ** 31:
+            raise ValueError(f"the textures hold {at} texels, fewer than 2^31 are allowed")
+        n = ctypes.c_size_t(at)
+    texels = torch.empty(int(n.value), dtype=torch.int32, device=device)
+    for k, t in enumerate(textures):
+        at = int(desc[k, 4]) & 0xFFFFFFFF
+        texels[at:at + t.width * t.height].view(torch.uint8).view(t.height, t.width, 4).copy_(t.image)
+    if mipmaps:
+        check(L.mgs_mesh_build_mips(T, desc.data_ptr(), ptr(texels), int(n.value), stream_handle()), "mgs_mesh_build_mips")
+    return TextureSet(desc, desc.to(device), texels, bool(mipmaps))
+
+
+def _texture_args(textures, face_uvs, face_textures, F: int, dev):
+    """The seven trailing arguments of the textured entry points before filter and stream, launch-ready."""
+    if not isinstance(textures, TextureSet):
+        raise ValueError(f"textures must be a TextureSet (build_texture_set), got {type(textures).__name__}")
+    if textures.device != dev:
+        raise ValueError(f"the texture set is on {textures.device}, the mesh is on {dev}")
+    face_uvs = _dev(face_uvs, (F, 3, 2), torch.float32, "face_uvs", dev)
+    face_textures = _dev(face_textures, (F,), torch.int32, "face_textures", dev)
+    return (ptr(face_uvs), ptr(face_textures), textures.n_textures, ptr(textures.descriptors), ptr(textures.texels),
+            textures.texel_count)
+
+
 # ---- stage operators (each mirrors one entry point; no synchronisation) ---------------------------------------------------
 @torch.no_grad()
 def mesh_vertices(vertices: Tensor, viewmats: Tensor, link_ids: Optional[Tensor] = None, rotations: Optional[Tensor] = None,
@@ -171,9 +254,15 @@ def _outputs(out: Optional[Dict], C: int, height: int, width: int, normals: bool
 @torch.no_grad()
 def mesh_resolve(verts_cam: Tensor, faces: Tensor, Ks: Tensor, width: int, height: int, workspace: Tensor,
                  vertex_colors: Optional[Tensor] = None, face_colors: Optional[Tensor] = None, headlight: bool = False,
-                 ambient: float = 0.3, return_normals: bool = False, out: Optional[Dict] = None) -> Dict:
+                 ambient: float = 0.3, return_normals: bool = False, out: Optional[Dict] = None, *,
+                 textures: Optional[TextureSet] = None, face_uvs: Optional[Tensor] = None,
+                 face_textures: Optional[Tensor] = None, texture_filter: str = "trilinear") -> Dict:
     """mgs_mesh_resolve on the workspace mesh_raster left: dict(rgb float32 [C,H,W,3], depth float32 [C,H,W], face_ids int32
-    [C,H,W] and, with return_normals, normals float32 [C,H,W,3]).  Uncovered pixels are (0, 0, 0), 0 and -1."""
+    [C,H,W] and, with return_normals, normals float32 [C,H,W,3]).  Uncovered pixels are (0, 0, 0), 0 and -1.
+
+    textures (a TextureSet) with face_uvs float32 [F,3,2] and face_textures int32 [F] goes through mgs_mesh_resolve_textured:
+    rgb = texel x tint x shade where the face is textured (texture_filter "trilinear" or "bilinear"), the same bits as
+    without textures everywhere else.  Without textures this is the untextured entry point, unchanged."""
     verts_cam = _dev(verts_cam, (-1, -1, 3), torch.float32, "verts_cam")
     dev, C, V = verts_cam.device, int(verts_cam.shape[0]), int(verts_cam.shape[1])
     faces = _dev(faces, (-1, 3), torch.int32, "faces", dev)
@@ -185,10 +274,17 @@ def mesh_resolve(verts_cam: Tensor, faces: Tensor, Ks: Tensor, width: int, heigh
     face_colors = _dev(face_colors, (F, 3), torch.float32, "face_colors", dev, nullable=True)
     workspace, pad = _workspace(_dev(workspace, (-1,), torch.uint8, "workspace", dev), mesh_workspace_bytes(C, V, F, width, height), dev)
     res = _outputs(out, C, height, width, return_normals, dev)
-    check(_lib.lib().mgs_mesh_resolve(C, V, ptr(verts_cam), F, ptr(faces), ptr(vertex_colors), ptr(face_colors), ptr(Ks), width,
-                                      height, int(bool(headlight)), float(ambient), workspace.data_ptr() + pad,
-                                      workspace.numel() - pad, ptr(res["rgb"]), ptr(res["depth"]), ptr(res["face_ids"]),
-                                      ptr(res.get("normals")), stream_handle()), "mgs_mesh_resolve")
+    args = (C, V, ptr(verts_cam), F, ptr(faces), ptr(vertex_colors), ptr(face_colors), ptr(Ks), width, height,
+            int(bool(headlight)), float(ambient), workspace.data_ptr() + pad, workspace.numel() - pad, ptr(res["rgb"]),
+            ptr(res["depth"]), ptr(res["face_ids"]), ptr(res.get("normals")))
+    if textures is None:
+        if face_uvs is not None or face_textures is not None:
+            raise ValueError("face_uvs and face_textures need textures=")
+        check(_lib.lib().mgs_mesh_resolve(*args, stream_handle()), "mgs_mesh_resolve")
+    else:
+        filt = _filter(texture_filter)
+        tex = _texture_args(textures, face_uvs, face_textures, F, dev)
+        check(_lib.lib().mgs_mesh_resolve_textured(*args, *tex, filt, stream_handle()), "mgs_mesh_resolve_textured")
     return res
 
 
@@ -205,7 +301,8 @@ class MeshRenderer:
 
     def __init__(self, mesh: Mesh, width: int, height: int, n_cams: int = 1, *, near_plane: float = 0.01,
                  far_plane: float = 1e10, cull_backfaces: bool = False, headlight: bool = False, ambient: float = 0.3,
-                 return_normals: bool = False, out: Optional[Dict] = None, workspace: Optional[Tensor] = None):
+                 return_normals: bool = False, out: Optional[Dict] = None, workspace: Optional[Tensor] = None,
+                 texture_filter: str = "trilinear"):
         if not isinstance(mesh, Mesh):
             raise ValueError(f"mesh must be a Mesh, got {type(mesh).__name__}")
         self.width, self.height, self.n_cams = int(width), int(height), int(n_cams)
@@ -227,6 +324,10 @@ class MeshRenderer:
         self.workspace, self._pad = _workspace(workspace, self.workspace_bytes, self.device)
         self.verts_cam = torch.empty((C, V, 3), dtype=torch.float32, device=self.device)
         self.out = _outputs(out, C, self.height, self.width, self.return_normals, self.device)
+        # a textured mesh: the texture set is packed and its mips built here, once; render() then takes the textured entry point
+        self._filter = _filter(texture_filter)
+        self.textures = build_texture_set(mesh.textures, self.device) if mesh.has_textures else None
+        self._tex = None if self.textures is None else _texture_args(self.textures, mesh.face_uvs, mesh.face_textures, F, self.device)
 
     @torch.no_grad()
     def render(self, viewmats: Tensor, Ks: Tensor, rotations: Optional[Tensor] = None, translations: Optional[Tensor] = None,
@@ -240,12 +341,16 @@ class MeshRenderer:
         Ks = _dev(Ks, (C, 3, 3), torch.float32, "Ks", self.device)
         L, rotations, translations, scales = _links(rotations, translations, scales, self.device)
         o = self.out
-        check(_lib.lib().mgs_rasterize_mesh(
-            C, m.n_vertices, ptr(self._vertices), ptr(self._link), L, ptr(rotations), ptr(translations), ptr(scales),
-            ptr(viewmats), ptr(Ks), m.n_faces, ptr(self._faces), ptr(self._vcol), ptr(self._fcol), self.width, self.height,
-            self.near_plane, self.far_plane, int(self.cull_backfaces), int(self.headlight), self.ambient,
-            self.workspace.data_ptr() + self._pad, self.workspace.numel() - self._pad, ptr(self.verts_cam), ptr(o["rgb"]),
-            ptr(o["depth"]), ptr(o["face_ids"]), ptr(o.get("normals")), stream_handle()), "mgs_rasterize_mesh")
+        args = (C, m.n_vertices, ptr(self._vertices), ptr(self._link), L, ptr(rotations), ptr(translations), ptr(scales),
+                ptr(viewmats), ptr(Ks), m.n_faces, ptr(self._faces), ptr(self._vcol), ptr(self._fcol), self.width, self.height,
+                self.near_plane, self.far_plane, int(self.cull_backfaces), int(self.headlight), self.ambient,
+                self.workspace.data_ptr() + self._pad, self.workspace.numel() - self._pad, ptr(self.verts_cam), ptr(o["rgb"]),
+                ptr(o["depth"]), ptr(o["face_ids"]), ptr(o.get("normals")))
+        if self._tex is None:
+            check(_lib.lib().mgs_rasterize_mesh(*args, stream_handle()), "mgs_rasterize_mesh")
+        else:
+            check(_lib.lib().mgs_rasterize_mesh_textured(*args, *self._tex, self._filter, stream_handle()),
+                  "mgs_rasterize_mesh_textured")
         meta = {"face_ids": o["face_ids"], "verts_cam": self.verts_cam}
         if self.return_normals:
             meta["normals"] = o["normals"]
@@ -263,7 +368,7 @@ def _to_device(x, dtype, device):
 def rasterize_mesh(mesh: Mesh, viewmats, Ks, width: int, height: int, *, rotations=None, translations=None, scales=None,
                    near_plane: float = 0.01, far_plane: float = 1e10, cull_backfaces: bool = False, headlight: bool = False,
                    ambient: float = 0.3, return_normals: bool = False, out: Optional[Dict] = None,
-                   workspace: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Dict]:
+                   workspace: Optional[Tensor] = None, texture_filter: str = "trilinear") -> Tuple[Tensor, Tensor, Dict]:
     """Render `mesh` (on the GPU) from C cameras: (rgb float32 [C,H,W,3], depth float32 [C,H,W], meta) with meta =
     dict(face_ids int32 [C,H,W] (-1 where uncovered), verts_cam float32 [C,V,3][, normals float32 [C,H,W,3]]).
 
@@ -273,8 +378,11 @@ def rasterize_mesh(mesh: Mesh, viewmats, Ks, width: int, height: int, *, rotatio
     static: len(rotations) < mesh.n_links() is not an error, because finding it would take a read-back.
     depth is the z-depth of the nearest face, 0 where there is none: what composite_over(fg_depth=) takes as it stands.
     rgb: vertex colours interpolated, else face colours, else 0.7 grey; headlight=True multiplies by ambient +
-    (1 - ambient) |cos| between the face normal and the pixel's ray.  out / workspace: buffers of an earlier call to reuse
-    (see MeshRenderer, which also keeps the checks and conversions out of a per-frame loop)."""
+    (1 - ambient) |cos| between the face normal and the pixel's ray.  A mesh with textures: rgb = texel x tint x shade on its
+    textured faces (tint: the vertex or face colour, else 1), filtered by texture_filter ("trilinear" with mipmaps, or
+    "bilinear"); the texture set is packed and its mips built in this call -- MeshRenderer does that once.  out / workspace:
+    buffers of an earlier call to reuse (see MeshRenderer, which also keeps the checks and conversions out of a per-frame
+    loop)."""
     if not isinstance(mesh, Mesh):
         raise ValueError(f"mesh must be a Mesh, got {type(mesh).__name__}")
     for what, x in (("viewmats", viewmats), ("Ks", Ks)):
@@ -300,9 +408,10 @@ def rasterize_mesh(mesh: Mesh, viewmats, Ks, width: int, height: int, *, rotatio
             raise ValueError(f"scales must be [{rotations.shape[0]}], got {list(torch.as_tensor(scales).shape)}")
     r = MeshRenderer(mesh, width, height, int(vm.shape[0]), near_plane=near_plane, far_plane=far_plane,
                      cull_backfaces=cull_backfaces, headlight=headlight, ambient=ambient, return_normals=return_normals,
-                     out=out, workspace=workspace)
+                     out=out, workspace=workspace, texture_filter=texture_filter)
     f32 = lambda x: _to_device(x, torch.float32, r.device)
     return r.render(f32(vm), f32(K), rotations=f32(rotations), translations=f32(translations), scales=f32(scales))
 
 
-__all__ = ["MeshRenderer", "rasterize_mesh", "mesh_vertices", "mesh_raster", "mesh_resolve", "mesh_workspace_bytes"]
+__all__ = ["MeshRenderer", "rasterize_mesh", "mesh_vertices", "mesh_raster", "mesh_resolve", "mesh_workspace_bytes",
+           "TextureSet", "build_texture_set"]
