@@ -32,21 +32,28 @@ __device__ __forceinline__ TileRect tile_rect(float mx, float my, int radius, fl
 // the ellipse sigma <= ln(255 opacity) (half extents sqrt(2 lim Sigma_xx), sqrt(2 lim Sigma_yy)),
 // intersected with the classic rectangle `r`.  Every dropped (tile, Gaussian) pair fails the
 // raster's alpha test at all 256 pixels, so the image and the gradients do not change by a bit
-// (tests/test_gpu_forward.py, test_gpu_backward.py) while the lists shrink by ~27 % at config 2.
+// while the lists shrink by ~27 % at config 2.  Held from both sides on the CPU -- conservative against the blend's
+// own fp32 alpha chain, tight against fp64 -- by tests/test_tile_rect_host.py (a g++ build of this header:
+// tests/host_harness/tile_rect_harness.cpp, reference tests/tile_rect_ref.py) and, as the kernels run it, by
+// tests/test_gpu_tile_rect.py.
 // Sigma = conic^-1 is taken from the fp32 conic the blend itself evaluates; a*c - b*b cancels
 // catastrophically for elongated footprints, so the determinant is Kahan-compensated (fma
 // residuals: exact to an ulp of the true value) and the extents carry a 1e-4 relative margin.
 // `lim` carries the same fp32 slack as the raster's own quadrant cull (raster_common.h).
+// The opacity gate is the raster's own (cull_opacity_ok, raster_common.h: the same expression), not 1/255: the blend's
+// fp32 alpha does come out at 1/255 on a pixel centre the mean sits on when the opacity is an ulp short of it, and a
+// rectangle emptied there would drop a pair the classic lists count.  Between the gate and 1/255 the extents are those
+// of an opacity of exactly 1/255 (thr = 0).
 __device__ __forceinline__ TileRect tighten_rect(TileRect r, float mx, float my, float a, float b,
                                                  float c, float opac, float tile_size) {
-  if (!(opac >= 1.0f / 255.0f)) { r.w = 0; r.h = 0; return r; }   // alpha <= opacity < 1/255
+  if (!(opac >= 0.95f * (1.0f / 255.0f))) { r.w = 0; r.h = 0; return r; }   // the raster never evaluates the pair
   // det = a c - b b with Kahan's compensated 2x2 determinant: exact products via fma residuals
   const float w = b * b, e = fmaf(-b, b, w), f = fmaf(a, c, -w);
   const float det = f + e;
   if (!(det > 0.f) || !(a > 0.f) || !(c > 0.f)) return r;          // degenerate: keep classic
   const float inv_det = 1.0f / det;
   const float sxx = c * inv_det, syy = a * inv_det;
-  const float thr = __logf(255.0f * opac);
+  const float thr = fmaxf(__logf(255.0f * opac), 0.f);
   const float e2 = 2.0f * (thr + 0.05f) * (sxx + syy);
   const float slack = 0.05f + 8e-6f * (fabsf(a) + fabsf(c) + 2.f * fabsf(b)) * (e2 + 512.f);
   const float lim = 2.0f * (thr + slack);
