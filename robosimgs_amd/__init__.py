@@ -17,7 +17,7 @@ _DEVICE_API = {"rasterization", "render", "check_isect_status", "fully_fused_pro
                "spherical_harmonics", "isect_tiles", "isect_offset_encode",
                "rasterize_to_pixels", "rasterize_labels", "rasterize_votes", "assign_classes", "lift_labels",
                "fit_hinge", "fit_hinge_points", "pose_gaussians", "bind_particles", "deform_gaussians",
-               "rasterize_mesh", "mesh_vertices", "mesh_raster", "mesh_resolve",
+               "deform_gaussians_autograd", "rasterize_mesh", "mesh_vertices", "mesh_raster", "mesh_resolve",
                "render_sharded", "gather_frames"}
 
 
@@ -49,7 +49,7 @@ def __getattr__(name):  # lazy: keeps `import robosimgs_amd` torch-free for host
         from . import pose
         return getattr(pose, name)
     if name in ("bind_particles", "deform_gaussians", "ParticleBinding", "deform_bind_raw", "deform_apply_raw",
-                "deform_apply_sh_raw"):
+                "deform_apply_sh_raw", "deform_gaussians_autograd", "deform_apply_bwd_raw"):
         from . import deform
         return getattr(deform, name)
     if name in ("Mesh", "Texture"):

@@ -134,6 +134,12 @@ _DEFORM_SIGNATURES = {
 _DEFORM_SH_SIGNATURES = {
     "mgs_deform_apply_sh": (_DEFORM_SIGNATURES["mgs_deform_apply"][0][:-1] + [i, i, p, p, i, p], c_int),
 }
+# every function include/mgs_deform_bwd.h declares (the same libraries again): the workspace size is a query of its own; the
+# three cotangents, the three rest gradients (as a set) and bwd_status are nullable
+_DEFORM_BWD_SIGNATURES = {
+    "mgs_deform_apply_bwd_workspace_bytes": ([i], c_size_t),
+    "mgs_deform_apply_bwd": ([i, p, p, p, p, p, p, i, p, p, p, p, p, p, p, p, p, p, p, p, p, c_size_t, p], c_int),
+}
 # every function include/mgs_mesh.h declares (the same libraries again): the workspace size is a query of its own; link_ids,
 # scales, the colours and normals are nullable
 _MESH_SIGNATURES = {
@@ -160,7 +166,7 @@ del p, i, f, u32, img
 # what _load binds: a new header adds its table here
 _SIGNATURE_TABLES = (_SIGNATURES, _OPTIM_SIGNATURES, _REFINE_SIGNATURES, _LABEL_SIGNATURES, _LIFT_SIGNATURES,
                      _HINGE_SIGNATURES, _POSE_SIGNATURES, _DEFORM_SIGNATURES, _DEFORM_SH_SIGNATURES, _MESH_SIGNATURES,
-                     _MESH_TEXTURE_SIGNATURES, _HYBRID_SIGNATURES)
+                     _MESH_TEXTURE_SIGNATURES, _HYBRID_SIGNATURES, _DEFORM_BWD_SIGNATURES)
 EXPORTS = list(_SIGNATURES)
 OPTIM_EXPORTS = list(_OPTIM_SIGNATURES)
 REFINE_EXPORTS = list(_REFINE_SIGNATURES)
@@ -170,6 +176,7 @@ HINGE_EXPORTS = list(_HINGE_SIGNATURES)
 POSE_EXPORTS = list(_POSE_SIGNATURES)
 DEFORM_EXPORTS = list(_DEFORM_SIGNATURES)
 DEFORM_SH_EXPORTS = list(_DEFORM_SH_SIGNATURES)
+DEFORM_BWD_EXPORTS = list(_DEFORM_BWD_SIGNATURES)
 MESH_EXPORTS = list(_MESH_SIGNATURES)
 HYBRID_EXPORTS = list(_HYBRID_SIGNATURES)
 MESH_TEXTURE_EXPORTS = list(_MESH_TEXTURE_SIGNATURES)

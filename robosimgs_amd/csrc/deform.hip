@@ -25,6 +25,7 @@
 #include "sh_rotate.h"
 #include "../../include/mgs_deform.h"
 #include "../../include/mgs_deform_sh.h"
+#include "../../include/mgs_deform_bwd.h"
 
 #include <float.h>
 #include <math.h>
@@ -483,6 +484,184 @@ __global__ __launch_bounds__(SH ? kDeformShGroup : kDeformGroup) void deform_app
   }
 }
 
+// deform_apply_bwd_kernel (include/mgs_deform_bwd.h, launch 1).  One thread per Gaussian.  P and the eigenpairs of
+// P^T P are formed exactly as deform_apply_kernel forms them (c itself has no part in the gradient: only its weights), so MGS_SHAPE_ROTATION gives the forward's R bit for bit; the
+// branch is the forward's status, not a second decision.  The chain v_omega -> y = G^-1 R^T v_omega -> v_P = R [y]x runs in
+// fp64 on named scalars; w and p stay in registers from the forward part to the 24 contributions at the end.  The
+// contributions go to the neighbour-major workspace ws [8][3][N] (coalesced), a pass-through row's as zeros.
+__global__ __launch_bounds__(kDeformGroup) void deform_apply_bwd_kernel(
+    int n, const float* __restrict__ quats, const int32_t* __restrict__ idx, const float* __restrict__ w,
+    const float* __restrict__ p, const float* __restrict__ rest, const uint8_t* __restrict__ flags, int m,
+    const float* __restrict__ now, const uint8_t* __restrict__ status, const float* __restrict__ ct_means,
+    const float* __restrict__ ct_quats, const float* __restrict__ ct_scales, float* __restrict__ v_means,
+    float* __restrict__ v_quats, float* __restrict__ v_scales, uint8_t* __restrict__ bwd_status, float* __restrict__ ws) {
+  const long long i = (long long)blockIdx.x * kDeformGroup + threadIdx.x;
+  if (i >= n) return;
+  const size_t N = (size_t)n;
+  float cm0 = 0.f, cm1 = 0.f, cm2 = 0.f, cs0 = 0.f, cs1 = 0.f, cs2 = 0.f;
+  float4 cq = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (ct_means) { cm0 = ct_means[3 * i + 0]; cm1 = ct_means[3 * i + 1]; cm2 = ct_means[3 * i + 2]; }
+  if (ct_quats) cq = reinterpret_cast<const float4*>(ct_quats)[i];
+  if (ct_scales) { cs0 = ct_scales[3 * i + 0]; cs1 = ct_scales[3 * i + 1]; cs2 = ct_scales[3 * i + 2]; }
+  float vm0 = cm0, vm1 = cm1, vm2 = cm2;             // v_means = v_d0: the cotangent itself unless the row turned
+  float4 vq = cq;
+  float vx[kK][3];                                   // the 24 contributions (constant indices only: registers)
+#pragma unroll
+  for (int k = 0; k < kK; ++k) { vx[k][0] = 0.f; vx[k][1] = 0.f; vx[k][2] = 0.f; }
+  unsigned bst = 0u;
+
+  const unsigned st = status[i];
+  if (!((flags[i] & kFlagUnbound) || (st & (kStatusUnbound | kStatusNonFinite)))) {
+    float x[kK][3];
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < kK; ++k) {
+      const int j = idx[k * N + i];
+      const bool in = j >= 0 && j < m;
+      const size_t jj = in ? (size_t)j : 0;
+      x[k][0] = now[3 * jj + 0]; x[k][1] = now[3 * jj + 1]; x[k][2] = now[3 * jj + 2];
+      ok = ok && in;
+    }
+    if (ok) {                                        // (a status that is not this frame's: nothing is followed out of range)
+      float wk[kK], pk[kK][3];
+      float P00 = 0.f, P01 = 0.f, P02 = 0.f, P10 = 0.f, P11 = 0.f, P12 = 0.f, P20 = 0.f, P21 = 0.f, P22 = 0.f;
+      wk[0] = 0.f; pk[0][0] = 0.f; pk[0][1] = 0.f; pk[0][2] = 0.f;
+#pragma unroll
+      for (int k = 1; k < kK; ++k) {
+        const float e0 = x[k][0] - x[0][0], e1 = x[k][1] - x[0][1], e2 = x[k][2] - x[0][2];
+        wk[k] = w[k * N + i];
+        const float pk0 = p[(3 * k + 0) * N + i], pk1 = p[(3 * k + 1) * N + i], pk2 = p[(3 * k + 2) * N + i];
+        pk[k][0] = pk0; pk[k][1] = pk1; pk[k][2] = pk2;
+        if (k == 1) {
+          P00 = e0 * pk0; P01 = e0 * pk1; P02 = e0 * pk2;
+          P10 = e1 * pk0; P11 = e1 * pk1; P12 = e1 * pk2;
+          P20 = e2 * pk0; P21 = e2 * pk1; P22 = e2 * pk2;
+        } else {
+          P00 = __builtin_fmaf(e0, pk0, P00); P01 = __builtin_fmaf(e0, pk1, P01); P02 = __builtin_fmaf(e0, pk2, P02);
+          P10 = __builtin_fmaf(e1, pk0, P10); P11 = __builtin_fmaf(e1, pk1, P11); P12 = __builtin_fmaf(e1, pk2, P12);
+          P20 = __builtin_fmaf(e2, pk0, P20); P21 = __builtin_fmaf(e2, pk1, P21); P22 = __builtin_fmaf(e2, pk2, P22);
+        }
+      }
+      // v_P, zero unless the row turned and the guard let the rotation's gradient through
+      double g00 = 0., g01 = 0., g02 = 0., g10 = 0., g11 = 0., g12 = 0., g20 = 0., g21 = 0., g22 = 0.;
+      if (!(st & kStatusThin)) {
+        const double p00 = P00, p01 = P01, p02 = P02, p10 = P10, p11 = P11, p12 = P12, p20 = P20, p21 = P21, p22 = P22;
+        double a00 = p00 * p00 + p10 * p10 + p20 * p20, a01 = p00 * p01 + p10 * p11 + p20 * p21;
+        double a02 = p00 * p02 + p10 * p12 + p20 * p22, a11 = p01 * p01 + p11 * p11 + p21 * p21;
+        double a12 = p01 * p02 + p11 * p12 + p21 * p22, a22 = p02 * p02 + p12 * p12 + p22 * p22;
+        double v00, v01, v02, v10, v11, v12, v20, v21, v22;
+        jacobi_solve3(a00, a01, a02, a11, a12, a22, v00, v01, v02, v10, v11, v12, v20, v21, v22);
+        if (a00 < a11) MGS_SWAP_PAIR(a00, a11, v00, v10, v20, v01, v11, v21);
+        if (a11 < a22) MGS_SWAP_PAIR(a11, a22, v01, v11, v21, v02, v12, v22);
+        if (a00 < a11) MGS_SWAP_PAIR(a00, a11, v00, v10, v20, v01, v11, v21);
+        MGS_SHAPE_ROTATION();
+        const double d0 = rest[0 * N + i], d1 = rest[1 * N + i], d2 = rest[2 * N + i];
+        const double m0 = cm0, m1 = cm1, m2 = cm2;
+        vm0 = (float)(r00 * m0 + r10 * m1 + r20 * m2);                      // v_d0 = R^T ct_mu
+        vm1 = (float)(r01 * m0 + r11 * m1 + r21 * m2);
+        vm2 = (float)(r02 * m0 + r12 * m1 + r22 * m2);
+        // S = R^T P (symmetric; the two triangles are averaged) and the guard on G's smallest eigenvalue, tr(S) - sigma_1
+        const double s00 = r00 * p00 + r10 * p10 + r20 * p20, s11 = r01 * p01 + r11 * p11 + r21 * p21;
+        const double s22 = r02 * p02 + r12 * p12 + r22 * p22;
+        const double s01 = 0.5 * ((r00 * p01 + r10 * p11 + r20 * p21) + (r01 * p00 + r11 * p10 + r21 * p20));
+        const double s02 = 0.5 * ((r00 * p02 + r10 * p12 + r20 * p22) + (r02 * p00 + r12 * p10 + r22 * p20));
+        const double s12 = 0.5 * ((r01 * p02 + r11 * p12 + r21 * p22) + (r02 * p01 + r12 * p11 + r22 * p21));
+        const double tr = s00 + s11 + s22, sig1 = sqrt(a00);
+        if (tr - sig1 < kDegenerate * sig1) {
+          bst = 1u;                                  // guarded: v_P = 0, v_q = ct_q
+        } else {
+          double aw, ax, ay, az;
+          rotmat_to_quat(r00, r01, r02, r10, r11, r12, r20, r21, r22, aw, ax, ay, az);
+          const float4 q = reinterpret_cast<const float4*>(quats)[i];
+          const double bw = q.x, bx = q.y, by = q.z, bz = q.w;
+          double ow = aw * bw - ax * bx - ay * by - az * bz, ox = aw * bx + ax * bw + ay * bz - az * by;
+          double oy = aw * by - ax * bz + ay * bw + az * bx, oz = aw * bz + ax * by - ay * bx + az * bw;
+          const double inv = 1.0 / sqrt(ow * ow + ox * ox + oy * oy + oz * oz);
+          ow *= inv; ox *= inv; oy *= inv; oz *= inv;                        // q'
+          const double tw = cq.x, tx = cq.y, ty = cq.z, tz = cq.w;
+          // v_q = conj(q_R) (x) (ct_q - <ct_q, q'> q') / |q_R (x) q|
+          const double dq = tw * ow + tx * ox + ty * oy + tz * oz;
+          const double uw = (tw - dq * ow) * inv, ux = (tx - dq * ox) * inv, uy = (ty - dq * oy) * inv, uz = (tz - dq * oz) * inv;
+          vq = make_float4((float)(aw * uw + ax * ux + ay * uy + az * uz), (float)(aw * ux - ax * uw - ay * uz + az * uy),
+                           (float)(aw * uy + ax * uz - ay * uw - az * ux), (float)(aw * uz - ax * uy + ay * ux - az * uw));
+          // v_omega = (R d0) x ct_mu + 1/2 sum_k e_k <ct_q, (0, e_k) (x) q'>
+          const double h0 = r00 * d0 + r01 * d1 + r02 * d2, h1 = r10 * d0 + r11 * d1 + r12 * d2;
+          const double h2 = r20 * d0 + r21 * d1 + r22 * d2;
+          const double o0 = (h1 * m2 - h2 * m1) + 0.5 * (tx * ow - tw * ox + tz * oy - ty * oz);
+          const double o1 = (h2 * m0 - h0 * m2) + 0.5 * (ty * ow - tw * oy + tx * oz - tz * ox);
+          const double o2 = (h0 * m1 - h1 * m0) + 0.5 * (tz * ow - tw * oz + ty * ox - tx * oy);
+          // y = G^-1 R^T v_omega, G = tr(S) I - S, by cofactors
+          const double z0 = r00 * o0 + r10 * o1 + r20 * o2, z1 = r01 * o0 + r11 * o1 + r21 * o2;
+          const double z2 = r02 * o0 + r12 * o1 + r22 * o2;
+          const double G00 = tr - s00, G11 = tr - s11, G22 = tr - s22, G01 = -s01, G02 = -s02, G12 = -s12;
+          const double c00 = G11 * G22 - G12 * G12, c01 = G02 * G12 - G01 * G22, c02 = G01 * G12 - G02 * G11;
+          const double c11 = G00 * G22 - G02 * G02, c12 = G01 * G02 - G00 * G12, c22 = G00 * G11 - G01 * G01;
+          const double idet = 1.0 / (G00 * c00 + G01 * c01 + G02 * c02);
+          const double y0 = (c00 * z0 + c01 * z1 + c02 * z2) * idet, y1 = (c01 * z0 + c11 * z1 + c12 * z2) * idet;
+          const double y2 = (c02 * z0 + c12 * z1 + c22 * z2) * idet;
+          // v_P = R [y]x,  [y]x = (0 -y2 y1 | y2 0 -y0 | -y1 y0 0)
+          g00 = r01 * y2 - r02 * y1; g01 = r02 * y0 - r00 * y2; g02 = r00 * y1 - r01 * y0;
+          g10 = r11 * y2 - r12 * y1; g11 = r12 * y0 - r10 * y2; g12 = r10 * y1 - r11 * y0;
+          g20 = r21 * y2 - r22 * y1; g21 = r22 * y0 - r20 * y2; g22 = r20 * y1 - r21 * y0;
+        }
+      }
+      // v_x_k = w_k ct_mu + v_P p_k (k = 1..7), v_x_0 = ct_mu - sum_k v_x_k: fp64, each rounded to fp32 once
+      double a0 = cm0, a1 = cm1, a2 = cm2;
+#pragma unroll
+      for (int k = 1; k < kK; ++k) {
+        const double wd = wk[k], q0 = pk[k][0], q1 = pk[k][1], q2 = pk[k][2];
+        const double t0 = wd * (double)cm0 + (g00 * q0 + g01 * q1 + g02 * q2);
+        const double t1 = wd * (double)cm1 + (g10 * q0 + g11 * q1 + g12 * q2);
+        const double t2 = wd * (double)cm2 + (g20 * q0 + g21 * q1 + g22 * q2);
+        a0 -= t0; a1 -= t1; a2 -= t2;
+        vx[k][0] = (float)t0; vx[k][1] = (float)t1; vx[k][2] = (float)t2;
+      }
+      vx[0][0] = (float)a0; vx[0][1] = (float)a1; vx[0][2] = (float)a2;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < kK; ++k) {
+    ws[(3 * k + 0) * N + i] = vx[k][0]; ws[(3 * k + 1) * N + i] = vx[k][1]; ws[(3 * k + 2) * N + i] = vx[k][2];
+  }
+  if (v_means) {
+    v_means[3 * i + 0] = vm0; v_means[3 * i + 1] = vm1; v_means[3 * i + 2] = vm2;
+    reinterpret_cast<float4*>(v_quats)[i] = vq;
+    v_scales[3 * i + 0] = cs0; v_scales[3 * i + 1] = cs1; v_scales[3 * i + 2] = cs2;
+  }
+  if (bwd_status) bwd_status[i] = (uint8_t)bst;
+}
+
+// deform_scatter_kernel (launch 2).  One wave per particle: lane l adds the contributions of the entries t_start[j] + l,
+// + 64, ... of its particle in ascending order, then a fixed xor tree.  An entry e = k N + i names ws[(3 k + c) N + i].
+__global__ __launch_bounds__(kDeformGroup) void deform_scatter_kernel(int n, int m, const int32_t* __restrict__ t_start,
+                                                                     const int32_t* __restrict__ t_entry,
+                                                                     const float* __restrict__ ws,
+                                                                     float* __restrict__ v_particles) {
+  const int lane = (int)(threadIdx.x & 63u);
+  const long long j = (long long)blockIdx.x * (kDeformGroup / 64) + (threadIdx.x >> 6);
+  if (j >= m) return;                                // (the whole wave)
+  const long long total = (long long)kK * n;
+  float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+  if (n > 0) {
+    long long lo = t_start[j], hi = t_start[j + 1];
+    lo = lo < 0 ? 0 : lo;
+    hi = hi > total ? total : hi;
+    const size_t N = (size_t)n;
+    for (long long t = lo + lane; t < hi; t += 64) {
+      const long long e = t_entry[t];
+      if (e >= 0 && e < total) {
+        const size_t k = (size_t)(e / n), at = (size_t)e + 2 * k * N;       // (3 k) N + i
+        s0 += ws[at]; s1 += ws[at + N]; s2 += ws[at + 2 * N];
+      }
+    }
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    s0 += __shfl_xor(s0, d); s1 += __shfl_xor(s1, d); s2 += __shfl_xor(s2, d);
+  }
+  if (lane == 0) { v_particles[3 * j + 0] = s0; v_particles[3 * j + 1] = s1; v_particles[3 * j + 2] = s2; }
+}
+
 #undef MGS_SWAP_PAIR
 #undef MGS_STORE_ROTATION
 #undef MGS_SHAPE_ROTATION
@@ -490,6 +669,14 @@ __global__ __launch_bounds__(SH ? kDeformShGroup : kDeformGroup) void deform_app
 size_t bind_workspace_bytes(int n) {
   Bump b(1);
   b.take(sizeof(float) * (size_t)kK * (size_t)n);      // d2 [8][n]: the sorted squared distances between the two launches
+  return b.total;
+}
+
+constexpr int kBwdMaxN = (1 << 28) - 1;               // t_entry holds k n + i < 8 n in an int32
+
+size_t apply_bwd_workspace_bytes(int n) {
+  Bump b(1);
+  b.take(sizeof(float) * 3 * (size_t)kK * (size_t)n);  // ws [8][3][n]: the contributions between the two launches
   return b.total;
 }
 
@@ -572,4 +759,44 @@ extern "C" int mgs_deform_apply_sh(int n, const float* means, const float* quats
                        status, sh_degree, stride_f, sh_coeffs, out_sh, copy_unbound != 0);
   });
   return check_launch("deform_apply_sh");
+}
+
+extern "C" size_t mgs_deform_apply_bwd_workspace_bytes(int n) {
+  if (n <= 0) return 0;
+  return apply_bwd_workspace_bytes(n);
+}
+
+extern "C" int mgs_deform_apply_bwd(int n, const float* quats, const int32_t* idx, const float* w, const float* p,
+                                    const float* rest, const uint8_t* flags, int m, const float* particles_now,
+                                    const uint8_t* status, const float* ct_means, const float* ct_quats,
+                                    const float* ct_scales, const int32_t* t_start, const int32_t* t_entry, float* v_means,
+                                    float* v_quats, float* v_scales, float* v_particles, uint8_t* bwd_status,
+                                    void* workspace, size_t workspace_bytes, mgs_stream_t stream) {
+  MGS_REQUIRE(n >= 0, "deform_apply_bwd: n %d is negative", n);
+  MGS_REQUIRE(n <= kBwdMaxN, "deform_apply_bwd: n %d, at most %d (t_entry is int32)", n, kBwdMaxN);
+  MGS_REQUIRE(m >= kK, "deform_apply_bwd: m %d particles, at least %d needed", m, kK);
+  MGS_REQUIRE(v_particles, "deform_apply_bwd: v_particles is null");
+  const bool rest_grads = v_means || v_quats || v_scales;
+  MGS_REQUIRE(!rest_grads || (v_means && v_quats && v_scales),
+              "deform_apply_bwd: rest gradients given only in part (v_means, v_quats, v_scales)");
+  hipStream_t s = (hipStream_t)stream;
+  float* ws = static_cast<float*>(workspace);
+  if (n > 0) {
+    MGS_REQUIRE(quats, "deform_apply_bwd: quats is null");
+    MGS_REQUIRE(idx && w && p && rest && flags, "deform_apply_bwd: a binding array (idx, w, p, rest, flags) is null");
+    MGS_REQUIRE(particles_now, "deform_apply_bwd: particles_now is null");
+    MGS_REQUIRE(status, "deform_apply_bwd: status is null (the forward's status is a required input)");
+    MGS_REQUIRE(t_start && t_entry, "deform_apply_bwd: the transposed binding (t_start, t_entry) is null");
+    MGS_REQUIRE(workspace, "deform_apply_bwd: workspace is null");
+    const size_t need = apply_bwd_workspace_bytes(n);
+    MGS_REQUIRE(workspace_bytes >= need, "deform_apply_bwd: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+    hipLaunchKernelGGL(deform_apply_bwd_kernel, dim3(div_up((unsigned)n, (unsigned)kDeformGroup)), dim3(kDeformGroup), 0, s,
+                       n, quats, idx, w, p, rest, flags, m, particles_now, status, ct_means, ct_quats, ct_scales, v_means,
+                       v_quats, v_scales, bwd_status, ws);
+    int rc = check_launch("deform_apply_bwd");
+    if (rc) return rc;
+  }
+  hipLaunchKernelGGL(deform_scatter_kernel, dim3(div_up((unsigned)m, (unsigned)(kDeformGroup / 64))), dim3(kDeformGroup), 0,
+                     s, n, m, t_start, t_entry, (const float*)ws, v_particles);
+  return check_launch("deform_apply_bwd");
 }

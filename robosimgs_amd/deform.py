@@ -18,6 +18,13 @@ rotate_sh=True (include/mgs_deform_sh.h) turns every Gaussian's SH rows by the r
 modes, so an affine frame has the colours of a rigid one -- in the same launch; the result then owns a `colors` tensor
 (192 bytes per Gaussian at degree 3).  Rows of thin, unbound and non-finite Gaussians are the rest rows bit for bit.
 `FrameRenderer(deform=binding[, deform_rotate_sh=True])` runs it inside every slot's graph (pipeline.py).
+
+    posed = deform_gaussians_autograd(tensors, binding, particles_now)                   # autograd sees through it
+
+`deform_gaussians_autograd` (include/mgs_deform_bwd.h) is the rigid mode with a backward: gradients reach the particles'
+current positions (state and system identification through a differentiable simulator) and the rest state's means, quats
+and scales (training a soft object from frames in which it is deformed).  Two launches, no floating-point atomics: the
+scatter from Gaussians to particles goes through the binding's transpose in a fixed order.
 """
 from __future__ import annotations
 
@@ -26,6 +33,7 @@ from typing import Dict, Optional
 
 import torch
 from torch import Tensor
+from torch.autograd.function import once_differentiable
 
 from . import _lib
 from ._lib import DEFORM_K, aligned_workspace, check, check_tensor, ptr, require_device, stream_handle
@@ -68,6 +76,7 @@ class ParticleBinding:
                  particles: Optional[Tensor] = None):
         self.idx, self.w, self.p, self.rest, self.flags, self.n, self.m = idx, w, p, rest, flags, int(n), int(m)
         self.particles = particles
+        self._transposed = None
         want = {"idx": ((DEFORM_K, self.n), torch.int32), "w": ((DEFORM_K, self.n), torch.float32),
                 "p": ((DEFORM_K, 3, self.n), torch.float32), "rest": ((REST_ROWS, self.n), torch.float32),
                 "flags": ((self.n,), torch.uint8)}
@@ -81,6 +90,32 @@ class ParticleBinding:
         sel = lambda t: t.index_select(t.dim() - 1, order).contiguous()
         return ParticleBinding(sel(self.idx), sel(self.w), sel(self.p), sel(self.rest), sel(self.flags),
                                int(order.shape[0]), self.m, self.particles)
+
+    def transposed(self):
+        """The transposed binding mgs_deform_apply_bwd scatters through (include/mgs_deform_bwd.h): (t_start int32 [m + 1],
+        t_entry int32 [8 n]).  t_entry lists k n + i for every (neighbour row k, Gaussian i), ordered by the particle
+        idx[k][i] and ascending within a particle (a stable sort); entries t_start[j] .. t_start[j + 1] - 1 are particle
+        j's.  Entries of unbound Gaussians (index -1) sort to the front, before t_start[0], and are never referenced.
+        Built once and cached (reordered() makes a new binding, which builds its own); no synchronising call."""
+        if self._transposed is None:
+            with torch.no_grad():
+                keys, order = torch.sort(self.idx.reshape(-1), stable=True)
+                ids = torch.arange(self.m + 1, dtype=torch.int32, device=self.idx.device)
+                t_start = torch.searchsorted(keys, ids).to(torch.int32)
+                self._transposed = (t_start.contiguous(), order.to(torch.int32).contiguous())
+        return self._transposed
+
+    @torch.no_grad()
+    def shift_offsets_(self, delta: Tensor) -> "ParticleBinding":
+        """rest[0:3] += delta^T for delta [n,3], in place: the offsets d0 = mu - Xbar follow a change of the means with
+        the neighbours and weights held fixed, which is the derivative deform_gaussians_autograd reports as the gradient
+        of `means` -- so a trained mean takes effect without a re-bind.  Rows of unbound Gaussians stay zero."""
+        _rows(delta, 3, "delta")
+        if delta.shape[0] != self.n:
+            raise ValueError(f"delta has {delta.shape[0]} rows, the binding was made for {self.n} Gaussians")
+        bound = ((self.flags & FLAG_UNBOUND) == 0).to(self.rest.dtype)
+        self.rest[0:3] += delta.to(self.rest.device, self.rest.dtype).t() * bound[None, :]
+        return self
 
     def n_bound(self) -> int:
         """How many Gaussians are bound (reads the flags back: one synchronising copy)."""
@@ -132,6 +167,123 @@ def deform_apply_sh_raw(means: Tensor, quats: Tensor, scales: Tensor, binding: P
                                          ptr(particles), ptr(out_means), ptr(out_quats), ptr(out_scales), ptr(status),
                                          int(sh_degree), int(colors.shape[1]), ptr(colors), ptr(out_colors),
                                          int(bool(copy_unbound)), stream_handle()), "mgs_deform_apply_sh")
+
+
+def apply_bwd_workspace_bytes(n: int) -> int:
+    """mgs_deform_apply_bwd_workspace_bytes: what the backward of n Gaussians needs."""
+    return int(_lib.lib().mgs_deform_apply_bwd_workspace_bytes(int(n)))
+
+
+def deform_apply_bwd_raw(quats: Tensor, binding: ParticleBinding, particles: Tensor, status: Tensor,
+                         ct_means: Optional[Tensor] = None, ct_quats: Optional[Tensor] = None,
+                         ct_scales: Optional[Tensor] = None, rest: bool = True, out: Optional[Dict] = None,
+                         bwd_status: Optional[Tensor] = None, workspace: Optional[Tensor] = None) -> Dict:
+    """mgs_deform_apply_bwd on torch's current stream: two launches, no synchronisation, capturable.  quats: the REST
+    quaternions float32 [n,4]; particles float32 [m,3]; status uint8 [n]: what the mode-0 forward wrote for these
+    arguments; ct_*: the cotangents of the deformed means / quats / scales (None = zero, no zero tensor is made).  rest:
+    also the rest-state gradients.  out: dict of preallocated contiguous float32 results (v_particles [m,3], and v_means,
+    v_quats, v_scales) -- those missing are allocated; bwd_status uint8 [n] or None (bit 0: the guard dropped the row's
+    rotation gradient); workspace: a uint8 tensor of at least apply_bwd_workspace_bytes(n) + 256 bytes (otherwise one is
+    allocated for the call).  Returns the dict."""
+    t_start, t_entry = binding.transposed()
+    require_device(quats, particles, status, ct_means, ct_quats, ct_scales, bwd_status, workspace, binding.idx)
+    n, m, dev = binding.n, binding.m, binding.idx.device
+    check_tensor("quats", quats, torch.float32, (n, 4))
+    check_tensor("particles", particles, torch.float32, (m, 3))
+    check_tensor("status", status, torch.uint8, (n,))
+    for name, t, cols in (("ct_means", ct_means, 3), ("ct_quats", ct_quats, 4), ("ct_scales", ct_scales, 3)):
+        if t is not None:
+            check_tensor(name, t, torch.float32, (n, cols))
+    if bwd_status is not None:
+        check_tensor("bwd_status", bwd_status, torch.uint8, (n,))
+    res = dict(out) if out is not None else {}
+    want = [("v_particles", (m, 3))] + ([("v_means", (n, 3)), ("v_quats", (n, 4)), ("v_scales", (n, 3))] if rest else [])
+    for name, shape in want:
+        if res.get(name) is None:
+            res[name] = torch.empty(shape, dtype=torch.float32, device=dev)
+        else:
+            check_tensor(f"out[{name!r}]", res[name], torch.float32, shape)
+    workspace, pad = aligned_workspace(workspace, apply_bwd_workspace_bytes(n) if workspace is None else 0, dev)
+    g = (lambda name: ptr(res[name])) if rest else (lambda name: None)
+    check(_lib.lib().mgs_deform_apply_bwd(
+        n, ptr(quats), ptr(binding.idx), ptr(binding.w), ptr(binding.p), ptr(binding.rest), ptr(binding.flags), m,
+        ptr(particles), ptr(status), ptr(ct_means), ptr(ct_quats), ptr(ct_scales), ptr(t_start), ptr(t_entry),
+        g("v_means"), g("v_quats"), g("v_scales"), ptr(res["v_particles"]), ptr(bwd_status),
+        workspace.data_ptr() + pad, max(0, workspace.numel() - pad), stream_handle()), "mgs_deform_apply_bwd")
+    return res
+
+
+def _aligned(t: Optional[Tensor]) -> Optional[Tensor]:
+    """A contiguous view at an odd storage offset is copied: the kernels load float4 (include/mgs_deform_bwd.h)."""
+    return t.clone() if t is not None and t.data_ptr() % 16 else t
+
+
+class _DeformFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, means, quats, scales, particles, binding, status):
+        mu, q, s, x = (_f32c(t.detach()) for t in (means, quats, scales, particles))
+        q = _aligned(q)
+        o_m, o_q, o_s = torch.empty_like(mu), torch.empty_like(q), torch.empty_like(s)
+        deform_apply_raw(mu, q, s, binding, MODES["rigid"], x, o_m, o_q, o_s, status=status)
+        ctx.save_for_backward(q, x, status)
+        ctx.set_materialize_grads(False)       # an output nobody used arrives as None: mgs_deform_apply_bwd takes NULL
+        ctx.binding = binding
+        ctx.dtypes = (means.dtype, quats.dtype, scales.dtype, particles.dtype)
+        return o_m, o_q, o_s
+
+    @staticmethod
+    @once_differentiable                      # the results come from a C call: a double backward raises
+    def backward(ctx, ct_m, ct_q, ct_s):
+        q, x, status = ctx.saved_tensors
+        ct = [_aligned(_f32c(g)) if g is not None else None for g in (ct_m, ct_q, ct_s)]
+        rest = any(ctx.needs_input_grad[:3])
+        res = deform_apply_bwd_raw(q, ctx.binding, x, status, ct[0], ct[1], ct[2], rest=rest)
+        names = ("v_means", "v_quats", "v_scales", "v_particles")
+        grads = [res[name].to(ctx.dtypes[i]) if ctx.needs_input_grad[i] else None for i, name in enumerate(names)]
+        return (*grads, None, None)
+
+
+def deform_gaussians_autograd(tensors: Dict, binding: ParticleBinding, particles: Tensor, status: Optional[Tensor] = None,
+                              mode: str = "rigid", rotate_sh: bool = False) -> Dict:
+    """`deform_gaussians` in the rigid mode that autograd can see through.  The forward is mgs_deform_apply, mode 0; the
+    backward is mgs_deform_apply_bwd (include/mgs_deform_bwd.h): a closed form on top of what the forward computes, and a
+    scatter from Gaussians to particles through the binding's transpose -- no floating-point atomics, the same bits in
+    every run.  `particles` and the rest state's `means`, `quats`, `scales` may each require grad; `opacities` and
+    `colors` are shared with `tensors`, so autograd passes through them by identity.  status: uint8 [N] that receives the
+    forward's STATUS_* bits (one is allocated where none is given: the backward follows the forward's branch from it, so
+    do not overwrite it before backward()).
+
+    The mean.  A bound Gaussian's position comes from the offset d0 in the binding, not from `means`: the gradient of a
+    bound row of `means` is DEFINED as that of d0 -- the derivative with the binding's neighbours and weights held fixed
+    and d0 = mu - Xbar following the mean.  After an optimiser step on the means, binding.shift_offsets_(delta) moves d0
+    by the same amount, so that the trained mean takes effect without a re-bind.  Rows that pass through (unbound, or a
+    non-finite neighbour this frame) take their cotangents bit for bit and give the particles exactly 0; thin rows are
+    translated only.  Where an inverted neighbourhood (det P < 0) leaves the rotation undetermined the rotation's gradient
+    is dropped for that row (the header's guard).
+
+    The affine mode and rotate_sh=True have no backward: NotImplementedError."""
+    if mode != "rigid":
+        if mode not in MODES:
+            raise ValueError(f"mode {mode!r} not in {tuple(MODES)}")
+        raise NotImplementedError(f"deform_gaussians_autograd: mode {mode!r} has no backward, only 'rigid' (use "
+                                  "deform_gaussians for a forward without gradients)")
+    if rotate_sh:
+        raise NotImplementedError("deform_gaussians_autograd: rotate_sh=True has no backward (use deform_gaussians for a "
+                                  "forward without gradients)")
+    n = binding.n
+    means, quats, scales = _rows(tensors["means"], 3, "means"), _rows(tensors["quats"], 4, "quats"), _rows(tensors["scales"], 3, "scales")
+    for t, what in ((means, "means"), (quats, "quats"), (scales, "scales")):
+        if t.shape[0] != n:
+            raise ValueError(f"{what} has {t.shape[0]} rows, the binding was made for {n} Gaussians")
+    _particles(particles, binding.m, "particles")
+    if status is not None:
+        check_tensor("status", status, torch.uint8, (n,))
+    require_device(means, quats, scales, particles, status, binding.idx)
+    if status is None:
+        status = torch.empty((n,), dtype=torch.uint8, device=means.device)
+    o_m, o_q, o_s = _DeformFn.apply(means, quats, scales, particles, binding, status)
+    return {"means": o_m, "quats": o_q, "scales": o_s, "opacities": tensors["opacities"], "colors": tensors["colors"],
+            "sh_degree": tensors.get("sh_degree")}
 
 
 @torch.no_grad()
@@ -220,5 +372,5 @@ def deform_gaussians(tensors: Dict, binding: ParticleBinding, particles: Tensor,
 
 
 __all__ = ["ParticleBinding", "bind_particles", "deform_gaussians", "deform_bind_raw", "deform_apply_raw", "deform_apply_sh_raw",
-           "bind_workspace_bytes", "MODES", "REST_ROWS", "FLAG_UNBOUND", "FLAG_FLAT", "FLAG_THIN", "STATUS_UNBOUND",
+           "deform_gaussians_autograd", "deform_apply_bwd_raw", "apply_bwd_workspace_bytes", "bind_workspace_bytes", "MODES", "REST_ROWS", "FLAG_UNBOUND", "FLAG_FLAT", "FLAG_THIN", "STATUS_UNBOUND",
            "STATUS_FALLBACK", "STATUS_THIN", "STATUS_NONFINITE"]
