@@ -19,8 +19,16 @@
 // of differences to the anchor x_0; the rotation and the deformed covariance are solved in fp64 with the same Jacobi.
 // Its SH instantiation (include/mgs_deform_sh.h) then turns the lane's SH rows by the rotation it found, in fp32 registers
 // (sh_rotate.h), rows of 16 coefficients staged through LDS (sh_staging.h); the instantiation without SH is untouched by it.
+//
+// deform_apply_bwd_kernel and deform_scatter_kernel (include/mgs_deform_bwd.h): the rigid mode's backward, one thread per
+// Gaussian into a neighbour-major workspace, then one wave per particle that adds its referents' rows in a fixed order.
+//
+// The shape matching itself -- gather, P, the eigenpairs of P^T P, the rotation, the quaternion product -- is in
+// deform_shape.h, once: the forward and the backward call the same functions, which is what makes the backward's R the
+// forward's.  The kernels below hold what differs: the branches, the affine covariance, the SH phase, the gradient chain.
 #include "mgs_common.h"
 #include "jacobi3.h"
+#include "deform_shape.h"
 #include "sh_staging.h"
 #include "sh_rotate.h"
 #include "../../include/mgs_deform.h"
@@ -36,16 +44,11 @@ namespace {
 constexpr int kDeformGroup = 256;         // threads of a workgroup (all three kernels)
 constexpr int kDeformTile = 1024;         // T: particles per LDS tile (16 KiB)
 constexpr int kDeformShGroup = 64;        // threads of a workgroup of the apply's SH instantiation: one wave
-constexpr int kK = MGS_DEFORM_K;
-constexpr int kRestRows = 12;
+constexpr int kRestRows = 12;             // (kK, the 8 neighbours, is deform_shape.h's)
 constexpr double kDegenerate = 1e-3;      // the flat / thin threshold on eigenvalue (bind) and singular-value (apply) ratios
 
 enum { kFlagUnbound = 1, kFlagFlat = 2, kFlagThin = 4 };
 enum { kStatusUnbound = 1, kStatusFallback = 2, kStatusThin = 4, kStatusNonFinite = 8 };
-
-__device__ __forceinline__ bool finite3(float x, float y, float z) {
-  return isfinite(x) && isfinite(y) && isfinite(z);
-}
 
 __global__ __launch_bounds__(kDeformGroup) void deform_knn_kernel(int n, const float* __restrict__ means,
                                                                  const uint8_t* __restrict__ select, int m,
@@ -195,64 +198,15 @@ __global__ __launch_bounds__(kDeformGroup) void deform_bind_kernel(int n, const 
   flags[i] = (uint8_t)((flat ? kFlagFlat : 0) | (thin ? kFlagThin : 0));
 }
 
-// exchange the eigenpairs a and b (the eigenvalue and column of v): names, not indices, so everything stays in registers
-#define MGS_SWAP_PAIR(la, lb, va0, va1, va2, vb0, vb1, vb2)                                    \
-  do {                                                                                         \
-    double t_ = la; la = lb; lb = t_;                                                          \
-    t_ = va0; va0 = vb0; vb0 = t_; t_ = va1; va1 = vb1; vb1 = t_; t_ = va2; va2 = vb2; vb2 = t_; \
-  } while (0)
-
-// the unit quaternion (w, x, y, z) of a proper rotation matrix, by the largest of the four pivots
-__device__ __forceinline__ void rotmat_to_quat(double r00, double r01, double r02, double r10, double r11, double r12,
-                                               double r20, double r21, double r22, double& qw, double& qx, double& qy,
-                                               double& qz) {
-  const double tr = r00 + r11 + r22;
-  if (tr > 0.0) {
-    const double s = 2.0 * sqrt(tr + 1.0);
-    qw = 0.25 * s; qx = (r21 - r12) / s; qy = (r02 - r20) / s; qz = (r10 - r01) / s;
-  } else if (r00 > r11 && r00 > r22) {
-    const double s = 2.0 * sqrt(1.0 + r00 - r11 - r22);
-    qw = (r21 - r12) / s; qx = 0.25 * s; qy = (r01 + r10) / s; qz = (r02 + r20) / s;
-  } else if (r11 > r22) {
-    const double s = 2.0 * sqrt(1.0 + r11 - r00 - r22);
-    qw = (r02 - r20) / s; qx = (r01 + r10) / s; qy = 0.25 * s; qz = (r12 + r21) / s;
-  } else {
-    const double s = 2.0 * sqrt(1.0 + r22 - r00 - r11);
-    qw = (r10 - r01) / s; qx = (r02 + r20) / s; qy = (r12 + r21) / s; qz = 0.25 * s;
-  }
-}
-
-// R = argmax over SO(3) of tr(R^T P) from the eigenpairs of P^T P, as doubles r00 .. r22 in the scope that uses it:
-// u1 = P v1 / sigma1, u2 = P v2 made orthonormal to u1, u3 = u1 x u2, v3 = v1 x v2, R = sum u_k v_k^T (v3 = v1 x v2 is w)
-#define MGS_SHAPE_ROTATION()                                                                                        \
-  const double is1 = 1.0 / sqrt(a00);                                                                               \
-  const double u10 = (p00 * v00 + p01 * v10 + p02 * v20) * is1, u11 = (p10 * v00 + p11 * v10 + p12 * v20) * is1;    \
-  const double u12 = (p20 * v00 + p21 * v10 + p22 * v20) * is1;                                                     \
-  double u20 = p00 * v01 + p01 * v11 + p02 * v21, u21 = p10 * v01 + p11 * v11 + p12 * v21;                          \
-  double u22 = p20 * v01 + p21 * v11 + p22 * v21;                                                                   \
-  const double dot = u10 * u20 + u11 * u21 + u12 * u22;                                                             \
-  u20 -= dot * u10; u21 -= dot * u11; u22 -= dot * u12;                                                             \
-  const double in2 = 1.0 / sqrt(u20 * u20 + u21 * u21 + u22 * u22);                                                 \
-  u20 *= in2; u21 *= in2; u22 *= in2;                                                                               \
-  const double u30 = u11 * u22 - u12 * u21, u31 = u12 * u20 - u10 * u22, u32 = u10 * u21 - u11 * u20;               \
-  const double w0 = v10 * v21 - v20 * v11, w1 = v20 * v01 - v00 * v21, w2 = v00 * v11 - v10 * v01;                  \
-  const double r00 = u10 * v00 + u20 * v01 + u30 * w0, r01 = u10 * v10 + u20 * v11 + u30 * w1;                      \
-  const double r02 = u10 * v20 + u20 * v21 + u30 * w2, r10 = u11 * v00 + u21 * v01 + u31 * w0;                      \
-  const double r11 = u11 * v10 + u21 * v11 + u31 * w1, r12 = u11 * v20 + u21 * v21 + u31 * w2;                      \
-  const double r20 = u12 * v00 + u22 * v01 + u32 * w0, r21 = u12 * v10 + u22 * v11 + u32 * w1;                      \
-  const double r22 = u12 * v20 + u22 * v21 + u32 * w2;
-
 // What the SH phase does with a lane's row: nothing (an unbound Gaussian, unless asked to copy), copy it through (bound
 // but not turning: thin, a non-finite neighbour) or rotate it.
 enum { kRowUnbound = 0, kRowCopy = 1, kRowRotate = 2 };
 
-// the SH phase's copy of R, rounded to fp32 once (row-major)
-#define MGS_STORE_ROTATION()                                                                                \
-  do {                                                                                                      \
-    Rf[0] = (float)r00; Rf[1] = (float)r01; Rf[2] = (float)r02; Rf[3] = (float)r10; Rf[4] = (float)r11;     \
-    Rf[5] = (float)r12; Rf[6] = (float)r20; Rf[7] = (float)r21; Rf[8] = (float)r22;                         \
-    row = kRowRotate;                                                                                       \
-  } while (0)
+// the SH phase's copy of R, rounded to fp32 once (row-major, as sh_rotate.h takes it)
+__device__ __forceinline__ void round_rotation(const Mat3d& r, float (&Rf)[9]) {
+  Rf[0] = (float)r.m00; Rf[1] = (float)r.m01; Rf[2] = (float)r.m02; Rf[3] = (float)r.m10; Rf[4] = (float)r.m11;
+  Rf[5] = (float)r.m12; Rf[6] = (float)r.m20; Rf[7] = (float)r.m21; Rf[8] = (float)r.m22;
+}
 
 // SH = false: the geometry alone, kDeformGroup threads, no LDS -- what mgs_deform_apply launches.
 // SH = true: one wave per workgroup (kDeformShGroup; the staging area of a wave is 13,312 B of LDS, so twelve resident
@@ -289,58 +243,21 @@ __global__ __launch_bounds__(SH ? kDeformShGroup : kDeformGroup) void deform_app
       st = kStatusUnbound;
       row = kRowUnbound;
     } else {
-      // the 8 current positions: the only random access
-      float x[kK][3];
-      bool ok = true;
-#pragma unroll
-      for (int k = 0; k < kK; ++k) {
-        const int j = idx[k * N + i];
-        const bool in = j >= 0 && j < m;
-        const size_t jj = in ? (size_t)j : 0;
-        x[k][0] = now[3 * jj + 0]; x[k][1] = now[3 * jj + 1]; x[k][2] = now[3 * jj + 2];
-        ok = ok && in && finite3(x[k][0], x[k][1], x[k][2]);
-      }
-      if (!ok) {
+      float x[kK][3], wk[kK], pk[kK][3];            // (wk and pk are the backward's: not touched here)
+      if (!gather_neighbours<true>(idx, N, i, m, now, x)) {
         st = kStatusNonFinite;
       } else {
-        // c = sum w_j e_j and P = sum e_j p_j^T over j = 1..7, e_j = x_j - x_0: fp32 fma chains in order of j
-        float c0 = 0.f, c1 = 0.f, c2 = 0.f;
-        float P00 = 0.f, P01 = 0.f, P02 = 0.f, P10 = 0.f, P11 = 0.f, P12 = 0.f, P20 = 0.f, P21 = 0.f, P22 = 0.f;
-#pragma unroll
-        for (int k = 1; k < kK; ++k) {
-          const float e0 = x[k][0] - x[0][0], e1 = x[k][1] - x[0][1], e2 = x[k][2] - x[0][2];
-          const float wk = w[k * N + i];
-          const float pk0 = p[(3 * k + 0) * N + i], pk1 = p[(3 * k + 1) * N + i], pk2 = p[(3 * k + 2) * N + i];
-          if (k == 1) {
-            c0 = wk * e0; c1 = wk * e1; c2 = wk * e2;
-            P00 = e0 * pk0; P01 = e0 * pk1; P02 = e0 * pk2;
-            P10 = e1 * pk0; P11 = e1 * pk1; P12 = e1 * pk2;
-            P20 = e2 * pk0; P21 = e2 * pk1; P22 = e2 * pk2;
-          } else {
-            c0 = __builtin_fmaf(wk, e0, c0); c1 = __builtin_fmaf(wk, e1, c1); c2 = __builtin_fmaf(wk, e2, c2);
-            P00 = __builtin_fmaf(e0, pk0, P00); P01 = __builtin_fmaf(e0, pk1, P01); P02 = __builtin_fmaf(e0, pk2, P02);
-            P10 = __builtin_fmaf(e1, pk0, P10); P11 = __builtin_fmaf(e1, pk1, P11); P12 = __builtin_fmaf(e1, pk2, P12);
-            P20 = __builtin_fmaf(e2, pk0, P20); P21 = __builtin_fmaf(e2, pk1, P21); P22 = __builtin_fmaf(e2, pk2, P22);
-          }
-        }
-        const float xb0 = x[0][0] + c0, xb1 = x[0][1] + c1, xb2 = x[0][2] + c2;
+        const Moment mo = moment_P<true>(x, w, p, N, i, wk, pk);
+        const Mat3f& P = mo.P;
+        const float xb0 = x[0][0] + mo.c0, xb1 = x[0][1] + mo.c1, xb2 = x[0][2] + mo.c2;
         const float d00 = rest[0 * N + i], d01 = rest[1 * N + i], d02 = rest[2 * N + i];
-
-        // P^T P and its eigenpairs, descending
-        const double p00 = P00, p01 = P01, p02 = P02, p10 = P10, p11 = P11, p12 = P12, p20 = P20, p21 = P21, p22 = P22;
-        double a00 = p00 * p00 + p10 * p10 + p20 * p20, a01 = p00 * p01 + p10 * p11 + p20 * p21;
-        double a02 = p00 * p02 + p10 * p12 + p20 * p22, a11 = p01 * p01 + p11 * p11 + p21 * p21;
-        double a12 = p01 * p02 + p11 * p12 + p21 * p22, a22 = p02 * p02 + p12 * p12 + p22 * p22;
-        double v00, v01, v02, v10, v11, v12, v20, v21, v22;
-        jacobi_solve3(a00, a01, a02, a11, a12, a22, v00, v01, v02, v10, v11, v12, v20, v21, v22);
-        if (a00 < a11) MGS_SWAP_PAIR(a00, a11, v00, v10, v20, v01, v11, v21);
-        if (a11 < a22) MGS_SWAP_PAIR(a11, a22, v01, v11, v21, v02, v12, v22);
-        if (a00 < a11) MGS_SWAP_PAIR(a00, a11, v00, v10, v20, v01, v11, v21);
+        const Mat3d Pd = widen(P);
+        const Eig3 eg = gram_eigen_desc(Pd);
         // sigma_mid < 1e-3 sigma_max  <=>  lambda_mid < 1e-6 lambda_max
-        const bool thin = (fl & kFlagThin) || !(a00 > 0.0) || a11 < kDegenerate * kDegenerate * a00;
+        const bool thin = (fl & kFlagThin) || !(eg.l0 > 0.0) || eg.l1 < kDegenerate * kDegenerate * eg.l0;
 
         bool rigid = mode == 0;
-        float A00 = 0.f, A01 = 0.f, A02 = 0.f, A10 = 0.f, A11 = 0.f, A12 = 0.f, A20 = 0.f, A21 = 0.f, A22 = 0.f;
+        Mat3f A = {};
         if (thin) {
           st = kStatusThin;
           mu0 = xb0 + d00; mu1 = xb1 + d01; mu2 = xb2 + d02;
@@ -350,44 +267,40 @@ __global__ __launch_bounds__(SH ? kDeformShGroup : kDeformGroup) void deform_app
           } else {                                    // A = P Q^-1 in fp32
             const float ixx = rest[3 * N + i], ixy = rest[4 * N + i], ixz = rest[5 * N + i];
             const float iyy = rest[6 * N + i], iyz = rest[7 * N + i], izz = rest[8 * N + i];
-            A00 = __builtin_fmaf(P02, ixz, __builtin_fmaf(P01, ixy, P00 * ixx));
-            A01 = __builtin_fmaf(P02, iyz, __builtin_fmaf(P01, iyy, P00 * ixy));
-            A02 = __builtin_fmaf(P02, izz, __builtin_fmaf(P01, iyz, P00 * ixz));
-            A10 = __builtin_fmaf(P12, ixz, __builtin_fmaf(P11, ixy, P10 * ixx));
-            A11 = __builtin_fmaf(P12, iyz, __builtin_fmaf(P11, iyy, P10 * ixy));
-            A12 = __builtin_fmaf(P12, izz, __builtin_fmaf(P11, iyz, P10 * ixz));
-            A20 = __builtin_fmaf(P22, ixz, __builtin_fmaf(P21, ixy, P20 * ixx));
-            A21 = __builtin_fmaf(P22, iyz, __builtin_fmaf(P21, iyy, P20 * ixy));
-            A22 = __builtin_fmaf(P22, izz, __builtin_fmaf(P21, iyz, P20 * ixz));
-            const double det = (double)A00 * ((double)A11 * A22 - (double)A12 * A21)
-                               - (double)A01 * ((double)A10 * A22 - (double)A12 * A20)
-                               + (double)A02 * ((double)A10 * A21 - (double)A11 * A20);
+            A.m00 = __builtin_fmaf(P.m02, ixz, __builtin_fmaf(P.m01, ixy, P.m00 * ixx));
+            A.m01 = __builtin_fmaf(P.m02, iyz, __builtin_fmaf(P.m01, iyy, P.m00 * ixy));
+            A.m02 = __builtin_fmaf(P.m02, izz, __builtin_fmaf(P.m01, iyz, P.m00 * ixz));
+            A.m10 = __builtin_fmaf(P.m12, ixz, __builtin_fmaf(P.m11, ixy, P.m10 * ixx));
+            A.m11 = __builtin_fmaf(P.m12, iyz, __builtin_fmaf(P.m11, iyy, P.m10 * ixy));
+            A.m12 = __builtin_fmaf(P.m12, izz, __builtin_fmaf(P.m11, iyz, P.m10 * ixz));
+            A.m20 = __builtin_fmaf(P.m22, ixz, __builtin_fmaf(P.m21, ixy, P.m20 * ixx));
+            A.m21 = __builtin_fmaf(P.m22, iyz, __builtin_fmaf(P.m21, iyy, P.m20 * ixy));
+            A.m22 = __builtin_fmaf(P.m22, izz, __builtin_fmaf(P.m21, iyz, P.m20 * ixz));
+            const double det = (double)A.m00 * ((double)A.m11 * A.m22 - (double)A.m12 * A.m21)
+                               - (double)A.m01 * ((double)A.m10 * A.m22 - (double)A.m12 * A.m20)
+                               + (double)A.m02 * ((double)A.m10 * A.m21 - (double)A.m11 * A.m20);
             if (!(det > 0.0)) rigid = true;
           }
           if (rigid) st = kStatusFallback;
         }
 
         if (!thin && rigid) {
-          MGS_SHAPE_ROTATION();
-          if constexpr (SH) MGS_STORE_ROTATION();
-          mu0 = (float)((double)xb0 + (r00 * d00 + r01 * d01 + r02 * d02));
-          mu1 = (float)((double)xb1 + (r10 * d00 + r11 * d01 + r12 * d02));
-          mu2 = (float)((double)xb2 + (r20 * d00 + r21 * d01 + r22 * d02));
-          double aw, ax, ay, az;
-          rotmat_to_quat(r00, r01, r02, r10, r11, r12, r20, r21, r22, aw, ax, ay, az);
-          const double bw = q.x, bx = q.y, by = q.z, bz = q.w;
-          const double ow = aw * bw - ax * bx - ay * by - az * bz, ox = aw * bx + ax * bw + ay * bz - az * by;
-          const double oy = aw * by - ax * bz + ay * bw + az * bx, oz = aw * bz + ax * by - ay * bx + az * bw;
-          const double inv = 1.0 / sqrt(ow * ow + ox * ox + oy * oy + oz * oz);
-          q = make_float4((float)(ow * inv), (float)(ox * inv), (float)(oy * inv), (float)(oz * inv));
+          const Mat3d R = shape_rotation(Pd, eg);
+          if constexpr (SH) { round_rotation(R, Rf); row = kRowRotate; }
+          mu0 = (float)((double)xb0 + (R.m00 * d00 + R.m01 * d01 + R.m02 * d02));
+          mu1 = (float)((double)xb1 + (R.m10 * d00 + R.m11 * d01 + R.m12 * d02));
+          mu2 = (float)((double)xb2 + (R.m20 * d00 + R.m21 * d01 + R.m22 * d02));
+          double inv;
+          const Quatd o = quat_mul_normalised(rotmat_to_quat(R), Quatd{q.x, q.y, q.z, q.w}, inv);
+          q = make_float4((float)o.w, (float)o.x, (float)o.y, (float)o.z);
         } else if (!thin) {
           if constexpr (SH) {                         // the colour field turns with the neighbourhood's rotation, it does not shear
-            MGS_SHAPE_ROTATION();
-            MGS_STORE_ROTATION();
+            round_rotation(shape_rotation(Pd, eg), Rf);
+            row = kRowRotate;
           }
-          mu0 = xb0 + __builtin_fmaf(A02, d02, __builtin_fmaf(A01, d01, A00 * d00));
-          mu1 = xb1 + __builtin_fmaf(A12, d02, __builtin_fmaf(A11, d01, A10 * d00));
-          mu2 = xb2 + __builtin_fmaf(A22, d02, __builtin_fmaf(A21, d01, A20 * d00));
+          mu0 = xb0 + __builtin_fmaf(A.m02, d02, __builtin_fmaf(A.m01, d01, A.m00 * d00));
+          mu1 = xb1 + __builtin_fmaf(A.m12, d02, __builtin_fmaf(A.m11, d01, A.m10 * d00));
+          mu2 = xb2 + __builtin_fmaf(A.m22, d02, __builtin_fmaf(A.m21, d01, A.m20 * d00));
           // M = A R(q) diag(s), Sigma' = M M^T
           double bw = q.x, bx = q.y, by = q.z, bz = q.w;
           const double inv = 1.0 / sqrt(bw * bw + bx * bx + by * by + bz * bz);
@@ -396,32 +309,26 @@ __global__ __launch_bounds__(SH ? kDeformShGroup : kDeformGroup) void deform_app
           const double g10 = 2.0 * (bx * by + bw * bz), g11 = 1.0 - 2.0 * (bx * bx + bz * bz), g12 = 2.0 * (by * bz - bw * bx);
           const double g20 = 2.0 * (bx * bz - bw * by), g21 = 2.0 * (by * bz + bw * bx), g22 = 1.0 - 2.0 * (bx * bx + by * by);
           const double t0 = s0, t1 = s1, t2 = s2;
-          const double m00 = ((double)A00 * g00 + (double)A01 * g10 + (double)A02 * g20) * t0;
-          const double m01 = ((double)A00 * g01 + (double)A01 * g11 + (double)A02 * g21) * t1;
-          const double m02 = ((double)A00 * g02 + (double)A01 * g12 + (double)A02 * g22) * t2;
-          const double m10 = ((double)A10 * g00 + (double)A11 * g10 + (double)A12 * g20) * t0;
-          const double m11 = ((double)A10 * g01 + (double)A11 * g11 + (double)A12 * g21) * t1;
-          const double m12 = ((double)A10 * g02 + (double)A11 * g12 + (double)A12 * g22) * t2;
-          const double m20 = ((double)A20 * g00 + (double)A21 * g10 + (double)A22 * g20) * t0;
-          const double m21 = ((double)A20 * g01 + (double)A21 * g11 + (double)A22 * g21) * t1;
-          const double m22 = ((double)A20 * g02 + (double)A21 * g12 + (double)A22 * g22) * t2;
-          double e00 = m00 * m00 + m01 * m01 + m02 * m02, e01 = m00 * m10 + m01 * m11 + m02 * m12;
-          double e02 = m00 * m20 + m01 * m21 + m02 * m22, e11 = m10 * m10 + m11 * m11 + m12 * m12;
-          double e12 = m10 * m20 + m11 * m21 + m12 * m22, e22 = m20 * m20 + m21 * m21 + m22 * m22;
-          double z00, z01, z02, z10, z11, z12, z20, z21, z22;
-          jacobi_solve3(e00, e01, e02, e11, e12, e22, z00, z01, z02, z10, z11, z12, z20, z21, z22);
-          if (e00 > e11) MGS_SWAP_PAIR(e00, e11, z00, z10, z20, z01, z11, z21);       // ascending
-          if (e11 > e22) MGS_SWAP_PAIR(e11, e22, z01, z11, z21, z02, z12, z22);
-          if (e00 > e11) MGS_SWAP_PAIR(e00, e11, z00, z10, z20, z01, z11, z21);
-          const double detz = z00 * (z11 * z22 - z12 * z21) - z01 * (z10 * z22 - z12 * z20) + z02 * (z10 * z21 - z11 * z20);
-          if (detz < 0.0) { z02 = -z02; z12 = -z12; z22 = -z22; }
-          double aw, ax, ay, az;
-          rotmat_to_quat(z00, z01, z02, z10, z11, z12, z20, z21, z22, aw, ax, ay, az);
-          const double qn = 1.0 / sqrt(aw * aw + ax * ax + ay * ay + az * az);
-          q = make_float4((float)(aw * qn), (float)(ax * qn), (float)(ay * qn), (float)(az * qn));
-          s0 = fmaxf((float)sqrt(fmax(e00, 0.0)), FLT_MIN);
-          s1 = fmaxf((float)sqrt(fmax(e11, 0.0)), FLT_MIN);
-          s2 = fmaxf((float)sqrt(fmax(e22, 0.0)), FLT_MIN);
+          const Mat3d M = {((double)A.m00 * g00 + (double)A.m01 * g10 + (double)A.m02 * g20) * t0,
+                           ((double)A.m00 * g01 + (double)A.m01 * g11 + (double)A.m02 * g21) * t1,
+                           ((double)A.m00 * g02 + (double)A.m01 * g12 + (double)A.m02 * g22) * t2,
+                           ((double)A.m10 * g00 + (double)A.m11 * g10 + (double)A.m12 * g20) * t0,
+                           ((double)A.m10 * g01 + (double)A.m11 * g11 + (double)A.m12 * g21) * t1,
+                           ((double)A.m10 * g02 + (double)A.m11 * g12 + (double)A.m12 * g22) * t2,
+                           ((double)A.m20 * g00 + (double)A.m21 * g10 + (double)A.m22 * g20) * t0,
+                           ((double)A.m20 * g01 + (double)A.m21 * g11 + (double)A.m22 * g21) * t1,
+                           ((double)A.m20 * g02 + (double)A.m21 * g12 + (double)A.m22 * g22) * t2};
+          Eig3 es = eigen_sorted<false>(gram(transposed(M)));       // ascending; its columns are the new axes
+          Mat3d& z = es.v;
+          const double detz = z.m00 * (z.m11 * z.m22 - z.m12 * z.m21) - z.m01 * (z.m10 * z.m22 - z.m12 * z.m20)
+                              + z.m02 * (z.m10 * z.m21 - z.m11 * z.m20);
+          if (detz < 0.0) { z.m02 = -z.m02; z.m12 = -z.m12; z.m22 = -z.m22; }
+          const Quatd a = rotmat_to_quat(z);
+          const double qn = 1.0 / sqrt(a.w * a.w + a.x * a.x + a.y * a.y + a.z * a.z);
+          q = make_float4((float)(a.w * qn), (float)(a.x * qn), (float)(a.y * qn), (float)(a.z * qn));
+          s0 = fmaxf((float)sqrt(fmax(es.l0, 0.0)), FLT_MIN);
+          s1 = fmaxf((float)sqrt(fmax(es.l1, 0.0)), FLT_MIN);
+          s2 = fmaxf((float)sqrt(fmax(es.l2, 0.0)), FLT_MIN);
         }
       }
     }
@@ -484,9 +391,10 @@ __global__ __launch_bounds__(SH ? kDeformShGroup : kDeformGroup) void deform_app
   }
 }
 
-// deform_apply_bwd_kernel (include/mgs_deform_bwd.h, launch 1).  One thread per Gaussian.  P and the eigenpairs of
-// P^T P are formed exactly as deform_apply_kernel forms them (c itself has no part in the gradient: only its weights), so MGS_SHAPE_ROTATION gives the forward's R bit for bit; the
-// branch is the forward's status, not a second decision.  The chain v_omega -> y = G^-1 R^T v_omega -> v_P = R [y]x runs in
+// deform_apply_bwd_kernel (include/mgs_deform_bwd.h, launch 1).  One thread per Gaussian.  P, the eigenpairs of P^T P,
+// R and q' come from the same functions deform_apply_kernel calls (deform_shape.h; c has no part in the gradient, only
+// its weights, so moment_P leaves it out), on the same inputs: the forward's R and q' bit for bit.  The branch is the
+// forward's status, not a second decision.  The chain v_omega -> y = G^-1 R^T v_omega -> v_P = R [y]x runs in
 // fp64 on named scalars; w and p stay in registers from the forward part to the 24 contributions at the end.  The
 // contributions go to the neighbour-major workspace ws [8][3][N] (coalesced), a pass-through row's as zeros.
 __global__ __launch_bounds__(kDeformGroup) void deform_apply_bwd_kernel(
@@ -513,48 +421,19 @@ __global__ __launch_bounds__(kDeformGroup) void deform_apply_bwd_kernel(
   const unsigned st = status[i];
   if (!((flags[i] & kFlagUnbound) || (st & (kStatusUnbound | kStatusNonFinite)))) {
     float x[kK][3];
-    bool ok = true;
-#pragma unroll
-    for (int k = 0; k < kK; ++k) {
-      const int j = idx[k * N + i];
-      const bool in = j >= 0 && j < m;
-      const size_t jj = in ? (size_t)j : 0;
-      x[k][0] = now[3 * jj + 0]; x[k][1] = now[3 * jj + 1]; x[k][2] = now[3 * jj + 2];
-      ok = ok && in;
-    }
-    if (ok) {                                        // (a status that is not this frame's: nothing is followed out of range)
+    const bool in_range = gather_neighbours<false>(idx, N, i, m, now, x);
+    if (in_range) {                                  // (a status that is not this frame's: nothing is followed out of range)
       float wk[kK], pk[kK][3];
-      float P00 = 0.f, P01 = 0.f, P02 = 0.f, P10 = 0.f, P11 = 0.f, P12 = 0.f, P20 = 0.f, P21 = 0.f, P22 = 0.f;
-      wk[0] = 0.f; pk[0][0] = 0.f; pk[0][1] = 0.f; pk[0][2] = 0.f;
-#pragma unroll
-      for (int k = 1; k < kK; ++k) {
-        const float e0 = x[k][0] - x[0][0], e1 = x[k][1] - x[0][1], e2 = x[k][2] - x[0][2];
-        wk[k] = w[k * N + i];
-        const float pk0 = p[(3 * k + 0) * N + i], pk1 = p[(3 * k + 1) * N + i], pk2 = p[(3 * k + 2) * N + i];
-        pk[k][0] = pk0; pk[k][1] = pk1; pk[k][2] = pk2;
-        if (k == 1) {
-          P00 = e0 * pk0; P01 = e0 * pk1; P02 = e0 * pk2;
-          P10 = e1 * pk0; P11 = e1 * pk1; P12 = e1 * pk2;
-          P20 = e2 * pk0; P21 = e2 * pk1; P22 = e2 * pk2;
-        } else {
-          P00 = __builtin_fmaf(e0, pk0, P00); P01 = __builtin_fmaf(e0, pk1, P01); P02 = __builtin_fmaf(e0, pk2, P02);
-          P10 = __builtin_fmaf(e1, pk0, P10); P11 = __builtin_fmaf(e1, pk1, P11); P12 = __builtin_fmaf(e1, pk2, P12);
-          P20 = __builtin_fmaf(e2, pk0, P20); P21 = __builtin_fmaf(e2, pk1, P21); P22 = __builtin_fmaf(e2, pk2, P22);
-        }
-      }
+      const Mat3d P = widen(moment_P<false>(x, w, p, N, i, wk, pk).P);
       // v_P, zero unless the row turned and the guard let the rotation's gradient through
       double g00 = 0., g01 = 0., g02 = 0., g10 = 0., g11 = 0., g12 = 0., g20 = 0., g21 = 0., g22 = 0.;
       if (!(st & kStatusThin)) {
-        const double p00 = P00, p01 = P01, p02 = P02, p10 = P10, p11 = P11, p12 = P12, p20 = P20, p21 = P21, p22 = P22;
-        double a00 = p00 * p00 + p10 * p10 + p20 * p20, a01 = p00 * p01 + p10 * p11 + p20 * p21;
-        double a02 = p00 * p02 + p10 * p12 + p20 * p22, a11 = p01 * p01 + p11 * p11 + p21 * p21;
-        double a12 = p01 * p02 + p11 * p12 + p21 * p22, a22 = p02 * p02 + p12 * p12 + p22 * p22;
-        double v00, v01, v02, v10, v11, v12, v20, v21, v22;
-        jacobi_solve3(a00, a01, a02, a11, a12, a22, v00, v01, v02, v10, v11, v12, v20, v21, v22);
-        if (a00 < a11) MGS_SWAP_PAIR(a00, a11, v00, v10, v20, v01, v11, v21);
-        if (a11 < a22) MGS_SWAP_PAIR(a11, a22, v01, v11, v21, v02, v12, v22);
-        if (a00 < a11) MGS_SWAP_PAIR(a00, a11, v00, v10, v20, v01, v11, v21);
-        MGS_SHAPE_ROTATION();
+        const Eig3 eg = gram_eigen_desc(P);
+        const Mat3d R = shape_rotation(P, eg);
+        const double r00 = R.m00, r01 = R.m01, r02 = R.m02, r10 = R.m10, r11 = R.m11, r12 = R.m12, r20 = R.m20, r21 = R.m21,
+                     r22 = R.m22;
+        const double p00 = P.m00, p01 = P.m01, p02 = P.m02, p10 = P.m10, p11 = P.m11, p12 = P.m12, p20 = P.m20, p21 = P.m21,
+                     p22 = P.m22;
         const double d0 = rest[0 * N + i], d1 = rest[1 * N + i], d2 = rest[2 * N + i];
         const double m0 = cm0, m1 = cm1, m2 = cm2;
         vm0 = (float)(r00 * m0 + r10 * m1 + r20 * m2);                      // v_d0 = R^T ct_mu
@@ -566,18 +445,15 @@ __global__ __launch_bounds__(kDeformGroup) void deform_apply_bwd_kernel(
         const double s01 = 0.5 * ((r00 * p01 + r10 * p11 + r20 * p21) + (r01 * p00 + r11 * p10 + r21 * p20));
         const double s02 = 0.5 * ((r00 * p02 + r10 * p12 + r20 * p22) + (r02 * p00 + r12 * p10 + r22 * p20));
         const double s12 = 0.5 * ((r01 * p02 + r11 * p12 + r21 * p22) + (r02 * p01 + r12 * p11 + r22 * p21));
-        const double tr = s00 + s11 + s22, sig1 = sqrt(a00);
+        const double tr = s00 + s11 + s22, sig1 = sqrt(eg.l0);
         if (tr - sig1 < kDegenerate * sig1) {
           bst = 1u;                                  // guarded: v_P = 0, v_q = ct_q
         } else {
-          double aw, ax, ay, az;
-          rotmat_to_quat(r00, r01, r02, r10, r11, r12, r20, r21, r22, aw, ax, ay, az);
+          const Quatd a = rotmat_to_quat(R);
           const float4 q = reinterpret_cast<const float4*>(quats)[i];
-          const double bw = q.x, bx = q.y, by = q.z, bz = q.w;
-          double ow = aw * bw - ax * bx - ay * by - az * bz, ox = aw * bx + ax * bw + ay * bz - az * by;
-          double oy = aw * by - ax * bz + ay * bw + az * bx, oz = aw * bz + ax * by - ay * bx + az * bw;
-          const double inv = 1.0 / sqrt(ow * ow + ox * ox + oy * oy + oz * oz);
-          ow *= inv; ox *= inv; oy *= inv; oz *= inv;                        // q'
+          double inv;
+          const Quatd o = quat_mul_normalised(a, Quatd{q.x, q.y, q.z, q.w}, inv);   // q'
+          const double aw = a.w, ax = a.x, ay = a.y, az = a.z, ow = o.w, ox = o.x, oy = o.y, oz = o.z;
           const double tw = cq.x, tx = cq.y, ty = cq.z, tz = cq.w;
           // v_q = conj(q_R) (x) (ct_q - <ct_q, q'> q') / |q_R (x) q|
           const double dq = tw * ow + tx * ox + ty * oy + tz * oz;
@@ -662,10 +538,6 @@ __global__ __launch_bounds__(kDeformGroup) void deform_scatter_kernel(int n, int
   if (lane == 0) { v_particles[3 * j + 0] = s0; v_particles[3 * j + 1] = s1; v_particles[3 * j + 2] = s2; }
 }
 
-#undef MGS_SWAP_PAIR
-#undef MGS_STORE_ROTATION
-#undef MGS_SHAPE_ROTATION
-
 size_t bind_workspace_bytes(int n) {
   Bump b(1);
   b.take(sizeof(float) * (size_t)kK * (size_t)n);      // d2 [8][n]: the sorted squared distances between the two launches
@@ -678,6 +550,47 @@ size_t apply_bwd_workspace_bytes(int n) {
   Bump b(1);
   b.take(sizeof(float) * 3 * (size_t)kK * (size_t)n);  // ws [8][3][n]: the contributions between the two launches
   return b.total;
+}
+
+// what mgs_deform_apply and mgs_deform_apply_sh hand to deform_apply_kernel, in its parameter order
+struct ApplyArgs {
+  int n; const float *means, *quats, *scales; const int32_t* idx; const float *w, *p, *rest; const uint8_t* flags;
+  int mode, m; const float* now; float *out_means, *out_quats, *out_scales; uint8_t* status;
+  int sh_degree, coeff_stride; const float* sh_in; float* sh_out; int copy_unbound;
+};
+
+// The argument checks of the two entry points in their one order (the first failing check decides the message); sh: the
+// SH entry point, whose own checks stand where it makes them.  n == 0 ends the list early: nothing is dereferenced.
+int check_apply(const char* name, const ApplyArgs& a, bool sh) {
+  MGS_REQUIRE(a.n >= 0, "%s: n %d is negative", name, a.n);
+  MGS_REQUIRE(a.m >= kK, "%s: m %d particles, at least %d needed", name, a.m, kK);
+  MGS_REQUIRE(a.mode == 0 || a.mode == 1, "%s: mode %d is neither 0 (rigid) nor 1 (affine)", name, a.mode);
+  if (sh) {
+    MGS_REQUIRE(a.sh_degree >= 0 && a.sh_degree <= 3, "%s: sh_degree %d is outside 0..3", name, a.sh_degree);
+    MGS_REQUIRE(a.coeff_stride >= (a.sh_degree + 1) * (a.sh_degree + 1),
+                "%s: rows of %d coefficients cannot hold the %d of degree %d", name, a.coeff_stride,
+                (a.sh_degree + 1) * (a.sh_degree + 1), a.sh_degree);
+  }
+  if (a.n == 0) return MGS_OK;
+  MGS_REQUIRE(a.means && a.quats && a.scales, "%s: means, quats or scales is null", name);
+  MGS_REQUIRE(a.idx && a.w && a.p && a.rest && a.flags, "%s: a binding array (idx, w, p, rest, flags) is null", name);
+  MGS_REQUIRE(a.now, "%s: particles_now is null", name);
+  MGS_REQUIRE(a.out_means && a.out_quats && a.out_scales, "%s: an output is null", name);
+  if (sh) {
+    MGS_REQUIRE(a.sh_in && a.sh_out, "%s: sh_coeffs or out_sh is null", name);
+    MGS_REQUIRE(a.sh_out != a.sh_in, "%s: out_sh is sh_coeffs (the rest rows must survive: every frame turns them anew)", name);
+  }
+  return MGS_OK;
+}
+
+template <bool SH, bool STAGED>
+int launch_apply(const char* name, const ApplyArgs& a, mgs_stream_t stream) {
+  constexpr int kGroup = SH ? kDeformShGroup : kDeformGroup;
+  hipLaunchKernelGGL((deform_apply_kernel<SH, STAGED>), dim3(div_up((unsigned)a.n, (unsigned)kGroup)), dim3(kGroup), 0,
+                     (hipStream_t)stream, a.n, a.means, a.quats, a.scales, a.idx, a.w, a.p, a.rest, a.flags, a.mode, a.m, a.now,
+                     a.out_means, a.out_quats, a.out_scales, a.status, a.sh_degree, a.coeff_stride * 3, a.sh_in, a.sh_out,
+                     a.copy_unbound);
+  return check_launch(name);
 }
 
 }  // namespace
@@ -717,19 +630,11 @@ extern "C" int mgs_deform_apply(int n, const float* means, const float* quats, c
                                 const float* w, const float* p, const float* rest, const uint8_t* flags, int mode, int m,
                                 const float* particles_now, float* out_means, float* out_quats, float* out_scales,
                                 uint8_t* status, mgs_stream_t stream) {
-  MGS_REQUIRE(n >= 0, "deform_apply: n %d is negative", n);
-  MGS_REQUIRE(m >= kK, "deform_apply: m %d particles, at least %d needed", m, kK);
-  MGS_REQUIRE(mode == 0 || mode == 1, "deform_apply: mode %d is neither 0 (rigid) nor 1 (affine)", mode);
-  if (n == 0) return MGS_OK;
-  MGS_REQUIRE(means && quats && scales, "deform_apply: means, quats or scales is null");
-  MGS_REQUIRE(idx && w && p && rest && flags, "deform_apply: a binding array (idx, w, p, rest, flags) is null");
-  MGS_REQUIRE(particles_now, "deform_apply: particles_now is null");
-  MGS_REQUIRE(out_means && out_quats && out_scales, "deform_apply: an output is null");
-  const dim3 grid(div_up((unsigned)n, (unsigned)kDeformGroup)), block(kDeformGroup);
-  hipLaunchKernelGGL((deform_apply_kernel<false, false>), grid, block, 0, (hipStream_t)stream, n, means, quats, scales, idx,
-                     w, p, rest, flags, mode, m, particles_now, out_means, out_quats, out_scales, status, 0, 0,
-                     (const float*)nullptr, (float*)nullptr, 0);
-  return check_launch("deform_apply");
+  const ApplyArgs a = {n, means, quats, scales, idx, w, p, rest, flags, mode, m, particles_now, out_means, out_quats,
+                       out_scales, status, 0, 0, nullptr, nullptr, 0};
+  const int rc = check_apply("deform_apply", a, false);
+  if (rc || n == 0) return rc;
+  return launch_apply<false, false>("deform_apply", a, stream);
 }
 
 extern "C" int mgs_deform_apply_sh(int n, const float* means, const float* quats, const float* scales, const int32_t* idx,
@@ -737,28 +642,14 @@ extern "C" int mgs_deform_apply_sh(int n, const float* means, const float* quats
                                    const float* particles_now, float* out_means, float* out_quats, float* out_scales,
                                    uint8_t* status, int sh_degree, int coeff_stride, const float* sh_coeffs, float* out_sh,
                                    int copy_unbound, mgs_stream_t stream) {
-  MGS_REQUIRE(n >= 0, "deform_apply_sh: n %d is negative", n);
-  MGS_REQUIRE(m >= kK, "deform_apply_sh: m %d particles, at least %d needed", m, kK);
-  MGS_REQUIRE(mode == 0 || mode == 1, "deform_apply_sh: mode %d is neither 0 (rigid) nor 1 (affine)", mode);
-  MGS_REQUIRE(sh_degree >= 0 && sh_degree <= 3, "deform_apply_sh: sh_degree %d is outside 0..3", sh_degree);
-  MGS_REQUIRE(coeff_stride >= (sh_degree + 1) * (sh_degree + 1),
-              "deform_apply_sh: rows of %d coefficients cannot hold the %d of degree %d", coeff_stride,
-              (sh_degree + 1) * (sh_degree + 1), sh_degree);
-  if (n == 0) return MGS_OK;
-  MGS_REQUIRE(means && quats && scales, "deform_apply_sh: means, quats or scales is null");
-  MGS_REQUIRE(idx && w && p && rest && flags, "deform_apply_sh: a binding array (idx, w, p, rest, flags) is null");
-  MGS_REQUIRE(particles_now, "deform_apply_sh: particles_now is null");
-  MGS_REQUIRE(out_means && out_quats && out_scales, "deform_apply_sh: an output is null");
-  MGS_REQUIRE(sh_coeffs && out_sh, "deform_apply_sh: sh_coeffs or out_sh is null");
-  MGS_REQUIRE(out_sh != sh_coeffs, "deform_apply_sh: out_sh is sh_coeffs (the rest rows must survive: every frame turns them anew)");
-  const dim3 grid(div_up((unsigned)n, (unsigned)kDeformShGroup)), block(kDeformShGroup);
-  const int stride_f = coeff_stride * 3;
-  with_bool(coeff_stride == 16, [&](auto staged) {
-    hipLaunchKernelGGL((deform_apply_kernel<true, decltype(staged)::value>), grid, block, 0, (hipStream_t)stream, n, means,
-                       quats, scales, idx, w, p, rest, flags, mode, m, particles_now, out_means, out_quats, out_scales,
-                       status, sh_degree, stride_f, sh_coeffs, out_sh, copy_unbound != 0);
+  const ApplyArgs a = {n, means, quats, scales, idx, w, p, rest, flags, mode, m, particles_now, out_means, out_quats,
+                       out_scales, status, sh_degree, coeff_stride, sh_coeffs, out_sh, copy_unbound != 0};
+  int rc = check_apply("deform_apply_sh", a, true);
+  if (rc || n == 0) return rc;
+  with_bool(coeff_stride == 16, [&](auto staged) {                // rows of 16 coefficients go through LDS
+    rc = launch_apply<true, decltype(staged)::value>("deform_apply_sh", a, stream);
   });
-  return check_launch("deform_apply_sh");
+  return rc;
 }
 
 extern "C" size_t mgs_deform_apply_bwd_workspace_bytes(int n) {

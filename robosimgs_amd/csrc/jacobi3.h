@@ -1,5 +1,6 @@
 // jacobi3.h -- the symmetric 3x3 eigenproblem in fp64 by cyclic Jacobi sweeps, shared by hinge.hip (the covariance of the
-// contact set) and deform.hip (a neighbourhood's moment matrix, P^T P and a deformed covariance, once per Gaussian).
+// contact set), deform.hip (a neighbourhood's moment matrix) and deform_shape.h (P^T P and a deformed covariance, once per
+// Gaussian).
 // Scalars throughout and every index a compile-time constant: each entry stays in a register, no scratch.
 #ifndef MGS_JACOBI3_H_
 #define MGS_JACOBI3_H_

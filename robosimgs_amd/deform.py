@@ -67,6 +67,19 @@ def _particles(x: Tensor, m: Optional[int], what: str) -> Tensor:
     return x
 
 
+def _rest_state(tensors: Dict, binding: "ParticleBinding", particles: Tensor, status: Optional[Tensor]):
+    """The checks deform_gaussians and deform_gaussians_autograd open with: rows for the binding's n Gaussians, its particle
+    set, status uint8 [n] or None.  The device check stays the callers': deform_gaussians' colours ValueError precedes it."""
+    means, quats, scales = _rows(tensors["means"], 3, "means"), _rows(tensors["quats"], 4, "quats"), _rows(tensors["scales"], 3, "scales")
+    for t, what in ((means, "means"), (quats, "quats"), (scales, "scales")):
+        if t.shape[0] != binding.n:
+            raise ValueError(f"{what} has {t.shape[0]} rows, the binding was made for {binding.n} Gaussians")
+    _particles(particles, binding.m, "particles")
+    if status is not None:
+        check_tensor("status", status, torch.uint8, (binding.n,))
+    return means, quats, scales
+
+
 class ParticleBinding:
     """What bind_particles made, neighbour-major device tensors (include/mgs_deform.h): idx int32 [8,N], w float32 [8,N],
     p float32 [8,3,N], rest float32 [12,N], flags uint8 [N]; n Gaussians, m particles.  `particles` (optional): the rest
@@ -270,17 +283,10 @@ def deform_gaussians_autograd(tensors: Dict, binding: ParticleBinding, particles
     if rotate_sh:
         raise NotImplementedError("deform_gaussians_autograd: rotate_sh=True has no backward (use deform_gaussians for a "
                                   "forward without gradients)")
-    n = binding.n
-    means, quats, scales = _rows(tensors["means"], 3, "means"), _rows(tensors["quats"], 4, "quats"), _rows(tensors["scales"], 3, "scales")
-    for t, what in ((means, "means"), (quats, "quats"), (scales, "scales")):
-        if t.shape[0] != n:
-            raise ValueError(f"{what} has {t.shape[0]} rows, the binding was made for {n} Gaussians")
-    _particles(particles, binding.m, "particles")
-    if status is not None:
-        check_tensor("status", status, torch.uint8, (n,))
+    means, quats, scales = _rest_state(tensors, binding, particles, status)
     require_device(means, quats, scales, particles, status, binding.idx)
     if status is None:
-        status = torch.empty((n,), dtype=torch.uint8, device=means.device)
+        status = torch.empty((binding.n,), dtype=torch.uint8, device=means.device)
     o_m, o_q, o_s = _DeformFn.apply(means, quats, scales, particles, binding, status)
     return {"means": o_m, "quats": o_q, "scales": o_s, "opacities": tensors["opacities"], "colors": tensors["colors"],
             "sh_degree": tensors.get("sh_degree")}
@@ -331,15 +337,8 @@ def deform_gaussians(tensors: Dict, binding: ParticleBinding, particles: Tensor,
         raise ValueError(f"mode {mode!r} not in {tuple(MODES)}")
     if out is tensors and out is not None:
         raise ValueError("out is tensors: deform_gaussians deforms the rest state anew every frame and must not overwrite it")
-    n = binding.n
-    means, quats, scales = _rows(tensors["means"], 3, "means"), _rows(tensors["quats"], 4, "quats"), _rows(tensors["scales"], 3, "scales")
-    for t, what in ((means, "means"), (quats, "quats"), (scales, "scales")):
-        if t.shape[0] != n:
-            raise ValueError(f"{what} has {t.shape[0]} rows, the binding was made for {n} Gaussians")
-    _particles(particles, binding.m, "particles")
-    if status is not None:
-        check_tensor("status", status, torch.uint8, (n,))
-    colors, deg = tensors["colors"], int(tensors.get("sh_degree") or 0)
+    means, quats, scales = _rest_state(tensors, binding, particles, status)
+    n, colors, deg = binding.n, tensors["colors"], int(tensors.get("sh_degree") or 0)
     do_sh = bool(rotate_sh) and torch.is_tensor(colors) and colors.dim() == 3 and colors.shape[1] >= (deg + 1) ** 2 and deg >= 1
     if do_sh and (colors.shape[0] != n or colors.shape[2] != 3 or not colors.dtype.is_floating_point):
         raise ValueError(f"colors must be [{n},K,3], got {colors.dtype} {list(colors.shape)}")
