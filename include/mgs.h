@@ -255,6 +255,9 @@ int mgs_project_color_fwd(int n, const float *means, const float *quats, const f
  * tile_ids[n_isect] (ty*tile_w+tx, ascending) and tile_offsets[n_tiles+1] (first sorted
  * index of each tile, last entry = n_isect).  Ordering is identical to a stable sort of
  * the 64-bit keys (tile << 32 | float_bits(depth)) emitted in Gaussian-index order.
+ * float_bits is the depth's 32-bit pattern read as an UNSIGNED integer and nothing else:
+ * every pattern is a key (zero, denormals, infinities; negative numbers and NaNs order by
+ * their bits, behind every positive number), equal patterns keep Gaussian-index order.
  * isect_ids[capacity] (nullable) receives those int64 keys, with `cam_id` folded in above
  * the tile bits exactly as gsplat encodes them.
  *

@@ -8,7 +8,8 @@
 //   2. DIRECT PATH (tile grids up to ~65 k tiles, below): a counting sort of the pairs on their tile GROUP (four
 //      consecutive tiles) with LDS-resident counters -- histogram per run of Gaussians, column scan, scatter;
 //   3. tile_sort.hip: one workgroup per tile picks its entries out of its group's segment and orders them by
-//      (depth bits, index); it also stores the tile's offset and the entries' tile ids.
+//      (depth bits, index); it also stores the tile's offset and the entries' tile ids.  A list over its LDS list is
+//      split into units by sample sort where the capacity says lists are long (two more launches: collect, units).
 // Sorting each tile's list by the full (depth, index) composite == the stable sort on (tile, depth) with
 // index-order ties: flatten_ids / isect_ids are bit-identical to the single-key
 // formulation, whatever order step 2 delivers the entries in.
@@ -554,8 +555,8 @@ __global__ __launch_bounds__(kDirectThreads) void direct_scatter_kernel(
     tile_offsets[n_tiles] = (int32_t)(total < capacity ? (uint32_t)total : capacity);
     *n_isect = total > 0xffffffffull ? 0xffffffffu : (uint32_t)total;
     *status = total > capacity ? MGS_STATUS_ISECT_OVERFLOW : 0u;
-    // the header of the per-tile sort's deferred lists (tile_sort.hip kListHeader: eight counters -- descriptors, unit
-    // table entries, collect chunks claimed), instead of a memset
+    // the header of the per-tile sort's deferred lists (tile_sort.hip kListHeader: eight words -- descriptors claimed, unit
+    // table entries claimed from the bottom and from the top, collect chunks claimed), instead of a memset
     if (zero_word) reinterpret_cast<uint4*>(zero_word)[0] = reinterpret_cast<uint4*>(zero_word)[1] = make_uint4(0u, 0u, 0u, 0u);
   }
   __syncthreads();

@@ -10,17 +10,21 @@
 // Per segment: most-significant-digit bucketing on the 64-bit composite key (depth << 32 | id):
 //   min / max of the composites -> highest differing bit hb -> 10-bit digit (comp >> (hb - 9)) & 1023
 //   LDS histogram (atomics), exclusive scan, scatter into the other scratch buffer (bucket order,
-//   arbitrary order inside a bucket), then every element of a bucket of <= 48 entries finds its final
+//   arbitrary order inside a bucket), then every element of a bucket of <= kSmall entries finds its final
 //   place by counting the smaller composites of its own bucket.  Depth keys of one tile share their
 //   exponent bits, so the digit lands on the top mantissa bits and buckets hold ~1 element: O(n).
-//   A bucket of more than 48 entries (many near-identical depths) goes onto an LDS stack and is
-//   bucketed again on ITS highest differing bit (ten bits further down at least), so any input
-//   terminates in at most seven levels; composites are distinct (ids are), ties cannot loop.
+//   A bucket of more than kSmall entries (many near-identical depths) goes onto an LDS stack of kStack
+//   pending buckets and is bucketed again on ITS highest differing bit (ten bits further down at least), so
+//   any input terminates in at most seven levels; composites are distinct (ids are), ties cannot loop.  Heavy
+//   buckets a level finds beyond the stack's room are rank-counted whatever their size (kBrute).
+//   The order is that of the UNSIGNED depth bits: every bit pattern of a key is defined, negative numbers,
+//   infinities and NaNs included (they sort behind the positive numbers, as the textbook sort's key does).
 // Lists of up to kFast entries (nearly all of them) take the fast path: ids and gathered depth keys
 // stay in registers through the histogram and the scatter, the scattered list sits in LDS, and the
-// only global traffic is the id load, the depth gather and the final store.  Longer lists, and the
-// heavy buckets of any list, run the generic loop whose elements live in two global scratch buffers
-// (L2-resident for the workgroup) -- only the 1024 counters are in LDS, so any length is handled.
+// only global traffic is the id load, the depth gather and the final store.  The heavy buckets of any
+// list, and whole longer lists where the capacity says lists are short (no further launch: tile_depth_sort),
+// run the generic loop whose elements live in two global scratch buffers (L2-resident for the workgroup)
+// -- only the counters are in LDS, so any length is handled.  Everywhere else a longer list becomes units:
 //
 // LISTS OVER THE LDS LIST ARE SPLIT INTO UNITS (round 6).  Where the capacity says lists can be long, a tile whose list
 // does not fit the main kernel's LDS list is not one workgroup's job (round 5: a second launch of 1,024-thread
@@ -59,8 +63,8 @@ constexpr int kSamplePerUnit = 24;                    // ... of which this many 
 constexpr int kCollectThreads = 256, kCollectPer = 8, kCollectGrid = 2048;   // unit_collect_kernel
 // header of the deferred lists (two 16-byte stores zero it): [0] descriptors claimed, [1] units claimed from the bottom of the
 // unit tables (lists of kBigList entries and more: their units read the whole list, the units' kernel starts with them),
-// [2] collect chunks claimed, [3] unused, [4] units
-// claimed from the top of the tables (all other lists)
+// [2] collect chunks claimed, [3] unused, [4] units claimed from the top of the tables (all other lists), [5..7] unused.
+// The two allocations grow towards each other; max_units_for() leaves room for every list's ceil(n / kUnit) units.
 constexpr int kListHeader = 8;
 constexpr int kBigList = 6144;
 // descriptor of a deferred list
@@ -94,7 +98,7 @@ constexpr int kFastShort = 1024;            // ... and where the capacity says l
 constexpr int kFastMid = 1536;              // ... and in between (up to 1,000 entries per tile on average: configs[4] has 806,
                                             // its longest list 1,479): 21 KiB, 7 workgroups per CU -- the stage 428 -> 414 us at
                                             // 4K, 1,024 -> 1,049 frames/s with three in flight (1,280 entries: 443 us, the
-                                            // long-list launch gets work); lists over it go to the second launch as ever
+                                            // units' launches get work); lists over it are split into units as ever
 constexpr uint32_t kBrute = 0x80000000u;
 
 __device__ __forceinline__ bool comp_less(uint32_t ka, uint32_t ia, uint32_t kb, uint32_t ib) {
@@ -664,8 +668,9 @@ __device__ __forceinline__ void sort_one_tile(
     if (htot == 0) return;                          // uniform
     __syncthreads();
   } else if (UNIT) {
-    // a unit over the LDS list (the sample missed a cluster, or a list of more than kMaxUnits units): the filter left it in
-    // buffer 0
+    // a unit over the LDS list (the sample missed a cluster, or a list of more than kMaxUnits * kUnit entries, whose units
+    // are larger; over kMaxUnits * kFastUnit entries some unit must be): the filter left it in buffer 0 of the units'
+    // own scratch and it walks the generic loop below, popped buckets that fit the LDS list going back through lds_level
     if (tid == 0) {
       stack_n = 1;
       stack_lo[0] = s; stack_hi[0] = e; stack_src[0] = 0;

@@ -157,9 +157,8 @@ def test_tile_depth_order_long_lists_and_depth_ties(ops, n, span, kind):
 def test_tile_depth_order_uneven_lists_under_each_capacity_rule(ops, per_list, tiles_w, kind):
     """Two full tiles among empty ones: the AVERAGE the capacity allows picks the per-tile sort's variant (1,024-entry LDS
     list and no second launch up to 640 per tile, 1,536 entries up to 1,000, 2,048 beyond), the two lists are far longer
-    than any of them -- the main kernel's own generic path under the short rule, the long-list kernel under the others
-    (its LDS fast path up to 8,192 entries; beyond it the levels through global scratch with heavy buckets finished out of
-    LDS).  Lists bit-identical to the stable sort whatever the variant."""
+    than any of them -- the main kernel's own generic path under the short rule, units of ~2,048 entries under the others
+    (the collect and the units' kernels).  Lists bit-identical to the stable sort whatever the variant."""
     rng = np.random.default_rng(per_list + tiles_w)
     n = 2 * per_list
     tw, th = tiles_w, 2
@@ -261,8 +260,10 @@ def test_isect_tiles_empty_and_overflow(ops):
 @pytest.mark.parametrize("cap_frac,opts", [(0.45, 0), (0.8, 0), (0.45, 4)])
 def test_deferred_lists_with_an_overflowed_capacity_stay_inside_their_buffers(ops, cap_frac, opts):
     """Lists over the LDS list (split into units: csrc/tile_sort.hip) while the capacity is too small for the pairs: the
-    overflow is flagged, every offset lies inside the capacity, nothing is written past the buffers (canaries behind
-    flatten_ids and tile_ids), and the lists that fit whole are the stable sort's."""
+    overflow is flagged, every offset lies inside the capacity, nothing is written past the buffers (0xA5 guard bands
+    behind every buffer the calls allocate -- flatten_ids, tile_ids, the workspace with its scratch arrays and unit tables
+    among them: tests/guard_bands.py), and the lists that fit whole are the stable sort's."""
+    from guard_bands import forget_workspaces, guarded_empty, guards_intact, workspace_slack_intact
     from robosimgs_amd import _lib
     rng = np.random.default_rng(7)
     n, tw, th = 24_000, 3, 2
@@ -276,9 +277,15 @@ def test_deferred_lists_with_an_overflowed_capacity_stay_inside_their_buffers(op
     lib = _dbg.__enter__()
     try:
         lib.mgs_debug_set_sort_opts(opts)
+        forget_workspaces()                                 # (the first call allocates its workspace behind a guard too)
+        guarded = guarded_empty()
+        guards = guarded.__enter__()
         for _ in range(2):
             tl = ops.isect_tiles_raw(_t(means2d), torch.from_numpy(radii).to(DEV), _t(depths), tw, th, cap)
             torch.cuda.synchronize()
+            # seven outputs per call and the workspace of the first: nothing behind any of them, nor in the workspace's
+            # unused quarter
+            assert len(guards) >= (8 if _ == 0 else 15) and guards_intact(guards) and workspace_slack_intact()
             assert int(tl.n_isect.item()) == total and int(tl.status.item()) & _lib.MGS_STATUS_ISECT_OVERFLOW
             off = tl.tile_offsets.cpu().numpy()
             assert off.min() >= 0 and off.max() <= cap and np.all(np.diff(off) >= 0)
@@ -289,6 +296,9 @@ def test_deferred_lists_with_an_overflowed_capacity_stay_inside_their_buffers(op
                 if ref_off[t_ + 1] <= cap and off[t_] == ref_off[t_] and off[t_ + 1] == ref_off[t_ + 1]:
                     np.testing.assert_array_equal(got[off[t_]:off[t_ + 1]], r_flat[ref_off[t_]:ref_off[t_ + 1]])
     finally:
+        if "guarded" in locals():
+            guarded.__exit__(None, None, None)
+        forget_workspaces()
         lib.mgs_debug_set_sort_opts(0)
         _dbg.__exit__(None, None, None)
 

@@ -4,20 +4,18 @@ cases and the sandwich of tests/test_tile_rect_host.py, which holds a g++ build 
 rule's contract on those cases: lists from tightened rectangles render and differentiate to the same bits as the classic
 ones.  numpy fp64 only; nothing is compiled here.
 """
-import contextlib
-
 import numpy as np
 import pytest
 import torch
 
 import project_color_ref as PR
+from guard_bands import guarded_empty, guards_intact as _guards_intact
 import tile_rect_ref as R
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
 W, H, TW, TH = 640, 480, 40, 30
-GUARD = 256                                   # bytes of 0xA5 behind every buffer a guarded call allocates
 
 
 def _t(a, dtype=torch.float32):
@@ -36,33 +34,6 @@ def _bits(t):
 def ops():
     from robosimgs_amd import ops as _ops
     return _ops
-
-
-@contextlib.contextmanager
-def guarded_empty():
-    """Every torch.empty inside the block hands out the front of a larger buffer whose last GUARD bytes are 0xA5; yields
-    the list of those guards (uint8 views), to be looked at after the call."""
-    real, guards = torch.empty, []
-
-    def empty(*size, dtype=None, device=None, **kw):
-        shape = tuple(size[0]) if len(size) == 1 and isinstance(size[0], (tuple, list, torch.Size)) else tuple(size)
-        dtype = dtype or torch.float32
-        item = torch.tensor([], dtype=dtype).element_size()
-        nbytes = int(np.prod(shape, dtype=np.int64)) * item
-        pad = -nbytes % 16
-        buf = torch.full((nbytes + pad + GUARD,), 0xA5, dtype=torch.uint8, device=device)
-        guards.append(buf[nbytes:])
-        return buf[:nbytes].view(dtype).view(shape)
-
-    torch.empty = empty
-    try:
-        yield guards
-    finally:
-        torch.empty = real
-
-
-def _guards_intact(guards):
-    return all(bool((g == 0xA5).all()) for g in guards)
 
 
 def _radii(z, planar):
