@@ -17,6 +17,20 @@
 #define MGS_HD inline
 #endif
 
+// First statement of project_gaussian and of every helper it calls: multiply-adds are fused where ONE source expression
+// holds both (the language's own rule, decided before inlining) and nowhere else.  hipcc's default for HIP is
+// -ffp-contract=fast-honor-pragmas: without a pragma the back end fuses across statements as it sees fit in each kernel the
+// function is inlined into, and mgs_projection_fwd and mgs_project_color_fwd then rounded conics and compensation differently
+// in the last bits (18 and 10 of 257 rows); with this pragma they are the same instructions in both
+// (tests/test_gpu_project_color_fwd.py::test_projection_fwd_is_the_fused_kernel_bit_for_bit).  The fused multiply-adds
+// themselves stay.  Do NOT add a literal -ffp-contract=fast to the build flags: that form overrides the pragma, the back end
+// fuses globally again and the agreement is lost.
+#if defined(__clang__)
+#define MGS_FP_CONTRACT_IN_EXPRESSION _Pragma("clang fp contract(on)")
+#else
+#define MGS_FP_CONTRACT_IN_EXPRESSION
+#endif
+
 namespace mgs {
 
 struct CameraParams {  // one camera, row-major viewmat (OpenCV world-to-camera)
@@ -65,6 +79,7 @@ MGS_HD float activate_opacity_grad(float o) { return o * (1.0f - o); }
 
 // a b - c d with one rounding's worth of error (Kahan): the product c d is rounded, its error recovered by an FMA
 MGS_HD float diff_of_products(float a, float b, float c, float d) {
+  MGS_FP_CONTRACT_IN_EXPRESSION
   const float w = c * d;
   const float e = fmaf(-c, d, w);     // w - c d exactly
   const float f = fmaf(a, b, -w);
@@ -73,6 +88,7 @@ MGS_HD float diff_of_products(float a, float b, float c, float d) {
 
 // C = A * B, all 3x3 row-major
 MGS_HD void mat3_mul(const float* A, const float* B, float* C) {
+  MGS_FP_CONTRACT_IN_EXPRESSION
   for (int i = 0; i < 3; ++i)
     for (int j = 0; j < 3; ++j)
       C[i * 3 + j] = A[i * 3 + 0] * B[0 * 3 + j] + A[i * 3 + 1] * B[1 * 3 + j] +
@@ -80,6 +96,7 @@ MGS_HD void mat3_mul(const float* A, const float* B, float* C) {
 }
 // C = A * B^T
 MGS_HD void mat3_mul_bt(const float* A, const float* B, float* C) {
+  MGS_FP_CONTRACT_IN_EXPRESSION
   for (int i = 0; i < 3; ++i)
     for (int j = 0; j < 3; ++j)
       C[i * 3 + j] = A[i * 3 + 0] * B[j * 3 + 0] + A[i * 3 + 1] * B[j * 3 + 1] +
@@ -95,13 +112,13 @@ MGS_HD void mat3_mul_at(const float* A, const float* B, float* C) {
 
 // A.2 step 1: normalised wxyz quaternion -> rotation
 MGS_HD void quat_to_rotmat(const float q[4], float R[9]) {
+  MGS_FP_CONTRACT_IN_EXPRESSION
   float inv = 1.0f / sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
   float w = q[0] * inv, x = q[1] * inv, y = q[2] * inv, z = q[3] * inv;
-  float x2 = x * x, y2 = y * y, z2 = z * z;
-  float xy = x * y, xz = x * z, yz = y * z, wx = w * x, wy = w * y, wz = w * z;
-  R[0] = 1.f - 2.f * (y2 + z2); R[1] = 2.f * (xy - wz);       R[2] = 2.f * (xz + wy);
-  R[3] = 2.f * (xy + wz);       R[4] = 1.f - 2.f * (x2 + z2); R[5] = 2.f * (yz - wx);
-  R[6] = 2.f * (xz - wy);       R[7] = 2.f * (yz + wx);       R[8] = 1.f - 2.f * (x2 + y2);
+  // (each entry one expression: its multiply-adds are fused under MGS_FP_CONTRACT_IN_EXPRESSION)
+  R[0] = 1.f - 2.f * (y * y + z * z); R[1] = 2.f * (x * y - w * z);       R[2] = 2.f * (x * z + w * y);
+  R[3] = 2.f * (x * y + w * z);       R[4] = 1.f - 2.f * (x * x + z * z); R[5] = 2.f * (y * z - w * x);
+  R[6] = 2.f * (x * z - w * y);       R[7] = 2.f * (y * z + w * x);       R[8] = 1.f - 2.f * (x * x + y * y);
 }
 
 struct Projected {
@@ -152,6 +169,7 @@ struct Projected {
 // Series with t = q / z^2:  s z = sum (-t)^n / (2n+1);  a z^3 = sum (-1)^(n+1) 2(n+1)/(2n+3) t^n;  b z^5 = d(a z^3)/dt.
 template <bool WITH_B>
 MGS_HD void fisheye_terms(float x, float y, float z, float& s, float& a, float& b, float& ir2) {
+  MGS_FP_CONTRACT_IN_EXPRESSION
   const float q = x * x + y * y;
   ir2 = 1.0f / (q + z * z);
   if (z > 0.f && q < MGS_FISHEYE_SERIES_T * (z * z)) {
@@ -184,6 +202,7 @@ struct FisheyeKb {
 };
 template <bool WITH_P2>
 MGS_HD FisheyeKb fisheye_kb_terms(const float k[4], float q, float z, float s, float a, float ir2) {
+  MGS_FP_CONTRACT_IN_EXPRESSION
   FisheyeKb t;
   const float u = s * s * q;
   t.u = u;
@@ -203,6 +222,7 @@ MGS_HD Projected project_gaussian(const float mean[3], const float quat[4],
                                   float H, float eps2d, float near_plane, float far_plane,
                                   float radius_clip, int radius_rule = MGS_RADIUS_CLASSIC,
                                   bool has_opacity = false, float opacity = 1.f, bool antialiased = false) {
+  MGS_FP_CONTRACT_IN_EXPRESSION
   Projected out;
   out.mean2d[0] = out.mean2d[1] = out.depth = 0.f;
   out.conic[0] = out.conic[1] = out.conic[2] = 0.f;
@@ -404,6 +424,24 @@ MGS_HD void sh_basis(int deg, float x, float y, float z, float* Y) {
   Y[13] = u * x;
   Y[14] = w * fC1;
   Y[15] = -0.5900435899266435f * fC2;
+}
+
+// Colour of one Gaussian: evaluate sum_k Y_k(dir) * coeff_k for KC = (DEG+1)^2 coefficients held in registers.
+template <int DEG>
+MGS_HD void sh_dot(const float dir[3], const float* c /*[KC*3]*/, float rgb[3]) {
+  constexpr int KC = (DEG + 1) * (DEG + 1);
+  float n2 = dir[0] * dir[0] + dir[1] * dir[1] + dir[2] * dir[2];
+  float inv = n2 > 0.f ? 1.0f / sqrtf(n2) : 0.f;
+  float Y[KC];
+  sh_basis(DEG, dir[0] * inv, dir[1] * inv, dir[2] * inv, Y);
+  float r = 0.f, g = 0.f, b = 0.f;
+#pragma unroll
+  for (int k = 0; k < KC; ++k) {
+    r += Y[k] * c[3 * k + 0];
+    g += Y[k] * c[3 * k + 1];
+    b += Y[k] * c[3 * k + 2];
+  }
+  rgb[0] = r; rgb[1] = g; rgb[2] = b;
 }
 
 // dY/dx, dY/dy, dY/dz of the polynomial basis above (treating x,y,z as independent).

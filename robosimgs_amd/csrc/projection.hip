@@ -56,24 +56,6 @@ __global__ __launch_bounds__(kBlock) void projection_fwd_kernel(
   if (compensations) compensations[g] = p.compensation;
 }
 
-// Evaluate sum_k Y_k(dir) * coeff_k for KC = (DEG+1)^2 coefficients held in registers.
-template <int DEG>
-__device__ __forceinline__ void sh_dot(const float dir[3], const float* c /*[KC*3]*/, float rgb[3]) {
-  constexpr int KC = (DEG + 1) * (DEG + 1);
-  float n2 = dir[0] * dir[0] + dir[1] * dir[1] + dir[2] * dir[2];
-  float inv = n2 > 0.f ? 1.0f / sqrtf(n2) : 0.f;
-  float Y[KC];
-  sh_basis(DEG, dir[0] * inv, dir[1] * inv, dir[2] * inv, Y);
-  float r = 0.f, g = 0.f, b = 0.f;
-#pragma unroll
-  for (int k = 0; k < KC; ++k) {
-    r += Y[k] * c[3 * k + 0];
-    g += Y[k] * c[3 * k + 1];
-    b += Y[k] * c[3 * k + 2];
-  }
-  rgb[0] = r; rgb[1] = g; rgb[2] = b;
-}
-
 // Fetch this lane's SH row (first KC*3 floats of a row of `stride_f` floats).
 //   STAGED (stride_f == 48): wave-cooperative lane-linear fetch through LDS.
 //   otherwise: direct per-lane loads (rows of 3 / 12 / 27 floats are short).
