@@ -47,7 +47,9 @@ extern "C" {
  * Not a bump, no parameter list changed: the parameter form as a policy, MGS_PARAMS_RAW -- a new bit of bin_flags, of the
  * mgs_render_frames* flags and of mgs_project_color_bwd's camera_model word; a caller that never sets it sees 450's
  * behaviour.  Likewise the fourth camera model, MGS_CAMERA_FISHEYE_KB: a new camera_model value and new flag bits
- * (include/mgs_lens.h); no parameter list changed, the `K` / `Ks` rows grow to 16 floats under that model only. */
+ * (include/mgs_lens.h); no parameter list changed, the `K` / `Ks` rows grow to 16 floats under that model only.  And the
+ * fifth, the pinhole camera with OpenCV's radial / tangential lens: camera_model value 4 and its flag bits, all stated in
+ * include/mgs_lens_pinhole.h, again with 16-float rows and no parameter list changed. */
 #define MGS_VERSION 450
 
 #define MGS_OK 0
@@ -93,6 +95,8 @@ extern "C" {
  *                       solve nothing).  A Gaussian with theta^2 >= u_max is culled like one behind the near plane.
  *                       All k zero gives MGS_CAMERA_FISHEYE's numbers.  A fourth instantiation; its flag bits
  *                       (MGS_BIN_CAMERA_FISHEYE_KB, MGS_FRAMES_CAMERA_FISHEYE_KB) are in include/mgs_lens.h.
+ *   (camera_model 4, the pinhole camera with OpenCV's k1 k2 p1 p2 k3 lens -- a fifth instantiation -- is defined and stated,
+ *    value, flag bits, row layout and culls, in include/mgs_lens_pinhole.h; every camera_model argument below takes it.)
  * Depth is camera z under every model (near / far cull, sort key, "D" / "ED"); the SH view direction is mean - campos. */
 #define MGS_CAMERA_PINHOLE 0
 #define MGS_CAMERA_ORTHO 1

@@ -37,13 +37,45 @@ def lens_theta_max(k) -> float:
     return best
 
 
+def pinhole_lens_u_max(k) -> float:
+    """Where the radial map r Rad(r^2) of the pinhole lens (OpenCV k1 k2 p1 p2 k3; Rad(u) = 1 + k1 u + k2 u^2 + k3 u^3, u =
+    x'^2 + y'^2 in normalised coordinates) stops growing: the smallest positive real root of d(r Rad)/dr =
+    1 + 3 k1 u + 5 k2 u^2 + 7 k3 u^3, or inf when there is none.  fp64; the renderer culls u >= u_max."""
+    k = [float(v) for v in k]
+    k1, k2, k3 = k[0], k[1], (k[4] if len(k) > 4 else 0.0)
+    coeffs = np.trim_zeros(np.array([7.0 * k3, 5.0 * k2, 3.0 * k1, 1.0]), "f")
+    best = math.inf
+    if len(coeffs) > 1:
+        for r in np.roots(coeffs):
+            if abs(r.imag) <= 1e-12 * max(1.0, abs(r.real)) and r.real > 0.0:
+                best = min(best, float(r.real))
+    return best
+
+
+def pinhole_lens_distort(a, b, k):
+    """OpenCV's radial / tangential lens at normalised points a = x/z, b = y/z (fp64 ndarrays), k = (k1, k2, p1, p2, k3):
+    (xd, yd, det Jd), Jd the 2 x 2 Jacobian of (xd, yd) in (a, b) (include/mgs_lens_pinhole.h)."""
+    k1, k2, p1, p2, k3 = (float(v) for v in k)
+    u = a * a + b * b
+    rad = 1.0 + u * (k1 + u * (k2 + u * k3))
+    rad1 = k1 + u * (2.0 * k2 + u * 3.0 * k3)
+    xd = a * rad + 2.0 * p1 * a * b + p2 * (u + 2.0 * a * a)
+    yd = b * rad + p1 * (u + 2.0 * b * b) + 2.0 * p2 * a * b
+    d00 = rad + 2.0 * a * a * rad1 + 2.0 * p1 * b + 6.0 * p2 * a
+    d01 = 2.0 * a * b * rad1 + 2.0 * p1 * a + 2.0 * p2 * b
+    d11 = rad + 2.0 * b * b * rad1 + 6.0 * p1 * b + 2.0 * p2 * a
+    return xd, yd, d00 * d11 - d01 * d01
+
+
 @dataclass
 class Camera:
     """One camera.  `c2w` is OpenGL camera-to-world (4x4, float64).  `model`: "pinhole", "ortho" (pixel =
     (fx x + cx, fy y + cy) in camera space: fx is pixels per world unit) or "fisheye" (ideal equidistant lens,
     pixel radius = f theta, theta the angle off the optical axis).  `distortion` (meaningful for "fisheye"): OpenCV fisheye
     coefficients (k1, k2, k3, k4), pixel radius = f theta (1 + k1 theta^2 + k2 theta^4 + k3 theta^6 + k4 theta^8) -- what
-    cv2.fisheye.calibrate and nerfstudio's OPENCV_FISHEYE store; None: the ideal lens."""
+    cv2.fisheye.calibrate and nerfstudio's OPENCV_FISHEYE store; None: the ideal lens.  `pinhole_distortion` (needs
+    "pinhole"): OpenCV's distCoeffs (k1, k2, p1, p2, k3) of cv2.calibrateCamera / nerfstudio's OPENCV -- four values mean
+    k3 = 0; None: no lens."""
 
     c2w: np.ndarray
     fx: float
@@ -56,11 +88,20 @@ class Camera:
     far: float = 1e10
     # keyword-only (Camera(..., distortion=(k1, k2, k3, k4))), so that `model` stays the last positional field
     distortion: Optional[Tuple[float, float, float, float]] = field(default=None, kw_only=True)
+    pinhole_distortion: Optional[Tuple[float, float, float, float, float]] = field(default=None, kw_only=True)
     model: str = "pinhole"
 
     def __post_init__(self):
         if self.model not in CAMERA_MODELS:
             raise ValueError(f"camera model {self.model!r} not in {CAMERA_MODELS}")
+        if self.pinhole_distortion is not None:
+            if self.model != "pinhole":
+                raise ValueError(f"pinhole_distortion (k1, k2, p1, p2, k3) needs model='pinhole', got {self.model!r}")
+            self.pinhole_distortion = tuple(float(v) for v in self.pinhole_distortion)
+            if len(self.pinhole_distortion) == 4:
+                self.pinhole_distortion += (0.0,)
+            if len(self.pinhole_distortion) != 5 or not all(math.isfinite(v) for v in self.pinhole_distortion):
+                raise ValueError("pinhole_distortion must be finite (k1, k2, p1, p2, k3), or (k1, k2, p1, p2) for k3 = 0")
         if self.distortion is not None:
             if self.model != "fisheye":
                 raise ValueError(f"distortion (fisheye k1..k4) needs model='fisheye', got {self.model!r}")
@@ -130,6 +171,16 @@ class Camera:
         if self.model == "pinhole":
             uvw = pc @ self.K.T
             uv = uvw[:, :2] / uvw[:, 2:]
+            if self.pinhole_distortion is not None and any(self.pinhole_distortion):
+                # the lens, and NaN where the renderer culls: past the radial fold, where the map folds, outside the box
+                with np.errstate(all="ignore"):
+                    xd, yd, det = pinhole_lens_distort(pc[:, 0] / pc[:, 2], pc[:, 1] / pc[:, 2], self.pinhole_distortion)
+                    u = (pc[:, 0] / pc[:, 2]) ** 2 + (pc[:, 1] / pc[:, 2]) ** 2
+                tanx, tany = 0.5 * self.width / self.fx, 0.5 * self.height / self.fy
+                keep = ((pc[:, 2] > 0.0) & (u < pinhole_lens_u_max(self.pinhole_distortion)) & (det > 0.0)
+                        & (xd <= (self.width - self.cx) / self.fx + 0.3 * tanx) & (xd >= -(self.cx / self.fx + 0.3 * tanx))
+                        & (yd <= (self.height - self.cy) / self.fy + 0.3 * tany) & (yd >= -(self.cy / self.fy + 0.3 * tany)))
+                uv = np.where(keep[:, None], np.stack([self.fx * xd + self.cx, self.fy * yd + self.cy], axis=-1), np.nan)
         else:
             xy = pc[:, :2]
             if self.model == "fisheye":       # r = f theta: scale the camera-plane offset by theta / rho
@@ -153,18 +204,22 @@ class Camera:
         return Camera(self.c2w.copy(), self.fx * factor, self.fy * factor,
                       self.cx * factor, self.cy * factor,
                       int(round(self.width * factor)), int(round(self.height * factor)),
-                      self.near, self.far, self.model, distortion=self.distortion)
+                      self.near, self.far, self.model, distortion=self.distortion,
+                      pinhole_distortion=self.pinhole_distortion)
 
 
 def cameras_from_transforms_json(path: str, width: int | None = None,
-                                 height: int | None = None, lens_distortion: bool = False) -> List[Camera]:
+                                 height: int | None = None, lens_distortion: bool = False,
+                                 pinhole_distortion: bool = False) -> List[Camera]:
     """nerfstudio `transforms.json` -> cameras.  Accepts global or per-frame intrinsics,
     the two layouts `parse_transforms_json` reads (nerf2physic_utils.py:30-45).
 
     nerfstudio's `camera_model` key (top level or per frame): "OPENCV_FISHEYE" is read as the ideal equidistant
     fisheye when its distortion coefficients k1..k4 are absent or zero; non-zero coefficients raise ValueError unless
     lens_distortion=True, which loads them into Camera.distortion (the renderer then applies the lens).  Every other value
-    -- "OPENCV" with its radial / tangential terms included -- loads as a pinhole camera, as before."""
+    loads as a pinhole camera; the radial / tangential terms k1, k2, k3, p1, p2 of an "OPENCV" frame (per-frame keys over
+    top-level ones) are dropped unless pinhole_distortion=True, which loads them into Camera.pinhole_distortion (the
+    renderer then applies the lens).  A non-zero k4 under "OPENCV" then raises: the rational model is not built."""
     with open(path, "rb") as f:
         t = json.load(f)
     cams = []
@@ -173,8 +228,9 @@ def cameras_from_transforms_json(path: str, width: int | None = None,
         w = int(src.get("w", t.get("w", width or round(2 * src["cx"]))))
         h = int(src.get("h", t.get("h", height or round(2 * src["cy"]))))
         model, dist = _transforms_camera_model(fr, t, lens_distortion)
+        pdist = _transforms_pinhole_lens(fr, t) if pinhole_distortion and model == "pinhole" else None
         cams.append(Camera(fr["transform_matrix"], src["fl_x"], src["fl_y"], src["cx"],
-                           src["cy"], w, h, model=model, distortion=dist))
+                           src["cy"], w, h, model=model, distortion=dist, pinhole_distortion=pdist))
     return cams
 
 
@@ -190,6 +246,17 @@ def _transforms_camera_model(frame: Dict, top: Dict, lens_distortion: bool = Fal
                          "not supported by default; pass lens_distortion=True to load it into Camera.distortion (without "
                          "it only the ideal equidistant fisheye, all k zero, is read)")
     return "fisheye", (tuple(ks.values()) if nonzero else None)
+
+
+def _transforms_pinhole_lens(frame: Dict, top: Dict):
+    """Camera.pinhole_distortion of one transforms.json frame whose camera_model is "OPENCV" (nerfstudio's default when
+    the key is absent): (k1, k2, p1, p2, k3), or None when all are zero or the frame names another pinhole-like model."""
+    if frame.get("camera_model", top.get("camera_model", "OPENCV")) != "OPENCV":
+        return None
+    ks = {k: float(frame.get(k, top.get(k, 0.0))) for k in ("k1", "k2", "p1", "p2", "k3", "k4")}
+    if ks.pop("k4") != 0.0:
+        raise ValueError("OPENCV with a non-zero k4: the rational model's k4..k6 are not supported (only k1, k2, k3, p1, p2)")
+    return tuple(ks.values()) if any(ks.values()) else None
 
 
 def cameras_from_camera_params_json(path: str) -> Dict[str, Camera]:

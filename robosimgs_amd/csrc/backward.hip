@@ -308,6 +308,7 @@ extern "C" int mgs_projection_bwd(int n, const float* means, const float* quats,
   MGS_REQUIRE(n >= 0 && width > 0 && height > 0, "projection_bwd: bad sizes");
   MGS_REQUIRE(is_camera_model(camera_model),
               "projection_bwd: camera_model %d is not MGS_CAMERA_PINHOLE, _ORTHO, _FISHEYE or _FISHEYE_KB", camera_model);
+  MGS_REQUIRE(camera_model != MGS_CAMERA_PINHOLE_BC || K, "projection_bwd: %s", kPinholeLensNeedsRow);
   if (n == 0) return MGS_OK;
   MGS_REQUIRE(means && quats && scales && viewmat && K && radii && conics && v_means2d &&
                   v_conics && v_means && v_quats && v_scales, "projection_bwd: null pointer");
@@ -358,6 +359,7 @@ extern "C" int mgs_project_color_bwd(int n, const float* means, const float* qua
   MGS_REQUIRE(is_camera_model(camera_model),
               "project_color_bwd: camera_model %d is not MGS_CAMERA_PINHOLE, _ORTHO, _FISHEYE or _FISHEYE_KB (optionally | "
               "MGS_PARAMS_RAW)", camera_model);
+  MGS_REQUIRE(camera_model != MGS_CAMERA_PINHOLE_BC || K, "project_color_bwd: %s", kPinholeLensNeedsRow);
   MGS_REQUIRE(!raw || (opacities && v_opac_out && v_opacities),
               "project_color_bwd: camera_model carries MGS_PARAMS_RAW, which needs opacities (the logits), v_opac_out and v_opacities");
   MGS_REQUIRE(sh_degree >= 0 && sh_degree <= 3, "project_color_bwd: sh_degree %d not in 0..3", sh_degree);

@@ -17,7 +17,7 @@ struct Frames {
   int bin_flags;       // mgs_project_color_fwd's: tile bounds, radius rule, camera
   int camera_model;    // MGS_CAMERA_* (mgs_project_color_bwd)
   bool raw;            // MGS_PARAMS_RAW: `scales` holds log-scales, `opacities` logits
-  size_t k_row;        // floats per camera in `Ks`: 9, or 16 under MGS_CAMERA_FISHEYE_KB
+  size_t k_row;        // floats per camera in `Ks`: 9, or 16 under MGS_CAMERA_FISHEYE_KB / _PINHOLE_BC
 };
 int frames_prologue(const char* fn, int n, int n_cams, int width, int height, int channels, int flags, const float* opacities,
                     uint32_t isect_capacity, const size_t* workspace_bytes, Frames* f,
@@ -28,7 +28,8 @@ int frames_prologue(const char* fn, int n, int n_cams, int width, int height, in
   MGS_REQUIRE(isect_capacity > 0, "%s: zero capacity", fn);
   MGS_REQUIRE((flags & (MGS_FRAMES_CAMERA_ORTHO | MGS_FRAMES_CAMERA_FISHEYE)) != (MGS_FRAMES_CAMERA_ORTHO | MGS_FRAMES_CAMERA_FISHEYE),
               "%s: flags set both MGS_FRAMES_CAMERA_ORTHO and MGS_FRAMES_CAMERA_FISHEYE", fn);
-  MGS_REQUIRE(!mgs::several_camera_bits(flags, MGS_FRAMES_CAMERA_ORTHO | MGS_FRAMES_CAMERA_FISHEYE | MGS_FRAMES_CAMERA_FISHEYE_KB),
+  MGS_REQUIRE(!mgs::several_camera_bits(flags, MGS_FRAMES_CAMERA_ORTHO | MGS_FRAMES_CAMERA_FISHEYE | MGS_FRAMES_CAMERA_FISHEYE_KB |
+                                                     MGS_FRAMES_CAMERA_PINHOLE_BC),
               "%s: flags set more than one MGS_FRAMES_CAMERA_* bit", fn);
   f->raw = (flags & MGS_PARAMS_RAW) != 0;
   MGS_REQUIRE(!f->raw || opacities, "%s: MGS_PARAMS_RAW needs opacities (the logits), got NULL", fn);
@@ -39,7 +40,8 @@ int frames_prologue(const char* fn, int n, int n_cams, int width, int height, in
                  ((flags & MGS_FRAMES_RADIUS_OPACITY_AWARE) ? MGS_BIN_RADIUS_OPACITY_AWARE : 0) |
                  ((flags & MGS_FRAMES_CAMERA_ORTHO) ? MGS_BIN_CAMERA_ORTHO : 0) |
                  ((flags & MGS_FRAMES_CAMERA_FISHEYE) ? MGS_BIN_CAMERA_FISHEYE : 0) |
-                 ((flags & MGS_FRAMES_CAMERA_FISHEYE_KB) ? MGS_BIN_CAMERA_FISHEYE_KB : 0) | (f->raw ? MGS_PARAMS_RAW : 0);
+                 ((flags & MGS_FRAMES_CAMERA_FISHEYE_KB) ? MGS_BIN_CAMERA_FISHEYE_KB : 0) |
+                 ((flags & MGS_FRAMES_CAMERA_PINHOLE_BC) ? MGS_BIN_CAMERA_PINHOLE_BC : 0) | (f->raw ? MGS_PARAMS_RAW : 0);
   f->camera_model = mgs::bin_camera_model(f->bin_flags);
   f->k_row = mgs::camera_row_floats(f->camera_model);
   return MGS_OK;
@@ -93,6 +95,10 @@ int render_frames_impl(int n, const float* means, const float* quats, const floa
   Frames f;
   int rc = frames_prologue("render_frames", n, n_cams, width, height, channels, flags, opacities, isect_capacity, workspace_bytes, &f);
   if (rc) return rc;
+  if ((ds_rgba || ds_distance) && f.camera_model == MGS_CAMERA_PINHOLE_BC)
+    return mgs::set_error(MGS_ERR_UNSUPPORTED, "render_frames: dataset output (ds_rgba / ds_distance) converts depth to ray "
+                                               "distance through an undistorted pinhole K^-1; it is not available under "
+                                               "the pinhole lens (MGS_FRAMES_CAMERA_PINHOLE_BC)");
   if ((ds_rgba || ds_distance) && f.camera_model != MGS_CAMERA_PINHOLE)
     return mgs::set_error(MGS_ERR_UNSUPPORTED, "render_frames: dataset output (ds_rgba / ds_distance) converts depth to ray "
                                                "distance through a pinhole K^-1; it is not available for an orthographic "

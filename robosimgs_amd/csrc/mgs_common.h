@@ -11,6 +11,7 @@
 
 #include "../../include/mgs.h"
 #include "../../include/mgs_lens.h"
+#include "../../include/mgs_lens_pinhole.h"
 
 namespace mgs {
 
@@ -62,11 +63,19 @@ template <int Lo, int Hi, class F> void with_int(int v, F&& f) {
   else if (v == Lo) f(int_c<Lo>{});
   else with_int<Lo + 1, Hi>(v, f);
 }
-// MGS_CAMERA_*: anything past MGS_CAMERA_FISHEYE is MGS_CAMERA_FISHEYE_KB
-template <class F> void with_camera(int model, F&& f) { with_int<MGS_CAMERA_PINHOLE, MGS_CAMERA_FISHEYE_KB>(model, f); }
-inline bool is_camera_model(int model) { return model >= MGS_CAMERA_PINHOLE && model <= MGS_CAMERA_FISHEYE_KB; }
-// floats per camera behind a `K` / `Ks` pointer (include/mgs.h at MGS_CAMERA_*)
-inline size_t camera_row_floats(int model) { return model == MGS_CAMERA_FISHEYE_KB ? MGS_LENS_ROW_FLOATS : 9; }
+// MGS_CAMERA_*: anything past MGS_CAMERA_FISHEYE_KB is MGS_CAMERA_PINHOLE_BC
+template <class F> void with_camera(int model, F&& f) { with_int<MGS_CAMERA_PINHOLE, MGS_CAMERA_PINHOLE_BC>(model, f); }
+inline bool is_camera_model(int model) { return model >= MGS_CAMERA_PINHOLE && model <= MGS_CAMERA_PINHOLE_BC; }
+// floats per camera behind a `K` / `Ks` pointer (include/mgs.h at MGS_CAMERA_*, include/mgs_lens_pinhole.h)
+inline size_t camera_row_floats(int model) {
+  return (model == MGS_CAMERA_FISHEYE_KB || model == MGS_CAMERA_PINHOLE_BC) ? MGS_LENS_ROW_FLOATS : 9;
+}
+// Where a call names the model in its camera_model argument (mgs_projection_fwd / _bwd, mgs_project_color_bwd),
+// MGS_CAMERA_PINHOLE_BC is taken only together with its camera row: K == NULL is refused before anything else, for n == 0
+// too (include/mgs_lens_pinhole.h).  The value 4 was "no camera model" before this model existed, and a caller that
+// probes for that with an empty call keeps getting MGS_ERR_INVALID_ARGUMENT.
+constexpr const char* kPinholeLensNeedsRow =
+    "camera_model MGS_CAMERA_PINHOLE_BC needs K, the camera's 16-float row (include/mgs_lens_pinhole.h), for n = 0 too";
 // SH degree 0..3: anything past 2 is 3
 template <class F> void with_sh_degree(int degree, F&& f) { with_int<0, 3>(degree, f); }
 // MGS_RADIUS_OPACITY_AWARE when per_axis, MGS_RADIUS_CLASSIC otherwise
@@ -89,7 +98,8 @@ template <class F> void with_channels(int channels, F&& f) {
 inline int bin_camera_model(int bin_flags) {
   return (bin_flags & MGS_BIN_CAMERA_ORTHO) ? MGS_CAMERA_ORTHO
          : (bin_flags & MGS_BIN_CAMERA_FISHEYE) ? MGS_CAMERA_FISHEYE
-         : (bin_flags & MGS_BIN_CAMERA_FISHEYE_KB) ? MGS_CAMERA_FISHEYE_KB : MGS_CAMERA_PINHOLE;
+         : (bin_flags & MGS_BIN_CAMERA_FISHEYE_KB) ? MGS_CAMERA_FISHEYE_KB
+         : (bin_flags & MGS_BIN_CAMERA_PINHOLE_BC) ? MGS_CAMERA_PINHOLE_BC : MGS_CAMERA_PINHOLE;
 }
 // more than one of the camera bits `bits` set in `flags`
 inline bool several_camera_bits(int flags, int bits) { const int c = flags & bits; return (c & (c - 1)) != 0; }

@@ -37,10 +37,13 @@ struct CameraParams {  // one camera, row-major viewmat (OpenCV world-to-camera)
   float R[9];
   float t[3];
   float fx, fy, cx, cy;
-  float k[4], u_max;   // MGS_CAMERA_FISHEYE_KB only: k1..k4 and theta_max^2 (floats 9..13 of the camera's 16-float row)
+  // the lens models only (the floats behind K in the camera's 16-float row), zero otherwise:
+  //   MGS_CAMERA_FISHEYE_KB  k1..k4 in k[0..3] and theta_max^2 (floats 9..13)
+  //   MGS_CAMERA_PINHOLE_BC  k1 k2 p1 p2 k3 in k[0..4] and the radial fold u_max (floats 9..14)
+  float k[5], u_max;
 };
 
-// CAM: the camera model of the caller's instantiation -- only MGS_CAMERA_FISHEYE_KB reads past K[8]
+// CAM: the camera model of the caller's instantiation -- only the two lens models read past K[8]
 template <int CAM = 0>
 MGS_HD CameraParams load_camera(const float* viewmat, const float* K) {
   CameraParams c;
@@ -50,8 +53,11 @@ MGS_HD CameraParams load_camera(const float* viewmat, const float* K) {
   c.fx = K[0]; c.cx = K[2]; c.fy = K[4]; c.cy = K[5];
   if constexpr (CAM == 3) {   // MGS_CAMERA_FISHEYE_KB
     c.k[0] = K[9]; c.k[1] = K[10]; c.k[2] = K[11]; c.k[3] = K[12]; c.u_max = K[13];
+    c.k[4] = 0.f;
+  } else if constexpr (CAM == 4) {   // MGS_CAMERA_PINHOLE_BC
+    c.k[0] = K[9]; c.k[1] = K[10]; c.k[2] = K[11]; c.k[3] = K[12]; c.k[4] = K[13]; c.u_max = K[14];
   } else {
-    c.k[0] = c.k[1] = c.k[2] = c.k[3] = 0.f; c.u_max = 0.f;
+    c.k[0] = c.k[1] = c.k[2] = c.k[3] = c.k[4] = 0.f; c.u_max = 0.f;
   }
   return c;
 }
@@ -147,6 +153,8 @@ struct Projected {
 //                       mean (fx s x + cx, fy s y + cy); J is the (dense) Jacobian of that map; no clamp
 //   MGS_CAMERA_FISHEYE_KB  that lens with OpenCV's fisheye polynomial: theta_d = theta P(theta^2) (fisheye_kb_terms below);
 //                       culled where theta^2 >= cam.u_max, the end of the polynomial's monotonic range
+//   MGS_CAMERA_PINHOLE_BC  the pinhole camera with OpenCV's radial / tangential lens (pinhole_bc_terms below): dense J, no
+//                       clamp; culled past the radial fold, where det Jd <= 0, and outside the pinhole's clamp box
 // Depth is camera z and near / far cull on it under every model.
 #ifndef MGS_CAMERA_PINHOLE
 #define MGS_CAMERA_PINHOLE 0
@@ -155,6 +163,9 @@ struct Projected {
 #endif
 #ifndef MGS_CAMERA_FISHEYE_KB
 #define MGS_CAMERA_FISHEYE_KB 3
+#endif
+#ifndef MGS_CAMERA_PINHOLE_BC
+#define MGS_CAMERA_PINHOLE_BC 4
 #endif
 
 // Below t = rho^2 / z^2 = 0.1 the fisheye terms come from their series in t (nine terms: truncation < 1e-8 relative):
@@ -215,6 +226,34 @@ MGS_HD FisheyeKb fisheye_kb_terms(const float k[4], float q, float z, float s, f
   return t;
 }
 
+// OpenCV's radial / tangential (Brown-Conrady) lens at the normalised point (a, b) = (x/z, y/z), include/mgs_lens_pinhole.h;
+// k = (k1, k2, p1, p2, k3), u = a^2 + b^2:
+//   Rad = 1 + k1 u + k2 u^2 + k3 u^3,  R1 = Rad',  R2 = Rad''  (backward only)
+//   xd = a Rad + 2 p1 a b + p2 (u + 2 a^2),  yd = b Rad + p1 (u + 2 b^2) + 2 p2 a b
+//   Jd = d(xd, yd)/d(a, b) = [[d00, d01], [d01, d11]]
+struct PinholeBc {
+  float u, R1, R2;
+  float xd, yd;
+  float d00, d01, d11;
+};
+template <bool WITH_R2>
+MGS_HD PinholeBc pinhole_bc_terms(const float k[5], float a, float b) {
+  MGS_FP_CONTRACT_IN_EXPRESSION
+  PinholeBc t;
+  const float aa = a * a, bb = b * b, ab = a * b, u = aa + bb;
+  const float p1 = k[2], p2 = k[3];
+  const float Rad = 1.f + u * (k[0] + u * (k[1] + u * k[4]));
+  t.u = u;
+  t.R1 = k[0] + u * (2.f * k[1] + u * (3.f * k[4]));
+  t.R2 = WITH_R2 ? 2.f * k[1] + u * (6.f * k[4]) : 0.f;
+  t.xd = a * Rad + 2.f * p1 * ab + p2 * (u + 2.f * aa);
+  t.yd = b * Rad + p1 * (u + 2.f * bb) + 2.f * p2 * ab;
+  t.d00 = Rad + 2.f * aa * t.R1 + 2.f * p1 * b + 6.f * p2 * a;
+  t.d01 = 2.f * ab * t.R1 + 2.f * p1 * a + 2.f * p2 * b;
+  t.d11 = Rad + 2.f * bb * t.R1 + 6.f * p1 * b + 2.f * p2 * a;
+  return t;
+}
+
 // A.2 steps 1-5.  Returns radius == 0 for culled Gaussians (all other fields zeroed).
 template <int CAM = MGS_CAMERA_PINHOLE>
 MGS_HD Projected project_gaussian(const float mean[3], const float quat[4],
@@ -238,6 +277,7 @@ MGS_HD Projected project_gaussian(const float mean[3], const float quat[4],
 
   // J = [[j00, j01, j02], [j10, j11, j12]]; j01 = j10 = 0 except under the fisheye model
   float j00, j01 = 0.f, j02, j10 = 0.f, j11, j12, rz, fs = 0.f;
+  [[maybe_unused]] float bcx = 0.f, bcy = 0.f;     // MGS_CAMERA_PINHOLE_BC: the distorted normalised point
   if constexpr (CAM == MGS_CAMERA_PINHOLE) {
     rz = 1.0f / z;
     float rz2 = rz * rz;
@@ -259,6 +299,20 @@ MGS_HD Projected project_gaussian(const float mean[3], const float quat[4],
     const float xya = x * y * fa;
     j00 = cam.fx * (fs + x * x * fa); j01 = cam.fx * xya; j02 = -cam.fx * x * ir2;
     j10 = cam.fy * xya; j11 = cam.fy * (fs + y * y * fa); j12 = -cam.fy * y * ir2;
+  } else if constexpr (CAM == MGS_CAMERA_PINHOLE_BC) {
+    rz = 1.0f / z;
+    const float pa = x * rz, pb = y * rz;
+    const PinholeBc bc = pinhole_bc_terms<false>(cam.k, pa, pb);
+    if (!(bc.u < cam.u_max)) return out;                                  // past the radial fold
+    if (!(diff_of_products(bc.d00, bc.d11, bc.d01, bc.d01) > 0.f)) return out;   // the lens map folds (det Jd <= 0)
+    // the pinhole's clamp box, here a cull on the distorted point: the frame plus 0.3 of the half field
+    float tanx = 0.5f * W / cam.fx, tany = 0.5f * H / cam.fy;
+    float lim_xp = (W - cam.cx) / cam.fx + 0.3f * tanx, lim_xn = cam.cx / cam.fx + 0.3f * tanx;
+    float lim_yp = (H - cam.cy) / cam.fy + 0.3f * tany, lim_yn = cam.cy / cam.fy + 0.3f * tany;
+    if (!(bc.xd <= lim_xp && bc.xd >= -lim_xn && bc.yd <= lim_yp && bc.yd >= -lim_yn)) return out;
+    bcx = bc.xd; bcy = bc.yd;
+    j00 = cam.fx * bc.d00 * rz; j01 = cam.fx * bc.d01 * rz; j02 = -cam.fx * rz * (bc.d00 * pa + bc.d01 * pb);
+    j10 = cam.fy * bc.d01 * rz; j11 = cam.fy * bc.d11 * rz; j12 = -cam.fy * rz * (bc.d01 * pa + bc.d11 * pb);
   } else {
     static_assert(CAM == MGS_CAMERA_FISHEYE_KB, "camera model");
     float es, ea, eb, ir2;
@@ -284,7 +338,7 @@ MGS_HD Projected project_gaussian(const float mean[3], const float quat[4],
   mat3_mul(R, Rq, RR);
   float m0[3], m1[3];
   for (int k = 0; k < 3; ++k) {
-    if constexpr (CAM == MGS_CAMERA_FISHEYE || CAM == MGS_CAMERA_FISHEYE_KB) {
+    if constexpr (CAM == MGS_CAMERA_FISHEYE || CAM == MGS_CAMERA_FISHEYE_KB || CAM == MGS_CAMERA_PINHOLE_BC) {
       m0[k] = (j00 * RR[k] + j01 * RR[3 + k] + j02 * RR[6 + k]) * scale[k];
       m1[k] = (j10 * RR[k] + j11 * RR[3 + k] + j12 * RR[6 + k]) * scale[k];
     } else {
@@ -310,7 +364,7 @@ MGS_HD Projected project_gaussian(const float mean[3], const float quat[4],
   mat3_mul(R, cov, tmp);        // R Sigma
   mat3_mul_bt(tmp, R, covc);    // R Sigma R^T
   float a, b, c;
-  if constexpr (CAM == MGS_CAMERA_FISHEYE || CAM == MGS_CAMERA_FISHEYE_KB) {
+  if constexpr (CAM == MGS_CAMERA_FISHEYE || CAM == MGS_CAMERA_FISHEYE_KB || CAM == MGS_CAMERA_PINHOLE_BC) {
     // cov2d = J covc J^T with a dense J: T = J covc (2 x 3), then T J^T
     float t0[3], t1[3];
     for (int k = 0; k < 3; ++k) {
@@ -330,7 +384,8 @@ MGS_HD Projected project_gaussian(const float mean[3], const float quat[4],
   a += eps2d;
   c += eps2d;
   float det = a * c - b * b;
-  if constexpr (CAM == MGS_CAMERA_FISHEYE_KB) {
+  if constexpr (CAM == MGS_CAMERA_FISHEYE_KB || CAM == MGS_CAMERA_PINHOLE_BC) {
+    // (MGS_CAMERA_PINHOLE_BC: the same towards its folds, where det Jd -> 0 squashes the splat along one axis.)
     // Towards theta_max the lens squashes a splat radially by D -> 0: cov2d turns needle-like whatever the Gaussian's own
     // shape, and a c - b^2 cancels (the compensation factor was off by 3e-3 relative within a few degrees of the fold).
     // So this model alone takes det(cov2d) as the sum of the squared 2 x 2 minors of M2 = J R Rq S (Cauchy-Binet, positive
@@ -353,6 +408,8 @@ MGS_HD Projected project_gaussian(const float mean[3], const float quat[4],
     mx = cam.fx * x * rz + cam.cx; my = cam.fy * y * rz + cam.cy;
   } else if constexpr (CAM == MGS_CAMERA_ORTHO) {
     mx = cam.fx * x + cam.cx; my = cam.fy * y + cam.cy;
+  } else if constexpr (CAM == MGS_CAMERA_PINHOLE_BC) {
+    mx = cam.fx * bcx + cam.cx; my = cam.fy * bcy + cam.cy;
   } else {
     mx = cam.fx * (fs * x) + cam.cx; my = cam.fy * (fs * y) + cam.cy;
   }
@@ -558,8 +615,14 @@ MGS_HD ProjectedGrad project_gaussian_vjp(const float mean[3], const float quat[
     j00 = cam.fx * (kb.S + x * x * kb.A); j01 = cam.fx * xya; j02 = -cam.fx * x * dr;
     j10 = cam.fy * xya; j11 = cam.fy * (kb.S + y * y * kb.A); j12 = -cam.fy * y * dr;
   }
+  [[maybe_unused]] PinholeBc bc;
+  if constexpr (CAM == MGS_CAMERA_PINHOLE_BC) {
+    bc = pinhole_bc_terms<true>(cam.k, xr, yr);
+    j00 = cam.fx * bc.d00 * rz; j01 = cam.fx * bc.d01 * rz; j02 = -cam.fx * rz * (bc.d00 * xr + bc.d01 * yr);
+    j10 = cam.fy * bc.d01 * rz; j11 = cam.fy * bc.d11 * rz; j12 = -cam.fy * rz * (bc.d01 * xr + bc.d11 * yr);
+  }
   static_assert(CAM == MGS_CAMERA_PINHOLE || CAM == MGS_CAMERA_ORTHO || CAM == MGS_CAMERA_FISHEYE ||
-                    CAM == MGS_CAMERA_FISHEYE_KB, "camera model");
+                    CAM == MGS_CAMERA_FISHEYE_KB || CAM == MGS_CAMERA_PINHOLE_BC, "camera model");
 
   // conic = inv(cov2d + eps I):  G2 = -conic * Vc * conic, Vc = [[va, vb/2],[vb/2, vc]]
   float ca = conic[0], cb = conic[1], cc = conic[2];
@@ -616,6 +679,35 @@ MGS_HD ProjectedGrad project_gaussian_vjp(const float mean[3], const float quat[
     vx = cam.fx * v_mean2d[0];
     vy = cam.fy * v_mean2d[1];
     vz = v_depth;
+  } else if constexpr (CAM == MGS_CAMERA_PINHOLE_BC) {
+    // Everything is a function of (a, b, rz) = (x/z, y/z, 1/z): with D = Jd,
+    //   J[r][0] = f_r D[r][0] rz,  J[r][1] = f_r D[r][1] rz,  J[r][2] = -f_r rz (D[r][0] a + D[r][1] b)
+    // so rz dJ/drz = J, and the cotangents of D's three entries and the direct ones of a, b follow from w = f_r vJ.
+    //   dd00/da = 6 a R1 + 4 a^3 R2 + 6 p2           dd00/db = dd01/da = Ta = 2 b R1 + 4 a^2 b R2 + 2 p1
+    //   dd11/db = 6 b R1 + 4 b^3 R2 + 6 p1           dd01/db = dd11/da = Tb = 2 a R1 + 4 a b^2 R2 + 2 p2
+    float vJ[6];
+    for (int r = 0; r < 2; ++r)
+      for (int c = 0; c < 3; ++c)
+        vJ[r * 3 + c] = GsJ[r * 3] * covc[c] + GsJ[r * 3 + 1] * covc[3 + c] + GsJ[r * 3 + 2] * covc[6 + c];
+    const float a = xr, b = yr, p1 = cam.k[2], p2 = cam.k[3];
+    const float w00 = cam.fx * vJ[0], w01 = cam.fx * vJ[1], w02 = cam.fx * vJ[2];
+    const float w10 = cam.fy * vJ[3], w11 = cam.fy * vJ[4], w12 = cam.fy * vJ[5];
+    const float gd00 = rz * (w00 - a * w02);
+    const float gd01 = rz * ((w01 - b * w02) + (w10 - a * w12));
+    const float gd11 = rz * (w11 - b * w12);
+    const float Ta = 2.f * b * bc.R1 + 4.f * a * a * b * bc.R2 + 2.f * p1;
+    const float Tb = 2.f * a * bc.R1 + 4.f * a * b * b * bc.R2 + 2.f * p2;
+    const float Haaa = 6.f * a * bc.R1 + 4.f * a * a * a * bc.R2 + 6.f * p2;
+    const float Hbbb = 6.f * b * bc.R1 + 4.f * b * b * b * bc.R2 + 6.f * p1;
+    const float vxd = cam.fx * v_mean2d[0], vyd = cam.fy * v_mean2d[1];
+    const float va_ = bc.d00 * vxd + bc.d01 * vyd + gd00 * Haaa + gd01 * Ta + gd11 * Tb -
+                      rz * (w02 * bc.d00 + w12 * bc.d01);
+    const float vb_ = bc.d01 * vxd + bc.d11 * vyd + gd00 * Ta + gd01 * Tb + gd11 * Hbbb -
+                      rz * (w02 * bc.d01 + w12 * bc.d11);
+    const float vJJ = vJ[0] * j00 + vJ[1] * j01 + vJ[2] * j02 + vJ[3] * j10 + vJ[4] * j11 + vJ[5] * j12;
+    vx = rz * va_;
+    vy = rz * vb_;
+    vz = -rz * (a * va_ + b * vb_ + vJJ) + v_depth;
   } else if constexpr (CAM == MGS_CAMERA_FISHEYE_KB) {
     // as the equidistant branch below, with S, A, D for s, a, 1.  With c = 2 s z / r2 (du/dx = c x, du/dy = c y) and
     // uz = du/dz = -2 s q / r2:

@@ -238,6 +238,7 @@ extern "C" int mgs_projection_fwd(int n, const float* means, const float* quats,
   MGS_REQUIRE(n >= 0 && width > 0 && height > 0, "projection_fwd: bad sizes n=%d %dx%d", n, width, height);
   MGS_REQUIRE(is_camera_model(camera_model),
               "projection_fwd: camera_model %d is not MGS_CAMERA_PINHOLE, _ORTHO, _FISHEYE or _FISHEYE_KB", camera_model);
+  MGS_REQUIRE(camera_model != MGS_CAMERA_PINHOLE_BC || K, "projection_fwd: %s", kPinholeLensNeedsRow);
   if (n == 0) return MGS_OK;
   MGS_REQUIRE(means && quats && scales && viewmat && K && radii && means2d && depths && conics,
               "projection_fwd: null pointer");
@@ -288,7 +289,8 @@ extern "C" int mgs_project_color_fwd(int n, const float* means, const float* qua
   const bool per_axis = (bin_flags & MGS_BIN_RADIUS_OPACITY_AWARE) != 0;
   MGS_REQUIRE((bin_flags & (MGS_BIN_CAMERA_ORTHO | MGS_BIN_CAMERA_FISHEYE)) != (MGS_BIN_CAMERA_ORTHO | MGS_BIN_CAMERA_FISHEYE),
               "project_color_fwd: bin_flags sets both MGS_BIN_CAMERA_ORTHO and MGS_BIN_CAMERA_FISHEYE");
-  MGS_REQUIRE(!several_camera_bits(bin_flags, MGS_BIN_CAMERA_ORTHO | MGS_BIN_CAMERA_FISHEYE | MGS_BIN_CAMERA_FISHEYE_KB),
+  MGS_REQUIRE(!several_camera_bits(bin_flags, MGS_BIN_CAMERA_ORTHO | MGS_BIN_CAMERA_FISHEYE | MGS_BIN_CAMERA_FISHEYE_KB |
+                                              MGS_BIN_CAMERA_PINHOLE_BC),
               "project_color_fwd: bin_flags sets more than one MGS_BIN_CAMERA_* bit");
   const int cam_model = bin_camera_model(bin_flags);
   const int params = bin_flags & (MGS_PARAMS_RAW | MGS_PARAMS_OPAC_PLAIN);

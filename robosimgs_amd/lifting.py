@@ -32,7 +32,7 @@ def lift_labels(means: Tensor, quats: Tensor, scales: Tensor, opacities: Tensor,
                 height: int, masks: Tensor, n_classes: int, *, min_vote: float = 0.0, votes: Optional[Tensor] = None,
                 eps2d: float = 0.3, near_plane: float = 0.01, far_plane: float = 1e10, radius_clip: float = 0.0,
                 rasterize_mode: str = "classic", radius_rule: str = "classic", camera_model: str = "pinhole",
-                distortion=None, _debug: Optional[list] = None) -> LiftResult:
+                distortion=None, pinhole_distortion=None, _debug: Optional[list] = None) -> LiftResult:
     """means [N,3], quats [N,4], scales [N,3], opacities [N] (activated), viewmats [C,4,4], Ks [C,3,3], masks uint8 [C,H,W]
     with values 0..n_classes-1 (anything else, 255 by convention, is "no class here"; a host tensor is uploaded camera by
     camera).  The projection arguments are `rasterization`'s and must be those the masks' frames were rendered with.
@@ -56,8 +56,8 @@ def lift_labels(means: Tensor, quats: Tensor, scales: Tensor, opacities: Tensor,
     n_classes = ops.check_n_classes(n_classes)
     antialiased = rasterize_mode == "antialiased"
     rule = ops.radius_rule_id(radius_rule)
-    camera = ops.camera_model_id(camera_model, distortion)
-    cam_rows = ops.lens_rows(Ks, distortion) if camera == ops.CAMERA_FISHEYE_KB else Ks
+    camera = ops.camera_model_id(camera_model, distortion, pinhole_distortion)
+    cam_rows = ops.lens_rows(Ks, distortion, pinhole_distortion) if camera in ops.LENS_CAMERAS else Ks
     if votes is None:
         votes = torch.zeros(N, n_classes, dtype=torch.int64, device=dev)
     else:

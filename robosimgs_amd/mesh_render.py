@@ -297,7 +297,8 @@ class MeshRenderer:
 
     options: near_plane=0.01, far_plane=1e10, cull_backfaces=False, headlight=False, ambient=0.3, return_normals=False;
     out: dict of preallocated outputs (rgb, depth, face_ids, normals), workspace: a uint8 tensor of
-    mesh_workspace_bytes(...) + 256 bytes."""
+    mesh_workspace_bytes(...) + 256 bytes.  The camera is the ideal pinhole: there is no lens here (rasterization's
+    pinhole_distortion= has no counterpart), so under a lens a mesh layer and a splat frame do not register."""
 
     def __init__(self, mesh: Mesh, width: int, height: int, n_cams: int = 1, *, near_plane: float = 0.01,
                  far_plane: float = 1e10, cull_backfaces: bool = False, headlight: bool = False, ambient: float = 0.3,
@@ -372,7 +373,8 @@ def rasterize_mesh(mesh: Mesh, viewmats, Ks, width: int, height: int, *, rotatio
     """Render `mesh` (on the GPU) from C cameras: (rgb float32 [C,H,W,3], depth float32 [C,H,W], meta) with meta =
     dict(face_ids int32 [C,H,W] (-1 where uncovered), verts_cam float32 [C,V,3][, normals float32 [C,H,W,3]]).
 
-    viewmats [C,4,4] (or [4,4]) and Ks [C,3,3] (or [3,3]): tensors or arrays of any float type; an OpenCV pinhole camera.
+    viewmats [C,4,4] (or [4,4]) and Ks [C,3,3] (or [3,3]): tensors or arrays of any float type; an OpenCV pinhole camera --
+    the ideal one: the mesh operators take no lens (rasterization's pinhole_distortion= has no counterpart here).
     rotations [L,3,3], translations [L,3], scales [L]: the convention of transform_gaussians (x' = s R x + t for the
     vertices of link l), so Hinge.pose(angle) feeds them directly (R [3,3] and t [3] are one link).  Link ids >= L are
     static: len(rotations) < mesh.n_links() is not an error, because finding it would take a read-back.

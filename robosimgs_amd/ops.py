@@ -77,18 +77,23 @@ CAMERA_FRAME_FLAGS = {0: 0, 1: FRAMES_CAMERA_ORTHO, 2: FRAMES_CAMERA_FISHEYE}   
 CAMERA_FISHEYE_KB = 3                                           # MGS_CAMERA_FISHEYE_KB
 BIN_CAMERA_FISHEYE_KB = FRAMES_CAMERA_FISHEYE_KB = 256          # its bin_flags / mgs_render_frames* bit
 LENS_ROW_FLOATS = 16       # floats per camera behind K / Ks under that model: K | k1..k4 | u_max | 0 0
+# The pinhole lens (include/mgs_lens_pinhole.h): camera_model="pinhole" with OpenCV's k1 k2 p1 p2 k3, the fifth model
+CAMERA_PINHOLE_BC = 4                                           # MGS_CAMERA_PINHOLE_BC
+BIN_CAMERA_PINHOLE_BC = FRAMES_CAMERA_PINHOLE_BC = 512          # its bin_flags / mgs_render_frames* bit
+LENS_CAMERAS = (CAMERA_FISHEYE_KB, CAMERA_PINHOLE_BC)           # the models whose K / Ks are 16-float rows (lens_rows)
 
 
 # (In the two lookups below the tables of the three named models come last, so an entry of theirs wins over the lens's:
 #  tests/test_gpu_camera_models.py puts a key 3 with two camera bits into them to reach the C ABI's both-bits error.)
 def camera_bin_flags(camera) -> int:
     """MGS_CAMERA_* -> the bin_flags bits that select it."""
-    return {CAMERA_FISHEYE_KB: BIN_CAMERA_FISHEYE_KB, **CAMERA_BIN_FLAGS}[int(camera)]
+    return {CAMERA_FISHEYE_KB: BIN_CAMERA_FISHEYE_KB, CAMERA_PINHOLE_BC: BIN_CAMERA_PINHOLE_BC, **CAMERA_BIN_FLAGS}[int(camera)]
 
 
 def camera_frame_flags(camera) -> int:
     """MGS_CAMERA_* -> the mgs_render_frames* bits that select it."""
-    return {CAMERA_FISHEYE_KB: FRAMES_CAMERA_FISHEYE_KB, **CAMERA_FRAME_FLAGS}[int(camera)]
+    return {CAMERA_FISHEYE_KB: FRAMES_CAMERA_FISHEYE_KB, CAMERA_PINHOLE_BC: FRAMES_CAMERA_PINHOLE_BC,
+            **CAMERA_FRAME_FLAGS}[int(camera)]
 
 
 def frames_flags(expected_last, latency, tight, per_axis, camera, raw=False) -> int:
@@ -100,7 +105,8 @@ def frames_flags(expected_last, latency, tight, per_axis, camera, raw=False) -> 
 
 class LensRows:
     """A lens that already sits on the device as camera rows: `rows` is a contiguous float32 [C,16] tensor in the layout
-    lens_rows() builds (K | k1..k4 | u_max | 0 0).  Given as distortion= by a caller that keeps the rows in a buffer of its
+    lens_rows() builds (K | k1..k4 | u_max | 0 0, or K | k1 k2 p1 p2 k3 | u_max | 0 under the pinhole lens).  Given as
+    distortion= (pinhole_distortion= for the pinhole lens) by a caller that keeps the rows in a buffer of its
     own and overwrites K in place (FrameRenderer's camera slots); the kernels then read K from the rows, not from Ks."""
     __slots__ = ("rows",)
 
@@ -128,11 +134,42 @@ def lens_coefficients(distortion, n_cams=None):
     return k if k.any() else None
 
 
-def camera_model_id(camera_model, distortion=None) -> int:
+def pinhole_lens_coefficients(pinhole_distortion, n_cams=None):
+    """pinhole_distortion= as the calls take it -- None, or host data (sequence / ndarray) [5] or [C,5] of OpenCV's
+    distCoeffs k1 k2 p1 p2 k3 ([4] / [C,4]: k3 = 0) -- -> None when there is no lens (None or all zero: the plain pinhole
+    instantiation), else a float64 ndarray [C,5] or [1,5] (one lens for every camera).  A LensRows is returned as it is."""
+    if pinhole_distortion is None or isinstance(pinhole_distortion, LensRows):
+        return pinhole_distortion
+    if torch.is_tensor(pinhole_distortion):
+        if pinhole_distortion.is_cuda:
+            raise ValueError("pinhole_distortion is host data (a sequence or ndarray [5] or [C,5]), not a device tensor")
+        pinhole_distortion = pinhole_distortion.numpy()
+    k = np.asarray(pinhole_distortion, dtype=np.float64)
+    if k.ndim == 1:
+        k = k[None]
+    if k.ndim != 2 or k.shape[1] not in (4, 5) or (n_cams is not None and k.shape[0] not in (1, int(n_cams))):
+        raise ValueError(f"pinhole_distortion must be [5] or [C,5] (k1 k2 p1 p2 k3 per camera; [4] / [C,4]: k3 = 0), got "
+                         f"{tuple(np.shape(pinhole_distortion))}")
+    if k.shape[1] == 4:
+        k = np.concatenate([k, np.zeros((k.shape[0], 1))], axis=1)
+    if not np.isfinite(k).all():
+        raise ValueError("pinhole_distortion coefficients must be finite")
+    return k if k.any() else None
+
+
+def camera_model_id(camera_model, distortion=None, pinhole_distortion=None) -> int:
     """MGS_CAMERA_* of camera_model; with distortion= (lens_coefficients: valid only with "fisheye") that are not all
-    zero, MGS_CAMERA_FISHEYE_KB."""
+    zero, MGS_CAMERA_FISHEYE_KB; with pinhole_distortion= (pinhole_lens_coefficients: valid only with "pinhole") that are
+    not all zero, MGS_CAMERA_PINHOLE_BC."""
     if camera_model not in CAMERA_MODELS:
         raise ValueError(f"camera_model {camera_model!r} not in {tuple(CAMERA_MODELS)}")
+    if pinhole_distortion is not None:
+        if distortion is not None:
+            raise ValueError("pinhole_distortion= (the pinhole lens, k1 k2 p1 p2 k3) and distortion= (the fisheye lens, "
+                             "k1..k4) are lenses of different camera models: give one of them")
+        if camera_model != "pinhole":
+            raise ValueError(f"pinhole_distortion= (OpenCV k1 k2 p1 p2 k3) needs camera_model='pinhole', got {camera_model!r}")
+        return CAMERA_PINHOLE_BC if pinhole_lens_coefficients(pinhole_distortion) is not None else CAMERA_MODELS["pinhole"]
     if distortion is not None:
         if camera_model != "fisheye":
             raise ValueError(f"distortion= (fisheye lens coefficients k1..k4) needs camera_model='fisheye', got {camera_model!r}")
@@ -148,16 +185,19 @@ _LENS_TAILS: dict = {}
 _LENS_TAILS_MAX = 4096
 
 
-def lens_rows(Ks: Tensor, distortion) -> Tensor:
+def lens_rows(Ks: Tensor, distortion, pinhole_distortion=None) -> Tensor:
     """The [C,16] camera rows of MGS_CAMERA_FISHEYE_KB for Ks [C,3,3] on the device and a lens (lens_coefficients):
     K row-major | k1..k4 | u_max | 0 0, u_max = theta_max^2 computed per camera on the host in fp64
-    (camera.lens_theta_max); a LensRows hands its own rows back.  The lens part is uploaded once per distinct lens and
+    (camera.lens_theta_max); with pinhole_distortion instead (pinhole_lens_coefficients) the rows of MGS_CAMERA_PINHOLE_BC:
+    K | k1 k2 p1 p2 k3 | u_max | 0, u_max the radial fold (camera.pinhole_lens_u_max; FLT_MAX without one).  A LensRows
+    hands its own rows back.  The lens part is uploaded once per distinct lens and
     device and kept for the life of the process, so a later call -- one under graph capture too -- only concatenates
     device tensors.  A lens this process has not seen cannot be uploaded under graph capture: ValueError (render once with it
     before capturing, as a warm-up does)."""
-    from .camera import lens_theta_max
+    from .camera import lens_theta_max, pinhole_lens_u_max
     C = Ks.shape[0]
-    k = lens_coefficients(distortion, C)
+    pinhole = pinhole_distortion is not None
+    k = pinhole_lens_coefficients(pinhole_distortion, C) if pinhole else lens_coefficients(distortion, C)
     if k is None:
         raise ValueError("lens_rows needs distortion coefficients that are not all zero")
     if isinstance(k, LensRows):
@@ -165,15 +205,18 @@ def lens_rows(Ks: Tensor, distortion) -> Tensor:
         require_device(rows)
         check_tensor("LensRows.rows", rows, torch.float32, (C, LENS_ROW_FLOATS), Ks.device)
         return rows
-    key = (k.tobytes(), k.shape[0], Ks.device)
+    key = (k.tobytes(), k.shape[0], Ks.device) + (("pinhole",) if pinhole else ())
     tail = _LENS_TAILS.get(key)
     if tail is None:
         if torch.cuda.is_current_stream_capturing():
             raise ValueError("this lens has not been used in this process yet and its coefficients cannot be uploaded under "
                              "graph capture: render once with distortion= before capturing")
         host = np.zeros((k.shape[0], LENS_ROW_FLOATS - 9))
-        host[:, :4] = k
-        host[:, 4] = [lens_theta_max(row) ** 2 for row in k]
+        host[:, :k.shape[1]] = k
+        if pinhole:
+            host[:, 5] = [min(pinhole_lens_u_max(row), float(np.finfo(np.float32).max)) for row in k]
+        else:
+            host[:, 4] = [lens_theta_max(row) ** 2 for row in k]
         tail = torch.from_numpy(host.astype(np.float32)).to(Ks.device)
         if len(_LENS_TAILS) < _LENS_TAILS_MAX:
             _LENS_TAILS[key] = tail
@@ -194,7 +237,8 @@ def radii_meta(radii):
 def projection_fwd_raw(means, quats, scales, viewmat, K, width, height, eps2d, near_plane,
                        far_plane, radius_clip, calc_compensations, opacities=None, radius_rule=0, camera=0):
     """radius_rule 1 (MGS_RADIUS_OPACITY_AWARE): radii comes back planar [2,N] (x extents, y extents).
-    camera: MGS_CAMERA_* (camera_model_id); under CAMERA_FISHEYE_KB `K` is the camera's 16-float row (lens_rows)."""
+    camera: MGS_CAMERA_* (camera_model_id); under CAMERA_FISHEYE_KB / CAMERA_PINHOLE_BC `K` is the camera's 16-float row
+    (lens_rows)."""
     n = means.shape[0]
     dev = means.device
     radii = torch.empty((2, n) if radius_rule else (n,), dtype=torch.int32, device=dev)
@@ -222,8 +266,8 @@ def project_color_fwd_raw(means, quats, scales, opacities, sh_degree, sh_coeffs,
     lean (needs want_splats and bin_seed): radii / means2d / conics / feats are not written and come back
     as None -- an inference frame, whose raster reads the records and whose binning reads the seed.
     per_axis: project with MGS_RADIUS_OPACITY_AWARE; radii is then planar [2,N] (radii_x / radii_meta).
-    camera: the camera model, MGS_CAMERA_* (camera_model_id); under CAMERA_FISHEYE_KB `K` (and `Ks` of the frames calls
-    below) holds 16-float camera rows (lens_rows).
+    camera: the camera model, MGS_CAMERA_* (camera_model_id); under CAMERA_FISHEYE_KB / CAMERA_PINHOLE_BC `K` (and `Ks` of the frames
+    calls below) holds 16-float camera rows (lens_rows).
     raw: scales are log-scales and opacities logits (MGS_PARAMS_RAW); every output is the activated form's.  Unless
     lean, the 5th item is then kept whether anti-aliased or not: the activated opacity (x compensation when
     anti-aliased), which the raster and project_color_bwd_raw need."""
@@ -972,7 +1016,8 @@ def fully_fused_projection(means: Tensor, covars: Optional[Tensor], quats: Tenso
                            far_plane: float = 1e10, radius_clip: float = 0.0,
                            packed: bool = False, sparse_grad: bool = False,
                            calc_compensations: bool = False, opacities: Optional[Tensor] = None,
-                           radius_rule: str = "classic", camera_model: str = "pinhole", distortion=None
+                           radius_rule: str = "classic", camera_model: str = "pinhole", distortion=None,
+                           pinhole_distortion=None
                            ) -> Tuple[Tensor, Tensor, Tensor, Tensor, Optional[Tensor]]:
     """World -> screen EWA projection of N Gaussians for C cameras.
     Returns radii [C,N] i32, means2d [C,N,2], depths [C,N], conics [C,N,3],
@@ -983,7 +1028,10 @@ def fully_fused_projection(means: Tensor, covars: Optional[Tensor], quats: Tenso
     camera_model: "pinhole", "ortho" or "fisheye" (ideal equidistant, r = f theta), as gsplat's operator; include/mgs.h
     MGS_CAMERA_* gives the maps.  Depths are camera z under every model.
     distortion (with "fisheye"): OpenCV fisheye coefficients k1..k4, host data [4] or [C,4] -- theta_d = theta (1 + k1 theta^2
-    + ... + k4 theta^8); Gaussians past the angle where that polynomial folds back are culled.  None / all zero: the ideal lens."""
+    + ... + k4 theta^8); Gaussians past the angle where that polynomial folds back are culled.  None / all zero: the ideal lens.
+    pinhole_distortion (with "pinhole"): OpenCV's distCoeffs k1 k2 p1 p2 k3, host data [5] or [C,5] ([4]: k3 = 0) -- the
+    radial / tangential lens of include/mgs_lens_pinhole.h with its three culls (rasterization's docstring).  None / all
+    zero: the plain pinhole."""
     if covars is not None:
         raise NotImplementedError("precomputed covariances are not supported; pass quats+scales")
     if packed:
@@ -997,9 +1045,9 @@ def fully_fused_projection(means: Tensor, covars: Optional[Tensor], quats: Tenso
     if viewmats.dim() != 3 or viewmats.shape[1:] != (4, 4) or Ks.shape != (viewmats.shape[0], 3, 3):
         raise ValueError("expected viewmats [C,4,4], Ks [C,3,3]")
     rule = radius_rule_id(radius_rule)
-    camera = camera_model_id(camera_model, distortion)
-    if camera == CAMERA_FISHEYE_KB:
-        Ks = lens_rows(Ks, distortion)
+    camera = camera_model_id(camera_model, distortion, pinhole_distortion)
+    if camera in LENS_CAMERAS:
+        Ks = lens_rows(Ks, distortion, pinhole_distortion)
     if opacities is not None:
         require_device(opacities)
         opacities = _f32c(opacities.detach())

@@ -106,7 +106,7 @@ class FrameRenderer:
                  sizing_camera=None, group_ids: Optional[torch.Tensor] = None, n_groups: int = 0,
                  rotate_sh: bool = True, reorder: Optional[str] = "morton", dataset_output=None, dataset_K=None,
                  dataset_keep_float: bool = False, class_ids: Optional[torch.Tensor] = None, n_classes: Optional[int] = None,
-                 labels: bool = False, distortion=None, deform=None, deform_mode: str = "rigid",
+                 labels: bool = False, distortion=None, pinhole_distortion=None, deform=None, deform_mode: str = "rigid",
                  deform_rotate_sh: bool = False, **raster_kw):
         """tensors: dict(means, quats, scales, opacities, colors, sh_degree) on the GPU
         (Gaussians.to_torch()); `self.t` is the renderer's own (by default Morton-ordered) copy.  isect_capacity: slots reserved for tile intersections per
@@ -137,6 +137,10 @@ class FrameRenderer:
         renderer like dataset_K.  The coefficients and the end of the lens's range sit behind the camera in every slot's
         buffer, written once at capture; a submit stays one 25-float copy.  Combines with group_ids and labels; refused
         with dataset_output (pinhole-only).
+
+        pinhole_distortion=(k1, k2, p1, p2, k3) with camera_model="pinhole": the lens of a calibrated pinhole camera
+        (rasterization's pinhole_distortion=), kept in every slot's camera buffer like the fisheye lens.  Combines with
+        group_ids and labels; refused with distortion= and with dataset_output.
 
         Soft objects: deform=bind_particles(tensors["means"], particles_rest, ...) -- a ParticleBinding in
         the order of `tensors` (the renderer permutes it along with its Morton copy) -- and deform_mode "rigid" or "affine".
@@ -224,9 +228,15 @@ class FrameRenderer:
         self.width, self.height, self.mode = int(width), int(height), render_mode
         self.kw = dict(raster_kw)
         # the lens: None when there is none (no coefficients, or all zero: the ideal fisheye)
-        ops.camera_model_id(self.kw.get("camera_model", "pinhole"), distortion)      # fisheye only
+        ops.camera_model_id(self.kw.get("camera_model", "pinhole"), distortion, pinhole_distortion)   # each with its own model
         k = ops.lens_coefficients(distortion, 1)
         self.distortion = tuple(float(v) for v in k[0]) if k is not None else None
+        # the pinhole lens (k1 k2 p1 p2 k3), kept the same way; None when all zero: the plain pinhole
+        if pinhole_distortion is not None and dataset_output is not None:
+            raise ValueError("dataset_output converts depth to ray distance through an undistorted pinhole K^-1: there is "
+                             "no dataset output with pinhole_distortion=")
+        k = ops.pinhole_lens_coefficients(pinhole_distortion, 1)
+        self.pinhole_distortion = tuple(float(v) for v in k[0]) if k is not None else None
         self.dataset_dtype, self.dataset_K, self.dataset_keep_float = dataset_output, None, bool(dataset_keep_float)
         if dataset_output is not None:
             if self.kw.get("camera_model", "pinhole") != "pinhole":
@@ -271,6 +281,8 @@ class FrameRenderer:
         kw = self.kw if schedule is None else dict(self.kw, raster_schedule=schedule)
         if self.distortion is not None:     # a slot's camera buffer carries the lens behind K; any other K gets it here
             kw = dict(kw, distortion=ops.LensRows(rows) if rows is not None else self.distortion)
+        if self.pinhole_distortion is not None:
+            kw = dict(kw, pinhole_distortion=ops.LensRows(rows) if rows is not None else self.pinhole_distortion)
         if labels and self.class_ids is not None:
             kw = dict(kw, class_ids=self.class_ids, n_classes=self.n_classes)
         return rasterization(t["means"], t["quats"], t["scales"], t["opacities"], t["colors"], vm,
@@ -291,6 +303,12 @@ class FrameRenderer:
             # is written here once, submit() overwrites the first 25 floats only
             from .camera import lens_theta_max
             cam[25:30].copy_(torch.tensor([*self.distortion, lens_theta_max(self.distortion) ** 2], dtype=torch.float32))
+            rows = cam[16:32].view(1, 16)
+        if self.pinhole_distortion is not None:
+            # the same under the pinhole lens (include/mgs_lens_pinhole.h): K | k1 k2 p1 p2 k3 | u_max | 0
+            from .camera import pinhole_lens_u_max
+            u_max = min(pinhole_lens_u_max(self.pinhole_distortion), float(np.finfo(np.float32).max))
+            cam[25:31].copy_(torch.tensor([*self.pinhole_distortion, u_max], dtype=torch.float32))
             rows = cam[16:32].view(1, 16)
         pose = None
         if self.group_ids is not None:       # dynamic scene: this slot's transforms and posed copy

@@ -320,6 +320,7 @@ def rasterization(means: Tensor, quats: Tensor, scales: Tensor, opacities: Tenso
                   dataset_out=None,
                   camera_model: str = "pinhole",
                   distortion=None,
+                  pinhole_distortion=None,
                   raw_params: bool = False,
                   class_ids: Optional[Tensor] = None,
                   n_classes: Optional[int] = None,
@@ -327,7 +328,8 @@ def rasterization(means: Tensor, quats: Tensor, scales: Tensor, opacities: Tenso
                   backdrop=None) -> Tuple[Tensor, Tensor, Dict]:
     """Render N Gaussians from C cameras.
 
-    foreground = (fg_rgb [C,H,W,3], fg_depth [C,H,W]), an opaque layer as rasterize_mesh returns it (z-depth, 0 where no
+    foreground = (fg_rgb [C,H,W,3], fg_depth [C,H,W]), an opaque layer as rasterize_mesh returns it (an ideal-pinhole
+    layer: the mesh operators take no lens, so combine it with pinhole_distortion= only if it was rendered to match; z-depth, 0 where no
     face is), with render_mode="RGB+ED": every frame also gets its exact composite with that layer (include/mgs_hybrid.h,
     DESIGN.md 4.17) -- meta["hybrid_rgb"] [C,H,W,3] and meta["hybrid_depth"] [C,H,W], the pixel's own front-to-back blend
     stopped at the foreground's depth with the foreground entering at the transmittance reached there, and
@@ -378,6 +380,19 @@ def rasterization(means: Tensor, quats: Tensor, scales: Tensor, opacities: Tenso
     theta_max, where the polynomial stops growing (camera.lens_theta_max, computed here on the host), is culled like one
     behind the near plane.  None or all zero: the ideal lens, bit for bit the call without the keyword.  meta is unchanged.
 
+    pinhole_distortion (camera_model="pinhole" only, else ValueError; not together with distortion= or dataset_out): the
+    lens of a calibrated pinhole camera, OpenCV's distCoeffs k1 k2 p1 p2 k3 as host data, a sequence or ndarray [5] (one
+    lens; [4]: k3 = 0) or [C,5] (one per camera) -- cv2.calibrateCamera / nerfstudio OPENCV: with x' = x/z, y' = y/z,
+    u = x'^2 + y'^2, Rad = 1 + k1 u + k2 u^2 + k3 u^3, the pixel is (fx xd + cx, fy yd + cy) at
+    xd = x' Rad + 2 p1 x' y' + p2 (u + 2 x'^2), yd = y' Rad + p1 (u + 2 y'^2) + 2 p2 x' y'.  Projection, Jacobian and every
+    gradient are the lens's (include/mgs_lens_pinhole.h MGS_CAMERA_PINHOLE_BC, a fifth instantiation of the projection
+    kernels).  The Jacobian is not clamped; instead a Gaussian is culled like one behind the near plane when its centre
+    lies past the radial fold (u >= u_max, camera.pinhole_lens_u_max, computed here on the host), where the lens map folds
+    (det of its 2 x 2 Jacobian <= 0), or when the distorted centre lies outside the frame grown by 0.3 of the half field
+    -- the box the plain pinhole clamps its Jacobian to.  That last cull is the one difference from the plain pinhole
+    besides the lens: a Gaussian centred outside the box is dropped rather than kept with a clamped J.  None or all zero:
+    no lens, bit for bit the call without the keyword.  meta is unchanged.
+
     backward_segment (SH path, when gradients are wanted): list entries per unit of work of the backward raster
     (a power of two >= 64; 0 = one unit per tile, the whole-list walk).  The training forward stores per-pixel
     checkpoints at that interval ((1 + channels) * 1 KB per tile and segment) and the backward walks the segments
@@ -417,7 +432,10 @@ def rasterization(means: Tensor, quats: Tensor, scales: Tensor, opacities: Tenso
     if tile_bounds not in ("tight", "classic"):
         raise ValueError(f"tile_bounds {tile_bounds!r} not in ('tight', 'classic')")
     rule = ops.radius_rule_id(radius_rule)
-    camera = ops.camera_model_id(camera_model, distortion)
+    camera = ops.camera_model_id(camera_model, distortion, pinhole_distortion)
+    if dataset_out is not None and pinhole_distortion is not None:
+        raise ValueError("dataset_out converts depth to ray distance through an undistorted pinhole K^-1: there is no "
+                         "dataset output with pinhole_distortion=")
     if dataset_out is not None and camera != 0:
         raise ValueError(f"dataset_out converts depth to ray distance through a pinhole K^-1: camera_model "
                          f"{camera_model!r} has no dataset output")
@@ -460,7 +478,7 @@ def rasterization(means: Tensor, quats: Tensor, scales: Tensor, opacities: Tenso
         raise ValueError("expected viewmats [C,4,4], Ks [C,3,3]")
     means, quats, scales, opacities = _f32c(means), _f32c(quats), _f32c(scales), _f32c(opacities)
     colors, viewmats, Ks, backgrounds = _f32c(colors), _f32c(viewmats), _f32c(Ks), _f32c(backgrounds)
-    lens_rows = ops.lens_rows(Ks, distortion) if camera == ops.CAMERA_FISHEYE_KB else None
+    lens_rows = ops.lens_rows(Ks, distortion, pinhole_distortion) if camera in ops.LENS_CAMERAS else None
     width, height = int(width), int(height)
     antialiased = rasterize_mode == "antialiased"
     want_rgb = render_mode.startswith("RGB")
@@ -537,7 +555,8 @@ def rasterization(means: Tensor, quats: Tensor, scales: Tensor, opacities: Tenso
         radii, means2d, depths, conics, comps = ops.fully_fused_projection(
             means, None, quats, scales, viewmats, Ks, width, height, eps2d, near_plane, far_plane,
             radius_clip, calc_compensations=antialiased, opacities=opacities if rule else None,
-            radius_rule=radius_rule, camera_model=camera_model, distortion=distortion)
+            radius_rule=radius_rule, camera_model=camera_model, distortion=distortion,
+            pinhole_distortion=pinhole_distortion)
         opac = opacities.unsqueeze(0).expand(C, N)
         if antialiased:
             opac = opac * comps
@@ -599,6 +618,8 @@ def render(gaussians, cameras: Sequence, sh_degree: Optional[int] = None,
     kw.setdefault("camera_model", cams[0].model)
     if cams[0].model == "fisheye" and any(c.distortion is not None for c in cams):
         kw.setdefault("distortion", np.array([c.distortion or (0.0,) * 4 for c in cams], dtype=np.float64))
+    if cams[0].model == "pinhole" and any(c.pinhole_distortion is not None for c in cams):
+        kw.setdefault("pinhole_distortion", np.array([c.pinhole_distortion or (0.0,) * 5 for c in cams], dtype=np.float64))
     t = tensors if tensors is not None else gaussians.to_torch(device, sh_degree)
     viewmats = torch.from_numpy(np.stack([c.viewmat() for c in cams]).astype(np.float32)).to(device)
     Ks = torch.from_numpy(np.stack([c.K for c in cams]).astype(np.float32)).to(device)

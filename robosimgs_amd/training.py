@@ -100,7 +100,10 @@ class Trainer:
 
     strategy = robosimgs_amd.MCMCStrategy(...): `step` ends with strategy.step(self) -- splatfacto-mcmc's relocation and
     growth when due (the strategy rebinds the trainer to the grown views of its storage) and its noise every step.
-    None (default): nothing is called."""
+    None (default): nothing is called.
+
+    raster_kwargs are rasterization's, the camera's among them: camera_model=, distortion= (the fisheye lens) and
+    pinhole_distortion= (OpenCV's k1 k2 p1 p2 k3 of a calibrated pinhole camera), so a scene trains against raw captures."""
 
     KEYS = ("means", "quats", "scales", "opacities", "colors")
 
