@@ -3,7 +3,7 @@ FrameRenderer, and in front of it a triangle mesh -- the reference's open box, i
 MeshRenderer and composited by depth.  The loop of examples/articulated_scene.py with the stand-in disc replaced by a
 mesh render.  Synthetic background, so it runs anywhere an MI355X is visible:
 
-    python examples/hybrid_scene.py [n_frames] [--exact] [--textured]
+    python examples/hybrid_scene.py [n_frames] [--exact] [--textured] [--lens k1,k2,p1,p2,k3]
 
 The mesh render and the composite run eagerly on the consumer stream, once per fetched frame: there is no graph around
 them (composite_over builds its backdrop tensor from a host list and allocates its outputs on every call, so it is not
@@ -16,6 +16,10 @@ the frame's expected depth once.  No FrameRenderer and no graph on that path.
 --textured gives the box a procedural base-colour texture generated here (planks and a coarse checker, 512 x 512, no asset
 file) with planar uvs per face; MeshRenderer packs it and builds its mipmaps once, and render() filters it trilinearly
 (DESIGN.md 4.18).
+
+--lens k1,k2,p1,p2,k3 renders BOTH layers under one OpenCV pinhole lens (cv2.calibrateCamera's distCoeffs): the Gaussians
+through pinhole_distortion= and the mesh at each pixel's own ray solved from the same lens, so the box
+sits on the background it was placed in, as in a raw, un-resampled capture.  With --exact too.  Not with --textured.
 """
 import math
 import os
@@ -67,17 +71,23 @@ def textured(box):
 def main():
     flags = ("--exact", "--textured")
     argv = [a for a in sys.argv[1:] if a not in flags]
+    lens = None
+    if "--lens" in argv:
+        at = argv.index("--lens")
+        lens = tuple(float(v) for v in argv[at + 1].split(","))
+        del argv[at:at + 2]
+    lens_kw = {} if lens is None else {"pinhole_distortion": lens}
     exact = "--exact" in sys.argv[1:]
     n_frames = int(argv[0]) if argv else 60
     W, H = 1280, 720
     scene = synthetic_scene(300_000, math.log(0.02), 3, seed=0)
     cams = camera_ring(n_frames, W, H, radius=7.0)
     r = None if exact else FrameRenderer(scene.to_torch("cuda", 3), W, H, render_mode="RGB+ED", frames_in_flight=3,
-                      sizing_camera=(cams[0].viewmat(), cams[0].K), capacity_margin=2.0)
+                      sizing_camera=(cams[0].viewmat(), cams[0].K), capacity_margin=2.0, **lens_kw)
     box, hinge = open_box()
     if "--textured" in sys.argv[1:]:
         box = textured(box)                                              # the vertex colours stay on as the tint
-    mesh = MeshRenderer(box.to("cuda"), W, H, headlight=True)           # workspace and outputs allocated once
+    mesh = MeshRenderer(box.to("cuda"), W, H, headlight=True, **lens_kw)            # workspace and outputs allocated once
     # per frame: the camera and the lid's pose, uploaded before the loop so that the loop itself copies nothing
     angles = 0.6 * (1.0 - np.cos(2 * np.pi * np.arange(n_frames) / n_frames)) / 2
     R, t = hinge.pose(angles)                                            # [n,3,3], [n,3]
@@ -99,7 +109,7 @@ def main():
         fg_rgb, fg_depth, meta = mesh.render(vm_dev[i], K_dev[i], rotations=R_dev[i], translations=t_dev[i])
         _, _, m = rasterization(t["means"], t["quats"], t["scales"], t["opacities"], t["colors"], vm_dev[i], K_dev[i], W, H,
                                 sh_degree=t["sh_degree"], render_mode="RGB+ED", foreground=(fg_rgb, fg_depth),
-                                backdrop=(0.05, 0.05, 0.08))
+                                backdrop=(0.05, 0.05, 0.08), **lens_kw)
         frames.append(frame_to_u8(m["hybrid_rgb"][0], torch.ones(H, W, device="cuda")).cpu())
         box_pixels.append((meta["face_ids"] >= 0).sum())
 
@@ -123,6 +133,8 @@ def main():
           f"{'the exact composite (eager)' if exact else 'compositing'}, 8-bit conversion and download")
     print("mean pixel value of the first / last frame:", float(frames[0].float().mean()), float(frames[-1].float().mean()))
     print("pixels of the box in the first / middle frame:", int(box_pixels[0]), int(box_pixels[n_frames // 2]))
+    if lens is not None:
+        print("both layers under the lens", lens)
 
 
 if __name__ == "__main__":

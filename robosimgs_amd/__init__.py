@@ -18,7 +18,7 @@ _DEVICE_API = {"rasterization", "render", "check_isect_status", "fully_fused_pro
                "rasterize_to_pixels", "rasterize_labels", "rasterize_votes", "assign_classes", "lift_labels",
                "fit_hinge", "fit_hinge_points", "pose_gaussians", "bind_particles", "deform_gaussians",
                "deform_gaussians_autograd", "rasterize_mesh", "mesh_vertices", "mesh_raster", "mesh_resolve",
-               "render_sharded", "gather_frames"}
+               "mesh_lens_rays", "render_sharded", "gather_frames"}
 
 
 def __getattr__(name):  # lazy: keeps `import robosimgs_amd` torch-free for host-only use
@@ -56,7 +56,7 @@ def __getattr__(name):  # lazy: keeps `import robosimgs_amd` torch-free for host
         from . import mesh
         return getattr(mesh, name)
     if name in ("rasterize_mesh", "MeshRenderer", "mesh_vertices", "mesh_raster", "mesh_resolve", "mesh_workspace_bytes",
-                "TextureSet", "build_texture_set"):
+                "TextureSet", "build_texture_set", "mesh_lens_rays", "mesh_lens_workspace_bytes", "MeshLensMap"):
         from . import mesh_render
         return getattr(mesh_render, name)
     if name in ("l1_loss", "l1_ssim_loss", "ssim", "unit_gradient"):

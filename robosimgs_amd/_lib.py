@@ -162,11 +162,21 @@ _MESH_TEXTURE_SIGNATURES = {
 _HYBRID_SIGNATURES = {
     "mgs_raster_over_opaque": ([i, p, p, p, p, i, p, p, p, p, p, p, i, i, i, i, p, p, p, p, p, p, p], c_int),
 }
+# every function include/mgs_mesh_lens.h declares (the same libraries again): mgs_mesh.h's raster, resolve and fused call
+# with (camera_model, lens_rows) in place of Ks and (lens_workspace, lens_workspace_bytes) behind the workspace
+_MESH_LENS_SIGNATURES = {
+    "mgs_mesh_lens_workspace_bytes": ([i, i, i, POINTER(c_size_t)], c_int),
+    "mgs_mesh_lens_rays": ([i, i, p, i, i, p, c_size_t, p], c_int),
+    "mgs_mesh_raster_lens": ([i, i, p, i, p, i, p, i, i, f, f, i, p, c_size_t, p, c_size_t, p], c_int),
+    "mgs_mesh_resolve_lens": ([i, i, p, i, p, p, p, i, p, i, i, i, f, p, c_size_t, p, c_size_t, p, p, p, p, p], c_int),
+    "mgs_rasterize_mesh_lens": ([i, i, p, p, i, p, p, p, p, i, p, i, p, p, p, i, i, f, f, i, i, f, p, c_size_t, p, c_size_t,
+                                 p, p, p, p, p, p], c_int),
+}
 del p, i, f, u32, img
 # what _load binds: a new header adds its table here
 _SIGNATURE_TABLES = (_SIGNATURES, _OPTIM_SIGNATURES, _REFINE_SIGNATURES, _LABEL_SIGNATURES, _LIFT_SIGNATURES,
                      _HINGE_SIGNATURES, _POSE_SIGNATURES, _DEFORM_SIGNATURES, _DEFORM_SH_SIGNATURES, _MESH_SIGNATURES,
-                     _MESH_TEXTURE_SIGNATURES, _HYBRID_SIGNATURES, _DEFORM_BWD_SIGNATURES)
+                     _MESH_TEXTURE_SIGNATURES, _HYBRID_SIGNATURES, _DEFORM_BWD_SIGNATURES, _MESH_LENS_SIGNATURES)
 EXPORTS = list(_SIGNATURES)
 OPTIM_EXPORTS = list(_OPTIM_SIGNATURES)
 REFINE_EXPORTS = list(_REFINE_SIGNATURES)
@@ -180,6 +190,8 @@ DEFORM_BWD_EXPORTS = list(_DEFORM_BWD_SIGNATURES)
 MESH_EXPORTS = list(_MESH_SIGNATURES)
 HYBRID_EXPORTS = list(_HYBRID_SIGNATURES)
 MESH_TEXTURE_EXPORTS = list(_MESH_TEXTURE_SIGNATURES)
+MESH_LENS_EXPORTS = list(_MESH_LENS_SIGNATURES)
+MESH_LENS_NEWTON_STEPS, MESH_LENS_SUPERBLOCK = 12, 8   # MGS_MESH_LENS_NEWTON_STEPS, MGS_MESH_LENS_SUPERBLOCK
 MESH_MAX_SIDE, MESH_LARGE_BLOCKS = 16368, 15   # MGS_MESH_MAX_SIDE, MGS_MESH_LARGE_BLOCKS
 # MGS_MESH_TEXTURE_MAX_SIDE, MGS_MESH_MAX_TEXTURES, MGS_MESH_TEXTURE_DESC_WORDS, MGS_MESH_WRAP_*, MGS_MESH_FILTER_*
 MESH_TEXTURE_MAX_SIDE, MESH_MAX_TEXTURES, MESH_TEXTURE_DESC_WORDS = 16384, 4096, 20

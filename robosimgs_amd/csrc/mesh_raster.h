@@ -211,32 +211,41 @@ MGS_MESH_HD bool face_setup(const float* verts_cam_c, int V, const int32_t* face
 }
 
 // ---- per pixel ---------------------------------------------------------------------------------------------------------------
-// e_i and S at the centre of pixel (px, py); true where the pixel is inside (e_i >= 0, inclusive, and S > 0)
-MGS_MESH_HD bool pixel_edges(const FaceRec& r, Cam k, int px, int py, float e[3], float& S) {
-  const float dx = ((float)px + 0.5f) - k.cx, dy = ((float)py + 0.5f) - k.cy;
+// The pixel enters only through (dx, dy), the first two components of its ray in the units of the planes: the pinhole's
+// (px + 0.5 - cx, py + 0.5 - cy) with planes set up under K, or a lens pixel's (x_u, y_u) with planes set up under
+// Cam{1, 1, 0, 0} (mesh_lens_raster.h).  e_i and S there; true where the pixel is inside (e_i >= 0, inclusive, and S > 0).
+MGS_MESH_HD bool pixel_edges_at(const FaceRec& r, float dx, float dy, float e[3], float& S) {
   for (int i = 0; i < 3; ++i) e[i] = fmaf(r.A[i], dx, fmaf(r.B[i], dy, r.C[i]));
   S = (e[0] + e[1]) + e[2];
   return e[0] >= 0.0f && e[1] >= 0.0f && e[2] >= 0.0f && S > 0.0f;
 }
-// the key of the face at the pixel; false where it does not count there
-MGS_MESH_HD bool pixel_key(const FaceRec& r, Cam k, int px, int py, float near_plane, float far_plane, uint64_t& key) {
+// the key of the face at (dx, dy); false where it does not count there
+MGS_MESH_HD bool pixel_key_at(const FaceRec& r, float dx, float dy, float near_plane, float far_plane, uint64_t& key) {
   float e[3], S;
-  if (!pixel_edges(r, k, px, py, e, S)) return false;
+  if (!pixel_edges_at(r, dx, dy, e, S)) return false;
   const float z = r.absdet / S;
   if (!(z >= near_plane && z <= far_plane)) return false;
   key = pack_key(z, r.face);
   return true;
 }
+// the pinhole's (dx, dy) at the centre of pixel (px, py)
+MGS_MESH_HD bool pixel_edges(const FaceRec& r, Cam k, int px, int py, float e[3], float& S) {
+  return pixel_edges_at(r, ((float)px + 0.5f) - k.cx, ((float)py + 0.5f) - k.cy, e, S);
+}
+MGS_MESH_HD bool pixel_key(const FaceRec& r, Cam k, int px, int py, float near_plane, float far_plane, uint64_t& key) {
+  return pixel_key_at(r, ((float)px + 0.5f) - k.cx, ((float)py + 0.5f) - k.cy, near_plane, far_plane, key);
+}
 
 // ---- resolve -----------------------------------------------------------------------------------------------------------------
 struct Shaded { float rgb[3], depth, normal[3]; int32_t face; };
 
-// From the winning key of pixel (px, py): depth, face id, colour from the barycentrics recomputed in the same order
-// (vertex colours, face colours or 0.7 grey, optionally times the headlight shade) and the unit normal turned toward the
-// camera.  Everything 0 and the id -1 where the pixel is uncovered (or the key names no valid face: never after the raster).
-MGS_MESH_HD Shaded resolve_pixel(uint64_t key, const float* verts_cam_c, int V, const int32_t* faces, int F,
-                                 const float* vertex_colors, const float* face_colors, Cam k, int px, int py, bool headlight,
-                                 float ambient) {
+// From the winning key of the pixel at (dx, dy) (see pixel_edges_at; k the camera the planes are set up under): depth, face
+// id, colour from the barycentrics recomputed in the same order (vertex colours, face colours or 0.7 grey, optionally times
+// the headlight shade) and the unit normal turned toward the camera.  Everything 0 and the id -1 where the pixel is
+// uncovered (or the key names no valid face: never after the raster).
+MGS_MESH_HD Shaded resolve_pixel_at(uint64_t key, const float* verts_cam_c, int V, const int32_t* faces, int F,
+                                    const float* vertex_colors, const float* face_colors, Cam k, float dx, float dy,
+                                    bool headlight, float ambient) {
   Shaded o;
   o.rgb[0] = o.rgb[1] = o.rgb[2] = 0.0f; o.depth = 0.0f; o.normal[0] = o.normal[1] = o.normal[2] = 0.0f; o.face = -1;
   if (key == kEmptyKey) return o;
@@ -252,7 +261,7 @@ MGS_MESH_HD Shaded resolve_pixel(uint64_t key, const float* verts_cam_c, int V, 
   r.face = f;
   if (!face_planes(a, b, c, k, false, r)) return o;
   float e[3], S;
-  pixel_edges(r, k, px, py, e, S);
+  pixel_edges_at(r, dx, dy, e, S);
   o.face = f;
   o.depth = key_depth(key);
   const float l0 = e[0] / S, l1 = e[1] / S, l2 = e[2] / S;
@@ -273,7 +282,7 @@ MGS_MESH_HD Shaded resolve_pixel(uint64_t key, const float* verts_cam_c, int V, 
   const float n2 = fmaf(n[2], n[2], fmaf(n[1], n[1], n[0] * n[0]));
   const float ninv = n2 > 0.0f ? 1.0f / sqrtf(n2) : 0.0f;
   const float nh[3] = {n[0] * ninv, n[1] * ninv, n[2] * ninv};
-  const float rx = (((float)px + 0.5f) - k.cx) / k.fx, ry = (((float)py + 0.5f) - k.cy) / k.fy;
+  const float rx = dx / k.fx, ry = dy / k.fy;
   const float rinv = 1.0f / sqrtf(fmaf(ry, ry, fmaf(rx, rx, 1.0f)));
   const float cosv = fmaf(nh[2], rinv, fmaf(nh[1], ry * rinv, nh[0] * (rx * rinv)));
   const float flip = cosv > 0.0f ? -1.0f : 1.0f;
@@ -283,6 +292,13 @@ MGS_MESH_HD Shaded resolve_pixel(uint64_t key, const float* verts_cam_c, int V, 
     for (int j = 0; j < 3; ++j) o.rgb[j] *= shade;
   }
   return o;
+}
+// the pinhole's (dx, dy) at the centre of pixel (px, py)
+MGS_MESH_HD Shaded resolve_pixel(uint64_t key, const float* verts_cam_c, int V, const int32_t* faces, int F,
+                                 const float* vertex_colors, const float* face_colors, Cam k, int px, int py, bool headlight,
+                                 float ambient) {
+  return resolve_pixel_at(key, verts_cam_c, V, faces, F, vertex_colors, face_colors, k, ((float)px + 0.5f) - k.cx,
+                          ((float)py + 0.5f) - k.cy, headlight, ambient);
 }
 
 }  // namespace mesh

@@ -21,6 +21,11 @@ csrc/mesh_texture.hip; semantics: tests/texture_ref.py): MeshRenderer packs the 
 once (build_texture_set), render() keeps its signature, texture_filter= chooses "trilinear" or "bilinear".  A mesh without
 textures goes down the untextured entry points, which are unchanged.
 
+Under a lens (camera_model="fisheye", distortion=, pinhole_distortion=: rasterization's keywords) the same triangles are
+rasterised at each pixel's own ray, solved from the lens per pixel (include/mgs_mesh_lens.h, csrc/mesh_lens.hip; semantics:
+tests/mesh_lens_ref.py): nothing is tessellated or resampled, and the mesh layer registers with a splat frame rendered
+under that lens.  mesh_lens_rays builds the ray map as a stage of its own; mesh_raster and mesh_resolve take it as rays=.
+
 Argument errors are ValueErrors raised before any launch.  There is no fallback: a missing library is an error.
 """
 from __future__ import annotations
@@ -35,6 +40,7 @@ from . import _lib
 from ._lib import (MESH_FILTER, MESH_MAX_SIDE, MESH_MAX_TEXTURES, MESH_TEXTURE_DESC_WORDS, MESH_TEXTURE_MAX_SIDE, MESH_WRAP,
                    aligned_workspace, check, ptr, stream_handle)
 from .mesh import Mesh, Texture
+from .ops import CAMERA_FISHEYE_KB, CAMERA_MODELS, CAMERA_PINHOLE_BC, LENS_ROW_FLOATS, camera_model_id, lens_rows
 
 
 def _check_sizes(n_cams: int, V: int, F: int, width: int, height: int) -> None:
@@ -115,6 +121,97 @@ def mesh_workspace_bytes(n_cams: int, n_vertices: int, n_faces: int, width: int,
 
 def _visibility(workspace: Tensor, pad: int, n_cams: int, width: int, height: int) -> Tensor:
     return workspace[pad:pad + 8 * n_cams * height * width].view(torch.int64).view(n_cams, height, width)
+
+
+# ---- the lens (include/mgs_mesh_lens.h) ---------------------------------------------------------------------------------------
+def _lens_model(camera_model: str, distortion, pinhole_distortion) -> Optional[int]:
+    """MGS_CAMERA_FISHEYE_KB or MGS_CAMERA_PINHOLE_BC of rasterization's three camera keywords (their checks are
+    ops.camera_model_id's), None for the plain pinhole -- all-zero pinhole_distortion included, as there.  The ideal fisheye is
+    MGS_CAMERA_FISHEYE_KB with every k zero.  The orthographic camera has parallel rays and no ray map: NotImplementedError."""
+    model = camera_model_id(camera_model, distortion, pinhole_distortion)
+    if model == CAMERA_MODELS["ortho"]:
+        raise NotImplementedError("camera_model='ortho': the mesh rasteriser has no orthographic camera (its rays are parallel: "
+                                  "there is no ray map of the lens path's form)")
+    if model == CAMERA_MODELS["pinhole"]:
+        return None
+    return CAMERA_PINHOLE_BC if model == CAMERA_PINHOLE_BC else CAMERA_FISHEYE_KB
+
+
+_IDEAL_FISHEYE_TAILS: dict = {}                # device -> [1,7] zeros | theta_max^2 | 0 0: uploaded once per device
+
+
+def _lens_rows(Ks: Tensor, model: int, distortion, pinhole_distortion) -> Tensor:
+    """The [C,16] camera rows of `model` for Ks [C,3,3] on the device (ops.lens_rows; the ideal fisheye's are built here)."""
+    if model == CAMERA_PINHOLE_BC:
+        return lens_rows(Ks, None, pinhole_distortion)
+    if camera_model_id("fisheye", distortion) == CAMERA_FISHEYE_KB:
+        return lens_rows(Ks, distortion)
+    tail = _IDEAL_FISHEYE_TAILS.get(Ks.device)
+    if tail is None:
+        from .camera import lens_theta_max
+        host = torch.zeros((1, LENS_ROW_FLOATS - 9), dtype=torch.float32)
+        host[0, 4] = lens_theta_max([0.0, 0.0, 0.0, 0.0]) ** 2
+        tail = _IDEAL_FISHEYE_TAILS[Ks.device] = host.to(Ks.device)
+    C = Ks.shape[0]
+    return torch.cat([Ks.reshape(C, 9), tail.expand(C, -1)], dim=1).contiguous()
+
+
+def mesh_lens_workspace_bytes(n_cams: int, width: int, height: int) -> int:
+    """mgs_mesh_lens_workspace_bytes: rays float [C,H,W,2], a rectangle per 8 x 8 block and one per 8 x 8 blocks."""
+    _check_sizes(n_cams, 1, 1, width, height)
+    n = ctypes.c_size_t(0)
+    check(_lib.lib().mgs_mesh_lens_workspace_bytes(int(n_cams), int(width), int(height), ctypes.byref(n)),
+          "mgs_mesh_lens_workspace_bytes")
+    return int(n.value)
+
+
+class MeshLensMap:
+    """The ray map of C cameras under a lens, as mgs_mesh_lens_rays left it in its workspace: model (MGS_CAMERA_*), rows
+    float32 [C,16] (the camera rows it was built from), rays float32 [C,H,W,2] (a view of the workspace: (x_u, y_u) per
+    pixel, NaN where the pixel has no ray).  mesh_raster(rays=) and mesh_resolve(rays=) take it."""
+
+    def __init__(self, model: int, rows: Tensor, workspace: Tensor, pad: int, n_cams: int, width: int, height: int):
+        self.model, self.rows, self.workspace, self.pad = model, rows, workspace, pad
+        self.n_cams, self.width, self.height = n_cams, width, height
+
+    @property
+    def rays(self) -> Tensor:
+        C, H, W = self.n_cams, self.height, self.width
+        return self.workspace[self.pad:self.pad + 8 * C * H * W].view(torch.float32).view(C, H, W, 2)
+
+    def _args(self, C: int, width: int, height: int, device):
+        if not (self.n_cams == C and self.width == width and self.height == height):
+            raise ValueError(f"rays= was built for {self.n_cams} cameras at {self.width} x {self.height}, the call is for {C} at "
+                             f"{width} x {height}")
+        if self.workspace.device != device:
+            raise ValueError(f"rays= is on {self.workspace.device}, the mesh is on {device}")
+        return self.model, ptr(self.rows), self.workspace.data_ptr() + self.pad, self.workspace.numel() - self.pad
+
+
+def _lens_map(rays, C: int, width: int, height: int, device):
+    if not isinstance(rays, MeshLensMap):
+        raise ValueError(f"rays must be a MeshLensMap (mesh_lens_rays), got {type(rays).__name__}")
+    return rays._args(C, width, height, device)
+
+
+@torch.no_grad()
+def mesh_lens_rays(Ks: Tensor, width: int, height: int, camera_model: str = "pinhole", distortion=None, pinhole_distortion=None,
+                   workspace: Optional[Tensor] = None) -> MeshLensMap:
+    """mgs_mesh_lens_rays: the per-pixel rays of C cameras under a lens and their block tables, as a MeshLensMap.  Ks float32
+    [C,3,3] on the GPU; camera_model, distortion (fisheye k1..k4) and pinhole_distortion (k1 k2 p1 p2 k3) as rasterization
+    takes them.  workspace: a uint8 tensor of mesh_lens_workspace_bytes(...) + 256 bytes, allocated where None.  A camera
+    without a lens (the plain pinhole) has no ray map: ValueError."""
+    model = _lens_model(camera_model, distortion, pinhole_distortion)
+    if model is None:
+        raise ValueError("mesh_lens_rays needs a lens: the plain pinhole camera goes down mesh_raster / mesh_resolve with Ks")
+    Ks = _dev(Ks, (-1, 3, 3), torch.float32, "Ks")
+    C, width, height = int(Ks.shape[0]), int(width), int(height)
+    _check_sizes(C, 1, 1, width, height)
+    rows = _lens_rows(Ks, model, distortion, pinhole_distortion)
+    workspace, pad = _workspace(workspace, mesh_lens_workspace_bytes(C, width, height), Ks.device)
+    check(_lib.lib().mgs_mesh_lens_rays(C, model, ptr(rows), width, height, workspace.data_ptr() + pad, workspace.numel() - pad,
+                                        stream_handle()), "mgs_mesh_lens_rays")
+    return MeshLensMap(model, rows, workspace, pad, C, width, height)
 
 
 # ---- textures (include/mgs_mesh_texture.h) -----------------------------------------------------------------------------------
@@ -218,10 +315,12 @@ def mesh_vertices(vertices: Tensor, viewmats: Tensor, link_ids: Optional[Tensor]
 
 @torch.no_grad()
 def mesh_raster(verts_cam: Tensor, faces: Tensor, Ks: Tensor, width: int, height: int, near_plane: float = 0.01,
-                far_plane: float = 1e10, cull_backfaces: bool = False, workspace: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+                far_plane: float = 1e10, cull_backfaces: bool = False, workspace: Optional[Tensor] = None,
+                rays: Optional[MeshLensMap] = None) -> Tuple[Tensor, Tensor]:
     """mgs_mesh_raster (clear + faces): (visibility, workspace).  visibility is an int64 view [C,H,W] of the workspace's first
     field: the bits of (float_bits(z) << 32) | face per pixel, -1 (all ones) where uncovered.  workspace: a uint8 tensor of
-    mesh_workspace_bytes(...) + 256 bytes, allocated where None; hand it to mesh_resolve."""
+    mesh_workspace_bytes(...) + 256 bytes, allocated where None; hand it to mesh_resolve.  rays (mesh_lens_rays): rasterise
+    under that lens (mgs_mesh_raster_lens); the map carries the camera, Ks is then only checked."""
     verts_cam = _dev(verts_cam, (-1, -1, 3), torch.float32, "verts_cam")
     dev, C, V = verts_cam.device, int(verts_cam.shape[0]), int(verts_cam.shape[1])
     faces = _dev(faces, (-1, 3), torch.int32, "faces", dev)
@@ -229,11 +328,19 @@ def mesh_raster(verts_cam: Tensor, faces: Tensor, Ks: Tensor, width: int, height
     _check_sizes(C, V, F, width, height)
     _check_planes(near_plane, far_plane)
     Ks = _dev(Ks, (C, 3, 3), torch.float32, "Ks", dev)
+    lens = None if rays is None else _lens_map(rays, C, width, height, dev)
     need = mesh_workspace_bytes(C, V, F, width, height)
     workspace, pad = _workspace(workspace, need, dev)
-    check(_lib.lib().mgs_mesh_raster(C, V, ptr(verts_cam), F, ptr(faces), ptr(Ks), width, height, float(near_plane),
-                                     float(far_plane), int(bool(cull_backfaces)), workspace.data_ptr() + pad,
-                                     workspace.numel() - pad, stream_handle()), "mgs_mesh_raster")
+    if rays is None:
+        check(_lib.lib().mgs_mesh_raster(C, V, ptr(verts_cam), F, ptr(faces), ptr(Ks), width, height, float(near_plane),
+                                         float(far_plane), int(bool(cull_backfaces)), workspace.data_ptr() + pad,
+                                         workspace.numel() - pad, stream_handle()), "mgs_mesh_raster")
+    else:
+        model, rows, lens_ws, lens_bytes = lens
+        check(_lib.lib().mgs_mesh_raster_lens(C, V, ptr(verts_cam), F, ptr(faces), model, rows, width, height, float(near_plane),
+                                              float(far_plane), int(bool(cull_backfaces)), workspace.data_ptr() + pad,
+                                              workspace.numel() - pad, lens_ws, lens_bytes, stream_handle()),
+              "mgs_mesh_raster_lens")
     return _visibility(workspace, pad, C, width, height), workspace
 
 
@@ -256,13 +363,17 @@ def mesh_resolve(verts_cam: Tensor, faces: Tensor, Ks: Tensor, width: int, heigh
                  vertex_colors: Optional[Tensor] = None, face_colors: Optional[Tensor] = None, headlight: bool = False,
                  ambient: float = 0.3, return_normals: bool = False, out: Optional[Dict] = None, *,
                  textures: Optional[TextureSet] = None, face_uvs: Optional[Tensor] = None,
-                 face_textures: Optional[Tensor] = None, texture_filter: str = "trilinear") -> Dict:
+                 face_textures: Optional[Tensor] = None, texture_filter: str = "trilinear",
+                 rays: Optional[MeshLensMap] = None) -> Dict:
     """mgs_mesh_resolve on the workspace mesh_raster left: dict(rgb float32 [C,H,W,3], depth float32 [C,H,W], face_ids int32
     [C,H,W] and, with return_normals, normals float32 [C,H,W,3]).  Uncovered pixels are (0, 0, 0), 0 and -1.
 
     textures (a TextureSet) with face_uvs float32 [F,3,2] and face_textures int32 [F] goes through mgs_mesh_resolve_textured:
     rgb = texel x tint x shade where the face is textured (texture_filter "trilinear" or "bilinear"), the same bits as
-    without textures everywhere else.  Without textures this is the untextured entry point, unchanged."""
+    without textures everywhere else.  Without textures this is the untextured entry point, unchanged.
+
+    rays (mesh_lens_rays, the map mesh_raster was given): mgs_mesh_resolve_lens; a pixel without a ray is uncovered.  Textures
+    under a lens are not built (their level of detail needs the ray map's derivatives): NotImplementedError."""
     verts_cam = _dev(verts_cam, (-1, -1, 3), torch.float32, "verts_cam")
     dev, C, V = verts_cam.device, int(verts_cam.shape[0]), int(verts_cam.shape[1])
     faces = _dev(faces, (-1, 3), torch.int32, "faces", dev)
@@ -277,7 +388,14 @@ def mesh_resolve(verts_cam: Tensor, faces: Tensor, Ks: Tensor, width: int, heigh
     args = (C, V, ptr(verts_cam), F, ptr(faces), ptr(vertex_colors), ptr(face_colors), ptr(Ks), width, height,
             int(bool(headlight)), float(ambient), workspace.data_ptr() + pad, workspace.numel() - pad, ptr(res["rgb"]),
             ptr(res["depth"]), ptr(res["face_ids"]), ptr(res.get("normals")))
-    if textures is None:
+    if rays is not None:
+        if textures is not None:
+            raise NotImplementedError("a textured mesh under a lens is not built: the texture's level of detail needs the ray "
+                                      "map's derivatives")
+        model, rows, lens_ws, lens_bytes = _lens_map(rays, C, width, height, dev)
+        check(_lib.lib().mgs_mesh_resolve_lens(*args[:7], model, rows, *args[8:14], lens_ws, lens_bytes, *args[14:],
+                                               stream_handle()), "mgs_mesh_resolve_lens")
+    elif textures is None:
         if face_uvs is not None or face_textures is not None:
             raise ValueError("face_uvs and face_textures need textures=")
         check(_lib.lib().mgs_mesh_resolve(*args, stream_handle()), "mgs_mesh_resolve")
@@ -297,15 +415,27 @@ class MeshRenderer:
 
     options: near_plane=0.01, far_plane=1e10, cull_backfaces=False, headlight=False, ambient=0.3, return_normals=False;
     out: dict of preallocated outputs (rgb, depth, face_ids, normals), workspace: a uint8 tensor of
-    mesh_workspace_bytes(...) + 256 bytes.  The camera is the ideal pinhole: there is no lens here (rasterization's
-    pinhole_distortion= has no counterpart), so under a lens a mesh layer and a splat frame do not register."""
+    mesh_workspace_bytes(...) + 256 bytes.
+
+    The camera: camera_model="pinhole" | "fisheye", distortion= (fisheye k1..k4) and pinhole_distortion= (OpenCV k1 k2 p1 p2
+    k3) with the meaning and the checks of rasterization's keywords, so that a mesh layer registers with a splat frame
+    rendered under the same lens.  Without a lens (all-zero pinhole coefficients included) this is the plain pinhole path,
+    unchanged.  Under a lens render() goes through mgs_rasterize_mesh_lens (include/mgs_mesh_lens.h; eight launches): every
+    pixel's ray is solved from the lens in every call (Ks may be overwritten in place between frames), meta["rays"] is that
+    map, float32 [C,H,W,2], NaN where the lens has no ray, and such a pixel is uncovered.  render() then builds the camera
+    rows from Ks (one small allocation).  A textured mesh under a lens and camera_model="ortho" raise NotImplementedError."""
 
     def __init__(self, mesh: Mesh, width: int, height: int, n_cams: int = 1, *, near_plane: float = 0.01,
                  far_plane: float = 1e10, cull_backfaces: bool = False, headlight: bool = False, ambient: float = 0.3,
                  return_normals: bool = False, out: Optional[Dict] = None, workspace: Optional[Tensor] = None,
-                 texture_filter: str = "trilinear"):
+                 texture_filter: str = "trilinear", camera_model: str = "pinhole", distortion=None, pinhole_distortion=None):
         if not isinstance(mesh, Mesh):
             raise ValueError(f"mesh must be a Mesh, got {type(mesh).__name__}")
+        self.lens_model = _lens_model(camera_model, distortion, pinhole_distortion)
+        self._distortion, self._pinhole_distortion = distortion, pinhole_distortion
+        if self.lens_model is not None and mesh.has_textures:
+            raise NotImplementedError("a textured mesh under a lens is not built: the texture's level of detail needs the ray "
+                                      "map's derivatives")
         self.width, self.height, self.n_cams = int(width), int(height), int(n_cams)
         _check_sizes(self.n_cams, mesh.n_vertices, mesh.n_faces, self.width, self.height)
         _check_planes(near_plane, far_plane)
@@ -325,6 +455,9 @@ class MeshRenderer:
         self.workspace, self._pad = _workspace(workspace, self.workspace_bytes, self.device)
         self.verts_cam = torch.empty((C, V, 3), dtype=torch.float32, device=self.device)
         self.out = _outputs(out, C, self.height, self.width, self.return_normals, self.device)
+        self.lens_workspace = None
+        if self.lens_model is not None:
+            self.lens_workspace, self._lens_pad = _workspace(None, mesh_lens_workspace_bytes(C, self.width, self.height), self.device)
         # a textured mesh: the texture set is packed and its mips built here, once; render() then takes the textured entry point
         self._filter = _filter(texture_filter)
         self.textures = build_texture_set(mesh.textures, self.device) if mesh.has_textures else None
@@ -336,7 +469,8 @@ class MeshRenderer:
         """viewmats float32 [C,4,4] (world to camera), Ks float32 [C,3,3], rotations float32 [L,3,3], translations [L,3],
         scales [L] or None: contiguous tensors on the mesh's device.  Link l of the mesh takes transform l; a link id >= L
         (or < 0) is static.  Returns (rgb [C,H,W,3], depth [C,H,W], meta) with meta = dict(face_ids int32 [C,H,W], verts_cam
-        [C,V,3][, normals [C,H,W,3]]): the renderer's own tensors, overwritten by the next call."""
+        [C,V,3][, normals [C,H,W,3]]): the renderer's own tensors, overwritten by the next call.  Under a lens also rays
+        float32 [C,H,W,2] (NaN where the lens has no ray) and lens_map, the MeshLensMap that mesh_raster(rays=) takes."""
         C, m = self.n_cams, self.mesh
         viewmats = _dev(viewmats, (C, 4, 4), torch.float32, "viewmats", self.device)
         Ks = _dev(Ks, (C, 3, 3), torch.float32, "Ks", self.device)
@@ -347,12 +481,20 @@ class MeshRenderer:
                 self.near_plane, self.far_plane, int(self.cull_backfaces), int(self.headlight), self.ambient,
                 self.workspace.data_ptr() + self._pad, self.workspace.numel() - self._pad, ptr(self.verts_cam), ptr(o["rgb"]),
                 ptr(o["depth"]), ptr(o["face_ids"]), ptr(o.get("normals")))
-        if self._tex is None:
+        meta = {"face_ids": o["face_ids"], "verts_cam": self.verts_cam}
+        if self.lens_model is not None:
+            rows = _lens_rows(Ks, self.lens_model, self._distortion, self._pinhole_distortion)
+            lens = MeshLensMap(self.lens_model, rows, self.lens_workspace, self._lens_pad, C, self.width, self.height)
+            check(_lib.lib().mgs_rasterize_mesh_lens(*args[:9], self.lens_model, ptr(rows), *args[10:23],
+                                                     self.lens_workspace.data_ptr() + self._lens_pad,
+                                                     self.lens_workspace.numel() - self._lens_pad, *args[23:], stream_handle()),
+                  "mgs_rasterize_mesh_lens")
+            meta["rays"], meta["lens_map"] = lens.rays, lens
+        elif self._tex is None:
             check(_lib.lib().mgs_rasterize_mesh(*args, stream_handle()), "mgs_rasterize_mesh")
         else:
             check(_lib.lib().mgs_rasterize_mesh_textured(*args, *self._tex, self._filter, stream_handle()),
                   "mgs_rasterize_mesh_textured")
-        meta = {"face_ids": o["face_ids"], "verts_cam": self.verts_cam}
         if self.return_normals:
             meta["normals"] = o["normals"]
         return o["rgb"], o["depth"], meta
@@ -369,12 +511,16 @@ def _to_device(x, dtype, device):
 def rasterize_mesh(mesh: Mesh, viewmats, Ks, width: int, height: int, *, rotations=None, translations=None, scales=None,
                    near_plane: float = 0.01, far_plane: float = 1e10, cull_backfaces: bool = False, headlight: bool = False,
                    ambient: float = 0.3, return_normals: bool = False, out: Optional[Dict] = None,
-                   workspace: Optional[Tensor] = None, texture_filter: str = "trilinear") -> Tuple[Tensor, Tensor, Dict]:
+                   workspace: Optional[Tensor] = None, texture_filter: str = "trilinear", camera_model: str = "pinhole",
+                   distortion=None, pinhole_distortion=None) -> Tuple[Tensor, Tensor, Dict]:
     """Render `mesh` (on the GPU) from C cameras: (rgb float32 [C,H,W,3], depth float32 [C,H,W], meta) with meta =
     dict(face_ids int32 [C,H,W] (-1 where uncovered), verts_cam float32 [C,V,3][, normals float32 [C,H,W,3]]).
 
-    viewmats [C,4,4] (or [4,4]) and Ks [C,3,3] (or [3,3]): tensors or arrays of any float type; an OpenCV pinhole camera --
-    the ideal one: the mesh operators take no lens (rasterization's pinhole_distortion= has no counterpart here).
+    viewmats [C,4,4] (or [4,4]) and Ks [C,3,3] (or [3,3]): tensors or arrays of any float type; an OpenCV pinhole camera,
+    or with camera_model= / distortion= / pinhole_distortion= (rasterization's keywords, with its checks) the same lens a
+    splat frame was rendered under: every pixel's ray is then solved from the lens, meta["rays"] float32 [C,H,W,2] is that
+    map (NaN where the lens has no ray: the pixel is uncovered), and the mesh registers with the frame.  All-zero
+    coefficients select the plain path, as there.  A textured mesh under a lens and camera_model="ortho": NotImplementedError.
     rotations [L,3,3], translations [L,3], scales [L]: the convention of transform_gaussians (x' = s R x + t for the
     vertices of link l), so Hinge.pose(angle) feeds them directly (R [3,3] and t [3] are one link).  Link ids >= L are
     static: len(rotations) < mesh.n_links() is not an error, because finding it would take a read-back.
@@ -410,10 +556,11 @@ def rasterize_mesh(mesh: Mesh, viewmats, Ks, width: int, height: int, *, rotatio
             raise ValueError(f"scales must be [{rotations.shape[0]}], got {list(torch.as_tensor(scales).shape)}")
     r = MeshRenderer(mesh, width, height, int(vm.shape[0]), near_plane=near_plane, far_plane=far_plane,
                      cull_backfaces=cull_backfaces, headlight=headlight, ambient=ambient, return_normals=return_normals,
-                     out=out, workspace=workspace, texture_filter=texture_filter)
+                     out=out, workspace=workspace, texture_filter=texture_filter, camera_model=camera_model,
+                     distortion=distortion, pinhole_distortion=pinhole_distortion)
     f32 = lambda x: _to_device(x, torch.float32, r.device)
     return r.render(f32(vm), f32(K), rotations=f32(rotations), translations=f32(translations), scales=f32(scales))
 
 
 __all__ = ["MeshRenderer", "rasterize_mesh", "mesh_vertices", "mesh_raster", "mesh_resolve", "mesh_workspace_bytes",
-           "TextureSet", "build_texture_set"]
+           "TextureSet", "build_texture_set", "mesh_lens_rays", "mesh_lens_workspace_bytes", "MeshLensMap"]

@@ -328,8 +328,9 @@ def rasterization(means: Tensor, quats: Tensor, scales: Tensor, opacities: Tenso
                   backdrop=None) -> Tuple[Tensor, Tensor, Dict]:
     """Render N Gaussians from C cameras.
 
-    foreground = (fg_rgb [C,H,W,3], fg_depth [C,H,W]), an opaque layer as rasterize_mesh returns it (an ideal-pinhole
-    layer: the mesh operators take no lens, so combine it with pinhole_distortion= only if it was rendered to match; z-depth, 0 where no
+    foreground = (fg_rgb [C,H,W,3], fg_depth [C,H,W]), an opaque layer as rasterize_mesh returns it (rendered to match:
+    under distortion= / pinhole_distortion= give rasterize_mesh the same camera_model and coefficients, and the two layers
+    register pixel for pixel; z-depth, 0 where no
     face is), with render_mode="RGB+ED": every frame also gets its exact composite with that layer (include/mgs_hybrid.h,
     DESIGN.md 4.17) -- meta["hybrid_rgb"] [C,H,W,3] and meta["hybrid_depth"] [C,H,W], the pixel's own front-to-back blend
     stopped at the foreground's depth with the foreground entering at the transmittance reached there, and
