@@ -59,7 +59,7 @@ def __getattr__(name):  # lazy: keeps `import robosimgs_amd` torch-free for host
                 "TextureSet", "build_texture_set", "mesh_lens_rays", "mesh_lens_workspace_bytes", "MeshLensMap"):
         from . import mesh_render
         return getattr(mesh_render, name)
-    if name in ("l1_loss", "l1_ssim_loss", "ssim", "unit_gradient"):
+    if name in ("l1_loss", "l1_ssim_loss", "ssim", "unit_gradient", "rgbd_loss"):
         from . import losses
         return getattr(losses, name)
     if name in ("FrameRenderer", "locality_order"):

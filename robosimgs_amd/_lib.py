@@ -29,6 +29,12 @@ class ImageLoss(ctypes.Structure):
                 ("ssim_weight", c_float), ("padding", c_int)]
 
 
+class RgbdLoss(ctypes.Structure):
+    """mgs_rgbd_loss (include/mgs_loss_rgbd.h): the frame layout and weights of the masked RGB-D loss."""
+    _fields_ = [("images", c_int), ("height", c_int), ("width", c_int), ("render_channels", c_int),
+                ("ssim_weight", c_float), ("padding", c_int), ("depth_weight", c_float)]
+
+
 class AdamGroup(ctypes.Structure):
     """mgs_adam_group (include/mgs_optim.h): one parameter group of mgs_adam_step, n rows of row_floats floats."""
     _fields_ = [("param", c_void_p), ("grad", c_void_p), ("exp_avg", c_void_p), ("exp_avg_sq", c_void_p),
@@ -172,11 +178,19 @@ _MESH_LENS_SIGNATURES = {
     "mgs_rasterize_mesh_lens": ([i, i, p, p, i, p, p, p, p, i, p, i, p, p, p, i, i, f, f, i, i, f, p, c_size_t, p, c_size_t,
                                  p, p, p, p, p, p], c_int),
 }
+# every function include/mgs_loss_rgbd.h declares (the same libraries again): (desc, render, target_rgb, target_depth, mask,
+# ...) with target_depth, mask and terms nullable; each ends in (workspace, workspace_bytes, stream)
+_RGBD_LOSS_SIGNATURES = {
+    "mgs_rgbd_loss_fwd": ([POINTER(RgbdLoss), p, p, p, p, p, p, p, POINTER(c_size_t), p], c_int),
+    "mgs_rgbd_loss_fwd_grad": ([POINTER(RgbdLoss), p, p, p, p, p, p, p, p, POINTER(c_size_t), p], c_int),
+    "mgs_rgbd_loss_bwd": ([POINTER(RgbdLoss), p, p, p, p, p, p, p, POINTER(c_size_t), p], c_int),
+}
 del p, i, f, u32, img
 # what _load binds: a new header adds its table here
 _SIGNATURE_TABLES = (_SIGNATURES, _OPTIM_SIGNATURES, _REFINE_SIGNATURES, _LABEL_SIGNATURES, _LIFT_SIGNATURES,
                      _HINGE_SIGNATURES, _POSE_SIGNATURES, _DEFORM_SIGNATURES, _DEFORM_SH_SIGNATURES, _MESH_SIGNATURES,
-                     _MESH_TEXTURE_SIGNATURES, _HYBRID_SIGNATURES, _DEFORM_BWD_SIGNATURES, _MESH_LENS_SIGNATURES)
+                     _MESH_TEXTURE_SIGNATURES, _HYBRID_SIGNATURES, _DEFORM_BWD_SIGNATURES, _MESH_LENS_SIGNATURES,
+                     _RGBD_LOSS_SIGNATURES)
 EXPORTS = list(_SIGNATURES)
 OPTIM_EXPORTS = list(_OPTIM_SIGNATURES)
 REFINE_EXPORTS = list(_REFINE_SIGNATURES)
@@ -191,6 +205,7 @@ MESH_EXPORTS = list(_MESH_SIGNATURES)
 HYBRID_EXPORTS = list(_HYBRID_SIGNATURES)
 MESH_TEXTURE_EXPORTS = list(_MESH_TEXTURE_SIGNATURES)
 MESH_LENS_EXPORTS = list(_MESH_LENS_SIGNATURES)
+RGBD_LOSS_EXPORTS = list(_RGBD_LOSS_SIGNATURES)
 MESH_LENS_NEWTON_STEPS, MESH_LENS_SUPERBLOCK = 12, 8   # MGS_MESH_LENS_NEWTON_STEPS, MGS_MESH_LENS_SUPERBLOCK
 MESH_MAX_SIDE, MESH_LARGE_BLOCKS = 16368, 15   # MGS_MESH_MAX_SIDE, MGS_MESH_LARGE_BLOCKS
 # MGS_MESH_TEXTURE_MAX_SIDE, MGS_MESH_MAX_TEXTURES, MGS_MESH_TEXTURE_DESC_WORDS, MGS_MESH_WRAP_*, MGS_MESH_FILTER_*

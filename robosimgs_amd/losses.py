@@ -13,7 +13,11 @@ SSIM is pytorch_msssim's `SSIM(data_range=1.0, size_average=True)`: an 11-tap Ga
 separably per channel, C1 = 0.01^2, C2 = 0.03^2, the mean over positions, channels and leading dimensions.
 padding="valid" (default; pytorch_msssim and gsplat's simple_trainer) takes S where the whole window lies inside the image,
 (H - 10) x (W - 10) positions, and raises ValueError below 11 pixels (pytorch_msssim instead skips filtering along such an
-axis, with a warning); padding="same" (the original 3DGS code's `ssim()`) zero-pads by 5 pixels and takes S at every pixel."""
+axis, with a warning); padding="same" (the original 3DGS code's `ssim()`) zero-pads by 5 pixels and takes S at every pixel.
+
+`rgbd_loss(render, target_rgb, target_depth, mask)` is that loss on the RGB+ED frame as the renderer leaves it: the mask
+applied to both images before either term, an L1 depth term on the fourth channel, the four-channel frame read in place
+and its complete cotangent written in the same launches (loss.hip: ssim_kernel<., true>)."""
 from __future__ import annotations
 
 import ctypes
@@ -160,3 +164,83 @@ def ssim(render: torch.Tensor, target: torch.Tensor, padding: str = "valid") -> 
     SSIM(data_range=1.0, size_average=True) for padding="valid", the original 3DGS `ssim()` for "same" (module docstring).
     Computed as 1 - l1_ssim_loss(render, target, ssim_lambda=1); gradient flows to `render` only."""
     return 1.0 - l1_ssim_loss(render, target, 1.0, padding)
+
+
+class _RGBD(torch.autograd.Function):
+    """_L1SSIM's pattern under an mgs_rgbd_loss descriptor: the forward leaves the complete [..., H, W, Cr] gradient for a
+    cotangent of 1 (mgs_rgbd_loss_fwd_grad), any other cotangent scales it once, a second backward recomputes it
+    (mgs_rgbd_loss_bwd).  Returns (loss, terms); terms carries no gradient."""
+
+    @staticmethod
+    def forward(ctx, render, target_rgb, target_depth, mask, desc):
+        L = _lib.lib()
+        loss = torch.empty((), dtype=torch.float32, device=render.device)
+        terms = torch.empty(4, dtype=torch.float32, device=render.device)
+        ctx.mark_non_differentiable(terms)
+        head = [ctypes.byref(desc), ptr(render), ptr(target_rgb), ptr(target_depth), ptr(mask)]
+        if not ctx.needs_input_grad[0]:
+            sized_call(L.mgs_rgbd_loss_fwd, head + [ptr(loss), ptr(terms)], render.device, cached=False)
+            return loss, terms
+        v_render = torch.empty_like(render)
+        sized_call(L.mgs_rgbd_loss_fwd_grad, head + [ptr(loss), ptr(terms), ptr(v_render)], render.device, cached=False)
+        ctx.save_for_backward(render, target_rgb, target_depth, mask)
+        ctx.v_render, ctx.desc = v_render, desc
+        return loss, terms
+
+    @staticmethod
+    def backward(ctx, v_loss, _v_terms):
+        g = _f32c(v_loss)
+        v_render, ctx.v_render = ctx.v_render, None
+        if v_render is not None:
+            if not _is_unit(g):
+                v_render.mul_(g)
+            return v_render, None, None, None, None
+        # a second backward through a retained graph: autograd owns the first buffer by now
+        render, target_rgb, target_depth, mask = ctx.saved_tensors
+        v_render = torch.empty_like(render)
+        sized_call(_lib.lib().mgs_rgbd_loss_bwd, [ctypes.byref(ctx.desc), ptr(render), ptr(target_rgb), ptr(target_depth),
+                                                  ptr(mask), ptr(g), ptr(v_render)], render.device, cached=False)
+        return v_render, None, None, None, None
+
+
+def rgbd_loss(render: torch.Tensor, target_rgb: torch.Tensor, target_depth: torch.Tensor = None, mask: torch.Tensor = None,
+              ssim_lambda: float = 0.2, depth_lambda: float = 0.0, padding: str = "valid", return_terms: bool = False):
+    """The masked RGB-D training loss on the frame the renderer returns, in one pass over it (include/mgs_loss_rgbd.h):
+
+        (1 - ssim_lambda) * mean|x - y| + ssim_lambda * (1 - ssim(x, y, padding)) + depth_lambda * D,
+
+    x = mask * render[..., :3], y = mask * target_rgb, the mean over every element (splatfacto's masked loss: not divided by
+    the mask's area); D = sum w |render[..., 3] - target_depth| / sum w over all images, w = mask where target_depth is finite
+    and > 0, else 0, and D = 0 where no pixel has weight.  Under mask == 0 nothing of render or of the targets enters: NaN
+    or inf there leave the loss as it is and receive a gradient of exactly 0.
+
+    render [..., H, W, 3] or [..., H, W, 4] (RGB, then expected depth: render_mode="RGB+ED"), read in place -- a contiguous
+    float32 frame is not copied, and the gradient arrives complete in its layout, the depth channel included (zeros when
+    depth_lambda == 0).  target_rgb [..., H, W, 3]; target_depth [..., H, W], needed (with a four-channel render) when
+    depth_lambda > 0; mask [..., H, W], float32 in [0, 1], may be soft, None: all ones.  A bool or uint8 mask is taken as
+    non-zero = 1 and converted on every call: keep masks resident as float32.  Gradient flows to `render` only.
+    return_terms: also a device tensor {mean|x - y|, ssim, D, sum w} for logging (D and sum w are 0 when depth_lambda == 0)."""
+    if render.dim() < 3 or render.shape[-1] not in (3, 4):
+        raise ValueError(f"render must be [..., H, W, 3] or [..., H, W, 4], got shape {tuple(render.shape)}")
+    lead = tuple(render.shape[:-1])
+    if tuple(target_rgb.shape) != lead + (3,):
+        raise ValueError(f"shape mismatch: target_rgb {tuple(target_rgb.shape)} vs render {tuple(render.shape)} (wants {lead + (3,)})")
+    if target_depth is not None and tuple(target_depth.shape) != lead:
+        raise ValueError(f"shape mismatch: target_depth {tuple(target_depth.shape)} vs render {tuple(render.shape)} (wants {lead})")
+    if mask is not None and tuple(mask.shape) != lead:
+        raise ValueError(f"shape mismatch: mask {tuple(mask.shape)} vs render {tuple(render.shape)} (wants {lead})")
+    depth_lambda = float(depth_lambda)
+    if not (math.isfinite(depth_lambda) and depth_lambda >= 0.0):
+        raise ValueError(f"depth_lambda = {depth_lambda} must be finite and >= 0")
+    if depth_lambda > 0.0 and render.shape[-1] != 4:
+        raise ValueError("depth_lambda > 0 needs a four-channel render (render_mode=\"RGB+ED\"): there is no depth channel")
+    if depth_lambda > 0.0 and target_depth is None:
+        raise ValueError("depth_lambda > 0 needs target_depth")
+    d = _image_loss(lead + (3,), ssim_lambda, padding)
+    desc = _lib.RgbdLoss(d.images, d.height, d.width, int(render.shape[-1]), d.ssim_weight, d.padding, depth_lambda)
+    require_device(render, target_rgb, target_depth, mask)
+    if mask is not None:
+        mask = (mask != 0).float() if mask.dtype in (torch.bool, torch.uint8) else _f32c(mask.detach())
+    depth = _f32c(target_depth.detach()) if depth_lambda > 0.0 else None
+    loss, terms = _RGBD.apply(_f32c(render), _f32c(target_rgb.detach()), depth, mask, desc)
+    return (loss, terms) if return_terms else loss
