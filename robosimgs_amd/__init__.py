@@ -18,7 +18,7 @@ _DEVICE_API = {"rasterization", "render", "check_isect_status", "fully_fused_pro
                "rasterize_to_pixels", "rasterize_labels", "rasterize_votes", "assign_classes", "lift_labels",
                "fit_hinge", "fit_hinge_points", "pose_gaussians", "bind_particles", "deform_gaussians",
                "deform_gaussians_autograd", "rasterize_mesh", "mesh_vertices", "mesh_raster", "mesh_resolve",
-               "mesh_lens_rays", "render_sharded", "gather_frames"}
+               "mesh_lens_rays", "render_sharded", "gather_frames", "TSDFVolume"}
 
 
 def __getattr__(name):  # lazy: keeps `import robosimgs_amd` torch-free for host-only use
@@ -62,6 +62,9 @@ def __getattr__(name):  # lazy: keeps `import robosimgs_amd` torch-free for host
     if name in ("l1_loss", "l1_ssim_loss", "ssim", "unit_gradient", "rgbd_loss"):
         from . import losses
         return getattr(losses, name)
+    if name in ("TSDFVolume", "tsdf_integrate_raw", "tsdf_extract_raw", "check_extract_status"):
+        from . import tsdf
+        return getattr(tsdf, name)
     if name in ("FrameRenderer", "locality_order"):
         from . import pipeline
         return getattr(pipeline, name)

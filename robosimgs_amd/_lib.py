@@ -55,6 +55,13 @@ class McmcStats(ctypes.Structure):
     _fields_ = [("total", c_double), ("n_dead", c_int32), ("n_live", c_int32)]
 
 
+class TsdfVolume(ctypes.Structure):
+    """mgs_tsdf_volume (include/mgs_tsdf.h): the grid, its truncation and weight cap, and its three arrays."""
+    _fields_ = [("nx", c_int), ("ny", c_int), ("nz", c_int), ("origin", c_float * 3), ("voxel_size", c_float),
+                ("trunc", c_float), ("max_weight", c_float), ("tsdf", c_void_p), ("weight", c_void_p), ("color", c_void_p)]
+
+
+TSDF_STATUS_OVERFLOW = 1                   # MGS_TSDF_STATUS_OVERFLOW
 MCMC_RELOCATE, MCMC_ADD = 0, 1             # mgs_mcmc_relocate.mode
 MCMC_MAX_RATIO = 51                        # MGS_MCMC_MAX_RATIO
 REFINE_MAX_GROUPS = 8                      # MGS_REFINE_MAX_GROUPS
@@ -185,12 +192,19 @@ _RGBD_LOSS_SIGNATURES = {
     "mgs_rgbd_loss_fwd_grad": ([POINTER(RgbdLoss), p, p, p, p, p, p, p, p, POINTER(c_size_t), p], c_int),
     "mgs_rgbd_loss_bwd": ([POINTER(RgbdLoss), p, p, p, p, p, p, p, POINTER(c_size_t), p], c_int),
 }
+# every function include/mgs_tsdf.h declares (the same libraries again): each starts with the volume; the count pass is its
+# own size query (a null workspace), and the emit pass takes that workspace with its size by value
+_TSDF_SIGNATURES = {
+    "mgs_tsdf_integrate": ([POINTER(TsdfVolume), i, i, i, p, i, p, f, f, p, p, i, p], c_int),
+    "mgs_tsdf_extract_count": ([POINTER(TsdfVolume), f, f, p, p, POINTER(c_size_t), p], c_int),
+    "mgs_tsdf_extract_emit": ([POINTER(TsdfVolume), f, f, p, p, c_size_t, p, p, c_int64, p, c_int64, p, p], c_int),
+}
 del p, i, f, u32, img
 # what _load binds: a new header adds its table here
 _SIGNATURE_TABLES = (_SIGNATURES, _OPTIM_SIGNATURES, _REFINE_SIGNATURES, _LABEL_SIGNATURES, _LIFT_SIGNATURES,
                      _HINGE_SIGNATURES, _POSE_SIGNATURES, _DEFORM_SIGNATURES, _DEFORM_SH_SIGNATURES, _MESH_SIGNATURES,
                      _MESH_TEXTURE_SIGNATURES, _HYBRID_SIGNATURES, _DEFORM_BWD_SIGNATURES, _MESH_LENS_SIGNATURES,
-                     _RGBD_LOSS_SIGNATURES)
+                     _RGBD_LOSS_SIGNATURES, _TSDF_SIGNATURES)
 EXPORTS = list(_SIGNATURES)
 OPTIM_EXPORTS = list(_OPTIM_SIGNATURES)
 REFINE_EXPORTS = list(_REFINE_SIGNATURES)
@@ -206,6 +220,7 @@ HYBRID_EXPORTS = list(_HYBRID_SIGNATURES)
 MESH_TEXTURE_EXPORTS = list(_MESH_TEXTURE_SIGNATURES)
 MESH_LENS_EXPORTS = list(_MESH_LENS_SIGNATURES)
 RGBD_LOSS_EXPORTS = list(_RGBD_LOSS_SIGNATURES)
+TSDF_EXPORTS = list(_TSDF_SIGNATURES)
 MESH_LENS_NEWTON_STEPS, MESH_LENS_SUPERBLOCK = 12, 8   # MGS_MESH_LENS_NEWTON_STEPS, MGS_MESH_LENS_SUPERBLOCK
 MESH_MAX_SIDE, MESH_LARGE_BLOCKS = 16368, 15   # MGS_MESH_MAX_SIDE, MGS_MESH_LARGE_BLOCKS
 # MGS_MESH_TEXTURE_MAX_SIDE, MGS_MESH_MAX_TEXTURES, MGS_MESH_TEXTURE_DESC_WORDS, MGS_MESH_WRAP_*, MGS_MESH_FILTER_*

@@ -244,6 +244,19 @@ class Mesh:
                     faces.append([i - 1 if i > 0 else len(verts) + i for i in idx])
         return Mesh(np.asarray(verts, np.float32).reshape(-1, 3), np.asarray(faces, np.int64).reshape(-1, 3))
 
+    def to_obj(self, path: str) -> None:
+        """Wavefront OBJ: a `v x y z` line per vertex, `v x y z r g b` where the mesh has vertex_colors (the colour extension
+        most viewers and simulators' importers read), and a `f a b c` line per face, 1-based.  Coordinates are written with
+        nine significant digits, so Mesh.from_obj reads back the float32 values given.  Face colours, link ids and textures
+        are not written.  Reads the arrays back when they are on the GPU."""
+        v = self.vertices.detach().cpu().numpy()
+        f = self.faces.detach().cpu().numpy().astype(np.int64) + 1
+        rows = v if self.vertex_colors is None else np.concatenate([v, self.vertex_colors.detach().cpu().numpy()], 1)
+        with open(path, "w", encoding="utf-8") as fh:
+            fh.write(f"# {len(v)} vertices, {len(f)} faces\n")
+            fh.writelines("v " + " ".join(f"{x:.9g}" for x in row) + "\n" for row in rows)
+            fh.writelines(f"f {a} {b} {c}\n" for a, b, c in f)
+
     @staticmethod
     def from_glb(path: str, textures: bool = False) -> "Mesh":
         """Binary glTF 2.0: POSITION, indices (u8 / u16 / u32, or none), optional COLOR_0 (float or normalised u8 / u16; alpha
