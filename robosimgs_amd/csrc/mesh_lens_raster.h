@@ -1,12 +1,13 @@
 // mesh_lens_raster.h -- the arithmetic of the mesh rasteriser under a lens (include/mgs_mesh_lens.h, csrc/mesh_lens.hip):
 // the per-pixel ray map (the inverse of the lens), its block tables and the face's box in ray space, as __host__
-// __device__-clean inline functions over mesh_raster.h.  mesh_lens.hip's kernels and the g++ harness
+// __device__-clean inline functions over mesh_raster.h, and LensView, the view through which mesh_raster.h's face setup,
+// key and resolve and mesh_kernels.h's kernels see a camera under a lens.  mesh_lens.hip and the g++ harness
 // (tests/host_harness/mesh_lens_harness.cpp) share this one text; the statement is tests/mesh_lens_ref.py.
 //
 // The raster is homogeneous: the pixel enters the edge test only through its ray.  Under a lens the triangle is unchanged
 // and a pixel's ray is (x_u, y_u, 1) with (x_u, y_u) the preimage of the pixel's distorted normalised point d under the
 // distortion map.  So the planes are mesh_raster.h's, set up under Cam{1, 1, 0, 0} (s / 1 is exact), and the walk is
-// pixel_edges_at at (x_u, y_u).
+// pixel_edges_at at (x_u, y_u): LensView below.
 //
 // Roundings (U = 2^-24) of one evaluation of the forward map, on its absolute value |D|(q) (every coefficient and
 // coordinate replaced by its modulus), in the order written below:
@@ -263,31 +264,46 @@ MGS_MESH_HD bool box_blocks(Rect box, const Rect* blocks, const Rect* supers, in
   return true;
 }
 
-// The whole setup of face `face` of one camera under a lens: face_setup with the planes under Cam{1, 1, 0, 0} and the box from
-// the block tables.  The three indices are checked BEFORE any vertex is loaded.
+// ---- the view of one camera under a lens (see PinholeView) ------------------------------------------------------------------
+// The planes are set up under Cam{1, 1, 0, 0}, the box comes from the block tables, and a pixel's ray is one 8-byte load from
+// the ray map: the headlight's ray is then (q, 1) normalised.  The tables hold all cameras, so the view of camera c is the
+// struct itself.
+struct LensView {
+  const Ray* rays;                            // [C,H,W]
+  const Rect* blocks;                         // [C,BY,BX]
+  const Rect* supers;                         // [C,SY,SX]
+  MGS_MESH_HD LensView camera(int) const { return *this; }
+  using P0 = Ray;
+  using P1 = Rect;
+  using P2 = Rect;
+  const P0* p0() const { return rays; }
+  const P1* p1() const { return blocks; }
+  const P2* p2() const { return supers; }
+  MGS_MESH_HD static LensView from(const P0* rays, const P1* blocks, const P2* supers) {
+    LensView v; v.rays = rays; v.blocks = blocks; v.supers = supers; return v;
+  }
+  MGS_MESH_HD Cam plane_cam() const { const Cam unit = {1.0f, 1.0f, 0.0f, 0.0f}; return unit; }
+  MGS_MESH_HD bool box(const float a[3], const float b[3], const float c[3], float near_plane, int cam_index, int width,
+                       int height, FaceRec& r) const {
+    Rect bx;
+    return face_ray_box(a, b, c, near_plane, bx) && box_blocks(bx, blocks, supers, cam_index, width, height, r);
+  }
+  MGS_MESH_HD bool ray(size_t at, int, int, float& dx, float& dy) const {
+    const Ray q = rays[at];
+    dx = q.x; dy = q.y;
+    return has_ray(q);
+  }
+};
+
+// The lens path's setup, key and resolve by their earlier names, for callers that hold the tables or one ray and no view
 MGS_MESH_HD bool face_setup_lens(const float* verts_cam_c, int V, const int32_t* faces, int face, float near_plane,
                                  const Rect* blocks, const Rect* supers, int c, int width, int height, bool cull, FaceRec& r) {
-  const int32_t i0 = faces[3 * (size_t)face + 0], i1 = faces[3 * (size_t)face + 1], i2 = faces[3 * (size_t)face + 2];
-  if (!index_ok(i0, V) || !index_ok(i1, V) || !index_ok(i2, V)) return false;
-  const float* pa = verts_cam_c + 3 * (size_t)i0;
-  const float* pb = verts_cam_c + 3 * (size_t)i1;
-  const float* pc = verts_cam_c + 3 * (size_t)i2;
-  const float a[3] = {pa[0], pa[1], pa[2]}, b[3] = {pb[0], pb[1], pb[2]}, cc[3] = {pc[0], pc[1], pc[2]};
-  const Cam unit = {1.0f, 1.0f, 0.0f, 0.0f};
-  r.face = face;
-  r.pad = 0;
-  Rect box;
-  return face_planes(a, b, cc, unit, cull, r) && face_ray_box(a, b, cc, near_plane, box) &&
-         box_blocks(box, blocks, supers, c, width, height, r);
+  const LensView view = {nullptr, blocks, supers};
+  return face_setup(view, verts_cam_c, V, faces, face, near_plane, c, width, height, cull, r);
 }
-
-// ---- per pixel ---------------------------------------------------------------------------------------------------------------
-// the key of the face at a pixel whose ray is q; a pixel without a ray is never inside
 MGS_MESH_HD bool pixel_key_lens(const FaceRec& r, Ray q, float near_plane, float far_plane, uint64_t& key) {
   return has_ray(q) && pixel_key_at(r, q.x, q.y, near_plane, far_plane, key);
 }
-// resolve_pixel_at under the unit camera at the pixel's ray: the headlight's ray is (q, 1) normalised; a pixel without a ray
-// is uncovered (depth 0, id -1, rgb 0)
 MGS_MESH_HD Shaded resolve_pixel_lens(uint64_t key, const float* verts_cam_c, int V, const int32_t* faces, int F,
                                       const float* vertex_colors, const float* face_colors, Ray q, bool headlight, float ambient) {
   const Cam unit = {1.0f, 1.0f, 0.0f, 0.0f};

@@ -1,9 +1,10 @@
 // mesh_raster.h -- the arithmetic of the triangle-mesh rasteriser (include/mgs_mesh.h, csrc/mesh.hip): everything that
-// decides an index or a value, as __host__ __device__-clean inline functions.  mesh.hip's kernels and the g++ harness
-// (tests/host_harness/mesh_harness.cpp, which walks the same launches serially on heap buffers of the ABI's sizes) share
-// this one text.  The semantics and the fp32 evaluation order are the statement's (tests/mesh_ref.py): adjugate rows in
-// the edge-difference form, cx / cy not folded in, the fmas exactly where the statement counts them -- so contraction is
-// switched off for this header and for what includes it: no product and sum is fused that is not written as fmaf here.
+// decides an index or a value, as __host__ __device__-clean inline functions.  The kernels (mesh_kernels.h, instantiated
+// by mesh.hip and mesh_lens.hip) and the g++ harnesses (tests/host_harness/mesh_walk.h, which walks the same launches
+// serially on heap buffers of the ABI's sizes) share this one text.  The semantics and the fp32 evaluation order are the
+// statement's (tests/mesh_ref.py): adjugate rows in the edge-difference form, cx / cy not folded in, the fmas exactly
+// where the statement counts them -- so contraction is switched off for this header and for what includes it: no product
+// and sum is fused that is not written as fmaf here.
 #ifndef MGS_MESH_RASTER_H_
 #define MGS_MESH_RASTER_H_
 
@@ -196,24 +197,71 @@ MGS_MESH_HD bool face_box(const float a[3], const float b[3], const float c[3], 
   return true;
 }
 
-// The whole setup of face `face` of one camera.  The three indices are checked BEFORE any vertex is loaded.
-MGS_MESH_HD bool face_setup(const float* verts_cam_c, int V, const int32_t* faces, int face, Cam k, float near_plane, int width,
-                            int height, bool cull, FaceRec& r) {
-  const int32_t i0 = faces[3 * (size_t)face + 0], i1 = faces[3 * (size_t)face + 1], i2 = faces[3 * (size_t)face + 2];
-  if (!index_ok(i0, V) || !index_ok(i1, V) || !index_ok(i2, V)) return false;
-  const float* pa = verts_cam_c + 3 * (size_t)i0;
-  const float* pb = verts_cam_c + 3 * (size_t)i1;
-  const float* pc = verts_cam_c + 3 * (size_t)i2;
-  const float a[3] = {pa[0], pa[1], pa[2]}, b[3] = {pb[0], pb[1], pb[2]}, c[3] = {pc[0], pc[1], pc[2]};
+// The vertex indices of face `face` and its vertices in one camera's frame.  False where an index is outside 0 .. V-1: the
+// three indices are checked BEFORE any vertex is loaded.
+struct FaceVerts { int32_t i0, i1, i2; float a[3], b[3], c[3]; };
+MGS_MESH_HD bool load_face(const float* verts_cam_c, int V, const int32_t* faces, int face, FaceVerts& t) {
+  t.i0 = faces[3 * (size_t)face + 0]; t.i1 = faces[3 * (size_t)face + 1]; t.i2 = faces[3 * (size_t)face + 2];
+  if (!index_ok(t.i0, V) || !index_ok(t.i1, V) || !index_ok(t.i2, V)) return false;
+  const float* pa = verts_cam_c + 3 * (size_t)t.i0;
+  const float* pb = verts_cam_c + 3 * (size_t)t.i1;
+  const float* pc = verts_cam_c + 3 * (size_t)t.i2;
+  t.a[0] = pa[0]; t.a[1] = pa[1]; t.a[2] = pa[2];
+  t.b[0] = pb[0]; t.b[1] = pb[1]; t.b[2] = pb[2];
+  t.c[0] = pc[0]; t.c[1] = pc[1]; t.c[2] = pc[2];
+  return true;
+}
+
+// ---- the view of one camera ----------------------------------------------------------------------------------------------
+// What the raster asks of a camera (the pinhole here, a lens in mesh_lens_raster.h):
+//   plane_cam()                                     the camera the planes of a face are set up under;
+//   box(a, b, c, near, cam_index, width, height, r) the blocks of a face's box into r, false where it has none;
+//   ray(at, px, py, dx, dy)                         (dx, dy), the first two components of the ray of pixel (px, py) (index
+//                                                   `at`) in the units of the planes, false where the pixel has no ray.
+// The pinhole's ray is (px + 0.5 - cx, py + 0.5 - cy) with planes set up under K.  The views of all cameras of a call
+// (PinholeViews: the K matrices) give camera(c).  They travel to a kernel as their three pointers p0(), p1(), p2() (types
+// P0, P1, P2; void and null where a view has fewer), which the kernel declares __restrict__ and puts together again with
+// from(): inside a by-value struct the pointers lose the qualifier, and the kernels are then not the ones they were
+// (profiles/mesh_refactor/README.md).
+struct PinholeView {
+  Cam k;
+  MGS_MESH_HD Cam plane_cam() const { return k; }
+  MGS_MESH_HD bool box(const float a[3], const float b[3], const float c[3], float near_plane, int, int width, int height,
+                       FaceRec& r) const {
+    return face_box(a, b, c, k, near_plane, width, height, r);
+  }
+  MGS_MESH_HD bool ray(size_t, int px, int py, float& dx, float& dy) const {
+    dx = ((float)px + 0.5f) - k.cx;
+    dy = ((float)py + 0.5f) - k.cy;
+    return true;
+  }
+};
+struct PinholeViews {
+  const float* Ks;                            // [C,3,3]
+  MGS_MESH_HD PinholeView camera(int c) const { PinholeView v; v.k = load_cam(Ks + 9 * (size_t)c); return v; }
+  using P0 = float;
+  using P1 = void;
+  using P2 = void;
+  const P0* p0() const { return Ks; }
+  const P1* p1() const { return nullptr; }
+  const P2* p2() const { return nullptr; }
+  MGS_MESH_HD static PinholeViews from(const P0* Ks, const P1*, const P2*) { PinholeViews v; v.Ks = Ks; return v; }
+};
+
+// The whole setup of face `face` of camera `cam_index`, whose vertices are verts_cam_c.
+template <class View>
+MGS_MESH_HD bool face_setup(const View& view, const float* verts_cam_c, int V, const int32_t* faces, int face, float near_plane,
+                            int cam_index, int width, int height, bool cull, FaceRec& r) {
+  FaceVerts t;
+  if (!load_face(verts_cam_c, V, faces, face, t)) return false;
   r.face = face;
   r.pad = 0;
-  return face_planes(a, b, c, k, cull, r) && face_box(a, b, c, k, near_plane, width, height, r);
+  return face_planes(t.a, t.b, t.c, view.plane_cam(), cull, r) && view.box(t.a, t.b, t.c, near_plane, cam_index, width, height, r);
 }
 
 // ---- per pixel ---------------------------------------------------------------------------------------------------------------
-// The pixel enters only through (dx, dy), the first two components of its ray in the units of the planes: the pinhole's
-// (px + 0.5 - cx, py + 0.5 - cy) with planes set up under K, or a lens pixel's (x_u, y_u) with planes set up under
-// Cam{1, 1, 0, 0} (mesh_lens_raster.h).  e_i and S there; true where the pixel is inside (e_i >= 0, inclusive, and S > 0).
+// The pixel enters only through (dx, dy), its view's ray.  e_i and S there; true where the pixel is inside (e_i >= 0,
+// inclusive, and S > 0).
 MGS_MESH_HD bool pixel_edges_at(const FaceRec& r, float dx, float dy, float e[3], float& S) {
   for (int i = 0; i < 3; ++i) e[i] = fmaf(r.A[i], dx, fmaf(r.B[i], dy, r.C[i]));
   S = (e[0] + e[1]) + e[2];
@@ -228,54 +276,47 @@ MGS_MESH_HD bool pixel_key_at(const FaceRec& r, float dx, float dy, float near_p
   key = pack_key(z, r.face);
   return true;
 }
-// the pinhole's (dx, dy) at the centre of pixel (px, py)
-MGS_MESH_HD bool pixel_edges(const FaceRec& r, Cam k, int px, int py, float e[3], float& S) {
-  return pixel_edges_at(r, ((float)px + 0.5f) - k.cx, ((float)py + 0.5f) - k.cy, e, S);
-}
-MGS_MESH_HD bool pixel_key(const FaceRec& r, Cam k, int px, int py, float near_plane, float far_plane, uint64_t& key) {
-  return pixel_key_at(r, ((float)px + 0.5f) - k.cx, ((float)py + 0.5f) - k.cy, near_plane, far_plane, key);
+// the key of the face at pixel (px, py) (index `at`) of a view; a pixel without a ray is never inside
+template <class View>
+MGS_MESH_HD bool pixel_key(const View& view, const FaceRec& r, size_t at, int px, int py, float near_plane, float far_plane,
+                           uint64_t& key) {
+  float dx, dy;
+  return view.ray(at, px, py, dx, dy) && pixel_key_at(r, dx, dy, near_plane, far_plane, key);
 }
 
 // ---- resolve -----------------------------------------------------------------------------------------------------------------
+// From the winning key of a pixel: depth, face id, colour from the barycentrics recomputed in the raster's order (vertex
+// colours, face colours or 0.7 grey, optionally times the headlight shade) and the unit normal turned toward the camera.
+// Everything 0 and the id -1 where the pixel is uncovered (or the key names no valid face: never after the raster).  In
+// three stages; the textured resolve (mesh_texture.h) writes out the first two and shares the third.
 struct Shaded { float rgb[3], depth, normal[3]; int32_t face; };
+MGS_MESH_HD void store_shaded(const Shaded& s, size_t at, float* rgb, float* depth, int32_t* face_ids, float* normals) {
+  rgb[3 * at + 0] = s.rgb[0]; rgb[3 * at + 1] = s.rgb[1]; rgb[3 * at + 2] = s.rgb[2];
+  depth[at] = s.depth;
+  face_ids[at] = s.face;
+  if (normals) { normals[3 * at + 0] = s.normal[0]; normals[3 * at + 1] = s.normal[1]; normals[3 * at + 2] = s.normal[2]; }
+}
 
-// From the winning key of the pixel at (dx, dy) (see pixel_edges_at; k the camera the planes are set up under): depth, face
-// id, colour from the barycentrics recomputed in the same order (vertex colours, face colours or 0.7 grey, optionally times
-// the headlight shade) and the unit normal turned toward the camera.  Everything 0 and the id -1 where the pixel is
-// uncovered (or the key names no valid face: never after the raster).
-MGS_MESH_HD Shaded resolve_pixel_at(uint64_t key, const float* verts_cam_c, int V, const int32_t* faces, int F,
-                                    const float* vertex_colors, const float* face_colors, Cam k, float dx, float dy,
-                                    bool headlight, float ambient) {
-  Shaded o;
-  o.rgb[0] = o.rgb[1] = o.rgb[2] = 0.0f; o.depth = 0.0f; o.normal[0] = o.normal[1] = o.normal[2] = 0.0f; o.face = -1;
-  if (key == kEmptyKey) return o;
-  const int32_t f = key_face(key);
-  if (f < 0 || f >= F) return o;
-  const int32_t i0 = faces[3 * (size_t)f + 0], i1 = faces[3 * (size_t)f + 1], i2 = faces[3 * (size_t)f + 2];
-  if (!index_ok(i0, V) || !index_ok(i1, V) || !index_ok(i2, V)) return o;
-  const float* pa = verts_cam_c + 3 * (size_t)i0;
-  const float* pb = verts_cam_c + 3 * (size_t)i1;
-  const float* pc = verts_cam_c + 3 * (size_t)i2;
-  const float a[3] = {pa[0], pa[1], pa[2]}, b[3] = {pb[0], pb[1], pb[2]}, c[3] = {pc[0], pc[1], pc[2]};
-  FaceRec r;
-  r.face = f;
-  if (!face_planes(a, b, c, k, false, r)) return o;
-  float e[3], S;
-  pixel_edges_at(r, dx, dy, e, S);
-  o.face = f;
-  o.depth = key_depth(key);
-  const float l0 = e[0] / S, l1 = e[1] / S, l2 = e[2] / S;
+// the face that covers a pixel: its vertices, its planes under k, S and the barycentrics at the pixel's ray
+struct Covered { FaceVerts t; FaceRec r; float S, l0, l1, l2; };
+
+// Stage 2: vertex colours, face colours, or 0.7 grey
+MGS_MESH_HD void base_colour(const Covered& cv, const float* vertex_colors, const float* face_colors, float rgb[3]) {
   if (vertex_colors) {
-    const float* c0 = vertex_colors + 3 * (size_t)i0;
-    const float* c1 = vertex_colors + 3 * (size_t)i1;
-    const float* c2 = vertex_colors + 3 * (size_t)i2;
-    for (int j = 0; j < 3; ++j) o.rgb[j] = fmaf(l2, c2[j], fmaf(l1, c1[j], l0 * c0[j]));
+    const float* c0 = vertex_colors + 3 * (size_t)cv.t.i0;
+    const float* c1 = vertex_colors + 3 * (size_t)cv.t.i1;
+    const float* c2 = vertex_colors + 3 * (size_t)cv.t.i2;
+    for (int j = 0; j < 3; ++j) rgb[j] = fmaf(cv.l2, c2[j], fmaf(cv.l1, c1[j], cv.l0 * c0[j]));
   } else if (face_colors) {
-    for (int j = 0; j < 3; ++j) o.rgb[j] = face_colors[3 * (size_t)f + j];
+    for (int j = 0; j < 3; ++j) rgb[j] = face_colors[3 * (size_t)cv.r.face + j];
   } else {
-    o.rgb[0] = o.rgb[1] = o.rgb[2] = 0.7f;
+    rgb[0] = rgb[1] = rgb[2] = 0.7f;
   }
-  // n = (b - a) x (c - a), normalised; the ray through the pixel centre, normalised; cos between them
+}
+
+// Stage 3: n = (b - a) x (c - a), normalised; the ray through the pixel, normalised; cos between them
+MGS_MESH_HD void normal_and_shade(const float a[3], const float b[3], const float c[3], Cam k, float dx, float dy, bool headlight,
+                                  float ambient, Shaded& o) {
   const float u[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]}, w[3] = {c[0] - a[0], c[1] - a[1], c[2] - a[2]};
   float n[3];
   n[0] = u[1] * w[2] - u[2] * w[1]; n[1] = u[2] * w[0] - u[0] * w[2]; n[2] = u[0] * w[1] - u[1] * w[0];
@@ -291,14 +332,60 @@ MGS_MESH_HD Shaded resolve_pixel_at(uint64_t key, const float* verts_cam_c, int 
     const float shade = fmaf(1.0f - ambient, fabsf(cosv), ambient);
     for (int j = 0; j < 3; ++j) o.rgb[j] *= shade;
   }
+}
+
+// The resolve of the pixel at (dx, dy) (k: the camera the planes are set up under).  Stage 1, the covered face: key decode,
+// index check, vertex loads, planes, e, S, barycentrics, with the uncovered pixel returned from where it is found.  Stage 2,
+// base_colour.  Stage 3, normal_and_shade.  Stage 1 is written here and not as a function that returns a flag: behind a
+// flag the early returns meet in one block and the compiler repeats three subtractions (profiles/mesh_refactor/README.md).
+MGS_MESH_HD Shaded resolve_pixel_at(uint64_t key, const float* verts_cam_c, int V, const int32_t* faces, int F,
+                                    const float* vertex_colors, const float* face_colors, Cam k, float dx, float dy,
+                                    bool headlight, float ambient) {
+  Shaded o;
+  o.rgb[0] = o.rgb[1] = o.rgb[2] = 0.0f; o.depth = 0.0f; o.normal[0] = o.normal[1] = o.normal[2] = 0.0f; o.face = -1;
+  if (key == kEmptyKey) return o;
+  const int32_t f = key_face(key);
+  if (f < 0 || f >= F) return o;
+  Covered cv;
+  if (!load_face(verts_cam_c, V, faces, f, cv.t)) return o;
+  cv.r.face = f;
+  if (!face_planes(cv.t.a, cv.t.b, cv.t.c, k, false, cv.r)) return o;
+  float e[3];
+  pixel_edges_at(cv.r, dx, dy, e, cv.S);
+  o.face = f;
+  o.depth = key_depth(key);
+  cv.l0 = e[0] / cv.S; cv.l1 = e[1] / cv.S; cv.l2 = e[2] / cv.S;
+  base_colour(cv, vertex_colors, face_colors, o.rgb);
+  normal_and_shade(cv.t.a, cv.t.b, cv.t.c, k, dx, dy, headlight, ambient, o);
   return o;
 }
-// the pinhole's (dx, dy) at the centre of pixel (px, py)
+
+// the pixel (px, py) (index `at`) of a view; a pixel without a ray is uncovered
+template <class View>
+MGS_MESH_HD Shaded resolve_pixel(const View& view, uint64_t key, const float* verts_cam_c, int V, const int32_t* faces, int F,
+                                 const float* vertex_colors, const float* face_colors, size_t at, int px, int py, bool headlight,
+                                 float ambient) {
+  float dx, dy;
+  const bool has = view.ray(at, px, py, dx, dy);
+  return resolve_pixel_at(has ? key : kEmptyKey, verts_cam_c, V, faces, F, vertex_colors, face_colors, view.plane_cam(), dx, dy,
+                          headlight, ambient);
+}
+
+// The pinhole's setup, key and resolve by their earlier names, for callers that hold a Cam and no view
+MGS_MESH_HD bool face_setup(const float* verts_cam_c, int V, const int32_t* faces, int face, Cam k, float near_plane, int width,
+                            int height, bool cull, FaceRec& r) {
+  const PinholeView view = {k};
+  return face_setup(view, verts_cam_c, V, faces, face, near_plane, 0, width, height, cull, r);
+}
+MGS_MESH_HD bool pixel_key(const FaceRec& r, Cam k, int px, int py, float near_plane, float far_plane, uint64_t& key) {
+  const PinholeView view = {k};
+  return pixel_key(view, r, 0, px, py, near_plane, far_plane, key);
+}
 MGS_MESH_HD Shaded resolve_pixel(uint64_t key, const float* verts_cam_c, int V, const int32_t* faces, int F,
                                  const float* vertex_colors, const float* face_colors, Cam k, int px, int py, bool headlight,
                                  float ambient) {
-  return resolve_pixel_at(key, verts_cam_c, V, faces, F, vertex_colors, face_colors, k, ((float)px + 0.5f) - k.cx,
-                          ((float)py + 0.5f) - k.cy, headlight, ambient);
+  const PinholeView view = {k};
+  return resolve_pixel(view, key, verts_cam_c, V, faces, F, vertex_colors, face_colors, 0, px, py, headlight, ambient);
 }
 
 }  // namespace mesh

@@ -144,10 +144,14 @@ MGS_MESH_HD int32_t key_texture(uint64_t key, const int32_t* face_textures, int 
   return face_texture(face_textures, f, T);
 }
 
-// resolve_pixel with a texture between the tint and the headlight: the same statements in the same order, so that a pixel
-// whose face has no texture (textured false), or whose uv or (trilinear) uv derivatives are not finite, gets resolve_pixel's
-// bits.  textured, tex: whether key_texture gave the pixel a texture, and that texture's descriptor (read only if textured:
-// a separate flag, so that a wave whose pixels agree can pass one wave-uniform pointer).
+// resolve_pixel under the pinhole with a texture between the tint and the shade: the statements of mesh_raster.h's
+// resolve_pixel_at in the same order, so that a pixel whose face has no texture (textured false), or whose uv or
+// (trilinear) uv derivatives are not finite, gets resolve_pixel's bits.  Stages 1 and 2 are written out here and only
+// stage 3 (normal_and_shade) is shared: as resolve_pixel_at with the texture block as its callable the same arithmetic
+// compiled to another control flow, and the trilinear kernel measured 1.1 us slower at 1080p
+// (profiles/mesh_refactor/README.md); this text compiles to the kernel it was.  textured, tex: whether key_texture gave
+// the pixel a texture, and that texture's descriptor (read only if textured: a separate flag, so that a wave whose
+// pixels agree can pass one wave-uniform pointer).
 MGS_MESH_HD Shaded resolve_pixel_textured(uint64_t key, const float* verts_cam_c, int V, const int32_t* faces, int F,
                                           const float* vertex_colors, const float* face_colors, Cam k, int px, int py,
                                           bool headlight, float ambient, const float* face_uvs, bool textured,
@@ -167,7 +171,8 @@ MGS_MESH_HD Shaded resolve_pixel_textured(uint64_t key, const float* verts_cam_c
   r.face = f;
   if (!face_planes(a, b, c, k, false, r)) return o;
   float e[3], S;
-  pixel_edges(r, k, px, py, e, S);
+  const float dx = ((float)px + 0.5f) - k.cx, dy = ((float)py + 0.5f) - k.cy;
+  pixel_edges_at(r, dx, dy, e, S);
   o.face = f;
   o.depth = key_depth(key);
   const float l0 = e[0] / S, l1 = e[1] / S, l2 = e[2] / S;
@@ -216,22 +221,7 @@ MGS_MESH_HD Shaded resolve_pixel_textured(uint64_t key, const float* verts_cam_c
       o.rgb[0] = o.rgb[1] = o.rgb[2] = 0.7f;             // shaded untextured: resolve_pixel's grey
     }
   }
-  // n = (b - a) x (c - a), normalised; the ray through the pixel centre, normalised; cos between them
-  const float eu[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]}, ew[3] = {c[0] - a[0], c[1] - a[1], c[2] - a[2]};
-  float n[3];
-  n[0] = eu[1] * ew[2] - eu[2] * ew[1]; n[1] = eu[2] * ew[0] - eu[0] * ew[2]; n[2] = eu[0] * ew[1] - eu[1] * ew[0];
-  const float n2 = fmaf(n[2], n[2], fmaf(n[1], n[1], n[0] * n[0]));
-  const float ninv = n2 > 0.0f ? 1.0f / sqrtf(n2) : 0.0f;
-  const float nh[3] = {n[0] * ninv, n[1] * ninv, n[2] * ninv};
-  const float rx = (((float)px + 0.5f) - k.cx) / k.fx, ry = (((float)py + 0.5f) - k.cy) / k.fy;
-  const float rinv = 1.0f / sqrtf(fmaf(ry, ry, fmaf(rx, rx, 1.0f)));
-  const float cosv = fmaf(nh[2], rinv, fmaf(nh[1], ry * rinv, nh[0] * (rx * rinv)));
-  const float flip = cosv > 0.0f ? -1.0f : 1.0f;
-  for (int j = 0; j < 3; ++j) o.normal[j] = flip * nh[j];
-  if (headlight) {
-    const float shade = fmaf(1.0f - ambient, fabsf(cosv), ambient);
-    for (int j = 0; j < 3; ++j) o.rgb[j] *= shade;
-  }
+  normal_and_shade(a, b, c, k, dx, dy, headlight, ambient, o);
   return o;
 }
 

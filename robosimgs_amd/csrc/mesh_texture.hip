@@ -1,7 +1,8 @@
 // mesh_texture.hip -- textured triangle meshes (include/mgs_mesh_texture.h), gfx950: the mip chain of a texture set and the
-// textured resolve stage.  The vertex and raster stages are mesh.hip's, untouched, and so is its resolve kernel: a mesh
+// textured resolve stage.  The vertex and raster stages are mesh.hip's, and so is the untextured resolve kernel: a mesh
 // without textures never comes here.  Every expression that decides an index or a value is mesh_texture.h's, shared with
-// the host harness (tests/host_harness/mesh_texture_harness.cpp); what is here is the launch shape.
+// the host harness (tests/host_harness/mesh_texture_harness.cpp); what is here is the launch shape.  The argument checks
+// are mesh_checks.h's, shared with mesh.hip and mesh_lens.hip.
 //
 // mesh_mips_kernel              one thread per texel of the destination level, one launch per (texture, level): four 32-bit
 //                               loads, the per-byte sums in registers, one 32-bit store.
@@ -16,6 +17,7 @@
 
 #define MGS_MESH_HD __host__ __device__ __forceinline__
 #include "mesh_texture.h"
+#include "mesh_checks.h"
 
 namespace mgs {
 namespace {
@@ -60,18 +62,8 @@ __global__ __launch_bounds__(kGroup) void mesh_resolve_textured_kernel(
   else
     s = resolve_pixel_textured(key, vc, V, faces, F, vertex_colors, face_colors, cam, px, py, headlight != 0, ambient, face_uvs,
                                tid >= 0, descs + (tid >= 0 ? tid : 0), texels, texel_count, kFilter);
-  if (!inside) return;
-  rgb[3 * at + 0] = s.rgb[0]; rgb[3 * at + 1] = s.rgb[1]; rgb[3 * at + 2] = s.rgb[2];
-  depth[at] = s.depth;
-  face_ids[at] = s.face;
-  if (normals) { normals[3 * at + 0] = s.normal[0]; normals[3 * at + 1] = s.normal[1]; normals[3 * at + 2] = s.normal[2]; }
+  if (inside) store_shaded(s, at, rgb, depth, face_ids, normals);
 }
-
-#define MGS_TRY(expr)        \
-  do {                       \
-    const int rc_ = (expr);  \
-    if (rc_) return rc_;     \
-  } while (0)
 
 int check_texture_count(const char* fn, int T) {
   MGS_REQUIRE(T >= 1 && T <= kTexMaxTextures, "%s: n_textures %d is outside 1 .. %d", fn, T, kTexMaxTextures);
@@ -155,19 +147,18 @@ extern "C" int mgs_mesh_resolve_textured(int n_cams, int V, const float* verts_c
                                          const int32_t* face_textures, int n_textures, const int32_t* descriptors,
                                          const void* texels, size_t texel_count, int filter, mgs_stream_t stream) {
   const char* fn = "mesh_resolve_textured";
+  // the sizes in this entry point's own order (n_cams above 65535 is reported before V, F and the image)
   MGS_REQUIRE(n_cams >= 1 && n_cams <= 65535, "%s: n_cams %d is outside 1 .. 65535", fn, n_cams);
   MGS_REQUIRE(V >= 1, "%s: V %d vertices, at least 1 needed", fn, V);
   MGS_REQUIRE(F >= 1, "%s: F %d faces, at least 1 needed", fn, F);
   MGS_REQUIRE(width >= 1 && width <= kMaxSide && height >= 1 && height <= kMaxSide, "%s: image %d x %d, each side must be in 1 .. %d",
               fn, width, height, kMaxSide);
-  MGS_REQUIRE(ambient >= 0.f && ambient <= 1.f, "%s: ambient %g is outside 0 .. 1", fn, (double)ambient);
+  MGS_TRY(check_ambient(fn, ambient));
   MGS_REQUIRE(verts_cam && faces && Ks, "%s: verts_cam, faces or Ks is null", fn);
   MGS_REQUIRE(rgb && depth && face_ids, "%s: an output (rgb, depth, face_ids) is null", fn);
   MGS_TRY(check_texture_args(fn, face_uvs, face_textures, n_textures, descriptors, texels, texel_count, filter));
   const Layout l = workspace_layout(n_cams, F, width, height);
-  MGS_REQUIRE(workspace, "%s: workspace is null", fn);
-  MGS_REQUIRE(((uintptr_t)workspace & 255u) == 0, "%s: workspace is not 256-byte aligned", fn);
-  MGS_REQUIRE(workspace_bytes >= l.total, "%s: workspace of %zu bytes, %zu needed", fn, workspace_bytes, l.total);
+  MGS_TRY(check_workspace(fn, "workspace", workspace, workspace_bytes, l.total));
   const unsigned long long* vis = reinterpret_cast<const unsigned long long*>(static_cast<const char*>(workspace) + l.vis);
   const size_t n_px = (size_t)width * (size_t)height;                        // <= 16368^2 < 2^28
   const dim3 grid((unsigned)((n_px + kGroup - 1) / kGroup), (unsigned)n_cams), block(kGroup);
@@ -195,17 +186,14 @@ extern "C" int mgs_rasterize_mesh_textured(int n_cams, int V, const float* verti
   // untextured operator's own checks below (mgs_mesh_vertices and mgs_mesh_raster check theirs before they launch)
   const char* fn = "rasterize_mesh_textured";
   MGS_TRY(check_texture_args(fn, face_uvs, face_textures, n_textures, descriptors, texels, texel_count, filter));
-  MGS_REQUIRE(ambient >= 0.f && ambient <= 1.f, "%s: ambient %g is outside 0 .. 1", fn, (double)ambient);
-  MGS_REQUIRE(near_plane > 0.f, "%s: near_plane %g is not a positive number", fn, (double)near_plane);
-  MGS_REQUIRE(far_plane >= near_plane, "%s: far_plane %g is not a number at or above near_plane %g", fn, (double)far_plane,
-              (double)near_plane);
-  MGS_REQUIRE(L >= 0 && (L == 0 || (rotations && translations)), "%s: L %d links is negative, or rotations or translations is null", fn, L);
+  MGS_TRY(check_ambient(fn, ambient));
+  MGS_TRY(check_planes(fn, near_plane, far_plane));
+  MGS_TRY(check_links(fn, L, rotations, translations));
   MGS_REQUIRE(vertices && viewmats && Ks && faces, "%s: vertices, viewmats, Ks or faces is null", fn);
   MGS_REQUIRE(verts_cam && rgb && depth && face_ids, "%s: an output (verts_cam, rgb, depth, face_ids) is null", fn);
   size_t need = 0;
   MGS_TRY(mgs_mesh_workspace_bytes(n_cams, V, F, width, height, &need));     // the sizes
-  MGS_REQUIRE(workspace && ((uintptr_t)workspace & 255u) == 0 && workspace_bytes >= need,
-              "%s: workspace is null, not 256-byte aligned or smaller than the %zu bytes needed", fn, need);
+  MGS_TRY(check_workspace(fn, "workspace", workspace, workspace_bytes, need));
   MGS_TRY(mgs_mesh_vertices(n_cams, V, vertices, link_ids, L, rotations, translations, scales, viewmats, verts_cam, stream));
   MGS_TRY(mgs_mesh_raster(n_cams, V, verts_cam, F, faces, Ks, width, height, near_plane, far_plane, cull_backfaces, workspace,
                           workspace_bytes, stream));

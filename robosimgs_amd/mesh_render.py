@@ -1,4 +1,4 @@
-"""Triangle meshes rendered on the GPU (include/mgs_mesh.h, csrc/mesh.hip): the opaque foreground of a hybrid frame, as an
+"""Triangle meshes rendered on the GPU (include/mgs_mesh.h, csrc/mesh.hip, csrc/mesh_kernels.h): the opaque foreground of a hybrid frame, as an
 operator of its own that the caller composites over a Gaussian render.
 
     box = Mesh.merge([Mesh.from_glb("lid.glb"), Mesh.from_glb("body.glb")], link_ids=[0, -1]).to("cuda")
@@ -25,6 +25,7 @@ Under a lens (camera_model="fisheye", distortion=, pinhole_distortion=: rasteriz
 rasterised at each pixel's own ray, solved from the lens per pixel (include/mgs_mesh_lens.h, csrc/mesh_lens.hip; semantics:
 tests/mesh_lens_ref.py): nothing is tessellated or resampled, and the mesh layer registers with a splat frame rendered
 under that lens.  mesh_lens_rays builds the ray map as a stage of its own; mesh_raster and mesh_resolve take it as rays=.
+The raster and resolve kernels are the pinhole path's own text (csrc/mesh_kernels.h), instantiated for the ray map.
 
 Argument errors are ValueErrors raised before any launch.  There is no fallback: a missing library is an error.
 """

@@ -24,7 +24,9 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import mesh_scenes as MS          # noqa: E402
 
 PEAK = 8e12                       # bytes / s, the figure the project's other rooflines use
-KERNELS = ["mesh_vertices_kernel", "mesh_clear_kernel", "mesh_faces_kernel", "mesh_large_kernel", "mesh_resolve_kernel"]
+# the raster and resolve kernels are one text per view (csrc/mesh_kernels.h): the pinhole's rows are the PinholeViews ones
+KERNELS = ["mesh_vertices_kernel", "mesh_clear_kernel", "mesh_faces_kernel<PinholeViews>", "mesh_large_kernel<PinholeViews>",
+           "mesh_resolve_kernel<PinholeViews>"]
 PROFILE_CALLS = 40
 
 
@@ -47,13 +49,23 @@ def floors(box, W, H, keys):
     return {k: {"bytes": v, "floor_us": round(v / PEAK * 1e6, 3)} for k, v in b.items()}
 
 
+def kernel_of(row_name, kernels):
+    """The entry of `kernels` a profiler row names, or None: `name` for a plain kernel, `name<View>` for an instantiation (the
+    row carries the view's qualified name as the template argument, or its mangled form).  No kernel's name contains another's."""
+    for k in kernels:
+        base, _, view = k.partition("<")
+        if base in row_name and view.rstrip(">") in row_name:
+            return k
+    return None
+
+
 def parse(directory):
     """Per configuration and kernel: median / p10 / p90 of the dispatch durations in a rocprofv3 kernel trace of --profile."""
     rows = []
     for path in glob.glob(os.path.join(directory, "**", "*kernel_trace.csv"), recursive=True):
         with open(path, newline="") as fh:
             for r in csv.DictReader(fh):
-                name = next((k for k in KERNELS if k in r["Kernel_Name"]), None)
+                name = kernel_of(r["Kernel_Name"], KERNELS)
                 if name:
                     rows.append((int(r["Start_Timestamp"]), name, int(r["End_Timestamp"]) - int(r["Start_Timestamp"])))
     rows.sort()

@@ -24,11 +24,11 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, os.path.join(ROOT, "scripts"))
 import mesh_scenes as MS          # noqa: E402
 import pinhole_lens_ref as PR     # noqa: E402
-from mesh_bench import stats      # noqa: E402
+from mesh_bench import KERNELS as PINHOLE, kernel_of, stats      # noqa: E402
 
-PINHOLE = ["mesh_vertices_kernel", "mesh_clear_kernel", "mesh_faces_kernel", "mesh_large_kernel", "mesh_resolve_kernel"]
-LENS = ["mesh_vertices_kernel", "mesh_rays_kernel", "mesh_lens_blocks_kernel", "mesh_lens_supers_kernel", "mesh_lens_clear_kernel",
-        "mesh_lens_faces_kernel", "mesh_lens_large_kernel", "mesh_lens_resolve_kernel"]
+# the same text as the pinhole's rows (csrc/mesh_kernels.h), instantiated for LensView
+LENS = ["mesh_vertices_kernel", "mesh_rays_kernel", "mesh_lens_blocks_kernel", "mesh_lens_supers_kernel", "mesh_clear_kernel",
+        "mesh_faces_kernel<LensView>", "mesh_large_kernel<LensView>", "mesh_resolve_kernel<LensView>"]
 PROFILE_CALLS = 40
 WARM = 10
 
@@ -41,13 +41,14 @@ def configs():
 
 def parse(directory):
     """Per configuration, path and kernel: median / p10 / p90 of the dispatch durations in a trace of --profile."""
-    names = sorted(set(PINHOLE + LENS), key=len, reverse=True)
+    # mesh_vertices_kernel and mesh_clear_kernel carry the same name on both paths: their rows are told apart by their place
+    # in the dispatch sequence (PROFILE_CALLS pinhole renders, then as many under the lens), which the assert below holds
+    names = sorted(set(PINHOLE + LENS))
     rows = []
     for path in glob.glob(os.path.join(directory, "**", "*kernel_trace.csv"), recursive=True):
         with open(path, newline="") as fh:
             for r in csv.DictReader(fh):
-                name = next((k for k in names if k + "(" in r["Kernel_Name"] or r["Kernel_Name"].endswith(k)
-                             or k + "E" in r["Kernel_Name"]), None)
+                name = kernel_of(r["Kernel_Name"], names)
                 if name:
                     rows.append((int(r["Start_Timestamp"]), name, int(r["End_Timestamp"]) - int(r["Start_Timestamp"])))
     rows.sort()
@@ -68,12 +69,16 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--lib", default=None, help="another build of libmgs.so to measure (an A/B of one kernel)")
     ap.add_argument("--profile", action="store_true", help="only enqueue renders, for a rocprofv3 kernel trace")
     ap.add_argument("--parse", default=None)
     args = ap.parse_args()
     if args.parse:
         return parse(args.parse)
     import torch
+    from robosimgs_amd import _lib
+    if args.lib:
+        _lib.LIB_PATH = os.path.abspath(args.lib)
     from robosimgs_amd import Mesh, MeshRenderer, mesh_lens_rays, mesh_raster, mesh_resolve
     assert torch.cuda.is_available(), "mesh_lens_bench measures on the GPU; there is no other path"
     box, cfgs = configs()
@@ -102,7 +107,7 @@ def main():
             torch.cuda.synchronize()
             return stats([a.elapsed_time(b) for a, b in ev])
 
-        res = {"config": name, "render_pinhole": timed(lambda: plain.render(vmd, Kd)), "render_lens": timed(lambda: lens.render(vmd, Kd))}
+        res = {"config": name, "lib": args.lib or "libmgs.so", "render_pinhole": timed(lambda: plain.render(vmd, Kd)), "render_lens": timed(lambda: lens.render(vmd, Kd))}
         _, _, meta = lens.render(vmd, Kd)
         m = mesh_lens_rays(Kd, W, H, pinhole_distortion=PR.MILD)
         res["stage_rays"] = timed(lambda: mesh_lens_rays(Kd, W, H, pinhole_distortion=PR.MILD, workspace=m.workspace))

@@ -58,11 +58,7 @@ extern "C" int mth_resolve(int n_cams, int V, const float* verts_cam, int F, con
       const Shaded s = resolve_pixel_textured(key, verts_cam + vertex_index(c, V, 0), V, faces, F, vertex_colors, face_colors,
                                               load_cam(Ks + 9 * (size_t)c), px, py, headlight != 0, ambient, face_uvs, tid >= 0,
                                               descs + (tid >= 0 ? tid : 0), texels, texel_count, filter);
-      if (!inside) continue;
-      rgb[3 * at + 0] = s.rgb[0]; rgb[3 * at + 1] = s.rgb[1]; rgb[3 * at + 2] = s.rgb[2];
-      depth[at] = s.depth;
-      face_ids[at] = s.face;
-      if (normals) { normals[3 * at + 0] = s.normal[0]; normals[3 * at + 1] = s.normal[1]; normals[3 * at + 2] = s.normal[2]; }
+      if (inside) store_shaded(s, at, rgb, depth, face_ids, normals);
     }
   free(vis);
   return 0;
