@@ -18,7 +18,7 @@ _DEVICE_API = {"rasterization", "render", "check_isect_status", "fully_fused_pro
                "rasterize_to_pixels", "rasterize_labels", "rasterize_votes", "assign_classes", "lift_labels",
                "fit_hinge", "fit_hinge_points", "pose_gaussians", "bind_particles", "deform_gaussians",
                "deform_gaussians_autograd", "rasterize_mesh", "mesh_vertices", "mesh_raster", "mesh_resolve",
-               "mesh_lens_rays", "render_sharded", "gather_frames", "TSDFVolume"}
+               "mesh_lens_rays", "render_sharded", "gather_frames", "TSDFVolume", "register_points"}
 
 
 def __getattr__(name):  # lazy: keeps `import robosimgs_amd` torch-free for host-only use
@@ -65,6 +65,9 @@ def __getattr__(name):  # lazy: keeps `import robosimgs_amd` torch-free for host
     if name in ("TSDFVolume", "tsdf_integrate_raw", "tsdf_extract_raw", "check_extract_status"):
         from . import tsdf
         return getattr(tsdf, name)
+    if name in ("register_points", "Registration", "register_icp_raw", "register_workspace"):
+        from . import registration
+        return getattr(registration, name)
     if name in ("FrameRenderer", "locality_order"):
         from . import pipeline
         return getattr(pipeline, name)

@@ -199,12 +199,18 @@ _TSDF_SIGNATURES = {
     "mgs_tsdf_extract_count": ([POINTER(TsdfVolume), f, f, p, p, POINTER(c_size_t), p], c_int),
     "mgs_tsdf_extract_emit": ([POINTER(TsdfVolume), f, f, p, p, c_size_t, p, p, c_int64, p, c_int64, p, p], c_int),
 }
+# every function include/mgs_register.h declares (the same libraries again): the workspace size is a query of its own, as
+# the hinge's is; init, correspondence, distance2 and history are nullable, result is 32 doubles behind a void pointer
+_REGISTER_SIGNATURES = {
+    "mgs_register_workspace_bytes": ([i, i, i], c_size_t),
+    "mgs_register_icp": ([i, p, i, p, f, i, i, c_double, p, p, c_size_t, p, p, p, p, p], c_int),
+}
 del p, i, f, u32, img
 # what _load binds: a new header adds its table here
 _SIGNATURE_TABLES = (_SIGNATURES, _OPTIM_SIGNATURES, _REFINE_SIGNATURES, _LABEL_SIGNATURES, _LIFT_SIGNATURES,
                      _HINGE_SIGNATURES, _POSE_SIGNATURES, _DEFORM_SIGNATURES, _DEFORM_SH_SIGNATURES, _MESH_SIGNATURES,
                      _MESH_TEXTURE_SIGNATURES, _HYBRID_SIGNATURES, _DEFORM_BWD_SIGNATURES, _MESH_LENS_SIGNATURES,
-                     _RGBD_LOSS_SIGNATURES, _TSDF_SIGNATURES)
+                     _RGBD_LOSS_SIGNATURES, _TSDF_SIGNATURES, _REGISTER_SIGNATURES)
 EXPORTS = list(_SIGNATURES)
 OPTIM_EXPORTS = list(_OPTIM_SIGNATURES)
 REFINE_EXPORTS = list(_REFINE_SIGNATURES)
@@ -221,6 +227,7 @@ MESH_TEXTURE_EXPORTS = list(_MESH_TEXTURE_SIGNATURES)
 MESH_LENS_EXPORTS = list(_MESH_LENS_SIGNATURES)
 RGBD_LOSS_EXPORTS = list(_RGBD_LOSS_SIGNATURES)
 TSDF_EXPORTS = list(_TSDF_SIGNATURES)
+REGISTER_EXPORTS = list(_REGISTER_SIGNATURES)
 MESH_LENS_NEWTON_STEPS, MESH_LENS_SUPERBLOCK = 12, 8   # MGS_MESH_LENS_NEWTON_STEPS, MGS_MESH_LENS_SUPERBLOCK
 MESH_MAX_SIDE, MESH_LARGE_BLOCKS = 16368, 15   # MGS_MESH_MAX_SIDE, MGS_MESH_LARGE_BLOCKS
 # MGS_MESH_TEXTURE_MAX_SIDE, MGS_MESH_MAX_TEXTURES, MGS_MESH_TEXTURE_DESC_WORDS, MGS_MESH_WRAP_*, MGS_MESH_FILTER_*

@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = ["api.hip", "projection.hip", "sort.hip", "binning.hip", "tile_sort.hip", "raster_fwd.hip",
            "raster_bwd.hip", "backward.hip", "composite.hip", "points.hip", "loss.hip", "transform.hip", "frame.hip",
            "optim.hip", "refine.hip", "labels.hip", "lift.hip", "hinge.hip", "pose.hip", "deform.hip", "mesh.hip",
-           "mesh_texture.hip", "hybrid.hip", "mesh_lens.hip", "tsdf.hip"]
+           "mesh_texture.hip", "hybrid.hip", "mesh_lens.hip", "tsdf.hip", "register.hip"]
 # every header of the library and of its public interface: a new one is in the stamp without being listed
 HEADERS = sorted(glob.glob(os.path.join(HERE, "*.h"))) + sorted(glob.glob(os.path.join(HERE, "../../include/*.h")))
 LIB = os.path.join(HERE, "libmgs.so")

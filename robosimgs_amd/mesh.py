@@ -257,6 +257,27 @@ class Mesh:
             fh.writelines("v " + " ".join(f"{x:.9g}" for x in row) + "\n" for row in rows)
             fh.writelines(f"f {a} {b} {c}\n" for a, b, c in f)
 
+    def sample_points(self, n: int, seed: int = 0) -> np.ndarray:
+        """n points on the surface, float32 [n,3] on the host: faces drawn with probability proportional to their area, a
+        uniform point in each (the square-root fold of two uniforms), from numpy.random.default_rng(seed) -- the same
+        points for the same seed.  The target cloud of register_points for a scanned object or a robot link.  Reads the
+        arrays back when they are on the GPU."""
+        n = int(n)
+        if n < 0:
+            raise ValueError(f"n must not be negative, got {n}")
+        v = self.vertices.detach().cpu().numpy().astype(np.float64)
+        f = self.faces.detach().cpu().numpy().astype(np.int64)
+        if f.shape[0] == 0:
+            raise ValueError("the mesh has no face to sample")
+        a, b, c = v[f[:, 0]], v[f[:, 1]], v[f[:, 2]]
+        area = 0.5 * np.linalg.norm(np.cross(b - a, c - a), axis=1)
+        if not (np.isfinite(area).all() and area.sum() > 0):
+            raise ValueError("the mesh has no finite positive area to sample")
+        rng = np.random.default_rng(seed)
+        face = rng.choice(f.shape[0], size=n, p=area / area.sum())
+        r1, r2 = np.sqrt(rng.random(n))[:, None], rng.random(n)[:, None]
+        return ((1.0 - r1) * a[face] + r1 * (1.0 - r2) * b[face] + r1 * r2 * c[face]).astype(np.float32)
+
     @staticmethod
     def from_glb(path: str, textures: bool = False) -> "Mesh":
         """Binary glTF 2.0: POSITION, indices (u8 / u16 / u32, or none), optional COLOR_0 (float or normalised u8 / u16; alpha
